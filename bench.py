@@ -29,7 +29,15 @@ steps and one warm-up all-reduce (RCCL sets its channels up on a communicator's
 first collective).  `per_rank` carries every rank's kernel / wall / all-reduce /
 barrier-wait split, gathered over the job's own channel after the window.
 
-Prints ONE JSON line on rank 0 (contract in the task statement) carrying
+A plain run (`bench.py --gpus N --steps K --warmup W`) sets up, warms up, times the K steps and prints ONE JSON line on
+rank 0: metric, value (reads/s), unit, higher_is_better, dtype, ms_per_step (wall milliseconds of one timed step), config,
+per_rank.  --dump-outputs DIR then also writes what the last timed step returned (per-gene counts, a fixed seeded sample of
+the last launch's per-pair results) as DIR/<name>.npy in float64 -- see dump_outputs; the inputs depend only on the
+arguments, so two builds can be compared file by file.
+
+--full adds the side legs to the same line (the --no-* options leave some of them out):
+  value_async    the timed passes again through the pipelined device-resident entry points
+  trimmed_reads  the headline index on batches with trimmed mates
   roofline       against the resource that binds the dominant kernel, in that
                  resource's units, frac <= 1: the headline index sits in LDS and
                  the kernel is bound by VALU issue (achieved = G wave-
@@ -895,12 +903,57 @@ def boundary_leg(h, batch, nb, L, kinds=("pageable", "pinned"), n_batches=12):
     return boundary
 
 
+DUMP_BYTES_MAX = 64 << 20       # --dump-outputs writes at most this much
+DUMP_SAMPLE_PAIRS = 1 << 21     # pairs of the last launch sampled for the per-pair arrays (all of them when the launch has fewer)
+DUMP_SAMPLE_SEED = 20250917
+
+
+def dump_outputs(d, res, counts, steps, n_genes):
+    """--dump-outputs DIR: what the timed path returned in its last step, as float64 .npy files (at most DUMP_BYTES_MAX in all).
+      gene_counts          the all-reduced per-gene counts of the timed window / steps = one step's counts, genes 0 .. n_genes-1
+      launch_totals        [pairs, associations, pairs with at least one association] of the step's last launch
+      sample_pair_index    a fixed, seeded sample of that launch's pairs (ascending)
+      sample_gene_count    gene_off[i + 1] - gene_off[i] of every sampled pair i
+      sample_gene_ids      the gene ids of the sampled pairs, concatenated in the order of the sample
+    `res` is the last shk_classify_device result of the timed window: its device buffers are read as they are, nothing is
+    classified again."""
+    import numpy as np
+    from shark_amd.capi import hip_memcpy_dtoh
+    n, n_assoc = int(res.n), int(res.n_assoc)
+    goff = np.empty(n + 1, np.uint32)
+    hip_memcpy_dtoh(goff, res.gene_off, goff.nbytes)
+    gids = np.empty(max(n_assoc, 1), np.uint16)
+    hip_memcpy_dtoh(gids, res.gene_ids, 2 * n_assoc)
+    gids = gids[:n_assoc]
+    per_pair = np.diff(goff.astype(np.int64))
+    out = {"gene_counts": np.asarray(counts, np.uint64)[:min(n_genes, 65536)] // np.uint64(steps),
+           "launch_totals": np.array([n, n_assoc, int((per_pair > 0).sum())])}
+    fixed = sum(8 * v.size for v in out.values())
+    s = min(n, DUMP_SAMPLE_PAIRS)
+    while True:
+        idx = np.arange(n) if s == n else np.sort(np.random.default_rng(DUMP_SAMPLE_SEED).choice(n, size=s, replace=False))
+        cnt = per_pair[idx]
+        if fixed + 8 * (2 * s + int(cnt.sum())) <= DUMP_BYTES_MAX or s == 1:
+            break
+        s //= 2
+    sel = np.repeat(goff[idx].astype(np.int64), cnt) + (np.arange(int(cnt.sum())) - np.repeat(np.cumsum(cnt) - cnt, cnt))
+    out.update(sample_pair_index=idx, sample_gene_count=cnt, sample_gene_ids=gids[sel])
+    os.makedirs(d, exist_ok=True)
+    for name, a in out.items():
+        np.save(os.path.join(d, name + ".npy"), np.ascontiguousarray(a, dtype=np.float64))
+    return {name: int(a.size) for name, a in out.items()}
+
+
 # =====================================================================================================================
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--gpus", type=int, default=1)
-    ap.add_argument("--steps", type=int, default=5)
-    ap.add_argument("--warmup", type=int, default=1)
+    ap.add_argument("--steps", type=int, default=5, help="timed steps")
+    ap.add_argument("--warmup", type=int, default=1, help="untimed steps in front of them")
+    ap.add_argument("--full", action="store_true", help="also the side legs: pipelined passes, trimmed batches, configs[2] / configs[4], "
+                                                        "counters and rooflines, batch boundary, CPU baseline, the shark command end to end "
+                                                        "(the --no-* options below leave some of them out); without it a run times the headline only")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None, help="after the timed steps, write what the last step returned as DIR/<name>.npy (float64)")
     ap.add_argument("--scaling", choices=["strong", "weak"], default="strong")
     ap.add_argument("--total-pairs", type=int, default=80_000_000, help="strong scaling: pairs of the read set over ALL GPUs")
     ap.add_argument("--reps-per-step", type=int, default=16, help="passes over the read set per step (the same at every N)")
@@ -945,6 +998,8 @@ def main():
         return
     if args.gpus < 1:
         ap.error("--gpus must be at least 1")
+    if args.steps < 1 or args.warmup < 0:
+        ap.error("--steps must be at least 1 and --warmup at least 0")
     if args.reps_per_step < 1:
         ap.error("--reps-per-step must be at least 1")
     if args.gpus > 1 and "WORLD_SIZE" not in os.environ:
@@ -1052,6 +1107,49 @@ def main():
                  "barrier_wait_ms": round(x[3], 3), "launches": int(x[4])} for r, x in enumerate(rows)]
     reads_per_step = 2 * pairs_per_pass_all * reps
     value = reads_per_step * args.steps / dt
+    out = {
+        "metric": "reads/s (paired 2x150 bp, k=%d)" % k,
+        "value": round(value, 1),
+        "unit": "reads/s",
+        "n_gpus": world,
+        "ranks_seen": ranks_seen,
+        "steps": args.steps,
+        "warmup": args.warmup,
+        "ms_per_step": round(dt / args.steps * 1e3, 3),
+        "higher_is_better": True,
+        "scaling": args.scaling,
+        "vs_baseline": None,
+        "dtype": "u64",
+        "data": "synthetic",
+        "full": args.full,
+        "config": {"workload": "configs[1]: %d gene(s) x %d bp, 2x150 bp pairs in launches of %d, k=%d c=%.1f bf=2^%d bits; a read set of %d pairs "
+                               "over %d GPU(s) (%s scaling), %d passes over it per step"
+                               % (args.genes, args.gene_len, chunk_pairs, k, c, args.bf_log2, pairs_per_pass_all, world, args.scaling, reps),
+                   "pairs_per_launch": chunk_pairs, "launches_per_step_per_gpu": len(my_chunks) * reps, "pairs_in_read_set": pairs_per_pass_all,
+                   "reps_per_step": reps, "pairs_per_step": pairs_per_pass_all * reps,
+                   "reads_per_step": reads_per_step, "on_target": args.on_target,
+                   "seed": synth.SEED, "index_build_s": round(t_build, 3), "n_set_bits": int(info["n_set_bits"]),
+                   "assoc_per_step": int(n_assoc.item()) // args.steps,
+                   "gene_count_checksum": int(np.asarray(counts, dtype=np.uint64).sum()) // args.steps,
+                   "gene_counts_allreduce": ("single GPU: no collective" if world == 1 else
+                                             "shk_dist_gene_counts_allreduce (RCCL inside libsharkhip; ranks_seen = ncclCommCount); one warm-up collective "
+                                             "before the window, the timed one is per_rank[].allreduce_ms" if sdist.backend_name() == "nccl"
+                                             else "gloo dry run (SHARK_DIST_BACKEND): torch.distributed all-reduce of the library's local counters"),
+                   "timed_window": "barrier, %d steps x %d passes x %d launches per GPU (each shk_classify_device call synchronises once), one all-reduce of "
+                                   "uint64[65536], barrier; max over ranks" % (args.steps, reps, len(my_chunks)),
+                   "long_reads": int(tm["last_n_long"]), "tie_reads": int(tm["last_n_tie"]), "probe_mode": h.probe_mode()},
+        "per_rank": per_rank,
+    }
+    if args.dump_outputs and rank == 0:
+        # (before any other leg: they reuse the context's result buffers)
+        out["dumped"] = dump_outputs(args.dump_outputs, res, counts, args.steps, args.genes)
+        log("outputs of the last step written to %s" % args.dump_outputs)
+    if not args.full:
+        # a plain run: the headline and nothing else
+        if rank == 0:
+            print(json.dumps(out), flush=True)
+        sdist.finalize()
+        return
     # ---- the same passes through the device-resident PIPELINE (shk_classify_device_submit / shk_classify_wait: three launches in
     # flight, no host synchronisation between two of them, the uniform read length vouched for by the caller as the host entry
     # points find it out themselves).  Never `value`: `value_async` next to it, with what a launch costs either way. ----
@@ -1429,45 +1527,15 @@ def main():
         except OSError:
             pass
 
-    out = {
-        "metric": "reads/s (paired 2x150 bp, k=%d)" % k,
-        "value": round(value, 1),
-        "unit": "reads/s",
-        "n_gpus": world,
-        "ranks_seen": ranks_seen,
-        "steps": args.steps,
-        "warmup": args.warmup,
-        "ms_per_step": round(dt / args.steps * 1e3, 3),
-        "higher_is_better": True,
-        "scaling": args.scaling,
-        "vs_baseline": None,
-        "dtype": "u64",
-        "data": "synthetic",
-        "config": {"workload": "configs[1]: %d gene(s) x %d bp, 2x150 bp pairs in launches of %d, k=%d c=%.1f bf=2^%d bits; a read set of %d pairs "
-                               "over %d GPU(s) (%s scaling), %d passes over it per step"
-                               % (args.genes, args.gene_len, chunk_pairs, k, c, args.bf_log2, pairs_per_pass_all, world, args.scaling, reps),
-                   "pairs_per_launch": chunk_pairs, "launches_per_step_per_gpu": len(my_chunks) * reps, "pairs_in_read_set": pairs_per_pass_all,
-                   "reps_per_step": reps, "pairs_per_step": pairs_per_pass_all * reps,
-                   "reads_per_step": reads_per_step, "on_target": args.on_target,
-                   "seed": synth.SEED, "index_build_s": round(t_build, 3), "n_set_bits": int(info["n_set_bits"]),
-                   "assoc_per_step": int(n_assoc.item()) // args.steps,
-                   "gene_count_checksum": int(np.asarray(counts, dtype=np.uint64).sum()) // args.steps,
-                   "gene_counts_allreduce": ("single GPU: no collective" if world == 1 else
-                                             "shk_dist_gene_counts_allreduce (RCCL inside libsharkhip; ranks_seen = ncclCommCount); one warm-up collective "
-                                             "before the window, the timed one is per_rank[].allreduce_ms" if sdist.backend_name() == "nccl"
-                                             else "gloo dry run (SHARK_DIST_BACKEND): torch.distributed all-reduce of the library's local counters"),
-                   "timed_window": "barrier, %d steps x %d passes x %d launches per GPU (each shk_classify_device call synchronises once), one all-reduce of "
-                                   "uint64[65536], barrier; max over ranks" % (args.steps, reps, len(my_chunks)),
-                   "long_reads": int(tm["last_n_long"]), "tie_reads": int(tm["last_n_tie"]), "probe_mode": h.probe_mode()},
+    out.update({
         "value_async": value_async,
-        "per_rank": per_rank,
         "roofline": roofline,
         "cpu_baseline": cpu,
         "configs": [cfg2, cfg4] if cfg2 else [],
         "trimmed_reads": trimmed,
         "batch_boundary": boundary,
         "cli_end_to_end": cli,
-    }
+    })
     print(json.dumps(out), flush=True)
     if cli is not None and cli.get("runs") is not None and not cli.get("all_runs_valid", True):
         # a command that printed something else than the library classified must not leave a throughput figure behind unnoticed

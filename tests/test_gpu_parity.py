@@ -431,7 +431,7 @@ def test_bench_ranks_dry_run(tmp_path, launcher, scaling, ranks):
         env.pop(v, None)
     reps = 2
     base = [os.path.join(root, "bench.py"), "--steps", "2", "--warmup", "1", "--pairs", "250000", "--total-pairs", "1000000", "--reps-per-step", str(reps),
-            "--scaling", scaling, "--no-configs", "--no-boundary", "--no-cpu-baseline", "--no-cli", "--no-live-counters"]
+            "--scaling", scaling, "--full", "--no-configs", "--no-boundary", "--no-cpu-baseline", "--no-cli", "--no-live-counters"]
     if launcher == "self":
         cmd = ["python3"] + base + ["--gpus", str(ranks)]
     else:
@@ -466,6 +466,43 @@ def test_bench_ranks_dry_run(tmp_path, launcher, scaling, ranks):
         assert j1["config"]["launches_per_step_per_gpu"] == ranks * j["config"]["launches_per_step_per_gpu"]
     else:
         assert j["config"]["reads_per_step"] == ranks * 2 * 250000 * reps
+
+
+def test_bench_plain_run_dumps_what_its_last_step_returned(oracle, tmp_path):
+    """a plain bench run (no --full) times the headline only and prints it; --dump-outputs writes the last timed step's per-gene
+    counts and a seeded sample of its last launch's per-pair results, which must be the oracle's on the same pairs"""
+    import json
+    import subprocess
+    import sys
+    from shark_amd import synth as dsynth
+    root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+    env = {k: v for k, v in os.environ.items() if k not in ("WORLD_SIZE", "RANK", "LOCAL_RANK", "SHARK_DIST_BACKEND")}
+    n, chunks, steps, reps, L = 250000, 4, 3, 2, 150
+    d = tmp_path / "dump"
+    r = subprocess.run([sys.executable, os.path.join(root, "bench.py"), "--gpus", "1", "--steps", str(steps), "--warmup", "1", "--pairs", str(n),
+                        "--total-pairs", str(chunks * n), "--reps-per-step", str(reps), "--dump-outputs", str(d)],
+                       capture_output=True, text=True, env=env, cwd=root, timeout=600)
+    assert r.returncode == 0, r.stderr[-3000:]
+    lines = [x for x in r.stdout.splitlines() if x.strip()]
+    assert len(lines) == 1, r.stdout[-2000:]
+    j = json.loads(lines[0])
+    assert j["full"] is False and j["steps"] == steps and j["value"] > 0 and j["ms_per_step"] > 0 and j["dtype"] == "u64"
+    assert not any(key in j for key in ("roofline", "cpu_baseline", "configs", "cli_end_to_end", "value_async"))
+    a = {f.name[:-4]: np.load(f) for f in d.iterdir()}
+    assert set(a) == {"gene_counts", "launch_totals", "sample_pair_index", "sample_gene_count", "sample_gene_ids"}
+    assert all(v.dtype == np.float64 for v in a.values()) and sum(f.stat().st_size for f in d.iterdir()) <= 64 << 20
+    assert int(a["gene_counts"].sum()) == j["config"]["gene_count_checksum"] == j["config"]["assoc_per_step"]
+    # the step's last launch: the last chunk of the read set (seed SEED + 1 + chunk), n pairs, all of them in the sample
+    assert a["launch_totals"].tolist()[0] == n and np.array_equal(a["sample_pair_index"], np.arange(n))
+    genes = dsynth.make_reference(1, 20000)
+    b = dsynth.make_pairs_device(n, genes, torch.device("cuda:0"), seed=dsynth.SEED + chunks, read_len=L, on_target=0.5)
+    hb = dsynth.to_host_sample(b, n, L)
+    o = oracle.Shark(k=17, c=0.6, bf_bits=1 << 33)
+    o.build([g.tobytes() for g in genes])
+    og, oi = o.classify(hb["seq1"], hb["off1"], hb["seq2"], hb["off2"], nthreads=8)
+    o.close()
+    assert np.array_equal(a["sample_gene_count"], np.diff(og.astype(np.int64)))
+    assert np.array_equal(a["sample_gene_ids"], oi) and a["launch_totals"].tolist()[1] == int(og[-1])
 
 
 def test_bench_refuses_a_rank_count_that_is_not_gpus():

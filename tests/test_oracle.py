@@ -3,7 +3,8 @@
  * example/*.truth.* (the reference's only golden files, README.md:60-69)
  * XXH64 known answers (python-xxhash)                     tests/golden/xxh64_kat.json
  * outputs of the REAL reference primitives (oracle/_ref)  tests/golden/ref_primitives.json
- * live cross-checks against oracle/_ref when the .so is present
+ * seeded random inputs + the reference's outputs         tests/golden/ref_random_primitives.npz
+   (and live cross-checks against oracle/_ref when the .so is present)
 """
 import ctypes as C
 import hashlib
@@ -137,29 +138,35 @@ def test_oracle_cli_reader_matches_reference_records(oracle, tmp_path):
 
 
 def test_live_reference_primitives(oracle):
-    """when oracle/_ref is built, compare on fresh random inputs (not only the committed fixture)"""
+    """2000 random k-mers and 300 random strings (tests/golden/gen_ref_random_primitives.py) against the reference's outputs
+    stored with them in tests/golden/ref_random_primitives.npz; when oracle/_ref is built, against the reference live as well"""
     R = oracle.ref()
-    if R is None:
-        pytest.skip("oracle/_ref/libsharkref.so not built")
     L = oracle.lib()
-    rng = np.random.default_rng(99)
-    for _ in range(2000):
-        k = int(rng.integers(1, 32))
-        v = int(rng.integers(0, 1 << 62)) & ((1 << (2 * k)) - 1)
-        c = int(rng.integers(0, 4))
-        assert L.so_revcompl(v, k) == R.ref_revcompl(v, k)
-        assert L.so_lsappend(v, c, k) == R.ref_lsappend(v, c, k)
-        assert L.so_rsprepend(v, c, k) == R.ref_rsprepend(v, c, k)
-        assert L.so_get_hash(v) == R.ref_get_hash(v)
-    alpha = np.frombuffer(b"ACGTacgtNn.", dtype=np.uint8)
-    for _ in range(300):
-        n = int(rng.integers(0, 120))
-        s = alpha[rng.integers(0, len(alpha), size=n)].tobytes()
-        k = int(rng.integers(1, 32))
+    fx = np.load(os.path.join(GOLD, "ref_random_primitives.npz"))
+    assert len(fx["prim_k"]) == 2000 and len(fx["str_k"]) == 300
+    for k, v, c, rc, ls, rs, hs in zip(*(fx["prim_" + name].tolist() for name in ("k", "kmer", "c", "revcompl", "lsappend", "rsprepend", "hash"))):
+        assert L.so_revcompl(v, k) == rc
+        assert L.so_lsappend(v, c, k) == ls
+        assert L.so_rsprepend(v, c, k) == rs
+        assert L.so_get_hash(v) == hs
+        if R is not None:
+            assert (R.ref_revcompl(v, k), R.ref_lsappend(v, c, k), R.ref_rsprepend(v, c, k), R.ref_get_hash(v)) == (rc, ls, rs, hs)
+    text, str_off = fx["text"].tobytes(), fx["str_off"].tolist()
+    starts, values, ends = fx["bk_start"].tolist(), fx["bk_value"].tolist(), fx["bk_pos"].tolist()
+    at = 0
+    for i, k in enumerate(fx["str_k"].tolist()):
+        s = text[str_off[i]:str_off[i + 1]]
+        n = len(s)
         for p0 in range(0, n + 1, 3):
-            p, q = C.c_int(p0), C.c_int(p0)
-            assert L.so_build_kmer(s, n, C.byref(p), k) == R.ref_build_kmer(s, n, C.byref(q), k)
-            assert p.value == q.value
+            assert starts[at] == p0
+            p = C.c_int(p0)
+            assert L.so_build_kmer(s, n, C.byref(p), k) == values[at]
+            assert p.value == ends[at]
+            if R is not None:
+                q = C.c_int(p0)
+                assert R.ref_build_kmer(s, n, C.byref(q), k) == values[at] and q.value == ends[at]
+            at += 1
+    assert at == len(values)
 
 
 def _brute_force_kmers(s, k):

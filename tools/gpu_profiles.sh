@@ -1,6 +1,6 @@
 #!/bin/bash
 # Profiles of the classify kernels for profiles/ (run on the GPU box through gpurun; then `python tools/collect_profiles.py rNN` here).
-#   kt       : rocprofv3 --kernel-trace --stats of the bench command (headline workload + configs[2] index + configs[4] shape)
+#   kt       : rocprofv3 --kernel-trace --stats of the bench command with --full (headline workload + configs[2] index + configs[4] shape)
 #   kt_trimmed: the same of tools/ragged_rate.py 10000000 100 0.8 (a batch with 20 % of its mates trimmed)
 #   counters : `bench.py --profile-passes` = the counter passes bench.py itself makes live (one rocprofv3 --pmc child per counter set,
 #              --kernel-trace only beside --pmc: gpurun refuses anything else), plus a fourth SQ set, for the headline workload at
@@ -8,7 +8,7 @@
 export TMPDIR=/tmp
 OUT=gpurun_out/profiles
 rm -rf $OUT; mkdir -p $OUT
-timeout -k 10 600 rocprofv3 --kernel-trace --stats --output-format csv -d $OUT/kt -- python3 bench.py --steps 2 --warmup 1 --reps-per-step 4 --no-cpu-baseline --no-boundary --no-cli --no-live-counters --no-trimmed > $OUT/kt.json 2> $OUT/kt.err || { tail -5 $OUT/kt.err; exit 1; }
+timeout -k 10 600 rocprofv3 --kernel-trace --stats --output-format csv -d $OUT/kt -- python3 bench.py --full --steps 2 --warmup 1 --reps-per-step 4 --no-cpu-baseline --no-boundary --no-cli --no-live-counters --no-trimmed > $OUT/kt.json 2> $OUT/kt.err || { tail -5 $OUT/kt.err; exit 1; }
 # keep only the stats summary of the trace (the per-dispatch CSVs are large)
 find $OUT/kt -name "*_kernel_trace.csv" -delete
 # a trimmed batch (20 % of the mates cut to 100-150 bases): the passes over the offsets and the class-by-class instantiation

@@ -4,7 +4,7 @@
 # one that timed out or was killed).  Steps:
 #   suite            the whole `pytest -m gpu` suite          scale      tests/test_gpu_scale.py (configs[2] / configs[4] shapes)
 #   t:<expr>         pytest tests/test_gpu_parity.py -k <expr>           fuzz       tests/test_gpu_fuzz.py
-#   bench            the default bench line (what the driver runs)       bench_quick  headline only, no side legs
+#   bench            bench.py --full (every leg)                         bench_quick  --full without the configs / boundary / cpu / cli legs
 #   bench:<args>     bench.py with the given arguments (separated by @)
 #   profiles         tools/gpu_profiles.sh (kernel stats + counter passes for profiles/)
 #   land:<args>      tools/landscape.py <args> (separated by @)         ragged:<genes>  tools/ragged_rate.py (GENES=<genes>)
@@ -28,8 +28,8 @@ for step in "$@"; do
     scale)       timeout -k 10 1150 python3 -m pytest tests/test_gpu_scale.py -x -q --durations=5 > $log 2>&1 ;;
     fuzz)        timeout -k 10 900 python3 -m pytest tests/test_gpu_fuzz.py -x -q -s > $log 2>&1 ;;
     t:*)         timeout -k 10 1150 python3 -m pytest tests/test_gpu_parity.py -k "${step#t:}" -x -q --durations=8 > $log 2>&1 ;;
-    bench)       timeout -k 10 900 python3 bench.py > $out/bench.json 2> $log ;;
-    bench_quick) timeout -k 10 600 python3 bench.py --no-configs --no-boundary --no-cpu-baseline --no-cli --no-live-counters > $out/bench_quick.json 2> $log ;;
+    bench)       timeout -k 10 900 python3 bench.py --full > $out/bench.json 2> $log ;;
+    bench_quick) timeout -k 10 600 python3 bench.py --full --no-configs --no-boundary --no-cpu-baseline --no-cli --no-live-counters > $out/bench_quick.json 2> $log ;;
     bench:*)     timeout -k 10 900 python3 bench.py $(echo "${step#bench:}" | tr '@' ' ') > $log.json 2> $log ;;
     profiles)    bash tools/gpu_profiles.sh > $log 2>&1 ;;
     land:*)      timeout -k 10 900 python3 tools/landscape.py $(echo "${step#land:}" | tr '@' ' ') > $log.jsonl 2> $log ;;
@@ -38,7 +38,7 @@ for step in "$@"; do
     ab:*)        IFS=: read -r _ ot libs <<< "$step"
                  for rep in 1 2; do for v in $(echo $libs | tr ':' ' '); do
                    if [ $v = base ]; then unset SHK_LIB_PATH; else export SHK_LIB_PATH=$PWD/tools/variants/$v.so; fi
-                   timeout -k 10 300 python3 bench.py --no-configs --no-cpu-baseline --no-boundary --no-cli --no-live-counters --no-async --no-trimmed --steps 2 --reps-per-step 2 --total-pairs 20000000 --on-target $ot 2>> $log \
+                   timeout -k 10 300 python3 bench.py --full --no-configs --no-cpu-baseline --no-boundary --no-cli --no-live-counters --no-async --no-trimmed --steps 2 --reps-per-step 2 --total-pairs 20000000 --on-target $ot 2>> $log \
                      | python3 -c "import json,sys; d=json.loads(sys.stdin.read().strip().splitlines()[-1]); print('$v', d['config']['on_target'], d['roofline']['kernel_ms'], d['config']['assoc_per_step'], d['roofline']['kernel_reported_by_library'])" | tee -a $log.txt
                  done; done; unset SHK_LIB_PATH ;;
     abpy:*)      # abpy:<lib>+<lib>..:<script@args>  the script on library variants (base = in-tree), interleaved, twice; one output line each
