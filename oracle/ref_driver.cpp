@@ -11,7 +11,9 @@
  *   FastaSplitter.hpp + kseq.h    FASTA record parsing / legend order
  *   small_vector.hpp              per-set-bit gene list container
  * bloomfilter.h, KmerBuilder.hpp, BloomfilterFiller.hpp, ReadAnalyzer.hpp and
- * main.cpp include <sdsl/...> and are therefore NOT built here.
+ * main.cpp include <sdsl/...>; they are not part of this library.  They are
+ * built, with main.cpp unchanged, into the reference CLI oracle/_ref/shark_ref
+ * against our sdsl stand-in (ref_shark_main.cpp, sdsl_standin/).
  */
 #include <cstdint>
 #include <cstring>
