@@ -19,7 +19,7 @@ import torch  # noqa: F401  (one HIP runtime for both)
 from oracle import pyoracle
 from shark_amd import SharkHip
 from shark_amd.capi import hip_memcpy_dtoh
-from tests import synth
+from tests import repeat_refs, synth
 
 ALL_MODES = ["bitvector-mod", "bitvector", "summary+bitvector", "table", "summary+table", "lds-summary+table", "table-mod",
              "lds-summary+table-mod", "lds-table", "minimiser-table"]
@@ -30,7 +30,9 @@ def run_case(seed, bias=""):
     """one random configuration -> (ok, probe mode, one-line description).
     bias: "" = the broad distribution; "uni" = what classify_uni_kernel takes (sparse filters, one length per mate);
     "mid" = indices of 10^5 .. 10^6 k-mers in filters of 2^26 .. 2^30 bits (L2-summary + table, big LDS summary, plain table);
-    "mod" = filter sizes that are not a power of two with a table; "ktab" = the minimiser-bucketed table (k = 15 ... 17)."""
+    "mod" = filter sizes that are not a power of two with a table; "ktab" = the minimiser-bucketed table (k = 15 ... 17);
+    "rep" = drawn as "pre" or "uni", but the genes are a random mix of tests/repeat_refs.py's builders (paralog families, an element in
+    10 ... 300 carriers, low-complexity runs, tandem copies) instead of uniform-random records."""
     rng = np.random.default_rng(seed)
     env = {}
     k = int(rng.choice([1, 2, 5, 11, 16, 17, 18, 21, 25, 31, int(rng.integers(1, 32))]))
@@ -51,6 +53,9 @@ def run_case(seed, bias=""):
     if rng.random() < 0.5:
         env["SHK_PROBE"] = "bitvector"
     var_len = bool(rng.random() < 0.6)
+    rep = bias == "rep"
+    drawn_as = ("pre" if rng.random() < 0.6 else "uni") if rep else bias      # ("rep" draws everything but its genes as one of those two)
+    bias, label = drawn_as, bias
     if bias == "uni":
         env.pop("SHK_PROBE", None)
         bf_bits = (1 << int(rng.integers(24, 34))) if rng.random() < 0.7 else int(rng.choice([3, 5, 6, 7])) << 32
@@ -111,7 +116,11 @@ def run_case(seed, bias=""):
         os.environ.pop(kk, None)
     os.environ.update(env)
     try:
-        genes = synth.make_genes(rng, n_genes, max(20, gl // 3), gl, share_every=int(rng.choice([0, 2, 5])))
+        if rep:
+            genes, _ = repeat_refs.mixed_reference(rng, k)
+            n_genes = len(genes)
+        else:
+            genes = synth.make_genes(rng, n_genes, max(20, gl // 3), gl, share_every=int(rng.choice([0, 2, 5])))
         kw = dict(k=k, c=c, bf_bits=bf_bits, min_quality=q, single=single)
         o = pyoracle.Shark(**kw)
         nidx = o.build([bytes(g) for g in genes])
@@ -151,9 +160,10 @@ def run_case(seed, bias=""):
             khg, khi = h.classify(kb["seq1"], kb["off1"], kb["seq2"], kb["off2"], kb["qual1"], kb["qual2"])
             ok = ok and np.array_equal(kog, khg) and np.array_equal(koi, khi)
         mode = h.probe_mode()
-        desc = "seed=%d bias=%s k=%d bf=%d genes=%d len=%d%s%s q=%d s=%d c=%.1f reads=%d%s mode=%s set=%d assoc=%d feat=%s" % (
-            seed, bias or "-", k, bf_bits, n_genes, read_len, "x2" if paired else "", "~" if var_len else "", q, single, c, n_reads,
-            "".join(" %s=%s" % kv for kv in sorted(env.items())), mode, info["n_set_bits"], int(og[-1]), "+".join(feats) or "-")
+        desc = "seed=%d bias=%s k=%d bf=%d genes=%d len=%d%s%s q=%d s=%d c=%.1f reads=%d%s mode=%s set=%d assoc=%d widest=%d feat=%s" % (
+            seed, label or "-", k, bf_bits, n_genes, read_len, "x2" if paired else "", "~" if var_len else "", q, single, c, n_reads,
+            "".join(" %s=%s" % kv for kv in sorted(env.items())), mode, info["n_set_bits"], int(og[-1]),
+            int(np.diff(og.astype(np.int64)).max()) if len(og) > 1 else 0, "+".join(feats) or "-")
         h.close()
         o.close()
         return ok, mode, desc

@@ -4,8 +4,9 @@
    against our sdsl stand-in; tests/golden/gen_ref_shark_cases.py), replayed through oracle_cli and the oracle's batch
    API -- always run, the recording needs nothing from the reference tree
  * the sdsl stand-in's rank and select against numpy (always run)
- * live, when oracle/_ref/shark_ref has been built: the reference CLI on the example truth files, and a seeded random
-   differential run of oracle_cli against it on fresh cases
+ * live, when oracle/_ref/shark_ref has been built: the reference CLI on the example truth files, a seeded random
+   differential run of oracle_cli against it on fresh cases, and the repeat-rich and long-list cases of tests/repeat_refs.py
+   (gene lists of 65 534 ... 70 000 entries: the oracle's inline lists and rank support were never pinned there)
 """
 import ctypes as C
 import os
@@ -14,6 +15,7 @@ import numpy as np
 import pytest
 
 from tests import ref_cases as rc
+from tests import repeat_refs as rr
 
 HERE = os.path.dirname(os.path.abspath(__file__))
 ROOT = os.path.dirname(HERE)
@@ -147,3 +149,18 @@ def test_live_differential_oracle_against_reference(oracle, seed, tmp_path):
             i, cs["k"], cs["c"], cs["q"], cs["single"], cs["bf_bits"], cs["paired"])
         n += 1
     assert n == 1200
+
+
+@needs_ref
+@pytest.mark.parametrize("name", rr.BUILDER_CASES + rr.LONG_CASES)
+def test_live_repeat_and_long_list_cases(oracle, name, tmp_path):
+    """one case per builder of tests/repeat_refs.py and the four long-list cases (a motif in 65 534 / 65 535 / 65 536 / 70 000 records,
+    the last with a wrapped record that holds one k-mer 69 984 times): oracle_cli against the reference CLI, byte for byte"""
+    cs = rr.program_case(name)
+    want = rc.run_case(SHARK_REF, cs, str(tmp_path), env_bits="REF_BF_BITS", timeout=600)
+    got = rc.run_case(oracle.CLI_PATH, cs, str(tmp_path), bits_flag="--bf-bits", timeout=600)
+    assert got == want
+    widest = max(len(a) for a in rc.associations(cs, want[0]))
+    if name in rr.LONG_CASES:
+        n = int(name[5:])
+        assert widest == (n if n <= 65536 else 4463)      # the tie the case is for, in the reference's own output
