@@ -7,10 +7,9 @@
 // order (input order, genes ascending).
 //
 // Host structure mirrors main.cpp's three functor stages per worker loop
-// (main.cpp:66-77): a splitter thread fills SoA batches (FastqSplitter role,
-// but WITHOUT joining or masking -- the device does that), one analyzer thread
-// per GPU calls shk_classify (ReadAnalyzer role), and the main thread writes
-// batches in input order (ReadOutput role).  Extra flags: --gpus N, --batch N.
+// (main.cpp:66-77: split / analyze / output); which threads play them here is
+// described at run_sample() below, and main() lists the stages of a run.
+// Extra flags: --gpus N, --devices LIST, --batch N, --gene-counts FILE.
 #include <getopt.h>
 #include <sched.h>
 #include <sys/stat.h>
@@ -31,7 +30,6 @@
 #include <sstream>
 #include <string>
 #include <thread>
-#include <type_traits>
 #include <utility>
 #include <vector>
 
@@ -446,7 +444,6 @@ class BatchSplitter {
     fast_ = m1_->usable() && (!paired_ || m2_->usable()) && !getenv("SHARK_SERIAL_READER");
   }
   bool ok() const { return r1_.ok() && (!paired_ || r2_->ok()); }
-  bool fast_path() const { return fast_; }
   // continue with the serial kseq-rule reader at a record boundary (behind the batches the parallel feed delivered)
   void resume_serial(uint64_t off1, uint64_t off2, uint64_t next_index, uint64_t n_reads)
   {
@@ -861,7 +858,7 @@ class ReadAnalyzer {
 class OffsetWriter {
  public:
   OffsetWriter() = default;
-  // (every error return of main() that runs while a writer is in scope comes through here: the helper threads are joined, never
+  // (every error return of run_sample() that runs while a writer is in scope comes through here: the helper threads are joined, never
   // destroyed while joinable -- that would be std::terminate instead of the exit code the caller was promised)
   ~OffsetWriter() { (void)close(); }
   OffsetWriter(const OffsetWriter &) = delete;
@@ -1178,11 +1175,9 @@ class ReadOutput {
   std::string carry_;   // previd at the end of the previous batch (only used when a batch starts mid-chunk)
 };
 
-}  // namespace
-
 // CPUs this process can actually run threads on: the machine's count, cut down to its affinity mask and to its cgroup's CPU quota
 // (cgroup v2 cpu.max, v1 cpu.cfs_quota_us / cpu.cfs_period_us)
-static unsigned usable_cpus()
+unsigned usable_cpus()
 {
   unsigned n = std::max(1u, std::thread::hardware_concurrency());
   cpu_set_t set;
@@ -1204,69 +1199,69 @@ static unsigned usable_cpus()
   return std::max(1u, n);
 }
 
-int main(int argc, char *argv[])
+// ---- the stages of main(), in the order it runs them ---------------------------------------------------------------------------
+// the reference opens its inputs unchecked (main.cpp:88-106) and then reads nothing from a file that is not there; here a
+// sample that cannot be opened is reported before any work is done
+bool samples_can_be_opened(const Options &opt)
 {
-  Options opt_parsed = parse_arguments(argc, argv);
-  if (!opt_parsed.batch_given) opt_parsed.batch = auto_batch(opt_parsed.sample1_path, opt_parsed.batch);
-  const Options opt = opt_parsed;
-  if (opt.verbose) timeline.on();
-  timeline("arguments parsed");
-
-  if (opt.verbose) {
-    std::cerr << "shark (MI355X): reference " << opt.fasta_path << ", sample " << opt.sample1_path;
-    if (opt.paired_flag) std::cerr << " + " << opt.sample2_path;
-    std::cerr << "; k=" << opt.k << " c=" << opt.c << " q=" << opt.min_quality << (opt.single ? " single" : "") << " bf=" << (opt.bf_size >> 33)
-              << "GB gpus=" << opt.gpus << " devices=";
-    for (size_t g = 0; g < opt.devices.size(); ++g) std::cerr << (g ? "," : "") << opt.devices[g];
-    std::cerr << "\n" << std::endl;
-  }
-
-  // the reference opens its inputs unchecked (main.cpp:88-106) and then reads nothing from a file that is not there; here a
-  // sample that cannot be opened is reported before any work is done
   for (const std::string *path : {&opt.sample1_path, &opt.sample2_path}) {
     if (path->empty()) continue;
     // (a pipe is not opened for the check: it can be opened once.  access() says whether it may be read.)
     struct stat st;
-    if (stat(path->c_str(), &st) == 0 && !S_ISREG(st.st_mode) && !S_ISDIR(st.st_mode)) {
-      if (access(path->c_str(), R_OK) == 0) continue;
+    const bool pipe = stat(path->c_str(), &st) == 0 && !S_ISREG(st.st_mode) && !S_ISDIR(st.st_mode);
+    FILE *f = pipe ? nullptr : fopen(path->c_str(), "rb");
+    if (f) fclose(f);
+    if (pipe ? access(path->c_str(), R_OK) != 0 : !f) {
       std::cerr << "shark: cannot open the sample " << *path << std::endl;
-      return EXIT_FAILURE;
+      return false;
     }
-    FILE *f = fopen(path->c_str(), "rb");
-    if (!f) {
-      std::cerr << "shark: cannot open the sample " << *path << std::endl;
-      return EXIT_FAILURE;
-    }
-    fclose(f);
   }
+  return true;
+}
 
-  // ---- contexts: one per GPU, index replicated by deterministic rebuild.  Creating the first context initialises the HIP runtime
-  // (a few hundred milliseconds); that happens on a thread of its own while this one reads the reference and the readers
-  // (which need no GPU) already parse the sample -------
-  const int n_gpus = opt.gpus;
-  std::vector<shk_ctx *> ctxs((size_t)n_gpus, nullptr);
-  int ctx_rc = SHK_OK, ctx_bad = -1;
-  std::mutex ctx_m;
-  std::condition_variable ctx_cv;
-  bool ctx_done = false, ctx_created = false;
-  BatchPool &pool = *new BatchPool;   // (never destroyed: the process leaves through _exit)
-  // what the ring of page-locked batches has to hold; known once the sample is partitioned (this thread), used by the context
-  // thread, which builds the ring as soon as the HIP runtime is up
-  struct RingPlan { bool known = false; size_t limit = 0, bytes = 0, reads = 0; bool paired = false, with_qual = false; } ring_plan;
+// set once by one thread, waited for by others
+class Flag {
+ public:
+  void set() { std::lock_guard<std::mutex> l(m_); on_ = true; cv_.notify_all(); }
+  void wait() { std::unique_lock<std::mutex> l(m_); cv_.wait(l, [&] { return on_; }); }
+ private:
+  std::mutex m_;
+  std::condition_variable cv_;
+  bool on_ = false;
+};
+
+struct RingPlan { size_t limit = 0, bytes = 0, reads = 0; bool paired = false, with_qual = false; };   // what the ring of batches has to hold; known once the sample is partitioned
+
+// ---- contexts: one per GPU, index replicated by deterministic rebuild.  Creating the first context initialises the HIP runtime
+// (a few hundred milliseconds); that happens on a thread of its own while the main thread reads the reference and the readers
+// (which need no GPU) already parse the sample.  Every return of main() waits for that thread (the destructor). -------
+class GpuStart {
+ public:
+  std::vector<shk_ctx *> ctxs;
+  int rc = SHK_OK, bad = -1;     // (valid once `created` is set) the first worker whose context could not be created
+  Flag created;                  // every shk_create has returned
+  Flag ring_ready;               // the ring of batches exists: the readers may acquire batches
+  GpuStart(const Options &opt, BatchPool &pool) : ctxs((size_t)opt.gpus, nullptr), opt_(opt), pool_(pool), th_([this] { run(); }) {}
+  ~GpuStart() { join(); }
+  void join() { if (th_.joinable()) th_.join(); }
   // The ring lives in ordinary memory by default: its buffers are handed round, so the runtime's registration of them is paid once
   // per buffer (measured: the same rate as page-locked buffers at what the readers deliver), it exists before the HIP runtime does --
-  // the readers fill it while the runtime initialises -- and it costs nothing to set up.  SHARK_PINNED=1: page-locked.
-  const bool pin_ring = getenv("SHARK_PINNED") && getenv("SHARK_PINNED")[0] == '1';
-  std::thread ctx_thread([&] {
+  // the readers fill it while the runtime initialises -- and it costs nothing to set up: the caller's thread builds it.
+  // SHARK_PINNED=1: page-locked memory, which only exists once the HIP runtime is up: the context thread builds it.
+  void make_ring(const RingPlan &plan) { plan_ = plan; if (pin_ring_) ring_planned_.set(); else build_ring(); }
+ private:
+  void run()
+  {
     // N workers start like N workers (main.cpp:219-223 starts the reference's N threads at once): every context is created on a
     // thread of its own -- the runtime comes up once, whoever gets there first; streams, the filter's allocation and its clearing,
     // the slots' buffers then proceed side by side (serially, two contexts took 2.3 x one context's time, eight would have taken
     // longer than a 16 M-pair sample on one GPU)
+    const int n_gpus = opt_.gpus;
     std::vector<int> rcs((size_t)n_gpus, SHK_OK);
     auto create = [&](const int g) {
       shk_params p{};
-      p.k = opt.k; p.c = opt.c; p.bf_bits = opt.bf_size; p.min_quality = opt.min_quality; p.single = opt.single;
-      p.device = opt.devices[(size_t)g];   // worker g's device (--devices)
+      p.k = opt_.k; p.c = opt_.c; p.bf_bits = opt_.bf_size; p.min_quality = opt_.min_quality; p.single = opt_.single;
+      p.device = opt_.devices[(size_t)g];   // worker g's device (--devices)
       rcs[(size_t)g] = shk_create(&p, &ctxs[(size_t)g]);
     };
     {
@@ -1276,82 +1271,41 @@ int main(int argc, char *argv[])
       for (auto &t : th) t.join();
     }
     for (int g = n_gpus - 1; g >= 0; --g)
-      if (rcs[(size_t)g] != SHK_OK) { ctx_rc = rcs[(size_t)g]; ctx_bad = g; }
+      if (rcs[(size_t)g] != SHK_OK) { rc = rcs[(size_t)g]; bad = g; }
     timeline("contexts created");
-    std::unique_lock<std::mutex> l(ctx_m);
-    ctx_created = true;
-    ctx_cv.notify_all();
-    if (pin_ring) {
-      // SHARK_PINNED=1: the ring in page-locked memory, which only exists once the HIP runtime is up
-      ctx_cv.wait(l, [&] { return ring_plan.known; });
-      const RingPlan plan = ring_plan;
-      l.unlock();
-      if (ctx_rc == SHK_OK) g_pin_batches = true;
-      pool.make_ring(plan.limit, plan.bytes, plan.reads, plan.paired, plan.with_qual);
-      timeline("batch ring ready");
-      l.lock();
-      ctx_done = true;
-      ctx_cv.notify_all();
-    }
-  });
-  struct CtxJoin {   // (every early return below has to wait for that thread)
-    std::thread &t;
-    ~CtxJoin() { if (t.joinable()) t.join(); }
-  } ctx_join{ctx_thread};
-  std::vector<std::string> legend_ID;   // gene names in file order (FastaSplitter.hpp:48); filled below, read by the output stage
-  // ---- 3. sample ---------------------------------------------------------------
-  // Three roles, as in main.cpp:66-77 (split / analyze / output), decoupled by queues:
-  //   readers   plain four-line FASTQ: a parallel newline count gives the byte range of every batch of each mate file
-  //             (fastq_partition.hpp), and `readers` threads parse whole batches independently into pinned
-  //             structure-of-arrays batches -- the feed scales with host cores instead of one splitter mutex
-  //             (FastqSplitter.hpp:48).  gzip'd or irregular input: the serial kseq-rule reader, from the first batch
-  //             that is not strict on.
-  //   analyzers one thread per GPU, batch i -> GPU i mod N, SHK_PIPE_DEPTH batches in flight per GPU
-  //   output    this thread, batches in input order (ReadOutput.hpp:37-50)
+    created.set();
+    if (!pin_ring_) return;
+    ring_planned_.wait();
+    if (rc == SHK_OK) g_pin_batches = true;
+    build_ring();
+  }
+  void build_ring() { pool_.make_ring(plan_.limit, plan_.bytes, plan_.reads, plan_.paired, plan_.with_qual); timeline("batch ring ready"); ring_ready.set(); }
+  const Options &opt_;
+  BatchPool &pool_;
+  const bool pin_ring_ = getenv("SHARK_PINNED") && getenv("SHARK_PINNED")[0] == '1';
+  RingPlan plan_;
+  Flag ring_planned_;            // (SHARK_PINNED=1) plan_ is set
+  std::thread th_;               // (last: it starts in the constructor and uses the members above)
+};
+
+// ---- the feed in use (parallel_feed: plain files; gz_feed: gzip'd files; neither: the serial reader alone) and the partition of the sample ----
+struct FeedPlan {
+  unsigned io_threads, n_readers = 0, n_gz_parsers = 0;
+  bool parallel_feed, gz_feed, fixed_width = false;
+  shk::BatchTable tab1, tab2;
+  uint64_t n_par_records = 0;       // records both mate files certainly have: the pair stream of the strict part
+  uint64_t n_par_batches = 0;
+  uint64_t window = 0;              // a reader runs at most that many batches ahead of the drain; also the ring's size
+  RingPlan ring;
+  std::unique_ptr<GzCutter> cut1, cut2;
+  FeedPlan(const Options &opt, unsigned io_threads_, bool need_qual) : io_threads(io_threads_)
   {
-    // readers / parsers / formatters: sixteen per worker (what one GPU's feed was measured to use), as far as this process has cores
-    // to run them on -- its affinity mask and its cgroup's CPU quota count, not the machine's (a one-GPU share of a host is 16 cores
-    // whatever hardware_concurrency() says: more threads than that only take turns)
-    const unsigned hw = usable_cpus();
-    unsigned io_threads = opt.nThreads > 1 ? (unsigned)opt.nThreads : std::max(1u, std::min(16u * (unsigned)n_gpus, hw));
-    // (the reference opens its outputs unchecked and writes nothing to a file it could not open, main.cpp:99-106: same here)
-    TextPool text_pool;               // (in front of the writers: they hand the last texts back while they close)
-    OffsetWriter w1, w2;
-    // one writer thread per output file: tmpfs takes 8.7 GB/s from ONE thread writing a file and 3.6-4.6 GB/s from 2-12 threads
-    // writing disjoint parts of it (tools/tmpfs_write_bench.cpp); the command with half the sample written out again, 32 M pairs,
-    // the same files: 2.74 / 2.80 s with one helper per file, 2.93-3.38 s with three, 3.65 s with two
-    unsigned write_helpers = 1;
-    if (const char *e = getenv("SHARK_WRITE_HELPERS")) write_helpers = (unsigned)std::max(1, atoi(e));
-    w1.open(opt.out1_path, write_helpers);
-    if (opt.paired_flag && opt.out2_path != "") w2.open(opt.out2_path, write_helpers);
-    OffsetWriter *out1 = w1.is_open() ? &w1 : nullptr, *out2 = w2.is_open() ? &w2 : nullptr;
-    ReadOutput ro(out1, out2, legend_ID);
-    setvbuf(stdout, nullptr, _IOFBF, 1 << 22);
-
-    // per-GPU input queues; batch i goes to GPU i mod N
-    std::vector<std::unique_ptr<BoundedQueue<std::unique_ptr<ReadBatch>>>> todo;
-    for (int g = 0; g < n_gpus; ++g) todo.emplace_back(new BoundedQueue<std::unique_ptr<ReadBatch>>(1u << 20));   // (the readers' window bounds what is in flight)
-    std::mutex done_m;
-    std::condition_variable done_cv;
-    std::map<uint64_t, std::unique_ptr<ReadBatch>> done;
-    uint64_t n_batches = 0;          // batches handed to the GPUs so far (guarded by done_m)
-    bool split_finished = false;
-    auto dispatch = [&](std::unique_ptr<ReadBatch> b) {
-      {
-        std::lock_guard<std::mutex> l(done_m);
-        n_batches = std::max(n_batches, b->index + 1);
-      }
-      todo[(size_t)(b->index % (uint64_t)n_gpus)]->push(std::move(b));
-    };
-
-    // ---- the parallel feed -------------------------------------------------------
-    shk::BatchTable tab1, tab2;
     // (the parallel feeds look into the sample files, read them twice and seek in them: regular files only -- a pipe goes to the
     //  serial reader, which opens it once and keeps names and qualities in memory)
     const bool samples_are_files = shk::regular_file(opt.sample1_path) && (!opt.paired_flag || shk::regular_file(opt.sample2_path));
-    bool parallel_feed = samples_are_files && !getenv("SHARK_SERIAL_READER") && !getenv("SHARK_SINGLE_SPLITTER");
-    // compressed samples (gzip magic in both mate files): inflated in parallel, cut and parsed from memory (GzCutter above);
-    // SHARK_GZ_SERIAL_PARSE=1: the serial kseq-rule reader behind the inflaters, as in round 3 (the tests run both)
+    parallel_feed = samples_are_files && !getenv("SHARK_SERIAL_READER") && !getenv("SHARK_SINGLE_SPLITTER");
+    // compressed samples (gzip magic in both mate files); SHARK_GZ_SERIAL_PARSE=1: the serial kseq-rule reader behind the
+    // inflaters instead (A/B timing; no test sets it)
     auto is_gzip = [](const std::string &path) {
       unsigned char h[2] = {0, 0};
       FILE *f = fopen(path.c_str(), "rb");
@@ -1359,537 +1313,583 @@ int main(int argc, char *argv[])
       if (f) fclose(f);
       return gz;
     };
-    const bool gz_feed = parallel_feed && !getenv("SHARK_GZ_SERIAL_PARSE") && is_gzip(opt.sample1_path) && (!opt.paired_flag || is_gzip(opt.sample2_path));
-    if (gz_feed) parallel_feed = false;
-    const unsigned gz_inflaters = std::max(2u, io_threads / (opt.paired_flag ? 2u : 1u));
-    const unsigned n_gz_parsers = gz_feed ? std::max(2u, io_threads / 3u) : 0u;
-    std::unique_ptr<GzCutter> cut1, cut2;
+    gz_feed = parallel_feed && !getenv("SHARK_GZ_SERIAL_PARSE") && is_gzip(opt.sample1_path) && (!opt.paired_flag || is_gzip(opt.sample2_path));
     if (gz_feed) {
+      parallel_feed = false;
+      const unsigned gz_inflaters = std::max(2u, io_threads / (opt.paired_flag ? 2u : 1u));
+      n_gz_parsers = std::max(2u, io_threads / 3u);
       cut1.reset(new GzCutter(opt.sample1_path, gz_inflaters, opt.batch));
       if (opt.paired_flag) cut2.reset(new GzCutter(opt.sample2_path, gz_inflaters, opt.batch));
       cut1->start();
       if (cut2) cut2->start();
     }
-    uint64_t n_par_records = 0;       // records both mate files certainly have: the pair stream of the strict part
-    bool fixed_width = false;
-    if (parallel_feed) {
-      // fixed-width records: batch offsets are arithmetic; otherwise a parallel newline count of both files
-      uint64_t rl1 = 0, rl2 = 0;
-      fixed_width = shk::fixed_record_file(opt.sample1_path, tab1, rl1) && (!opt.paired_flag || shk::fixed_record_file(opt.sample2_path, tab2, rl2));
-      if (fixed_width) {
-        n_par_records = opt.paired_flag ? std::min(tab1.n_records, tab2.n_records) : tab1.n_records;
-        shk::fixed_record_batches(tab1, rl1, opt.batch, n_par_records);
-        if (opt.paired_flag) shk::fixed_record_batches(tab2, rl2, opt.batch, n_par_records);
-      } else {
-        if (tab1.fd >= 0) { ::close(tab1.fd); tab1.fd = -1; }
-        if (tab2.fd >= 0) { ::close(tab2.fd); tab2.fd = -1; }
-        std::vector<uint64_t> cnt1, cnt2;
-        shk::count_file(opt.sample1_path, io_threads, tab1, cnt1);
-        parallel_feed = tab1.ok;
-        if (parallel_feed && opt.paired_flag) {
-          shk::count_file(opt.sample2_path, io_threads, tab2, cnt2);
-          parallel_feed = tab2.ok;
-        }
-        if (parallel_feed) {
-          n_par_records = opt.paired_flag ? std::min(tab1.n_records, tab2.n_records) : tab1.n_records;
-          shk::locate_batches(tab1, cnt1, opt.batch, n_par_records, io_threads);
-          if (opt.paired_flag) shk::locate_batches(tab2, cnt2, opt.batch, n_par_records, io_threads);
-          parallel_feed = tab1.ok && (!opt.paired_flag || tab2.ok);
-          if (!parallel_feed) n_par_records = 0;
-        }
-      }
-    }
+    if (parallel_feed) partition(opt);
     timeline("sample partitioned");
-    const uint64_t n_par_batches = (n_par_records + opt.batch - 1) / opt.batch;
-    std::atomic<uint64_t> next_batch{0};
-    std::atomic<uint64_t> irregular_at{UINT64_MAX};     // first batch a reader found not to be strict four-line FASTQ
-    const unsigned n_readers = parallel_feed ? (unsigned)std::max<uint64_t>(1, std::min<uint64_t>(io_threads, n_par_batches)) : 0;
-    std::vector<double> t_reader(n_readers, 0.0);
-    // a reader must not run ahead of the drain without bound: at most `window` batches beyond the one being written
+    n_par_batches = (n_par_records + opt.batch - 1) / opt.batch;
+    n_readers = parallel_feed ? (unsigned)std::max<uint64_t>(1, std::min<uint64_t>(io_threads, n_par_batches)) : 0;
     // the ring: a batch per reader, what the GPUs hold in flight, and a few being turned into text or waiting for their turn to be written
     // (never more batches than the sample has, plus what the serial reader and the GPU pipelines need: --batch may be large)
-    const uint64_t window = gz_feed ? (uint64_t)n_gz_parsers + (uint64_t)n_gpus * (SHK_PIPE_DEPTH + 2) + 6
-                                    : std::min<uint64_t>((uint64_t)n_readers + (uint64_t)n_gpus * (SHK_PIPE_DEPTH + 2) + 6,
-                                                         n_par_batches + (uint64_t)n_gpus * (SHK_PIPE_DEPTH + 2) + 2);
+    const uint64_t in_flight = (uint64_t)opt.gpus * (SHK_PIPE_DEPTH + 2);
+    window = gz_feed ? n_gz_parsers + in_flight + 6 : std::min<uint64_t>(n_readers + in_flight + 6, n_par_batches + in_flight + 2);
+    uint64_t widest = 0;
+    for (uint64_t i = 0; i < n_par_batches; ++i) {
+      widest = std::max(widest, tab1.off[i + 1] - tab1.off[i]);
+      if (opt.paired_flag) widest = std::max(widest, tab2.off[i + 1] - tab2.off[i]);
+    }
+    ring = RingPlan{(size_t)window, n_par_batches ? (size_t)(widest / 2 + 64) : (gz_feed ? (size_t)opt.batch * 160 : 0),
+                    (n_par_batches || gz_feed) ? (size_t)opt.batch : 0, opt.paired_flag, need_qual};
+  }
+ private:
+  // fixed-width records: batch offsets are arithmetic; otherwise a parallel newline count of both files
+  void partition(const Options &opt)
+  {
+    uint64_t rl1 = 0, rl2 = 0;
+    std::vector<uint64_t> cnt1, cnt2;
+    fixed_width = shk::fixed_record_file(opt.sample1_path, tab1, rl1) && (!opt.paired_flag || shk::fixed_record_file(opt.sample2_path, tab2, rl2));
+    if (!fixed_width) {
+      if (tab1.fd >= 0) { ::close(tab1.fd); tab1.fd = -1; }
+      if (tab2.fd >= 0) { ::close(tab2.fd); tab2.fd = -1; }
+      shk::count_file(opt.sample1_path, io_threads, tab1, cnt1);
+      if (tab1.ok && opt.paired_flag) shk::count_file(opt.sample2_path, io_threads, tab2, cnt2);
+      parallel_feed = tab1.ok && (!opt.paired_flag || tab2.ok);
+      if (!parallel_feed) return;
+    }
+    n_par_records = opt.paired_flag ? std::min(tab1.n_records, tab2.n_records) : tab1.n_records;
+    if (fixed_width) {
+      shk::fixed_record_batches(tab1, rl1, opt.batch, n_par_records);
+      if (opt.paired_flag) shk::fixed_record_batches(tab2, rl2, opt.batch, n_par_records);
+      return;
+    }
+    shk::locate_batches(tab1, cnt1, opt.batch, n_par_records, io_threads);
+    if (opt.paired_flag) shk::locate_batches(tab2, cnt2, opt.batch, n_par_records, io_threads);
+    parallel_feed = tab1.ok && (!opt.paired_flag || tab2.ok);
+    if (!parallel_feed) n_par_records = 0;
+  }
+};
+
+// ---- the order of the batches ---------------------------------------------------------------------------------------------------
+// Batches leave the readers, go round the workers (batch i to worker i mod N) and the formatters in any order, and are written in
+// input order.  Two rules hold them together:
+//  * a reader must not run ahead of the drain without bound: at most `window` batches beyond the one being written;
+//  * batch j may only leave a reader once every batch before it is KNOWN to be strict four-line FASTQ: an irregular batch
+//    i < j that keeps the four-line alignment (an empty read, a sequence/quality length mismatch, a lone CR, a NUL) lets
+//    batch j validate, yet everything from i on belongs to the serial reader -- which numbers its batches from i again
+//    and may cut the records differently.
+class BatchOrder {
+ public:
+  using Queue = BoundedQueue<std::unique_ptr<ReadBatch>>;
+  // (the inputs' capacity is never reached: the readers' window bounds what is in flight)
+  BatchOrder(int n_workers, uint64_t window) : window_(window) { for (int g = 0; g < n_workers; ++g) todo_.emplace_back(new Queue(1u << 20)); }
+  // -- the parallel readers, for the batch i each of them holds --
+  // waits until batch i is inside the window; false: it belongs to the serial reader
+  bool admit(uint64_t i)
+  {
+    if (i >= irregular_at_.load()) return false;
+    std::unique_lock<std::mutex> l(m_);
+    cv_.wait(l, [&] { return i < drained_ + window_ || i >= irregular_at_.load(); });
+    return i < irregular_at_.load();
+  }
+  // batch i is not strict four-line FASTQ: it and everything behind it belongs to the serial reader
+  void mark_irregular(uint64_t i)
+  {
+    uint64_t cur = irregular_at_.load();
+    while (i < cur && !irregular_at_.compare_exchange_weak(cur, i)) {}
+    { std::lock_guard<std::mutex> l(m_); }   // (a waiter that has just found its predicate false is asleep before it is notified)
+    cv_.notify_all();
+  }
+  // batch i is strict: waits until every batch before it is, too; false: one of them was not
+  // (batch indices are handed out in increasing order, so the reader of the smallest outstanding one never waits here)
+  bool commit(uint64_t i)
+  {
     {
-      uint64_t widest = 0;
-      for (uint64_t i = 0; i < n_par_batches; ++i) {
-        widest = std::max(widest, tab1.off[i + 1] - tab1.off[i]);
-        if (opt.paired_flag) widest = std::max(widest, tab2.off[i + 1] - tab2.off[i]);
-      }
-      std::lock_guard<std::mutex> l(ctx_m);
-      ring_plan.known = true;
-      ring_plan.limit = (size_t)window;
-      ring_plan.bytes = n_par_batches ? (size_t)(widest / 2 + 64) : (gz_feed ? (size_t)opt.batch * 160 : 0);
-      ring_plan.reads = (n_par_batches || gz_feed) ? (size_t)opt.batch : 0;
-      ring_plan.paired = opt.paired_flag;
-      ring_plan.with_qual = static_cast<char>(opt.min_quality) != 0;
-      ctx_cv.notify_all();
+      std::unique_lock<std::mutex> l(m_);
+      cv_.wait(l, [&] { return validated_ == i || i >= irregular_at_.load(); });
+      if (i >= irregular_at_.load()) return false;
+      validated_ = i + 1;
     }
-    if (!pin_ring) {
-      pool.make_ring(ring_plan.limit, ring_plan.bytes, ring_plan.reads, ring_plan.paired, ring_plan.with_qual);
-      timeline("batch ring ready");
-      std::lock_guard<std::mutex> l(ctx_m);
-      ctx_done = true;
-      ctx_cv.notify_all();
-    }
-    uint64_t drained = 0;                                // guarded by done_m
-    // Batch j may only leave a reader once every batch before it is KNOWN to be strict four-line FASTQ: an irregular batch
-    // i < j that keeps the four-line alignment (an empty read, a sequence/quality length mismatch, a lone CR, a NUL) lets
-    // batch j validate, yet everything from i on belongs to the serial reader -- which numbers its batches from i again
-    // and may cut the records differently.  `validated` = number of leading batches known to be strict (guarded by done_m).
-    uint64_t validated = 0;
-    const bool need_qual = static_cast<char>(opt.min_quality) != 0;   // the device reads qualities only with -q (the reference's char, argument_parser.hpp:144)
-    shk::RecordLayout lay1, lay2;                                     // the layout of each file's first record: the readers' fast check
-    if (parallel_feed) {
+    cv_.notify_all();
+    return true;
+  }
+  uint64_t first_irregular() const { return irregular_at_.load(); }
+  // -- any reader: a batch on its way to its worker --
+  void dispatch(std::unique_ptr<ReadBatch> b)
+  {
+    { std::lock_guard<std::mutex> l(m_); n_batches_ = std::max(n_batches_, b->index + 1); }
+    todo_[(size_t)(b->index % todo_.size())]->push(std::move(b));
+  }
+  Queue &input(int worker) { return *todo_[(size_t)worker]; }
+  void close_inputs() { for (auto &q : todo_) q->close(); }
+  // no batch will be dispatched any more
+  void feed_closed() { std::lock_guard<std::mutex> l(m_); split_finished_ = true; cv_.notify_all(); }
+  // -- the formatters: a batch that is ready to be written --
+  void finished(std::unique_ptr<ReadBatch> b) { std::lock_guard<std::mutex> l(m_); done_[b->index] = std::move(b); cv_.notify_all(); }
+  // -- the drain: the next batch in input order (nullptr behind the last one), and the step behind it --
+  std::unique_ptr<ReadBatch> next_in_order()
+  {
+    std::unique_lock<std::mutex> l(m_);
+    cv_.wait(l, [&] { return done_.count(drained_) || (split_finished_ && drained_ >= n_batches_); });
+    auto it = done_.find(drained_);
+    if (it == done_.end()) return nullptr;
+    std::unique_ptr<ReadBatch> b = std::move(it->second);
+    done_.erase(it);
+    return b;
+  }
+  void advance() { { std::lock_guard<std::mutex> l(m_); ++drained_; } cv_.notify_all(); }
+ private:
+  std::vector<std::unique_ptr<Queue>> todo_;            // per-worker input queues
+  const uint64_t window_;
+  std::atomic<uint64_t> irregular_at_{UINT64_MAX};      // first batch a reader found not to be strict four-line FASTQ
+  std::mutex m_;                                        // guards everything below
+  std::condition_variable cv_;
+  std::map<uint64_t, std::unique_ptr<ReadBatch>> done_;
+  uint64_t n_batches_ = 0;                              // batches handed to the workers so far
+  uint64_t validated_ = 0;                              // number of leading batches known to be strict
+  uint64_t drained_ = 0;                                // the drain's position: batches written
+  bool split_finished_ = false;
+};
+
+// ---- the parallel feed: readers of plain files; or, compressed samples, a joiner of the two cutters' pieces and parsers ---------
+class ParallelFeed {
+ public:
+  ParallelFeed(const Options &opt, FeedPlan &plan, BatchOrder &order, BatchPool &pool, Flag &ring_ready, bool need_qual)
+      : t_reader(plan.n_readers, 0.0), opt_(opt), plan_(plan), order_(order), pool_(pool), ring_ready_(ring_ready), need_qual_(need_qual)
+  {
+    if (plan.parallel_feed) {
       std::vector<char> head(1u << 16);
       for (int m = 0; m < (opt.paired_flag ? 2 : 1); ++m) {
-        shk::BatchTable &t = m ? tab2 : tab1;
+        shk::BatchTable &t = m ? plan.tab2 : plan.tab1;
         const size_t got = (size_t)std::min<uint64_t>(head.size(), t.file_size);
-        if (got && shk::pread_all(t.fd, head.data(), 0, got)) shk::layout_of(head.data(), got, m ? lay2 : lay1);
+        if (got && shk::pread_all(t.fd, head.data(), 0, got)) shk::layout_of(head.data(), got, m ? lay2_ : lay1_);
       }
     }
-    std::vector<std::thread> readers;
-    for (unsigned r = 0; r < n_readers; ++r) {
-      readers.emplace_back([&, r] {
-        shk::LeanScratch sc;
-        {
-          std::unique_lock<std::mutex> l(ctx_m);   // the ring of batches exists (at once; page-locked: once the HIP runtime is up)
-          ctx_cv.wait(l, [&] { return ctx_done; });
-        }
-        for (;;) {
-          const uint64_t i = next_batch.fetch_add(1);
-          if (i >= n_par_batches || i >= irregular_at.load()) break;
-          {
-            std::unique_lock<std::mutex> l(done_m);
-            done_cv.wait(l, [&] { return i < drained + window || i >= irregular_at.load(); });
-          }
-          if (i >= irregular_at.load()) break;
-          auto t0 = std::chrono::steady_clock::now();
-          const size_t want = (size_t)std::min<uint64_t>(opt.batch, n_par_records - i * opt.batch);
-          std::unique_ptr<ReadBatch> b = pool.acquire();
-          if (!b) break;
-          b->index = i;
-          b->first_read = i * opt.batch;
-          b->lean = true;
-          size_t ok1 = shk::lean_parse_range(tab1.fd, tab1.off[i], tab1.off[i + 1], want, lay1, need_qual, sc, b->seq1.bytes, b->seq1.off, b->qual1.bytes, b->part1);
-          size_t ok2 = want;
-          if (opt.paired_flag && ok1 == want)
-            ok2 = shk::lean_parse_range(tab2.fd, tab2.off[i], tab2.off[i + 1], want, lay2, need_qual, sc, b->seq2.bytes, b->seq2.off, b->qual2.bytes, b->part2);
-          if (ok1 < want || ok2 < want) {
-            // not strict here: this batch and everything behind it belongs to the serial reader
-            pool.release(std::move(b));
-            uint64_t cur = irregular_at.load();
-            while (i < cur && !irregular_at.compare_exchange_weak(cur, i)) {}
-            done_cv.notify_all();
-            break;
-          }
-          t_reader[r] += std::chrono::duration<double>(std::chrono::steady_clock::now() - t0).count();
-          {
-            // (batch indices are handed out in increasing order, so the reader of the smallest outstanding one never waits here)
-            std::unique_lock<std::mutex> l(done_m);
-            done_cv.wait(l, [&] { return validated == i || i >= irregular_at.load(); });
-            if (i >= irregular_at.load()) { l.unlock(); pool.release(std::move(b)); break; }
-            validated = i + 1;
-          }
-          done_cv.notify_all();
-          dispatch(std::move(b));
-        }
-      });
+    for (unsigned r = 0; r < plan.n_readers; ++r) threads_.emplace_back([this, r] { plain_reader(r); });
+    if (plan.gz_feed) {
+      gz_joiner_ = std::thread([this] { join_pieces(); });
+      for (unsigned r = 0; r < plan.n_gz_parsers; ++r) threads_.emplace_back([this] { gz_parser(); });
     }
-
-    // ---- compressed samples: pieces of the two mates joined by index, parsed from memory by n_gz_parsers threads ----
-    struct GzJob { uint64_t index; std::unique_ptr<GzPiece> p1, p2; size_t want; };
-    BoundedQueue<std::unique_ptr<GzJob>> gz_jobs(2);
-    std::atomic<uint64_t> gz_batches{0};          // batches the joiner handed out
-    std::thread gz_joiner;
-    if (gz_feed) {
-      gz_joiner = std::thread([&] {
-        for (uint64_t i = 0;; ++i) {
-          std::unique_ptr<GzPiece> a = cut1->next(), b2;
-          if (cut2) b2 = cut2->next();
-          if (!a || (cut2 && !b2)) break;
-          // the pair stream ends with the shorter mate file (FastqSplitter.hpp:60)
-          const size_t want = cut2 ? std::min(a->records, b2->records) : a->records;
-          const bool ends = a->last || (b2 && b2->last) || want < opt.batch;
-          if (want) {
-            std::unique_ptr<GzJob> j(new GzJob{i, std::move(a), std::move(b2), want});
-            gz_batches = i + 1;
-            gz_jobs.push(std::move(j));
-          }
-          if (ends || i >= irregular_at.load()) break;
-        }
-        gz_jobs.close();
-        // (whatever the cutters still hold is not part of the pair stream -- or belongs to the serial reader)
-        cut1->stop();
-        if (cut2) cut2->stop();
-      });
-      for (unsigned r = 0; r < n_gz_parsers; ++r) {
-        readers.emplace_back([&] {
-          {
-            std::unique_lock<std::mutex> l(ctx_m);
-            ctx_cv.wait(l, [&] { return ctx_done; });
-          }
-          shk::RecordLayout gl1, gl2;
-          std::unique_ptr<GzJob> j;
-          while (gz_jobs.pop(j)) {
-            const uint64_t i = j->index;
-            if (i >= irregular_at.load()) continue;
-            {
-              std::unique_lock<std::mutex> l(done_m);
-              done_cv.wait(l, [&] { return i < drained + window || i >= irregular_at.load(); });
-            }
-            if (i >= irregular_at.load()) continue;
-            std::unique_ptr<ReadBatch> b = pool.acquire();
-            if (!b) break;
-            b->index = i;
-            b->first_read = i * opt.batch;
-            b->lean = true;
-            // the text moves into the batch (its old buffer goes back to the cutter); a piece with more records than the pair
-            // stream takes is cut behind the want-th record
-            auto take = [&](GzPiece &p, std::vector<char, default_init_allocator<char>> &text, shk::RecordLayout &lay) -> size_t {
-              text.swap(p.text);
-              size_t len = text.size();
-              if (p.records > j->want) {
-                uint64_t found = 0;
-                len = newlines_until(text.data(), text.size(), 4 * (uint64_t)j->want, found);
-              }
-              if (!lay.usable()) shk::layout_of(text.data(), len, lay);
-              return len;
-            };
-            const size_t len1 = take(*j->p1, b->text1, gl1);
-            size_t ok1 = shk::lean_parse_mem(b->text1.data(), len1, j->want, gl1, need_qual, b->seq1.bytes, b->seq1.off, b->qual1.bytes, b->part1);
-            size_t ok2 = j->want;
-            if (j->p2 && ok1 == j->want) {
-              const size_t len2 = take(*j->p2, b->text2, gl2);
-              ok2 = shk::lean_parse_mem(b->text2.data(), len2, j->want, gl2, need_qual, b->seq2.bytes, b->seq2.off, b->qual2.bytes, b->part2);
-            }
-            cut1->recycle(std::move(j->p1));
-            if (j->p2) cut2->recycle(std::move(j->p2));
-            if (ok1 < j->want || ok2 < j->want) {
-              // not strict four-line FASTQ here: this batch and everything behind it belongs to the serial reader
-              pool.release(std::move(b));
-              uint64_t cur = irregular_at.load();
-              while (i < cur && !irregular_at.compare_exchange_weak(cur, i)) {}
-              done_cv.notify_all();
-              continue;
-            }
-            {
-              std::unique_lock<std::mutex> l(done_m);
-              done_cv.wait(l, [&] { return validated == i || i >= irregular_at.load(); });
-              if (i >= irregular_at.load()) { l.unlock(); pool.release(std::move(b)); continue; }
-              validated = i + 1;
-            }
-            done_cv.notify_all();
-            dispatch(std::move(b));
-          }
-        });
-      }
-    }
-
-    // ---- 1+2. reference: legend in file order (FastaSplitter.hpp:48) + index -- while the readers above already parse the sample ----
-    auto stop_feed = [&] {
-      // a failure before the analyzers exist: end the readers (they stop at an irregular batch 0) and take their batches back
-      uint64_t cur = irregular_at.load();
-      while (0 < cur && !irregular_at.compare_exchange_weak(cur, 0)) {}
-      for (auto &q : todo) q->close();
-      pool.shutdown();
-      done_cv.notify_all();
-      std::thread drain_q([&] {
-        for (auto &q : todo) {
-          std::unique_ptr<ReadBatch> b;
-          while (q->pop(b)) {}
-        }
-      });
-      if (gz_feed) {
-        // (the parsers drop every job once batch 0 counts as irregular; the joiner notices the same and stops the cutters)
-        std::thread drop_jobs([&] { std::unique_ptr<GzJob> j; while (gz_jobs.pop(j)) {} });
-        if (gz_joiner.joinable()) gz_joiner.join();
-        drop_jobs.join();
-      }
-      for (auto &t : readers) t.join();
-      drain_q.join();
-    };
-    {
-      shk::FastxReader fa(opt.fasta_path);
-      if (!fa.ok()) {
-        stop_feed();
-        std::cerr << "shark: cannot open " << opt.fasta_path << std::endl;
-        return EXIT_FAILURE;
-      }
-      {
-        std::unique_lock<std::mutex> l(ctx_m);   // (the contexts; that thread goes on to build the batch ring)
-        ctx_cv.wait(l, [&] { return ctx_created; });
-      }
-      if (ctx_rc != SHK_OK) {
-        stop_feed();
-        std::cerr << "shark: cannot create a context on GPU " << opt.devices[(size_t)ctx_bad] << ": " << shk_strerror(ctx_rc) << std::endl;
-        return EXIT_FAILURE;
-      }
-      shk::FastxRecord rec;
-      while (fa.read(rec) >= 0) {
-        legend_ID.push_back(rec.name.c_str());
-        const size_t len = strnlen(rec.seq.data(), rec.seq.size());  // C-string semantics (main.cpp:164)
-        for (auto *ctx : ctxs) {
-          const int rc = shk_ref_add(ctx, rec.seq.data(), len);
-          if (rc != SHK_OK) {
-            stop_feed();
-            std::cerr << "shark: " << shk_strerror(rc) << std::endl;
-            return EXIT_FAILURE;
-          }
-        }
-      }
-    }
-    pelapsed("Transcript file processed");
-    timeline("reference read");
-    {
-      std::vector<std::thread> th;
-      std::vector<int> rcs((size_t)n_gpus, 0);
-      for (int g = 0; g < n_gpus; ++g) th.emplace_back([&, g] { rcs[(size_t)g] = shk_ref_finalize(ctxs[(size_t)g]); });
-      for (auto &t : th) t.join();
-      for (int g = 0; g < n_gpus; ++g)
-        if (rcs[(size_t)g] != SHK_OK) {
-          stop_feed();
-          std::cerr << "shark: index build failed on GPU " << g << ": " << shk_strerror(rcs[(size_t)g]) << " " << shk_last_error(ctxs[(size_t)g]) << std::endl;
-          return EXIT_FAILURE;
-        }
-    }
-    timeline("index built");
-    pelapsed("First switch performed");
-    {
-      shk_index_info info{};
-      shk_index_info_get(ctxs[0], &info);
-      pelapsed("BF created from transcripts (" + std::to_string(info.nidx) + " genes)");
-    }
-    pelapsed("Second switch performed");
-
-    // ---- the serial feed: everything the parallel readers did not (or could not) deliver ---------
-    std::unique_ptr<BatchSplitter> fs;
-    bool serial_needed = false, serial_failed = false;
-    std::thread splitter([&] {
-      if (gz_feed && gz_joiner.joinable()) gz_joiner.join();
-      for (auto &t : readers) t.join();
-      timeline("parallel readers done");
-      if (gz_feed) {
-        // compressed sample: the parsers delivered batches [0, stop); an irregular record sends the rest through the serial reader,
-        // which reads over the records already delivered (they are strict: the kseq reader's records are the same)
-        const uint64_t stop = std::min<uint64_t>(irregular_at.load(), gz_batches.load());
-        serial_needed = irregular_at.load() != UINT64_MAX;
-        bool serial_ok = true;
-        if (serial_needed) {
-          fs.reset(new BatchSplitter(opt, io_threads, pool));
-          serial_ok = fs->ok();
-          if (serial_ok) {
-            fs->skip_records(stop * opt.batch, stop);
-            for (;;) {
-              auto b = (*fs)();
-              if (!b) break;
-              dispatch(std::move(b));
-            }
-          }
-        }
-        serial_failed = !serial_ok;
-        for (auto &q : todo) q->close();
-        timeline("serial reader done");
-        std::lock_guard<std::mutex> l(done_m);
-        split_finished = true;
-        done_cv.notify_all();
-        return;
-      }
-      const uint64_t stop = std::min<uint64_t>(irregular_at.load(), n_par_batches);   // batches [0, stop) came from the readers
-      // nothing left when the readers delivered every batch and a mate file ends exactly there (the pair stream ends with the
-      // shorter file, FastqSplitter.hpp:60)
-      serial_needed = !parallel_feed || stop < n_par_batches || !(tab1.off[stop] >= tab1.file_size || (opt.paired_flag && tab2.off[stop] >= tab2.file_size));
-      bool serial_ok = true;
-      if (serial_needed) {
-        fs.reset(new BatchSplitter(opt, io_threads, pool));
-        serial_ok = fs->ok();
-      }
-      serial_failed = !serial_ok;
-      if (serial_needed && serial_ok && parallel_feed) {
-        const uint64_t o1 = tab1.off[stop];
-        const uint64_t o2 = opt.paired_flag ? tab2.off[stop] : 0;
-        fs->resume_serial(o1, o2, stop, std::min<uint64_t>(stop * opt.batch, n_par_records));
-      }
-      if (serial_needed && serial_ok) {
-        for (;;) {
-          auto b = (*fs)();
-          if (!b) break;
-          dispatch(std::move(b));
-        }
-      }
-      for (auto &q : todo) q->close();
-      timeline("serial reader done");
-      std::lock_guard<std::mutex> l(done_m);
-      split_finished = true;
-      done_cv.notify_all();
-    });
-
-    std::vector<double> t_gpu((size_t)n_gpus, 0.0);
-    // classified batches are turned into text by `formatters` threads, in any order (ReadOutput::format: names and qualities of
-    // the associated reads are fetched from the sample files there); the drain below writes the text in input order
-    BoundedQueue<std::unique_ptr<ReadBatch>> to_format(1u << 20);
-    auto hand_over = [&](std::unique_ptr<ReadBatch> b) {
-      std::lock_guard<std::mutex> l(done_m);
-      done[b->index] = std::move(b);
-      done_cv.notify_all();
-    };
-    std::vector<std::thread> formatters;
-    // half as many formatters as readers: with half the sample written out again the two writer threads are what the command waits for,
-    // and they get their cores only if the others leave some (-t 12 on a 16-core share, 16 M / 64 M pairs at 0.50 on-target: 0.84-0.85 /
-    // 2.25 s with twelve formatters, 0.75 / 2.09 s with six, 0.81 / 2.07 s with four, 1.12 s with three -- then THEY are the wait)
-    unsigned n_formatters = std::max(2u, (io_threads + 1) / 2);
-    if (const char *e = getenv("SHARK_FORMATTERS")) n_formatters = (unsigned)std::max(1, atoi(e));      // (A/B timing)
-    for (unsigned f = 0; f < n_formatters; ++f) {
-      formatters.emplace_back([&] {
-        std::unique_ptr<ReadBatch> b;
-        while (to_format.pop(b)) {
-          if (b->rc == SHK_OK) {
-            std::shared_ptr<FormattedBatch> text = text_pool.get();
-            ro.format(*b, *text);
-            b->text = text;
-          }
-          hand_over(std::move(b));
-        }
-      });
-    }
-    std::vector<std::thread> analyzers;
-    for (int g = 0; g < n_gpus; ++g) {
-      analyzers.emplace_back([&, g] {
-        ReadAnalyzer ra(ctxs[(size_t)g], need_qual);
-        bool open = true;
-        while (open || ra.in_flight()) {
-          // keep the pipeline full; block for input only when nothing is in flight
-          while (open && ra.in_flight() < SHK_PIPE_DEPTH) {
-            std::unique_ptr<ReadBatch> b;
-            int got;
-            if (ra.in_flight() == 0) got = todo[(size_t)g]->pop(b) ? 1 : -1;
-            else got = todo[(size_t)g]->try_pop(b);
-            if (got < 0) { open = false; break; }
-            if (got == 0) break;
-            auto t0 = std::chrono::steady_clock::now();
-            if (!ra.submit(std::move(b))) to_format.push(ra.take_failed());
-            t_gpu[(size_t)g] += std::chrono::duration<double>(std::chrono::steady_clock::now() - t0).count();
-          }
-          if (ra.in_flight()) {
-            auto t0 = std::chrono::steady_clock::now();
-            std::unique_ptr<ReadBatch> b = ra.wait();
-            t_gpu[(size_t)g] += std::chrono::duration<double>(std::chrono::steady_clock::now() - t0).count();
-            to_format.push(std::move(b));
-          }
-        }
-      });
-    }
-    // ordered drain
-    uint64_t next = 0;
-    int failed = 0;
-    double t_out = 0;
-    for (;;) {
-      std::unique_ptr<ReadBatch> b;
-      {
-        std::unique_lock<std::mutex> l(done_m);
-        done_cv.wait(l, [&] { return done.count(next) || (split_finished && next >= n_batches); });
-        if (!done.count(next)) break;
-        b = std::move(done[next]);
-        done.erase(next);
-      }
-      if (b->rc != SHK_OK) {
-        failed = b->rc;
-      } else {
-        auto t0 = std::chrono::steady_clock::now();
-        ro.emit(b->text);
-        t_out += std::chrono::duration<double>(std::chrono::steady_clock::now() - t0).count();
-      }
-      pool.release(std::move(b));
-      ++next;
-      {
-        std::lock_guard<std::mutex> l(done_m);
-        drained = next;
-      }
-      done_cv.notify_all();
-    }
-    timeline("drain done");
-    splitter.join();
-    for (auto &t : analyzers) t.join();
-    to_format.close();
-    for (auto &t : formatters) t.join();
-    text_pool.retire(std::min(8u, io_threads));
-    fflush(stdout);
-    timeline("pipeline threads joined");
-    if (serial_failed) {
-      std::cerr << "shark: cannot open the sample" << std::endl;
-      return EXIT_FAILURE;
-    }
-    if (ro.failed()) {
-      std::cerr << "shark: cannot read the sample again for the output" << std::endl;
-      return EXIT_FAILURE;
-    }
-    if (shk::parallel_gunzip_out_of_memory().load()) {
-      std::cerr << "shark: out of memory while inflating the sample" << std::endl;
-      return EXIT_FAILURE;
-    }
-    if (opt.verbose) {
-      double tr = 0;
-      for (double x : t_reader) tr += x;
-      std::cerr << "[shark/io] threads " << io_threads << ", parallel readers " << n_readers << (fixed_width ? " fixed-width records (" : " (") << std::min<uint64_t>(irregular_at.load(), n_par_batches)
-                << " batches, " << tr << " thread-seconds), serial reader: " << (fs ? "index " + std::to_string(fs->t_index) + " s (" + fs->stage_report() + "), fill " + std::to_string(fs->t_fill) + " s, serial " + std::to_string(fs->t_serial) + " s" : std::string("not needed"))
-                << "; classify(gpu0) " << t_gpu[0] << " s, output " << t_out << " s" << std::endl;
-      // per GPU: seconds its analyzer thread spent inside shk_classify_submit / _wait (the host-fed multi-GPU leg of bench.py reads this)
-      std::cerr << "[shark/gpu-busy]";
-      for (int g = 0; g < n_gpus; ++g) std::cerr << " " << t_gpu[(size_t)g];
-      std::cerr << std::endl;
-    }
-    bool written = true;
-    if (out1) written = w1.close() && written;
-    if (out2) written = w2.close() && written;
-    text_pool.finish();
-    if (opt.verbose)
-      std::cerr << "[shark/writers] " << w1.bytes_written() << " + " << w2.bytes_written() << " bytes, busy " << w1.busy_seconds() << " + " << w2.busy_seconds() << " s" << std::endl;
-    if (!written) {
-      std::cerr << "shark: cannot write the output FASTQ" << std::endl;
-      return EXIT_FAILURE;
-    }
-    if (failed) {
-      std::cerr << "shark: classification failed: " << shk_strerror(failed) << std::endl;
-      return EXIT_FAILURE;
-    }
-    timeline("output files closed");
   }
+  // every batch the feed can deliver is dispatched
+  void join() { if (gz_joiner_.joinable()) gz_joiner_.join(); for (auto &t : threads_) t.join(); threads_.clear(); }
+  // a failure before the workers take batches: end the readers (they stop at an irregular batch 0) and take their batches back
+  void stop()
+  {
+    order_.mark_irregular(0);
+    order_.close_inputs();
+    pool_.shutdown();
+    // (the parsers drop every job once batch 0 counts as irregular; the joiner notices the same and stops the cutters)
+    std::thread drop_jobs([&] { std::unique_ptr<GzJob> j; while (plan_.gz_feed && gz_jobs_.pop(j)) {} });
+    join();
+    drop_jobs.join();
+    std::unique_ptr<ReadBatch> b;   // (the inputs never fill up: nobody waited for this)
+    for (int g = 0; g < opt_.gpus; ++g) while (order_.input(g).pop(b)) {}
+  }
+  uint64_t gz_batches() const { return gz_batches_.load(); }
+  std::vector<double> t_reader;   // seconds each plain reader spent parsing (verbose report)
+ private:
+  struct GzJob { uint64_t index; std::unique_ptr<GzPiece> p1, p2; size_t want; };
+  enum class Delivery { done, serial, stopped };   // dispatched; the batch belongs to the serial reader; the pool is shut down
+  // The one hand-over of a strict batch i: `parse` fills the batch and says whether all its records are strict.
+  template <typename Parse>
+  Delivery deliver(uint64_t i, Parse &&parse)
+  {
+    if (!order_.admit(i)) return Delivery::serial;
+    std::unique_ptr<ReadBatch> b = pool_.acquire();
+    if (!b) return Delivery::stopped;
+    b->index = i; b->first_read = i * opt_.batch; b->lean = true;
+    if (!parse(*b)) { pool_.release(std::move(b)); order_.mark_irregular(i); return Delivery::serial; }
+    if (!order_.commit(i)) { pool_.release(std::move(b)); return Delivery::serial; }
+    order_.dispatch(std::move(b));
+    return Delivery::done;
+  }
+  void plain_reader(unsigned r)
+  {
+    shk::LeanScratch sc;
+    ring_ready_.wait();   // the ring of batches exists (at once; page-locked: once the HIP runtime is up)
+    const shk::BatchTable &tab1 = plan_.tab1, &tab2 = plan_.tab2;
+    for (;;) {
+      const uint64_t i = next_batch_.fetch_add(1);
+      if (i >= plan_.n_par_batches) break;
+      const size_t want = (size_t)std::min<uint64_t>(opt_.batch, plan_.n_par_records - i * opt_.batch);
+      const Delivery d = deliver(i, [&](ReadBatch &b) {
+        const auto t0 = std::chrono::steady_clock::now();
+        size_t ok1 = shk::lean_parse_range(tab1.fd, tab1.off[i], tab1.off[i + 1], want, lay1_, need_qual_, sc, b.seq1.bytes, b.seq1.off, b.qual1.bytes, b.part1);
+        size_t ok2 = want;
+        if (opt_.paired_flag && ok1 == want)
+          ok2 = shk::lean_parse_range(tab2.fd, tab2.off[i], tab2.off[i + 1], want, lay2_, need_qual_, sc, b.seq2.bytes, b.seq2.off, b.qual2.bytes, b.part2);
+        if (ok1 < want || ok2 < want) return false;
+        t_reader[r] += std::chrono::duration<double>(std::chrono::steady_clock::now() - t0).count();
+        return true;
+      });
+      // a plain reader ENDS at the first batch that is not its to deliver: every index it could claim next lies behind it
+      if (d != Delivery::done) break;
+    }
+  }
+  // compressed samples: the pieces of the two mates, joined by index
+  void join_pieces()
+  {
+    GzCutter *cut1 = plan_.cut1.get(), *cut2 = plan_.cut2.get();
+    for (uint64_t i = 0;; ++i) {
+      std::unique_ptr<GzPiece> a = cut1->next(), b2;
+      if (cut2) b2 = cut2->next();
+      if (!a || (cut2 && !b2)) break;
+      // the pair stream ends with the shorter mate file (FastqSplitter.hpp:60)
+      const size_t want = cut2 ? std::min(a->records, b2->records) : a->records;
+      const bool ends = a->last || (b2 && b2->last) || want < opt_.batch;
+      if (want) {
+        std::unique_ptr<GzJob> j(new GzJob{i, std::move(a), std::move(b2), want});
+        gz_batches_ = i + 1;
+        gz_jobs_.push(std::move(j));
+      }
+      if (ends || i >= order_.first_irregular()) break;
+    }
+    gz_jobs_.close();
+    // (whatever the cutters still hold is not part of the pair stream -- or belongs to the serial reader)
+    cut1->stop();
+    if (cut2) cut2->stop();
+  }
+  void gz_parser()
+  {
+    ring_ready_.wait();
+    shk::RecordLayout gl1, gl2;
+    std::unique_ptr<GzJob> j;
+    while (gz_jobs_.pop(j)) {
+      const Delivery d = deliver(j->index, [&](ReadBatch &b) {
+        // the text moves into the batch (its old buffer goes back to the cutter); a piece with more records than the pair
+        // stream takes is cut behind the want-th record
+        auto take = [&](GzPiece &p, std::vector<char, default_init_allocator<char>> &text, shk::RecordLayout &lay) -> size_t {
+          text.swap(p.text);
+          size_t len = text.size();
+          if (p.records > j->want) {
+            uint64_t found = 0;
+            len = newlines_until(text.data(), text.size(), 4 * (uint64_t)j->want, found);
+          }
+          if (!lay.usable()) shk::layout_of(text.data(), len, lay);
+          return len;
+        };
+        const size_t len1 = take(*j->p1, b.text1, gl1);
+        size_t ok1 = shk::lean_parse_mem(b.text1.data(), len1, j->want, gl1, need_qual_, b.seq1.bytes, b.seq1.off, b.qual1.bytes, b.part1);
+        size_t ok2 = j->want;
+        if (j->p2 && ok1 == j->want) {
+          const size_t len2 = take(*j->p2, b.text2, gl2);
+          ok2 = shk::lean_parse_mem(b.text2.data(), len2, j->want, gl2, need_qual_, b.seq2.bytes, b.seq2.off, b.qual2.bytes, b.part2);
+        }
+        plan_.cut1->recycle(std::move(j->p1));
+        if (j->p2) plan_.cut2->recycle(std::move(j->p2));
+        return ok1 == j->want && ok2 == j->want;
+      });
+      // Unlike a plain reader, a parser GOES ON behind a batch that is not its to deliver, dropping the jobs: the joiner pushes
+      // into a queue of two and must never be left blocked there -- the serial feed and stop() join it before the parsers.  Only a
+      // pool that is shut down (stop(), which empties the queue itself) ends a parser early.
+      if (d == Delivery::stopped) break;
+    }
+  }
+  const Options &opt_;
+  FeedPlan &plan_;
+  BatchOrder &order_;
+  BatchPool &pool_;
+  Flag &ring_ready_;
+  const bool need_qual_;            // the device reads qualities only with -q
+  shk::RecordLayout lay1_, lay2_;   // the layout of each plain file's first record: the readers' fast check
+  std::atomic<uint64_t> next_batch_{0};
+  BoundedQueue<std::unique_ptr<GzJob>> gz_jobs_{2};
+  std::atomic<uint64_t> gz_batches_{0};   // batches the joiner handed out
+  std::vector<std::thread> threads_;      // plain readers or gzip parsers
+  std::thread gz_joiner_;
+};
+
+// ---- 1+2. reference: legend in file order (FastaSplitter.hpp:48) + index -- while the readers already parse the sample.
+// Returns the message of the failure that ended it (empty: none). ----
+std::string build_index(const Options &opt, GpuStart &gpu, std::vector<std::string> &legend_ID)
+{
+  {
+    shk::FastxReader fa(opt.fasta_path);
+    if (!fa.ok()) return "shark: cannot open " + opt.fasta_path;
+    gpu.created.wait();
+    if (gpu.rc != SHK_OK)
+      return "shark: cannot create a context on GPU " + std::to_string(opt.devices[(size_t)gpu.bad]) + ": " + shk_strerror(gpu.rc);
+    shk::FastxRecord rec;
+    while (fa.read(rec) >= 0) {
+      legend_ID.push_back(rec.name.c_str());
+      const size_t len = strnlen(rec.seq.data(), rec.seq.size());  // C-string semantics (main.cpp:164)
+      for (auto *ctx : gpu.ctxs) {
+        const int rc = shk_ref_add(ctx, rec.seq.data(), len);
+        if (rc != SHK_OK) return std::string("shark: ") + shk_strerror(rc);
+      }
+    }
+  }
+  pelapsed("Transcript file processed");
+  timeline("reference read");
+  {
+    const size_t n = gpu.ctxs.size();
+    std::vector<std::thread> th;
+    std::vector<int> rcs(n, 0);
+    for (size_t g = 0; g < n; ++g) th.emplace_back([&, g] { rcs[g] = shk_ref_finalize(gpu.ctxs[g]); });
+    for (auto &t : th) t.join();
+    for (size_t g = 0; g < n; ++g)
+      if (rcs[g] != SHK_OK)
+        return "shark: index build failed on GPU " + std::to_string(g) + ": " + shk_strerror(rcs[g]) + " " + shk_last_error(gpu.ctxs[g]);
+  }
+  timeline("index built");
+  pelapsed("First switch performed");
+  shk_index_info info{};
+  shk_index_info_get(gpu.ctxs[0], &info);
+  pelapsed("BF created from transcripts (" + std::to_string(info.nidx) + " genes)");
+  pelapsed("Second switch performed");
+  return "";
+}
+
+// ---- the serial feed: everything the parallel feed did not (or could not) deliver, through the kseq-rule reader `fs` (created
+// only when there is something left; failed: it could not open the sample) ----
+void serial_feed(const Options &opt, const FeedPlan &plan, ParallelFeed &feed, BatchOrder &order, BatchPool &pool, std::unique_ptr<BatchSplitter> &fs, bool &failed)
+{
+  feed.join();
+  timeline("parallel readers done");
+  const shk::BatchTable &tab1 = plan.tab1, &tab2 = plan.tab2;
+  // the parallel feed delivered batches [0, stop); an irregular record sends the rest through the serial reader
+  const uint64_t irregular = order.first_irregular();
+  const uint64_t stop = std::min<uint64_t>(irregular, plan.gz_feed ? feed.gz_batches() : plan.n_par_batches);
+  // plain files: nothing is left when the readers delivered every batch and a mate file ends exactly there (the pair stream ends
+  // with the shorter file, FastqSplitter.hpp:60); compressed samples: the joiner saw the end of the pair stream
+  const bool needed = plan.gz_feed ? irregular != UINT64_MAX
+                                   : !plan.parallel_feed || stop < plan.n_par_batches ||
+                                         !(tab1.off[stop] >= tab1.file_size || (opt.paired_flag && tab2.off[stop] >= tab2.file_size));
+  if (needed) fs.reset(new BatchSplitter(opt, plan.io_threads, pool));
+  failed = needed && !fs->ok();
+  if (needed && !failed) {
+    // behind what was delivered: compressed samples are read over (the delivered records are strict: the kseq reader's records are
+    // the same), plain files are entered at the batch's offset, a purely serial run starts at the start
+    if (plan.gz_feed) fs->skip_records(stop * opt.batch, stop);
+    else if (plan.parallel_feed) fs->resume_serial(tab1.off[stop], opt.paired_flag ? tab2.off[stop] : 0, stop, std::min<uint64_t>(stop * opt.batch, plan.n_par_records));
+    while (std::unique_ptr<ReadBatch> b = (*fs)()) order.dispatch(std::move(b));
+  }
+  order.close_inputs();
+  timeline("serial reader done");
+  order.feed_closed();
+}
+
+// analyzers: one thread per worker, SHK_PIPE_DEPTH batches in flight each; t_gpu[g]: seconds inside shk_classify_submit / _wait
+std::vector<std::thread> start_analyzers(const std::vector<shk_ctx *> &ctxs, bool need_qual, BatchOrder &order, BatchOrder::Queue &to_format, std::vector<double> &t_gpu)
+{
+  std::vector<std::thread> analyzers;
+  for (int g = 0; g < (int)ctxs.size(); ++g) {
+    analyzers.emplace_back([&, g, need_qual] {
+      ReadAnalyzer ra(ctxs[(size_t)g], need_qual);
+      BatchOrder::Queue &todo = order.input(g);
+      bool open = true;
+      while (open || ra.in_flight()) {
+        // keep the pipeline full; block for input only when nothing is in flight
+        while (open && ra.in_flight() < SHK_PIPE_DEPTH) {
+          std::unique_ptr<ReadBatch> b;
+          int got;
+          if (ra.in_flight() == 0) got = todo.pop(b) ? 1 : -1;
+          else got = todo.try_pop(b);
+          if (got < 0) { open = false; break; }
+          if (got == 0) break;
+          auto t0 = std::chrono::steady_clock::now();
+          if (!ra.submit(std::move(b))) to_format.push(ra.take_failed());
+          t_gpu[(size_t)g] += std::chrono::duration<double>(std::chrono::steady_clock::now() - t0).count();
+        }
+        if (ra.in_flight()) {
+          auto t0 = std::chrono::steady_clock::now();
+          std::unique_ptr<ReadBatch> b = ra.wait();
+          t_gpu[(size_t)g] += std::chrono::duration<double>(std::chrono::steady_clock::now() - t0).count();
+          to_format.push(std::move(b));
+        }
+      }
+    });
+  }
+  return analyzers;
+}
+
+// ---- 3. sample ---------------------------------------------------------------
+// Three roles, as in main.cpp:66-77 (split / analyze / output), decoupled by queues; the host does NOT join or mask the reads: the device does.
+//   readers    the parallel feed (plain four-line FASTQ: whole batches parsed independently into structure-of-arrays batches --
+//              the feed scales with host cores instead of one splitter mutex, FastqSplitter.hpp:48; gzip: cut and parsed from
+//              memory) and, from the first batch that is not strict on or for anything else, the serial kseq-rule reader
+//   analyzers  one thread per GPU, batch i -> GPU i mod N, SHK_PIPE_DEPTH batches in flight per GPU (ReadAnalyzer role)
+//   formatters classified batches -> text, in any order
+//   output     this thread, batches in input order (ReadOutput.hpp:37-50)
+// The reference is read and the index built in between, while the readers already parse.  Returns main()'s exit code.
+int run_sample(const Options &opt, GpuStart &gpu, BatchPool &pool, std::vector<std::string> &legend_ID)
+{
+  // readers / parsers / formatters: sixteen per worker (what one GPU's feed was measured to use), as far as this process has cores
+  // to run them on -- its affinity mask and its cgroup's CPU quota count, not the machine's (a one-GPU share of a host is 16 cores
+  // whatever hardware_concurrency() says: more threads than that only take turns)
+  const unsigned io_threads = opt.nThreads > 1 ? (unsigned)opt.nThreads : std::max(1u, std::min(16u * (unsigned)opt.gpus, usable_cpus()));
+  const bool need_qual = static_cast<char>(opt.min_quality) != 0;   // the device reads qualities only with -q (the reference's char, argument_parser.hpp:144)
+  // (the reference opens its outputs unchecked and writes nothing to a file it could not open, main.cpp:99-106: same here)
+  TextPool text_pool;               // (in front of the writers: they hand the last texts back while they close)
+  OffsetWriter w1, w2;
+  // one writer thread per output file: tmpfs takes 8.7 GB/s from ONE thread writing a file and 3.6-4.6 GB/s from 2-12 threads
+  // writing disjoint parts of it (tools/tmpfs_write_bench.cpp); the command with half the sample written out again, 32 M pairs,
+  // the same files: 2.74 / 2.80 s with one helper per file, 2.93-3.38 s with three, 3.65 s with two
+  unsigned write_helpers = 1;
+  if (const char *e = getenv("SHARK_WRITE_HELPERS")) write_helpers = (unsigned)std::max(1, atoi(e));
+  w1.open(opt.out1_path, write_helpers);
+  if (opt.paired_flag && opt.out2_path != "") w2.open(opt.out2_path, write_helpers);
+  OffsetWriter *out1 = w1.is_open() ? &w1 : nullptr, *out2 = w2.is_open() ? &w2 : nullptr;
+  ReadOutput ro(out1, out2, legend_ID);
+  setvbuf(stdout, nullptr, _IOFBF, 1 << 22);
+
+  FeedPlan plan(opt, io_threads, need_qual);
+  BatchOrder order(opt.gpus, plan.window);
+  gpu.make_ring(plan.ring);
+  ParallelFeed feed(opt, plan, order, pool, gpu.ring_ready, need_qual);
+  // (the one early exit while the feed runs: whatever fails in there, the feed is stopped first)
+  const std::string index_error = build_index(opt, gpu, legend_ID);
+  if (!index_error.empty()) {
+    feed.stop();
+    std::cerr << index_error << std::endl;
+    return EXIT_FAILURE;
+  }
+  std::unique_ptr<BatchSplitter> fs;
+  bool serial_failed = false;
+  std::thread splitter([&] { serial_feed(opt, plan, feed, order, pool, fs, serial_failed); });
+  std::vector<double> t_gpu((size_t)opt.gpus, 0.0);
+  // classified batches are turned into text by `n_formatters` threads, in any order (ReadOutput::format: names and qualities of
+  // the associated reads are fetched from the sample files there); the drain below writes the text in input order
+  BatchOrder::Queue to_format(1u << 20);
+  // half as many formatters as readers: with half the sample written out again the two writer threads are what the command waits for,
+  // and they get their cores only if the others leave some (-t 12 on a 16-core share, 16 M / 64 M pairs at 0.50 on-target: 0.84-0.85 /
+  // 2.25 s with twelve formatters, 0.75 / 2.09 s with six, 0.81 / 2.07 s with four, 1.12 s with three -- then THEY are the wait)
+  unsigned n_formatters = std::max(2u, (io_threads + 1) / 2);
+  if (const char *e = getenv("SHARK_FORMATTERS")) n_formatters = (unsigned)std::max(1, atoi(e));      // (A/B timing)
+  std::vector<std::thread> formatters;
+  for (unsigned f = 0; f < n_formatters; ++f) {
+    formatters.emplace_back([&] {
+      std::unique_ptr<ReadBatch> b;
+      while (to_format.pop(b)) {
+        if (b->rc == SHK_OK) {
+          std::shared_ptr<FormattedBatch> text = text_pool.get();
+          ro.format(*b, *text);
+          b->text = text;
+        }
+        order.finished(std::move(b));
+      }
+    });
+  }
+  std::vector<std::thread> analyzers = start_analyzers(gpu.ctxs, need_qual, order, to_format, t_gpu);
+  // ordered drain
+  int failed = 0;
+  double t_out = 0;
+  while (std::unique_ptr<ReadBatch> b = order.next_in_order()) {
+    if (b->rc != SHK_OK) {
+      failed = b->rc;
+    } else {
+      auto t0 = std::chrono::steady_clock::now();
+      ro.emit(b->text);
+      t_out += std::chrono::duration<double>(std::chrono::steady_clock::now() - t0).count();
+    }
+    pool.release(std::move(b));
+    order.advance();
+  }
+  timeline("drain done");
+  splitter.join();
+  for (auto &t : analyzers) t.join();
+  to_format.close();
+  for (auto &t : formatters) t.join();
+  text_pool.retire(std::min(8u, io_threads));
+  fflush(stdout);
+  timeline("pipeline threads joined");
+  const char *error = serial_failed                                  ? "shark: cannot open the sample"
+                      : ro.failed()                                  ? "shark: cannot read the sample again for the output"
+                      : shk::parallel_gunzip_out_of_memory().load() ? "shark: out of memory while inflating the sample"
+                                                                     : nullptr;
+  if (error) {
+    std::cerr << error << std::endl;
+    return EXIT_FAILURE;
+  }
+  if (opt.verbose) {
+    double tr = 0;
+    for (double x : feed.t_reader) tr += x;
+    std::cerr << "[shark/io] threads " << io_threads << ", parallel readers " << plan.n_readers << (plan.fixed_width ? " fixed-width records (" : " (") << std::min<uint64_t>(order.first_irregular(), plan.n_par_batches)
+              << " batches, " << tr << " thread-seconds), serial reader: " << (fs ? "index " + std::to_string(fs->t_index) + " s (" + fs->stage_report() + "), fill " + std::to_string(fs->t_fill) + " s, serial " + std::to_string(fs->t_serial) + " s" : std::string("not needed"))
+              << "; classify(gpu0) " << t_gpu[0] << " s, output " << t_out << " s" << std::endl;
+    // per GPU: seconds its analyzer thread spent inside shk_classify_submit / _wait (the host-fed multi-GPU leg of bench.py reads this)
+    std::cerr << "[shark/gpu-busy]";
+    for (double t : t_gpu) std::cerr << " " << t;
+    std::cerr << std::endl;
+  }
+  bool written = true;
+  if (out1) written = w1.close() && written;
+  if (out2) written = w2.close() && written;
+  text_pool.finish();
+  if (opt.verbose)
+    std::cerr << "[shark/writers] " << w1.bytes_written() << " + " << w2.bytes_written() << " bytes, busy " << w1.busy_seconds() << " + " << w2.busy_seconds() << " s" << std::endl;
+  if (!written) {
+    std::cerr << "shark: cannot write the output FASTQ" << std::endl;
+    return EXIT_FAILURE;
+  }
+  if (failed) {
+    std::cerr << "shark: classification failed: " << shk_strerror(failed) << std::endl;
+    return EXIT_FAILURE;
+  }
+  timeline("output files closed");
+  return EXIT_SUCCESS;
+}
+
+// per-gene assigned-read counts: the one exchange step of the sharded run (RCCL all-reduce over xGMI)
+bool gene_counts(const Options &opt, std::vector<shk_ctx *> &ctxs, const std::vector<std::string> &legend_ID)
+{
+  const int n_gpus = opt.gpus;
+  std::vector<uint64_t> totals(legend_ID.size() ? legend_ID.size() : 1, 0);
+  const uint32_t ng = (uint32_t)std::min<size_t>(legend_ID.size(), 65536);
+  {
+    std::vector<int> distinct(opt.devices);
+    std::sort(distinct.begin(), distinct.end());
+    distinct.erase(std::unique(distinct.begin(), distinct.end()), distinct.end());
+    if (distinct.size() != opt.devices.size())
+      std::cerr << "shark: " << n_gpus << " workers on " << distinct.size() << " device(s): the per-gene counts of workers that share a device are "
+                << "added on it" << (distinct.size() > 1 ? ", RCCL reduces over the distinct devices" : " (no collective)") << std::endl;
+  }
+  const int rc = shk_gene_counts_allreduce(ctxs.data(), n_gpus, totals.data(), ng);
+  if (rc != SHK_OK) {
+    std::cerr << "shark: gene count reduction failed: " << shk_strerror(rc) << " " << shk_last_error(ctxs[0]) << std::endl;
+    return false;
+  }
+  if (opt.gene_counts_path != "") {
+    FILE *gc = fopen(opt.gene_counts_path.c_str(), "w");
+    if (gc) {
+      for (uint32_t g = 0; g < ng; ++g)
+        if (totals[g]) fprintf(gc, "%s %llu\n", legend_ID[g].c_str(), (unsigned long long)totals[g]);
+      fclose(gc);
+    }
+  }
+  if (opt.verbose) {
+    uint64_t sum = 0;
+    for (uint32_t g = 0; g < ng; ++g) sum += totals[g];
+    std::cerr << "[shark/counts] " << sum << " associations over " << n_gpus << " GPU(s)" << std::endl;
+  }
+  return true;
+}
+
+}  // namespace
+
+int main(int argc, char *argv[])
+{
+  Options opt_parsed = parse_arguments(argc, argv);
+  if (!opt_parsed.batch_given) opt_parsed.batch = auto_batch(opt_parsed.sample1_path, opt_parsed.batch);
+  const Options opt = opt_parsed;
+  if (opt.verbose) timeline.on();
+  timeline("arguments parsed");
+  if (opt.verbose) {
+    std::cerr << "shark (MI355X): reference " << opt.fasta_path << ", sample " << opt.sample1_path;
+    if (opt.paired_flag) std::cerr << " + " << opt.sample2_path;
+    std::cerr << "; k=" << opt.k << " c=" << opt.c << " q=" << opt.min_quality << (opt.single ? " single" : "") << " bf=" << (opt.bf_size >> 33)
+              << "GB gpus=" << opt.gpus << " devices=";
+    for (size_t g = 0; g < opt.devices.size(); ++g) std::cerr << (g ? "," : "") << opt.devices[g];
+    std::cerr << "\n" << std::endl;
+  }
+  if (!samples_can_be_opened(opt)) return EXIT_FAILURE;
+
+  BatchPool &pool = *new BatchPool;     // (never destroyed: the process leaves through _exit)
+  GpuStart gpu(opt, pool);              // the contexts come up on a thread of their own from here on
+  std::vector<std::string> legend_ID;   // gene names in file order (FastaSplitter.hpp:48); filled by build_index, read by the output stage
+  if (const int rc = run_sample(opt, gpu, pool, legend_ID)) return rc;
   timeline("outputs closed");
   pelapsed("Sample completed");
 
-  // per-gene assigned-read counts: the one exchange step of the sharded run (RCCL all-reduce over xGMI)
-  if (opt.gene_counts_path != "" || (opt.verbose && n_gpus > 1)) {
-    std::vector<uint64_t> totals(legend_ID.size() ? legend_ID.size() : 1, 0);
-    const uint32_t ng = (uint32_t)std::min<size_t>(legend_ID.size(), 65536);
-    {
-      std::vector<int> distinct(opt.devices);
-      std::sort(distinct.begin(), distinct.end());
-      distinct.erase(std::unique(distinct.begin(), distinct.end()), distinct.end());
-      if (distinct.size() != opt.devices.size())
-        std::cerr << "shark: " << n_gpus << " workers on " << distinct.size() << " device(s): the per-gene counts of workers that share a device are "
-                  << "added on it" << (distinct.size() > 1 ? ", RCCL reduces over the distinct devices" : " (no collective)") << std::endl;
-    }
-    const int rc = shk_gene_counts_allreduce(ctxs.data(), n_gpus, totals.data(), ng);
-    if (rc != SHK_OK) {
-      std::cerr << "shark: gene count reduction failed: " << shk_strerror(rc) << " " << shk_last_error(ctxs[0]) << std::endl;
-      return EXIT_FAILURE;
-    }
-    if (opt.gene_counts_path != "") {
-      FILE *gc = fopen(opt.gene_counts_path.c_str(), "w");
-      if (gc) {
-        for (uint32_t g = 0; g < ng; ++g)
-          if (totals[g]) fprintf(gc, "%s %llu\n", legend_ID[g].c_str(), (unsigned long long)totals[g]);
-        fclose(gc);
-      }
-    }
-    if (opt.verbose) {
-      uint64_t sum = 0;
-      for (uint32_t g = 0; g < ng; ++g) sum += totals[g];
-      std::cerr << "[shark/counts] " << sum << " associations over " << n_gpus << " GPU(s)" << std::endl;
-    }
-  }
-
+  if ((opt.gene_counts_path != "" || (opt.verbose && opt.gpus > 1)) && !gene_counts(opt, gpu.ctxs, legend_ID)) return EXIT_FAILURE;
   if (opt.verbose) {
     // (what the process still holds is what its end has to give back: resident and peak resident memory)
     std::ifstream st("/proc/self/status");
@@ -1898,8 +1898,8 @@ int main(int argc, char *argv[])
       if (line.compare(0, 6, "VmRSS:") == 0 || line.compare(0, 6, "VmHWM:") == 0 || line.compare(0, 8, "RssAnon:") == 0 || line.compare(0, 9, "RssShmem:") == 0)
         std::cerr << "[shark/mem] " << line << std::endl;
   }
-  if (ctx_thread.joinable()) ctx_thread.join();
-  for (auto *ctx : ctxs) shk_destroy(ctx);
+  gpu.join();
+  for (auto *ctx : gpu.ctxs) shk_destroy(ctx);
   timeline("contexts destroyed");
   pelapsed("Association done");
   // everything is written and closed; leaving through _exit skips the teardown of the HIP runtime and of the worker threads'

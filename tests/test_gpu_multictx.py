@@ -207,6 +207,57 @@ def test_irregular_records_hand_over_with_several_workers(oracle, tmp_path, n, d
             assert {ln.split()[0]: int(ln.split()[1]) for ln in got["gc"].splitlines()} == want_counts
 
 
+@pytest.mark.parametrize("n,devs", [(1, "0")] + WORKERS)
+def test_gzip_irregular_records_hand_over_to_the_serial_reader(oracle, tmp_path, n, devs):
+    """(c') the same two files, gzip'd (both mates): the gzip feed's parsers deliver the strict batches in front of the first
+    irregular record, the serial reader reads over exactly those records (BatchSplitter::skip_records) and delivers the rest.
+    Small inflate chunks and 64-read batches put dozens of pieces in front of and behind the hand-over; one and several
+    workers print the oracle CLI's bytes, run after run"""
+    rng = np.random.default_rng(77)
+    genes = synth.make_genes(rng, 4, 600, 1200)
+    fa = tmp_path / "g.fa"
+    _write_fasta(fa, genes)
+
+    def rec(i, g, L, style):
+        st = int(rng.integers(0, len(g) - L))
+        s = bytes(g[st:st + L]).decode()
+        q = "".join(chr(int(x)) for x in rng.integers(35, 74, size=L))
+        if style == "empty":
+            return "@r%d\n\n+\n\n" % i
+        if style == "nul":
+            return "@r%d\n%s\x00%s\n+\n%s\n" % (i, s[:30], s[31:], q)
+        if style == "mismatch":
+            return "@r%d\n%s\n+\n%s\n" % (i, s, q[:-7])
+        return "@r%d\n%s\n+\n%s\n" % (i, s, q)
+
+    env = dict(os.environ, SHARK_GZ_CHUNK="4096")
+    for styles in (["s"] * 700 + ["empty"] + ["s"] * 1500,
+                   ["s"] * 300 + ["empty"] + ["s"] * 400 + ["nul"] + ["s"] * 500 + ["mismatch"] + ["s"] * 900):
+        t1 = "".join(rec(i, genes[i % 4], 100, st) for i, st in enumerate(styles))
+        t2 = "".join(rec(i, genes[i % 4], 100, "s") for i, st in enumerate(styles))
+        f1, f2 = tmp_path / "a.fq.gz", tmp_path / "b.fq.gz"
+        f1.write_bytes(gzip.compress(t1.encode("latin-1"), 1))
+        f2.write_bytes(gzip.compress(t2.encode("latin-1"), 1))
+        args = ["-r", str(fa), "-1", str(f1), "-2", str(f2), "-k", "15"]
+        ossv = tmp_path / "o.ssv"
+        oracle.run_cli(args + ["-o", str(tmp_path / "o1.fq"), "-p", str(tmp_path / "o2.fq")], str(ossv))
+        want = ossv.read_bytes()
+        assert want.count(b"\n") > 500
+        want_counts = {}
+        for line in want.splitlines():
+            g = line.split()[1]
+            want_counts[g] = want_counts.get(g, 0) + 1
+        for rep in range(3):
+            o1, o2, gc = tmp_path / "h.1.fq", tmp_path / "h.2.fq", tmp_path / "h.gc"
+            cmd = args + ["-o", str(o1), "-p", str(o2), "--gene-counts", str(gc), "--batch", "64", "-t", "8", "--gpus", str(n), "--devices", devs]
+            r = _shark(cmd, tmp_path, env=env)
+            assert r.returncode == 0, (cmd, r.stderr.decode()[-2000:])
+            assert r.stdout == want, rep
+            assert o1.read_bytes() == (tmp_path / "o1.fq").read_bytes()
+            assert o2.read_bytes() == (tmp_path / "o2.fq").read_bytes()
+            assert {ln.split()[0]: int(ln.split()[1]) for ln in gc.read_bytes().splitlines()} == want_counts
+
+
 @pytest.mark.parametrize("n,devs", WORKERS)
 def test_gzip_sample_with_several_workers(oracle, tmp_path, n, devs):
     """(d) a gzip sample (parallel inflate, cut and parsed from memory) feeding N workers: the oracle CLI's bytes on a
