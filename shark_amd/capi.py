@@ -206,6 +206,33 @@ class SharkHip:
         self._check(self.L.shk_index_copy_lists(self.h, _ptr(off), _ptr(ids)), "shk_index_copy_lists")
         return off, ids[:info["tot_idx"]]
 
+    # ---- test-only read-back of the derived index arrays (shk_debug_index_array: exported, not in the header, not in EXPORTS) ----
+    DEBUG_ARRAYS = {"rank_w": np.uint32, "ent": np.uint32, "ids": np.uint16, "sum32": np.uint32, "lsum32": np.uint32,
+                    "lbig32": np.uint32, "tab": np.uint64, "atab": np.uint64, "ltab": np.uint32, "ref2": np.uint32,
+                    "refpay": np.uint32, "refext": np.uint32, "refmul": np.uint32}
+    DEBUG_META = ("tab_lg", "sum_shift", "lsum_shift", "lbig_shift", "ltab_mul", "ref_total", "n_set", "tot_idx", "pow2", "wrap",
+                  "ent_len", "ids_len", "bf_bits", "bf_words64", "sum_bits", "ktab_lg")
+
+    def _debug_read(self, name, dtype):
+        fn = self.L.shk_debug_index_array
+        fn.restype = C.c_int
+        fn.argtypes = [C.c_void_p, C.c_char_p, C.c_void_p, C.c_uint64, C.POINTER(C.c_uint64)]
+        need = C.c_uint64()
+        self._check(fn(self.h, name.encode(), None, 0, C.byref(need)), "shk_debug_index_array(%s)" % name)
+        a = np.zeros(need.value // np.dtype(dtype).itemsize, dtype=dtype)
+        if need.value:
+            self._check(fn(self.h, name.encode(), _ptr(a), need.value, C.byref(need)), "shk_debug_index_array(%s)" % name)
+        return a
+
+    def debug_index_array(self, name):
+        """the named device array as allocated, padding included (`ent`: u32 words, two per entry -- start, len | gene0 << 16);
+        empty when this index does not carry it"""
+        return self._debug_read(name, self.DEBUG_ARRAYS[name])
+
+    def debug_index_meta(self):
+        """the scalars that decode the arrays"""
+        return dict(zip(self.DEBUG_META, (int(x) for x in self._debug_read("meta", np.uint64))))
+
     # ---- classification --------------------------------------------------------
     def _host_batch(self, seq1, off1, seq2, off2, qual1, qual2):
         seq1, seq2, qual1, qual2 = _u8(seq1), _u8(seq2), _u8(qual1), _u8(qual2)

@@ -606,6 +606,8 @@ int build_index(Ctx *ctx)
   hipLaunchKernelGGL(list_entry_kernel, dim3(grid_for(n_set + 1, 256)), dim3(256), 0, st, (const uint32_t *)d_csr_off, (const uint16_t *)ix.ids, n_set, tot32, ix.ent);
   BI_HIP(hipGetLastError());
   ix.tot_idx = tot_idx;
+  ix.ent_len = n_set + 1;
+  ix.ids_len = tot_idx + 8;
 
   BI_HIP(hipStreamSynchronize(st));
 
@@ -772,6 +774,7 @@ int build_index(Ctx *ctx)
             AX_HIP(hipStreamSynchronize(st));
             (void)hipFree(ix.ent); (void)hipFree(ix.ids);
             ix.ent = ent_all; ix.ids = ids_all;
+            ix.ent_len = n_set + 1 + total + 1; ix.ids_len = tot_idx + R + 8;
             ent_all = nullptr; ids_all = nullptr;
             hipLaunchKernelGGL(ref_multi_write_kernel, dim3(grid_for(total + 1, 256)), dim3(256), 0, st, ix.refpay, total, ix.ent, n_set, ix.ids, (uint32_t)tot_idx,
                                (const uint32_t *)d_lens);

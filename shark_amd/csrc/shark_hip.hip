@@ -778,6 +778,50 @@ int shk_index_copy_lists(const shk_ctx *cctx, uint32_t *offsets, uint16_t *ids)
   return SHK_OK;
 }
 
+// Test-only read-back of the derived index arrays (shark_internal.hpp, next to DeviceIndex); not declared in shark_hip.h.
+int shk_debug_index_array(const shk_ctx *cctx, const char *name, void *dst, uint64_t dst_bytes, uint64_t *bytes_needed)
+{
+  shk_ctx *ctx = const_cast<shk_ctx *>(cctx);
+  if (!ctx || !name || !bytes_needed) return SHK_ERR_ARG;
+  if (ctx->mode != 2) return SHK_ERR_STATE;
+  const DeviceIndex &ix = ctx->idx;
+  const std::string what(name);
+  const uint64_t slots = ix.tab_lg ? (2ull << ix.tab_lg) : 0;
+  const uint64_t total = ix.ref_total;
+  if (what == "meta") {
+    const uint64_t meta[SHK_DEBUG_META_WORDS] = {ix.tab_lg, ix.sum_shift, ix.lsum_shift, ix.lbig_shift, ix.ltab ? ix.ltab_mul : 0, total, ix.n_set, ix.tot_idx,
+                                                 ix.pow2 ? 1u : 0u, ix.wrap ? 1u : 0u, ix.ent_len, ix.ids_len, ix.bf_bits, ix.bf_words64, ix.sum_bits, ix.ktab_lg};
+    *bytes_needed = sizeof(meta);
+    if (!dst) return SHK_OK;
+    if (dst_bytes < sizeof(meta)) return SHK_ERR_ARG;
+    memcpy(dst, meta, sizeof(meta));
+    return SHK_OK;
+  }
+  const void *src = nullptr;
+  uint64_t bytes = 0;
+  if (what == "rank_w") { src = ix.rank_w; bytes = (ix.bf_words64 + 2) * sizeof(uint32_t); }
+  else if (what == "ent") { src = ix.ent; bytes = ix.ent_len * sizeof(ListEntry); }
+  else if (what == "ids") { src = ix.ids; bytes = ix.ids_len * sizeof(uint16_t); }
+  else if (what == "sum32") { src = ix.sum_shift ? ix.sum32 : nullptr; bytes = ((ix.sum_bits + 31) / 32 + 2) * sizeof(uint32_t); }
+  else if (what == "lsum32") { src = ix.lsum_shift ? ix.lsum32 : nullptr; bytes = (LDS_SUM_BITS / 32 + 2) * sizeof(uint32_t); }
+  else if (what == "lbig32") { src = ix.lbig_shift ? ix.lbig32 : nullptr; bytes = ((1u << 20) / 32 + 2) * sizeof(uint32_t); }
+  else if (what == "tab") { src = slots ? ix.tab : nullptr; bytes = (slots + 2) * sizeof(uint64_t); }
+  else if (what == "atab") { src = slots && total ? ix.atab : nullptr; bytes = (slots + 2) * sizeof(uint64_t); }
+  else if (what == "ltab") { src = ix.ltab; bytes = LTAB_BYTES; }
+  else if (what == "ref2") { src = total ? ix.ref2 : nullptr; bytes = ((total + 15) / 16 + 4) * sizeof(uint32_t); }
+  else if (what == "refpay") { src = total ? ix.refpay : nullptr; bytes = (total + 8) * sizeof(uint32_t); }
+  else if (what == "refext") { src = total ? ix.refext : nullptr; bytes = (total + 8) * sizeof(uint32_t); }
+  else if (what == "refmul") { src = total ? ix.refmul : nullptr; bytes = ((total + 31) / 32 + 2) * sizeof(uint32_t); }
+  else return SHK_ERR_ARG;
+  if (!src) bytes = 0;
+  *bytes_needed = bytes;
+  if (!dst || bytes == 0) return SHK_OK;
+  if (dst_bytes < bytes) return SHK_ERR_ARG;
+  SHK_HIP(ctx, hipSetDevice(ctx->prm.device));
+  SHK_HIP(ctx, hipMemcpy(dst, src, bytes, hipMemcpyDeviceToHost));
+  return SHK_OK;
+}
+
 static int check_batch(const shk_ctx *ctx, const shk_batch *b)
 {
   if (!b) return SHK_ERR_ARG;

@@ -74,7 +74,8 @@ struct DeviceIndex {
   bool tab_with_summary = false;
   uint64_t n_set = 0;
   uint64_t tot_idx = 0;
-  bool wrap = false;         // more than 65 536 genes: lists sorted by 16-bit id WITH duplicates (index_build.hip), WRAP kernels
+  uint64_t ent_len = 0, ids_len = 0;   // entries of `ent` / `ids` as allocated (padding and the per-position copies included)
+  bool wrap = false;        // more than 65 536 genes: lists sorted by 16-bit id WITH duplicates (index_build.hip), WRAP kernels
   // ---- the reference itself, for the anchored extension of the table kernels (classify_uni.hpp) ----
   //   ref2   : all records back to back as 2-bit codes, base p in bits [2 (p & 15), +2) of dword p >> 4 (LSB first, invalid
   //            characters as 0), padded by four dwords
@@ -106,6 +107,14 @@ struct DeviceIndex {
   uint32_t ktab_w = 0;       // w (the minimiser's length)
   uint64_t ktab_keys = 0;    // keys it holds (reference k-mers + false positives of the filter)
 };
+// Test-only read-back of the arrays above (tests/index_audit.py audits them entry by entry):
+//   extern "C" int shk_debug_index_array(const shk_ctx *, const char *name, void *dst, uint64_t dst_bytes, uint64_t *bytes_needed)
+// copies the named device array to the host exactly as allocated, padding included.  Names: rank_w, ent, ids, sum32, lsum32,
+// lbig32, tab, atab, ltab, ref2, refpay, refext, refmul.  dst == NULL only reports the size; the size is 0 when this index does
+// not carry the array.  "meta" gives SHK_DEBUG_META_WORDS uint64_t scalars in this order: tab_lg, sum_shift, lsum_shift,
+// lbig_shift, ltab_mul, ref_total, n_set, tot_idx, pow2, wrap, ent_len, ids_len, bf_bits, bf_words64, sum_bits, ktab_lg.
+// Exported from the library but deliberately not declared in include/shark_hip.h; no classify path uses it.
+constexpr uint32_t SHK_DEBUG_META_WORDS = 16;
 constexpr uint32_t REFEXT_NONE = 0xFFFFFFFFu, REFEXT_CLIP = 254u;   // (an extent never reads 255: no entry looks like REFEXT_NONE)
 constexpr uint32_t REFPAY_NONE = 0xFFFFFFFFu;   // (multi with payload 2^30-1: not a rank, n_set <= 2^30-1 entries have ranks below that)
 
