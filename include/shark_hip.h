@@ -103,7 +103,10 @@ const char *shk_probe_mode(const shk_ctx *ctx);
  * device which of the two launched instantiations did the work).  On a panel-sized index the choice depends on the batch
  * before (shk_probe_mode names the index's chains, this names what ran), so a timing or a profile can say what it measured.
  * New: the reference has no counterpart.  The environment's test switches (SHK_FORCE_GENERIC, SHK_BIG_LDS_ALWAYS) are read
- * once, by shk_create. */
+ * once, by shk_create.  classify_fast_kernel and classify_general_kernel are named here without their last template argument
+ * (evidence mode: "false" in a profile for the ordinary instantiations, which this call leaves out as it always has, "true" for
+ * the evidence ones, which this call spells "evidence"): "classify_fast_kernel<5, 3, false>" here is
+ * "classify_fast_kernel<5, 3, false, false>" in rocprofv3, "classify_fast_kernel<5, 3, false, evidence>" is "<5, 3, false, true>". */
 const char *shk_last_kernel(const shk_ctx *ctx);
 
 /* Parity introspection: copy the device-resident index to host buffers.
@@ -187,6 +190,36 @@ int shk_classify_device(shk_ctx *ctx, const shk_batch *batch, uint32_t max_read_
  *                  returns SHK_ERR_ARG for a batch whose caller vouched wrongly (no results are handed out). */
 int shk_classify_device_submit(shk_ctx *ctx, const shk_batch *batch, uint32_t max_read_len, uint32_t uniform_len1, uint32_t uniform_len2,
                                uint64_t *ticket);
+
+/* ---- evidence: the three numbers a read's decision is made from ------------ */
+/* The reference computes, per read, the best gene's coverage `max`, its k-mer count `maxk` and the number of valid characters
+ * `len` of the joined and masked string, keeps the genes that reach (max, maxk) if max >= c * len (and, with --single, only a
+ * lone one), and throws the three numbers away (ReadAnalyzer.hpp:90-104).  In evidence mode they leave the device with the
+ * associations, one record per read (pair) of the batch:
+ *   cov, nk   the maximum over ALL genes in the reference's order of comparison (coverage first, then k-mer count), whether or
+ *             not it then passes c * len or --single; 0, 0 for a read shorter than k, without a valid k-mer, or without a hit
+ *   len       valid characters of the joined string (the joiner 'N', invalid characters and bases masked by -q do not count)
+ * so a read has associations at confidence c iff nk > 0 and (double)cov >= c * (double)len (without --single): one run at c = 0
+ * answers for every c.  New: the reference has no counterpart beyond the lines named above.
+ *
+ * The mode has a price: the kernels that are fast because they never compute a read's final coverage (the table kernels' bound
+ * cut and early decision, the base-for-base verdict) are not used (how much slower that is: DESIGN.md 6), every k-mer of every read is probed
+ * (shk_last_kernel then names the evidence instantiation: "classify_fast_kernel<5, 3, false, evidence>", "classify_general_kernel<wrap, evidence>").  gene_off, gene_ids, n_assoc
+ * and shk_gene_counts are the same with the mode on and off; with it off nothing changes at all. */
+typedef struct shk_read_evidence { uint32_t cov, nk, len; } shk_read_evidence;
+typedef struct shk_evidence {
+  uint64_t                 n;       /* records = reads of that batch */
+  const shk_read_evidence *reads;
+} shk_evidence;
+/* Switches evidence mode on (enable != 0) or off for the batches submitted AFTERWARDS, through any of the four families
+ * (shk_classify, shk_classify_submit / _wait, shk_classify_device, shk_classify_device_submit).  SHK_ERR_STATE while tickets are
+ * outstanding: the batches in flight of one context are all of one kind. */
+int shk_evidence_enable(shk_ctx *ctx, int enable);
+/* The evidence of the batch whose result was handed out LAST by shk_classify, shk_classify_device or shk_classify_wait: the same
+ * lifetime as that result and the same memory space -- pinned host memory owned by the context for host batches, DEVICE memory
+ * for resident ones.  (shk_count_work hands out none: SHK_ERR_STATE behind it.)  SHK_ERR_STATE if that batch was submitted with the mode off, if its wait returned an error, or if no batch
+ * has been waited for yet. */
+int shk_evidence_last(const shk_ctx *ctx, shk_evidence *out);
 
 /* Per-gene number of assigned reads accumulated over all classify calls (all
  * waited tickets) since the last reset (counts[g] for g in [0, 65536)); the quantity all-reduced

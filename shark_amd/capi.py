@@ -39,6 +39,10 @@ class ShkTiming(C.Structure):
                 ("last_n_long", C.c_uint64), ("last_n_tie", C.c_uint64), ("last_n_assoc", C.c_uint64), ("prepass_ms", C.c_double)]
 
 
+class ShkEvidence(C.Structure):
+    _fields_ = [("n", C.c_uint64), ("reads", C.c_void_p)]
+
+
 class ShkWorkCounters(C.Structure):
     _fields_ = [("n_kmers", C.c_uint64), ("n_hits", C.c_uint64), ("n_list_ids", C.c_uint64), ("n_bases", C.c_uint64)]
 
@@ -53,6 +57,7 @@ EXPORTS = [
     "shk_dist_info", "shk_measure_random_lookups", "shk_last_kernel", "shk_classify_device_submit",
     "shk_measure_valu_mix",
     "shk_measure_valu_mix_clock",
+    "shk_evidence_enable", "shk_evidence_last",
 ]
 SHK_PIPE_DEPTH = 3
 SHK_DIST_ID_BYTES = 128
@@ -112,6 +117,8 @@ def load():
         "shk_measure_random_lookups": (C.c_int, [p, C.c_uint64, C.c_uint64, C.c_int, C.POINTER(C.c_double)]),
         "shk_measure_valu_mix": (C.c_int, [p, C.c_int, C.c_uint32, C.POINTER(C.c_double), C.POINTER(C.c_uint64)]),
         "shk_measure_valu_mix_clock": (C.c_int, [p, C.c_int, C.c_uint32, C.POINTER(C.c_double), C.POINTER(C.c_uint64), C.POINTER(C.c_double)]),
+        "shk_evidence_enable": (C.c_int, [p, C.c_int]),
+        "shk_evidence_last": (C.c_int, [p, C.POINTER(ShkEvidence)]),
     }
     variant = bool(os.environ.get("SHK_LIB_PATH"))
     for name, (res, args) in later.items():
@@ -151,6 +158,7 @@ class SharkHip:
             self.h = C.c_void_p()
             raise SharkHipError("shk_create: %s" % self.L.shk_strerror(rc).decode())
         self.k, self.c, self.bf_bits = k, c, bf_bits
+        self._last_on_host = True     # which memory space the last result handed out lives in (evidence_last)
 
     def _check(self, rc, what):
         if rc != 0:
@@ -254,6 +262,7 @@ class SharkHip:
         b, keep = self._host_batch(seq1, off1, seq2, off2, qual1, qual2)
         r = ShkResult()
         self._check(self.L.shk_classify(self.h, C.byref(b), C.byref(r)), "shk_classify")
+        self._last_on_host = True
         return self._host_result(r)
 
     def submit(self, seq1, off1, seq2=None, off2=None, qual1=None, qual2=None):
@@ -266,6 +275,7 @@ class SharkHip:
     def wait(self, ticket, copy=True):
         r = ShkResult()
         self._check(self.L.shk_classify_wait(self.h, ticket[0], C.byref(r)), "shk_classify_wait")
+        self._last_on_host = True
         return self._host_result(r, copy)
 
     def classify_device(self, n, seq1, off1, seq2=0, off2=0, qual1=0, qual2=0, max_read_len=0):
@@ -273,6 +283,7 @@ class SharkHip:
         b = ShkBatch(n, seq1 or None, off1 or None, seq2 or None, off2 or None, qual1 or None, qual2 or None)
         r = ShkResult()
         self._check(self.L.shk_classify_device(self.h, C.byref(b), max_read_len, C.byref(r)), "shk_classify_device")
+        self._last_on_host = False
         return r
 
     def submit_device(self, n, seq1, off1, seq2=0, off2=0, qual1=0, qual2=0, max_read_len=0, uniform_len1=0, uniform_len2=0):
@@ -285,6 +296,7 @@ class SharkHip:
     def wait_device(self, ticket):
         r = ShkResult()
         self._check(self.L.shk_classify_wait(self.h, ticket, C.byref(r)), "shk_classify_wait")
+        self._last_on_host = False
         return r
 
     def count_work(self, n, seq1, off1, seq2=0, off2=0, qual1=0, qual2=0):
@@ -292,6 +304,25 @@ class SharkHip:
         w = ShkWorkCounters()
         self._check(self.L.shk_count_work(self.h, C.byref(b), C.byref(w)), "shk_count_work")
         return {f: getattr(w, f) for f, _ in ShkWorkCounters._fields_}
+
+    # ---- evidence: per read the best gene's coverage, its k-mer count, the read's valid length --------
+    def evidence_enable(self, on=True):
+        """batches submitted from now on carry evidence (and run the full-probe kernels); refused while tickets are outstanding"""
+        self._check(self.L.shk_evidence_enable(self.h, int(bool(on))), "shk_evidence_enable")
+
+    def evidence_last(self):
+        """evidence of the batch whose result was handed out last: an (n, 3) uint32 array (cov, nk, len) copied from the context's
+        pinned memory for a host batch (classify, wait); for a resident one (classify_device, wait_device) the DEVICE pointer of its
+        n records, 12 bytes each -- read them back with hip_memcpy_dtoh.  Raises (SHK_ERR_STATE) when that batch was submitted
+        with evidence off"""
+        e = ShkEvidence()
+        self._check(self.L.shk_evidence_last(self.h, C.byref(e)), "shk_evidence_last")
+        n = int(e.n)
+        if not self._last_on_host:
+            return e.reads
+        if n == 0:
+            return np.zeros((0, 3), dtype=np.uint32)
+        return np.ctypeslib.as_array(C.cast(e.reads, C.POINTER(C.c_uint32)), shape=(n, 3)).copy()
 
     def gene_counts(self, n=65536):
         a = np.zeros(n, dtype=np.uint64)

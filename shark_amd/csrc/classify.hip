@@ -47,7 +47,12 @@ namespace shk {
 // and 1 to the k-mer count; at the first k-mer itself (handled separately at :56-62, `nk = 1`, last = pos - 1) every
 // repetition adds min(k, 1) = 1 to the coverage and leaves the count at 1.  So with m_j = multiplicity of gene g in the
 // list of hit j:  nk = sum m_j - (m_first - 1),  cov = (union of the k-mer intervals) + (m_first - 1).
-template <int U, int MODE, bool HASQ, bool FAST, bool EMIT, bool WRAP = false>
+//
+// EVID (evidence mode, shk_evidence_enable): the three numbers the decision is made from leave the device as well -- the best
+// gene's coverage and k-mer count (ReadAnalyzer.hpp:90-102: the maximum over all genes, whether or not it then passes c * len or
+// --single) and the read's number of valid characters (:46-49), one shk_read_evidence per read next to count[read]; (0, 0, len)
+// for a read shorter than k, without a valid k-mer or without a hit.  len is then summed for every read, not only behind a hit.
+template <int U, int MODE, bool HASQ, bool FAST, bool EMIT, bool WRAP = false, bool EVID = false>
 __device__ __forceinline__ void process_read(const ClassifyParams &P, const uint64_t read, const int lane, const WaveStore st,
                                              const uint32_t slot_cap, const uint32_t tie_cov, const uint32_t tie_nk,
                                              const uint32_t *lsum, const ReadMeta meta, const bool pre, const Raw8 pre_w, const Raw8 pre_q)
@@ -380,11 +385,12 @@ __device__ __forceinline__ void process_read(const ClassifyParams &P, const uint
   uint32_t best_id[SHK_INLINE_IDS] = {0, 0, 0, 0};
   uint32_t n_emit = 0;
   uint32_t len = 0;
+  if (EVID) len = wave_sum_u32(my_valid);
   const uint32_t first_valid = WRAP ? wave_min_u32(my_first) : 0u;   // the read's first valid k-mer (ReadAnalyzer.hpp:51-62)
   if (any_hit && !SHK_ABL(P, 2u)) {   // ablation 2: skip the vote
     // len = number of valid characters of the joined string (ReadAnalyzer.hpp:46-49);
-    // only needed for the threshold, i.e. when something hit
-    len = wave_sum_u32(my_valid);
+    // only needed for the threshold, i.e. when something hit (evidence mode has it already)
+    if (!EVID) len = wave_sum_u32(my_valid);
     if (!FAST) {
       __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
       __builtin_amdgcn_wave_barrier();
@@ -508,6 +514,7 @@ __device__ __forceinline__ void process_read(const ClassifyParams &P, const uint
     // of `count`, the per-gene counts from gather_inline_kernel (wave-aggregated).
     const ClassifyOut *O = out_ptrs(P);
     O->count[read] = n_out;
+    if (EVID) O->evid[read] = shk_read_evidence{best_cov, best_nk, len};   // (12 bytes, one store)
     if (n_out > 0) {
       uint16_t *o = O->inl + read * SHK_INLINE_IDS;
 #pragma unroll
@@ -536,7 +543,9 @@ struct FastGeom {
   static constexpr uint32_t SUM_WORDS64 = pm_lds(MODE) ? LDS_SUM_BITS / 64 : 0;
 };
 
-template <int U, int MODE, bool HASQ>
+// EVID: the evidence instantiations (process_read's EVID).  Every batch submitted in evidence mode on an index of up to 65 536
+// genes runs there, whatever its lengths: classify_uni_kernel and anchor_verdict_kernel never compute a read's final coverage.
+template <int U, int MODE, bool HASQ, bool EVID = false>
 __global__ __launch_bounds__((FastGeom<MODE, U>::THREADS), (FastGeom<MODE, U>::MIN_WAVES_PER_SIMD)) void classify_fast_kernel(const ClassifyParams P)
 {
   using G = FastGeom<MODE, U>;
@@ -586,7 +595,7 @@ __global__ __launch_bounds__((FastGeom<MODE, U>::THREADS), (FastGeom<MODE, U>::M
     if (have_nxt) fetch_group<HASQ>(P, m_nxt, (uint32_t)lane, w_nxt, q_nxt);
     const uint32_t nn = (have_nxt && n32 - nxt > stride) ? nxt + stride : n32;
     ReadMetaRaw r_nn = fetch_meta_issue(P, nn < n32 ? nn : read);          // clamped index
-    process_read<U, MODE, HASQ, true, false>(P, read, lane, st, S, 0u, 0u, lsum, m_cur, true, w_cur, q_cur);
+    process_read<U, MODE, HASQ, true, false, false, EVID>(P, read, lane, st, S, 0u, 0u, lsum, m_cur, true, w_cur, q_cur);
     if (!have_nxt) break;
     // The prefetched bases landed long ago.  Retire them HERE and hand the compiler plain register
     // values: otherwise it carries "a load may be pending" around the loop and, because the number of
@@ -931,7 +940,8 @@ __global__ __launch_bounds__(1024) void class_scatter_kernel(const ClassifyParam
 // fast kernel's capacity (MAIN) and to write out tie lists longer than
 // SHK_INLINE_IDS (EMIT).  Work items come from a queue.
 // ---------------------------------------------------------------------------
-template <bool POW2, bool HASQ, bool EMIT, bool WRAP>
+// EVID: the evidence instantiations of the non-EMIT pass (whole batches on wrapped indices, the long-read queue)
+template <bool POW2, bool HASQ, bool EMIT, bool WRAP, bool EVID = false>
 __global__ __launch_bounds__(CF_THREADS) void classify_general_kernel(const ClassifyParams P)
 {
   constexpr int U = 4;
@@ -962,7 +972,7 @@ __global__ __launch_bounds__(CF_THREADS) void classify_general_kernel(const Clas
     } else if (P.work) {
       read = P.work[w];
     }
-    process_read<U, POW2 ? PM_BV : PM_BV_MOD, HASQ, false, EMIT, WRAP>(P, read, lane, st, S, tc, tn, nullptr, fetch_meta(P, read), false, Raw8{0u, 0u, 0u, 0u}, Raw8{0u, 0u, 0u, 0u});
+    process_read<U, POW2 ? PM_BV : PM_BV_MOD, HASQ, false, EMIT, WRAP, EVID>(P, read, lane, st, S, tc, tn, nullptr, fetch_meta(P, read), false, Raw8{0u, 0u, 0u, 0u}, Raw8{0u, 0u, 0u, 0u});
   }
 }
 
@@ -1108,6 +1118,17 @@ __global__ __launch_bounds__(256) void publish_results_kernel(const uint32_t *__
   if (tid < CTR_WORDS) h_counters[tid] = tid == CTR_VERDICT ? (uni_flag ? 1u + uni_flag[0] : 0u) : counters[tid];
 }
 
+// ... and a host batch's evidence records (evidence mode), three words per read, the same way
+__global__ __launch_bounds__(256) void publish_evidence_kernel(const uint32_t *__restrict__ evid, uint32_t *__restrict__ h_evid, uint64_t n_words)
+{
+  const uint64_t tid = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x, nth = (uint64_t)gridDim.x * blockDim.x;
+  const uint64_t n4 = n_words / 4;
+  const uint4 *src = reinterpret_cast<const uint4 *>(evid);
+  uint4 *dst = reinterpret_cast<uint4 *>(h_evid);
+  for (uint64_t i = tid; i < n4; i += nth) dst[i] = src[i];
+  for (uint64_t i = n4 * 4 + tid; i < n_words; i += nth) h_evid[i] = evid[i];
+}
+
 // off[i] = i * stride: batches whose reads all have one length need no offsets over PCIe
 __global__ void fill_offsets_kernel(uint64_t *__restrict__ off, uint64_t n_plus_1, uint64_t stride)
 {
@@ -1149,9 +1170,10 @@ const char *probe_mode_name(const Ctx *ctx)
 }
 
 template <int U>
-static void launch_fast_u(const ClassifyParams &p, int mode, bool hasq, unsigned grid, hipStream_t s)
+static void launch_fast_u(const ClassifyParams &p, int mode, bool hasq, bool evidence, unsigned grid, hipStream_t s)
 {
-#define LF(M_, HQ_) hipLaunchKernelGGL((classify_fast_kernel<U, M_, HQ_>), dim3(grid), dim3(FastGeom<M_, U>::THREADS), 0, s, p)
+#define LF(M_, HQ_) do { if (evidence) hipLaunchKernelGGL((classify_fast_kernel<U, M_, HQ_, true>), dim3(grid), dim3(FastGeom<M_, U>::THREADS), 0, s, p); \
+                         else hipLaunchKernelGGL((classify_fast_kernel<U, M_, HQ_>), dim3(grid), dim3(FastGeom<M_, U>::THREADS), 0, s, p); } while (0)
   switch (mode) {
   case PM_BV_MOD: if (hasq) LF(PM_BV_MOD, true); else LF(PM_BV_MOD, false); break;
   case PM_BV: if (hasq) LF(PM_BV, true); else LF(PM_BV, false); break;
@@ -1165,7 +1187,7 @@ static void launch_fast_u(const ClassifyParams &p, int mode, bool hasq, unsigned
 #undef LF
 }
 
-int launch_classify_fast(Ctx *ctx, const ClassifyParams &p, uint32_t max_slots, hipStream_t stream)
+int launch_classify_fast(Ctx *ctx, const ClassifyParams &p, uint32_t max_slots, hipStream_t stream, bool evidence)
 {
   if (p.n == 0) return SHK_OK;
   const bool hasq = p.hasq != 0;
@@ -1177,15 +1199,15 @@ int launch_classify_fast(Ctx *ctx, const ClassifyParams &p, uint32_t max_slots, 
   const uint64_t cap = pm_lds(mode) ? (u <= 5 ? 1024 : 768) : 4096;   // (u = 10 likewise 768: six waves per SIMD at most)   // LDS mode: exactly the resident workgroups
   const uint64_t want = (p.n + wpb - 1) / wpb;
   const unsigned grid = (unsigned)(want < cap ? want : cap);
-  if (u == 2) launch_fast_u<2>(p, mode, hasq, grid, stream);
-  else if (u == 3) launch_fast_u<3>(p, mode, hasq, grid, stream);
-  else if (u == 4) launch_fast_u<4>(p, mode, hasq, grid, stream);
-  else if (u == 5) launch_fast_u<5>(p, mode, hasq, grid, stream);
-  else if (u == 6) launch_fast_u<6>(p, mode, hasq, grid, stream);
-  else if (u == 8) launch_fast_u<8>(p, mode, hasq, grid, stream);
-  else launch_fast_u<10>(p, mode, hasq, grid, stream);
+  if (u == 2) launch_fast_u<2>(p, mode, hasq, evidence, grid, stream);
+  else if (u == 3) launch_fast_u<3>(p, mode, hasq, evidence, grid, stream);
+  else if (u == 4) launch_fast_u<4>(p, mode, hasq, evidence, grid, stream);
+  else if (u == 5) launch_fast_u<5>(p, mode, hasq, evidence, grid, stream);
+  else if (u == 6) launch_fast_u<6>(p, mode, hasq, evidence, grid, stream);
+  else if (u == 8) launch_fast_u<8>(p, mode, hasq, evidence, grid, stream);
+  else launch_fast_u<10>(p, mode, hasq, evidence, grid, stream);
   SHK_HIP(ctx, hipGetLastError());
-  snprintf(ctx->last_kernel, sizeof(ctx->last_kernel), "classify_fast_kernel<%u, %d, %s>", u, mode, hasq ? "true" : "false");
+  snprintf(ctx->last_kernel, sizeof(ctx->last_kernel), "classify_fast_kernel<%u, %d, %s%s>", u, mode, hasq ? "true" : "false", evidence ? ", evidence" : "");
   return SHK_OK;
 }
 
@@ -1380,11 +1402,20 @@ int launch_uniform_check(const ClassifyParams &p, uint32_t slot_cap, uint32_t *f
   return hipGetLastError() == hipSuccess ? SHK_OK : SHK_ERR_HIP;
 }
 
-int launch_classify_general(Ctx *ctx, const ClassifyParams &p, bool emit, unsigned n_waves, hipStream_t stream)
+int launch_classify_general(Ctx *ctx, const ClassifyParams &p, bool emit, unsigned n_waves, hipStream_t stream, bool evidence)
 {
   if (p.n_work == 0 && !p.work_count) return SHK_OK;
   const bool pow2 = ctx->idx.pow2, hasq = p.hasq != 0, wrap = ctx->idx.wrap;
   const unsigned grid = (n_waves + CF_WAVES - 1) / CF_WAVES;
+  if (evidence && !emit) {
+#define LGE(P2_, HQ_) do { if (wrap) hipLaunchKernelGGL((classify_general_kernel<P2_, HQ_, false, true, true>), dim3(grid), dim3(CF_THREADS), 0, stream, p); \
+                           else hipLaunchKernelGGL((classify_general_kernel<P2_, HQ_, false, false, true>), dim3(grid), dim3(CF_THREADS), 0, stream, p); } while (0)
+    if (pow2) { if (hasq) LGE(true, true); else LGE(true, false); }
+    else { if (hasq) LGE(false, true); else LGE(false, false); }
+#undef LGE
+    SHK_HIP(ctx, hipGetLastError());
+    return SHK_OK;
+  }
 #define LG3(P2_, HQ_, EM_) do { if (wrap) hipLaunchKernelGGL((classify_general_kernel<P2_, HQ_, EM_, true>), dim3(grid), dim3(CF_THREADS), 0, stream, p); \
                                 else hipLaunchKernelGGL((classify_general_kernel<P2_, HQ_, EM_, false>), dim3(grid), dim3(CF_THREADS), 0, stream, p); } while (0)
 #define LG(P2_, HQ_, EM_) LG3(P2_, HQ_, EM_)
@@ -1437,6 +1468,15 @@ int launch_publish_results(const uint32_t *counters, uint32_t *h_counters, const
   const uint64_t want = h_gene_off ? (n_off / 4 + 255) / 256 : 1;
   hipLaunchKernelGGL(publish_results_kernel, dim3((unsigned)(want < 1 ? 1 : (want < 512 ? want : 512))), dim3(256), 0, stream, counters, h_counters,
                      gene_off, h_gene_off, n_off, gene_ids, h_gene_ids, h_ids_cap, uni_flag);
+  return hipGetLastError() == hipSuccess ? SHK_OK : SHK_ERR_HIP;
+}
+
+int launch_publish_evidence(const shk_read_evidence *evid, shk_read_evidence *h_evid, uint64_t n, hipStream_t stream)
+{
+  if (n == 0) return SHK_OK;
+  const uint64_t want = (3 * n / 4 + 255) / 256;
+  hipLaunchKernelGGL(publish_evidence_kernel, dim3((unsigned)(want < 1 ? 1 : (want < 512 ? want : 512))), dim3(256), 0, stream,
+                     reinterpret_cast<const uint32_t *>(evid), reinterpret_cast<uint32_t *>(h_evid), 3 * n);
   return hipGetLastError() == hipSuccess ? SHK_OK : SHK_ERR_HIP;
 }
 

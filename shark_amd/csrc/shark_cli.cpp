@@ -69,6 +69,9 @@ const char *USAGE_MESSAGE =
     "                                        named more than once: several workers then share it)\n"
     "          --batch N                     reads per device batch (default:65536, up to 262144 for large plain samples)\n"
     "          --gene-counts FILE            write <gene> <assigned reads> per gene (summed over the GPUs with RCCL)\n"
+    "          --evidence FILE               write <read> <coverage> <kmers> <valid bases> of every read (pair), in input order: the best\n"
+    "                                        gene's figures, which pass iff kmers > 0 and coverage >= c * valid bases (slower: every\n"
+    "                                        k-mer of every read is probed)\n"
     "      -t N also sets the number of host threads that parse FASTQ / format output (default: up to 16)\n";
 
 struct Options {
@@ -86,6 +89,8 @@ struct Options {
   uint64_t batch = 1u << 16;
   bool batch_given = false;     // (--batch; otherwise the sample's size decides: auto_batch below)
   std::string gene_counts_path;
+  std::string evidence_path;
+  FILE *evidence_file = nullptr;   // (--evidence, opened by main() before any work is done)
 };
 
 // The command line is described by one table: option names, whether a value follows, and a handler that
@@ -164,6 +169,7 @@ const OptionRow OPTION_TABLE[] = {
      }},
     {1001, "batch", true, [](Options &o, const char *v) { o.batch = std::max<uint64_t>(1, value_of<uint64_t>(v)); o.batch_given = true; }},
     {1002, "gene-counts", true, [](Options &o, const char *v) { o.gene_counts_path = value_of<std::string>(v); }},
+    {1004, "evidence", true, [](Options &o, const char *v) { o.evidence_path = value_of<std::string>(v); }},
 };
 
 // Reads per device batch when --batch does not say.  A batch costs the device path 0.5-2 ms of launches, copies and bookkeeping
@@ -349,6 +355,7 @@ struct ReadBatch {
   // result
   std::vector<uint32_t> gene_off;
   std::vector<uint16_t> gene_ids;
+  std::vector<shk_read_evidence> evidence;   // (--evidence) one record per read
   int rc = 0;
   void reset()
   {
@@ -356,7 +363,7 @@ struct ReadBatch {
     qual_as_read1.clear(); qual_as_read2.clear();
     lean = false;
     text.reset();
-    gene_off.clear(); gene_ids.clear();
+    gene_off.clear(); gene_ids.clear(); evidence.clear();
     rc = 0;
   }
 };
@@ -801,7 +808,7 @@ class GzCutter {
 // flight: the copies of the next batches overlap the kernels of the current one (shk_classify_submit / _wait).
 class ReadAnalyzer {
  public:
-  ReadAnalyzer(shk_ctx *ctx, bool need_qual) : ctx_(ctx), need_qual_(need_qual) {}
+  ReadAnalyzer(shk_ctx *ctx, bool need_qual, bool evidence) : ctx_(ctx), need_qual_(need_qual), evidence_(evidence) {}
   // false: the batch failed at once (b.rc is set) and is not in flight
   bool submit(std::unique_ptr<ReadBatch> b)
   {
@@ -837,13 +844,18 @@ class ReadAnalyzer {
     if (b->rc == SHK_OK) {
       b->gene_off.assign(out.gene_off, out.gene_off + out.n + 1);
       b->gene_ids.assign(out.gene_ids, out.gene_ids + out.n_assoc);
+      if (evidence_) {
+        shk_evidence ev{};
+        b->rc = shk_evidence_last(ctx_, &ev);
+        if (b->rc == SHK_OK) b->evidence.assign(ev.reads, ev.reads + ev.n);
+      }
     }
     return b;
   }
 
  private:
   shk_ctx *ctx_;
-  bool need_qual_;
+  bool need_qual_, evidence_;
   std::deque<std::pair<uint64_t, std::unique_ptr<ReadBatch>>> flying_;
   std::unique_ptr<ReadBatch> failed_;
 };
@@ -951,12 +963,13 @@ class OffsetWriter {
 // of a batch that starts in the middle of a 50 000-read chunk repeats the previous batch's last read name.
 struct FormattedSegment {
   std::string ssv, fq1, fq2;        // fq: the FASTQ records behind the segment's first one
+  std::string evd;                  // (--evidence) <id> <cov> <nk> <len> of every read of the segment
   std::string head1, head2;         // the first associated read's FASTQ records, printed unless its name equals the carried one
   std::string head_id, last_id;
   bool has_assoc = false, carries = false;
   void reset()
   {
-    ssv.clear(); fq1.clear(); fq2.clear(); head1.clear(); head2.clear(); head_id.clear(); last_id.clear();
+    ssv.clear(); fq1.clear(); fq2.clear(); evd.clear(); head1.clear(); head2.clear(); head_id.clear(); last_id.clear();
     has_assoc = carries = false;
   }
 };
@@ -1006,7 +1019,7 @@ class TextPool {
             st->free.pop_back();
           }
           for (FormattedSegment &sg : q->segs)
-            for (std::string *x : {&sg.ssv, &sg.fq1, &sg.fq2}) drop_pages(*x);
+            for (std::string *x : {&sg.ssv, &sg.fq1, &sg.fq2, &sg.evd}) drop_pages(*x);
           // (the object itself and its small strings are left to the process's end)
         }
       });
@@ -1044,8 +1057,10 @@ class TextPool {
 
 class ReadOutput {
  public:
-  ReadOutput(OffsetWriter *out1, OffsetWriter *out2, const std::vector<std::string> &legend) : out1_(out1), out2_(out2), legend_(legend) {}
+  ReadOutput(OffsetWriter *out1, OffsetWriter *out2, const std::vector<std::string> &legend, FILE *evidence = nullptr)
+      : out1_(out1), out2_(out2), legend_(legend), evidence_(evidence) {}
   bool failed() const { return failed_.load(); }
+  bool evidence_write_failed() const { return failed_write_; }
 
   // thread-safe; nothing is written
   void format(const ReadBatch &b, FormattedBatch &out) const
@@ -1066,7 +1081,7 @@ class ReadOutput {
       if (b.lean) {
         // many associated reads in this segment: its byte range in one read; few: one read per record
         const size_t n_assoc = b.gene_off[last] - b.gene_off[first];
-        if (n_assoc * 10 > last - first) {
+        if (n_assoc * 10 > last - first || evidence_) {     // (--evidence names every read)
           f1.load_dense(b.part1, first, last);
           if (out2_) f2.load_dense(b.part2, first, last);
         } else {
@@ -1074,19 +1089,31 @@ class ReadOutput {
           f2.unload();
         }
       }
+      if (evidence_) sg.evd.reserve((last - first) * 48);
       for (size_t i = first; i < last; ++i) {
-        if (b.gene_off[i] == b.gene_off[i + 1]) continue;
+        const bool assoc = b.gene_off[i] != b.gene_off[i + 1];
+        if (!assoc && !evidence_) continue;
         shk::RecordFetcher::View v1{nullptr, 0, nullptr, 0, nullptr}, v2{nullptr, 0, nullptr, 0, nullptr};
         const char *id;
         size_t id_len;
         if (b.lean) {
-          if (!f1.get(b.part1, i, v1) || (out2_ && !f2.get(b.part2, i, v2))) { failed_ = true; continue; }
+          if (!f1.get(b.part1, i, v1) || (assoc && out2_ && !f2.get(b.part2, i, v2))) { failed_ = true; continue; }
           id = v1.id;
           id_len = v1.id_len;
         } else {
           id = b.id1.at(i);
           id_len = b.id1.len(i);
         }
+        if (evidence_ && b.evidence.size() != n) failed_ = true;      // (a batch without a record per read: an error exit, never a short file)
+        if (evidence_ && i < b.evidence.size()) {
+          // the read's name as the ssv prints it, then the best gene's coverage and k-mer count and the read's valid length
+          char num[48];
+          const shk_read_evidence &e = b.evidence[i];
+          const int w = snprintf(num, sizeof(num), " %u %u %u\n", e.cov, e.nk, e.len);
+          sg.evd.append(id, id_len);
+          sg.evd.append(num, (size_t)w);
+        }
+        if (!assoc) continue;
         for (uint32_t j = b.gene_off[i]; j < b.gene_off[i + 1]; ++j) {
           const std::string &gene = legend_[b.gene_ids[j]];
           sg.ssv.append(id, id_len);
@@ -1132,6 +1159,7 @@ class ReadOutput {
     for (size_t si = 0; si < f.n; ++si) {
       const FormattedSegment &sg = f.segs[si];
       fwrite(sg.ssv.data(), 1, sg.ssv.size(), stdout);
+      if (evidence_ && fwrite(sg.evd.data(), 1, sg.evd.size(), evidence_) != sg.evd.size()) failed_write_ = true;
       // (ReadOutput.hpp:44-48: a read's FASTQ records are printed unless its name equals the one printed just before it)
       const bool head_repeats = sg.carries && sg.has_assoc && sg.head_id == carry_;
       if (out1_) {
@@ -1171,6 +1199,8 @@ class ReadOutput {
   }
   OffsetWriter *out1_, *out2_;
   const std::vector<std::string> &legend_;
+  FILE *evidence_;          // (--evidence) written by emit(), in input order
+  bool failed_write_ = false;
   mutable std::atomic<bool> failed_{false};   // a record could not be read back from its file (I/O error)
   std::string carry_;   // previd at the end of the previous batch (only used when a batch starts mid-chunk)
 };
@@ -1202,7 +1232,7 @@ unsigned usable_cpus()
 // ---- the stages of main(), in the order it runs them ---------------------------------------------------------------------------
 // the reference opens its inputs unchecked (main.cpp:88-106) and then reads nothing from a file that is not there; here a
 // sample that cannot be opened is reported before any work is done
-bool samples_can_be_opened(const Options &opt)
+bool samples_can_be_opened(const Options &opt, bool report = true)
 {
   for (const std::string *path : {&opt.sample1_path, &opt.sample2_path}) {
     if (path->empty()) continue;
@@ -1212,7 +1242,7 @@ bool samples_can_be_opened(const Options &opt)
     FILE *f = pipe ? nullptr : fopen(path->c_str(), "rb");
     if (f) fclose(f);
     if (pipe ? access(path->c_str(), R_OK) != 0 : !f) {
-      std::cerr << "shark: cannot open the sample " << *path << std::endl;
+      if (report) std::cerr << "shark: cannot open the sample " << *path << std::endl;
       return false;
     }
   }
@@ -1668,12 +1698,12 @@ void serial_feed(const Options &opt, const FeedPlan &plan, ParallelFeed &feed, B
 }
 
 // analyzers: one thread per worker, SHK_PIPE_DEPTH batches in flight each; t_gpu[g]: seconds inside shk_classify_submit / _wait
-std::vector<std::thread> start_analyzers(const std::vector<shk_ctx *> &ctxs, bool need_qual, BatchOrder &order, BatchOrder::Queue &to_format, std::vector<double> &t_gpu)
+std::vector<std::thread> start_analyzers(const std::vector<shk_ctx *> &ctxs, bool need_qual, bool evidence, BatchOrder &order, BatchOrder::Queue &to_format, std::vector<double> &t_gpu)
 {
   std::vector<std::thread> analyzers;
   for (int g = 0; g < (int)ctxs.size(); ++g) {
-    analyzers.emplace_back([&, g, need_qual] {
-      ReadAnalyzer ra(ctxs[(size_t)g], need_qual);
+    analyzers.emplace_back([&, g, need_qual, evidence] {
+      ReadAnalyzer ra(ctxs[(size_t)g], need_qual, evidence);
       BatchOrder::Queue &todo = order.input(g);
       bool open = true;
       while (open || ra.in_flight()) {
@@ -1728,7 +1758,7 @@ int run_sample(const Options &opt, GpuStart &gpu, BatchPool &pool, std::vector<s
   w1.open(opt.out1_path, write_helpers);
   if (opt.paired_flag && opt.out2_path != "") w2.open(opt.out2_path, write_helpers);
   OffsetWriter *out1 = w1.is_open() ? &w1 : nullptr, *out2 = w2.is_open() ? &w2 : nullptr;
-  ReadOutput ro(out1, out2, legend_ID);
+  ReadOutput ro(out1, out2, legend_ID, opt.evidence_file);
   setvbuf(stdout, nullptr, _IOFBF, 1 << 22);
 
   FeedPlan plan(opt, io_threads, need_qual);
@@ -1742,6 +1772,14 @@ int run_sample(const Options &opt, GpuStart &gpu, BatchPool &pool, std::vector<s
     std::cerr << index_error << std::endl;
     return EXIT_FAILURE;
   }
+  // (--evidence: every worker's batches carry their reads' evidence from the first one on; the contexts exist, nothing is in flight)
+  if (opt.evidence_file)
+    for (shk_ctx *ctx : gpu.ctxs)
+      if (const int rc = shk_evidence_enable(ctx, 1)) {
+        feed.stop();
+        std::cerr << "shark: evidence mode could not be switched on: " << shk_strerror(rc) << std::endl;
+        return EXIT_FAILURE;
+      }
   std::unique_ptr<BatchSplitter> fs;
   bool serial_failed = false;
   std::thread splitter([&] { serial_feed(opt, plan, feed, order, pool, fs, serial_failed); });
@@ -1768,7 +1806,7 @@ int run_sample(const Options &opt, GpuStart &gpu, BatchPool &pool, std::vector<s
       }
     });
   }
-  std::vector<std::thread> analyzers = start_analyzers(gpu.ctxs, need_qual, order, to_format, t_gpu);
+  std::vector<std::thread> analyzers = start_analyzers(gpu.ctxs, need_qual, opt.evidence_file != nullptr, order, to_format, t_gpu);
   // ordered drain
   int failed = 0;
   double t_out = 0;
@@ -1792,7 +1830,7 @@ int run_sample(const Options &opt, GpuStart &gpu, BatchPool &pool, std::vector<s
   fflush(stdout);
   timeline("pipeline threads joined");
   const char *error = serial_failed                                  ? "shark: cannot open the sample"
-                      : ro.failed()                                  ? "shark: cannot read the sample again for the output"
+                      : ro.failed()                                  ? "shark: cannot read the sample again for the output (or a batch came back without its evidence)"
                       : shk::parallel_gunzip_out_of_memory().load() ? "shark: out of memory while inflating the sample"
                                                                      : nullptr;
   if (error) {
@@ -1811,6 +1849,7 @@ int run_sample(const Options &opt, GpuStart &gpu, BatchPool &pool, std::vector<s
     std::cerr << std::endl;
   }
   bool written = true;
+  const bool evidence_written = !opt.evidence_file || (fclose(opt.evidence_file) == 0 && !ro.evidence_write_failed());
   if (out1) written = w1.close() && written;
   if (out2) written = w2.close() && written;
   text_pool.finish();
@@ -1818,6 +1857,10 @@ int run_sample(const Options &opt, GpuStart &gpu, BatchPool &pool, std::vector<s
     std::cerr << "[shark/writers] " << w1.bytes_written() << " + " << w2.bytes_written() << " bytes, busy " << w1.busy_seconds() << " + " << w2.busy_seconds() << " s" << std::endl;
   if (!written) {
     std::cerr << "shark: cannot write the output FASTQ" << std::endl;
+    return EXIT_FAILURE;
+  }
+  if (!evidence_written) {
+    std::cerr << "shark: cannot write the evidence file " << opt.evidence_path << std::endl;
     return EXIT_FAILURE;
   }
   if (failed) {
@@ -1869,6 +1912,9 @@ int main(int argc, char *argv[])
 {
   Options opt_parsed = parse_arguments(argc, argv);
   if (!opt_parsed.batch_given) opt_parsed.batch = auto_batch(opt_parsed.sample1_path, opt_parsed.batch);
+  // (--evidence: the file is created only once the samples are known to be readable -- a run that fails on its inputs leaves an
+  //  earlier evidence file alone)
+  if (opt_parsed.evidence_path != "" && samples_can_be_opened(opt_parsed, false)) opt_parsed.evidence_file = fopen(opt_parsed.evidence_path.c_str(), "w");
   const Options opt = opt_parsed;
   if (opt.verbose) timeline.on();
   timeline("arguments parsed");
@@ -1881,6 +1927,10 @@ int main(int argc, char *argv[])
     std::cerr << "\n" << std::endl;
   }
   if (!samples_can_be_opened(opt)) return EXIT_FAILURE;
+  if (opt.evidence_path != "" && !opt.evidence_file) {   // (the samples are there: it is the evidence file that could not be opened)
+    std::cerr << "shark: cannot open the evidence file " << opt.evidence_path << std::endl;
+    return EXIT_FAILURE;
+  }
 
   BatchPool &pool = *new BatchPool;     // (never destroyed: the process leaves through _exit)
   GpuStart gpu(opt, pool);              // the contexts come up on a thread of their own from here on

@@ -111,7 +111,8 @@ static void slot_free(Slot &s)
 {
   hipFree(s.d_seq1); hipFree(s.d_seq2); hipFree(s.d_qual1); hipFree(s.d_qual2); hipFree(s.d_off1); hipFree(s.d_off2);
   hipFree(s.d_count); hipFree(s.d_inl); hipFree(s.d_gene_off); hipFree(s.d_gene_ids);
-  hipFree(s.d_long_queue); hipFree(s.d_tie_queue); hipFree(s.d_counters); hipFree(s.d_scan_temp); hipFree(s.d_out); hipFree(s.d_plan); hipFree(s.d_cls_entries); hipFree(s.d_cls_list); hipFree(s.d_cls_share); hipFree(s.d_cls_hist);
+  hipFree(s.d_long_queue); hipFree(s.d_tie_queue); hipFree(s.d_counters); hipFree(s.d_scan_temp); hipFree(s.d_out); hipFree(s.d_plan); hipFree(s.d_cls_entries); hipFree(s.d_cls_list); hipFree(s.d_cls_share); hipFree(s.d_cls_hist); hipFree(s.d_evid);
+  if (s.h_evid) (void)hipHostFree(s.h_evid);
   if (s.h_counters) (void)hipHostFree(s.h_counters);
   if (s.h_gene_off) (void)hipHostFree(s.h_gene_off);
   if (s.h_gene_ids) (void)hipHostFree(s.h_gene_ids);
@@ -134,7 +135,10 @@ static int slot_reserve(Ctx *ctx, Slot &s, uint64_t n)
   if ((rc = ensure_capacity(ctx, &s.d_scan_temp, &s.cap_scan_temp, scan_temp_words(n + 1)))) return rc;
   // associations: two per read to start with; a batch that needs more is finished by the overflow path
   if ((rc = ensure_capacity(ctx, &s.d_gene_ids, &s.cap_gene_ids, 2 * n + 4096))) return rc;
-  ClassifyOut ho;
+  // (evidence mode only: 12 bytes per read that no other batch pays for)
+  if (s.evidence && (rc = ensure_capacity(ctx, &s.d_evid, &s.cap_evid, n + 1))) return rc;
+  ClassifyOut ho{};
+  ho.evid = s.evidence ? s.d_evid : nullptr;
   ho.count = s.d_count; ho.inl = s.d_inl; ho.counters = s.d_counters; ho.long_queue = s.d_long_queue; ho.tie_queue = s.d_tie_queue;
   if (memcmp(&ho, &s.out_shadow, sizeof(ho)) != 0) {
     SHK_HIP(ctx, hipMemcpy(s.d_out, &ho, sizeof(ho), hipMemcpyHostToDevice));
@@ -213,7 +217,7 @@ static int run_long_reads(Ctx *ctx, Slot &s, uint32_t n_long)
   p.work = s.d_long_queue;
   p.n_work = n_long;
   p.work_count = nullptr;
-  return launch_classify_general(ctx, p, false, n_waves, ctx->stream);
+  return launch_classify_general(ctx, p, false, n_waves, ctx->stream, s.evidence);
 }
 
 // Everything behind the classify kernels, WITHOUT a host round trip: per-read counts -> offsets (scan), inline ids ->
@@ -249,6 +253,12 @@ static int enqueue_tail(Ctx *ctx, Slot &s, bool skip_hist_if_long, bool count_ge
   if ((rc = launch_publish_results(s.d_counters, s.h_counters, s.d_gene_off, s.host_batch ? s.h_gene_off : nullptr, n + 1, s.d_gene_ids,
                                    s.h_gene_ids, s.cap_h_gene_ids, s.p.uni_flag, st)))
     return rc;
+  // (evidence mode: the records follow the associations, by kernel stores as well; a redone batch comes through here again, behind the
+  //  general kernel that has written its long reads' records)
+  if (s.evidence && s.host_batch) {
+    if ((rc = ensure_pinned(ctx, &s.h_evid, &s.cap_h_evid, n + 1))) return rc;
+    if ((rc = launch_publish_evidence(s.d_evid, s.h_evid, n, st))) return rc;
+  }
   SHK_HIP(ctx, hipEventRecord(s.ev_done, st));
   return SHK_OK;
 }
@@ -285,6 +295,7 @@ static int enqueue_classify(Ctx *ctx, Slot &s, const shk_batch *b, uint32_t max_
   hipStream_t st = ctx->stream;
   const uint64_t n = b->n;
   int rc;
+  s.evidence = ctx->evidence;
   if ((rc = slot_reserve(ctx, s, n))) return rc;
   s.n = n;
   fill_params(ctx, s, b);
@@ -294,7 +305,9 @@ static int enqueue_classify(Ctx *ctx, Slot &s, const shk_batch *b, uint32_t max_
   s.gen_slots = s.fast_cap;
   // an index with a position table: classify_uni_kernel, uniform or not -- unless the batch is known to hold reads of more
   // than 64 staging groups (> 512 bases per pair), which only classify_fast_kernel stages without the general kernel's help
-  const bool table_kernel = uni_kernel_available(ctx) && n != 0 && groups_fit;
+  // (evidence mode: never -- that kernel and anchor_verdict_kernel decide without a read's final coverage and k-mer count; the batch
+  //  takes the evidence instantiation of classify_fast_kernel, and none of the passes in front of the table kernels is made)
+  const bool table_kernel = uni_kernel_available(ctx) && n != 0 && groups_fit && !s.evidence;
   // a batch of mixed lengths on an index whose uniform batches take the exact table in LDS: sorted by the pairs' two lengths on
   // the device and classified class by class (classify_uni_kernel's CLS instantiation) -- when the classes are few enough for
   // the histogram (the caller's bound on the read length says) and, the device decides, full enough; also when the host knows
@@ -401,12 +414,12 @@ static int enqueue_classify(Ctx *ctx, Slot &s, const shk_batch *b, uint32_t max_
     p.work = nullptr;
     p.n_work = n;
     p.work_count = nullptr;
-    if ((rc = launch_classify_general(ctx, p, false, n_waves, st))) return rc;
-    snprintf(ctx->last_kernel, sizeof(ctx->last_kernel), "classify_general_kernel<wrap>");
+    if ((rc = launch_classify_general(ctx, p, false, n_waves, st, s.evidence))) return rc;
+    snprintf(ctx->last_kernel, sizeof(ctx->last_kernel), s.evidence ? "classify_general_kernel<wrap, evidence>" : "classify_general_kernel<wrap>");
   }
   if (!ctx->idx.wrap) {
     if (!table_kernel) {
-      if ((rc = launch_classify_fast(ctx, s.p, max_slots, st))) return rc;           // bit-vector probe chains
+      if ((rc = launch_classify_fast(ctx, s.p, max_slots, st, s.evidence))) return rc;           // bit-vector probe chains; every index in evidence mode
     } else {
       // what the host knows decides the launch; when only the device knows, both are made and one returns at once
       if (uni_mode != UNI_NO && (rc = launch_classify_uni(ctx, s.p, max_slots, 1, st))) return rc;
@@ -465,6 +478,7 @@ static int classify_resident(Ctx *ctx, const shk_batch *b, uint32_t max_read_len
   hipStream_t st = ctx->stream;
   Slot &s = ctx->slots[PIPE_DEPTH];
   const uint64_t n = b->n;
+  ctx->last_evid_valid = false;   // (until this batch's result is handed out)
   if (n >= 0xFFFFFFFFull) { ctx->last_error = "batch too large (n must be < 2^32-1)"; return SHK_ERR_ARG; }
   const bool paired = b->seq2 != nullptr;
   const uint32_t max_slots = max_read_len ? slots_for_len(max_read_len, ctx->prm.k, paired) : 0;
@@ -512,6 +526,10 @@ static int classify_resident(Ctx *ctx, const shk_batch *b, uint32_t max_read_len
   res->gene_off = s.d_gene_off;
   res->gene_ids = s.d_gene_ids;
   res->n_assoc = n_assoc;
+  // (shk_count_work is a measurement, not one of the calls that hand out evidence: none is left behind it)
+  ctx->last_evid_valid = s.evidence && wc == nullptr;
+  ctx->last_evid = s.d_evid;
+  ctx->last_evid_n = n;
   return SHK_OK;
 }
 
@@ -1001,6 +1019,7 @@ int shk_classify_wait(shk_ctx *ctx, uint64_t ticket, shk_result *result)
   TraceRange tr("shk_classify_wait");
   Slot &s = ctx->slots[(ticket - 1) % PIPE_DEPTH];
   if (s.ticket != ticket || s.waited) { ctx->last_error = "unknown or already waited ticket"; return SHK_ERR_STATE; }
+  ctx->last_evid_valid = false;   // (a batch that is refused below hands out no evidence either, and leaves none of an earlier batch behind)
   SHK_HIP(ctx, hipEventSynchronize(s.ev_done));
   bool redone = false;
   int rc = finish_classify(ctx, s, s.long_speculative, true, &redone);
@@ -1024,6 +1043,30 @@ int shk_classify_wait(shk_ctx *ctx, uint64_t ticket, shk_result *result)
   result->gene_off = s.host_batch ? s.h_gene_off : s.d_gene_off;     // (a device-resident ticket: device pointers)
   result->gene_ids = s.host_batch ? s.h_gene_ids : s.d_gene_ids;
   result->n_assoc = n_assoc;
+  ctx->last_evid_valid = s.evidence;
+  ctx->last_evid = s.host_batch ? s.h_evid : s.d_evid;
+  ctx->last_evid_n = n;
+  return SHK_OK;
+}
+
+int shk_evidence_enable(shk_ctx *ctx, int enable)
+{
+  if (!ctx) return SHK_ERR_ARG;
+  for (int i = 0; i < PIPE_DEPTH; ++i)
+    if (ctx->slots[i].ticket != 0 && !ctx->slots[i].waited) {
+      ctx->last_error = "shk_evidence_enable: tickets are outstanding (wait for them first)";
+      return SHK_ERR_STATE;
+    }
+  ctx->evidence = enable != 0;
+  return SHK_OK;
+}
+
+int shk_evidence_last(const shk_ctx *ctx, shk_evidence *out)
+{
+  if (!ctx || !out) return SHK_ERR_ARG;
+  if (!ctx->last_evid_valid) return SHK_ERR_STATE;
+  out->n = ctx->last_evid_n;
+  out->reads = ctx->last_evid;
   return SHK_OK;
 }
 

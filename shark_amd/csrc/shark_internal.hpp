@@ -133,6 +133,7 @@ struct ClassifyOut {
   uint32_t *counters;        // see CTR_*
   uint32_t *long_queue;      // read indices that did not fit the fast kernel
   uint32_t *tie_queue;       // 3 words per entry: read index, best cov, best nk
+  shk_read_evidence *evid;   // n : {best cov, best nk, valid length} per read -- written by the evidence instantiations only (nullptr otherwise)
 };
 
 // ---- classify kernel parameters (passed by value) --------------------------
@@ -261,6 +262,7 @@ struct Slot {
   uint16_t *d_inl = nullptr;      size_t cap_inl = 0;
   uint32_t *d_gene_off = nullptr; size_t cap_gene_off = 0;
   uint16_t *d_gene_ids = nullptr; size_t cap_gene_ids = 0;
+  shk_read_evidence *d_evid = nullptr; size_t cap_evid = 0;   // evidence mode: one record per read (allocated with the first such batch)
   uint32_t *d_long_queue = nullptr; size_t cap_long_queue = 0;
   uint32_t *d_tie_queue = nullptr;  size_t cap_tie_queue = 0;
   uint32_t *d_counters = nullptr;
@@ -278,6 +280,7 @@ struct Slot {
   uint32_t *h_counters = nullptr;  // CTR_WORDS
   uint32_t *h_gene_off = nullptr;  size_t cap_h_gene_off = 0;
   uint16_t *h_gene_ids = nullptr;  size_t cap_h_gene_ids = 0;
+  shk_read_evidence *h_evid = nullptr; size_t cap_h_evid = 0;   // (host batches in evidence mode; filled by publish_evidence_kernel)
   hipEvent_t ev_h2d = nullptr, ev_done = nullptr, ev_d2h = nullptr;
   // the batch
   uint64_t ticket = 0;             // 0 = free
@@ -286,6 +289,7 @@ struct Slot {
   ClassifyParams p{};              // launch parameters (kept for the slow paths)
   uint32_t fast_cap = 0, gen_slots = 0;
   bool host_batch = false;
+  bool evidence = false;           // submitted in evidence mode: the evidence instantiations ran and d_evid (h_evid) hold its records
   bool long_speculative = false;   // (device-resident submit) the caller's length bound was taken on trust: checked in wait
 };
 
@@ -295,9 +299,9 @@ struct Ctx;
 int build_index(Ctx *ctx);
 
 // classify.hip
-int launch_classify_fast(Ctx *ctx, const ClassifyParams &p, uint32_t max_slots, hipStream_t stream);
+int launch_classify_fast(Ctx *ctx, const ClassifyParams &p, uint32_t max_slots, hipStream_t stream, bool evidence = false);
 const char *probe_mode_name(const Ctx *ctx);
-int launch_classify_general(Ctx *ctx, const ClassifyParams &p, bool emit, unsigned n_waves, hipStream_t stream);
+int launch_classify_general(Ctx *ctx, const ClassifyParams &p, bool emit, unsigned n_waves, hipStream_t stream, bool evidence = false);   // evidence: the non-EMIT pass only
 int launch_gather_inline(const uint32_t *count, const uint16_t *inl, const uint32_t *gene_off, uint16_t *gene_ids, uint64_t n,
                          const uint32_t *counters, hipStream_t stream);
 int launch_finalize_total(const uint64_t *total, uint32_t *counters, uint64_t gene_ids_cap, hipStream_t stream);
@@ -307,6 +311,7 @@ int launch_fill_offsets(uint64_t *off, uint64_t n_plus_1, uint64_t stride, hipSt
 int launch_vouch_check(const ClassifyParams &p, uint32_t L1, uint32_t L2, uint32_t *counters, hipStream_t stream);
 int launch_publish_results(const uint32_t *counters, uint32_t *h_counters, const uint32_t *gene_off, uint32_t *h_gene_off, uint64_t n_off,
                            const uint16_t *gene_ids, uint16_t *h_gene_ids, uint64_t h_ids_cap, const uint32_t *uni_flag, hipStream_t stream);
+int launch_publish_evidence(const shk_read_evidence *evid, shk_read_evidence *h_evid, uint64_t n, hipStream_t stream);
 int launch_classify_uni(Ctx *ctx, const ClassifyParams &p, uint32_t max_slots, int rmode, hipStream_t stream);   // 0 ragged, 1 uniform, 2 by classes (CLS)
 int launch_class_prepass(const ClassifyParams &p, uint32_t slot_cap, uint32_t *flag, hipStream_t stream);   // behind launch_uniform_check: histogram, plan, scatter
 bool class_kernel_available(const Ctx *ctx, uint32_t max_slots);
@@ -366,6 +371,12 @@ struct Ctx {
   uint32_t env_cls_min_fill = CLS_MIN_FILL;   // SHK_CLS_MIN_FILL: pairs per non-empty class a batch needs to go class by class (0: never; tests: 1)
   // which classify kernel the last batch's main launch was (shk_last_kernel): the choice can depend on the batch before it
   char last_kernel[160] = "";
+  // evidence mode (shk_evidence_enable): batches submitted while it is on run the evidence instantiations.  last_evid: the
+  // records of the batch whose result was handed out last (last_evid_valid = false: that batch had none, or it was refused)
+  bool evidence = false;
+  bool last_evid_valid = false;
+  const shk_read_evidence *last_evid = nullptr;
+  uint64_t last_evid_n = 0;
 
   // timing
   bool timing = false;
