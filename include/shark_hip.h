@@ -106,7 +106,11 @@ const char *shk_probe_mode(const shk_ctx *ctx);
  * once, by shk_create.  classify_fast_kernel and classify_general_kernel are named here without their last template argument
  * (evidence mode: "false" in a profile for the ordinary instantiations, which this call leaves out as it always has, "true" for
  * the evidence ones, which this call spells "evidence"): "classify_fast_kernel<5, 3, false>" here is
- * "classify_fast_kernel<5, 3, false, false>" in rocprofv3, "classify_fast_kernel<5, 3, false, evidence>" is "<5, 3, false, true>". */
+ * "classify_fast_kernel<5, 3, false, false>" in rocprofv3, "classify_fast_kernel<5, 3, false, evidence>" is "<5, 3, false, true>".
+ * Candidates mode (below) added one more trailing template argument the same way: a profile shows the ordinary instantiation as
+ * "classify_fast_kernel<5, 3, false, false, false>", the evidence one as "<5, 3, false, true, false>" and the candidates one, which
+ * this call spells "classify_fast_kernel<5, 3, false, candidates>" (and "classify_general_kernel<wrap, candidates>"), as
+ * "<5, 3, false, true, true>": it computes the evidence record as well. */
 const char *shk_last_kernel(const shk_ctx *ctx);
 
 /* Parity introspection: copy the device-resident index to host buffers.
@@ -220,6 +224,42 @@ int shk_evidence_enable(shk_ctx *ctx, int enable);
  * for resident ones.  (shk_count_work hands out none: SHK_ERR_STATE behind it.)  SHK_ERR_STATE if that batch was submitted with the mode off, if its wait returned an error, or if no batch
  * has been waited for yet. */
 int shk_evidence_last(const shk_ctx *ctx, shk_evidence *out);
+
+/* ---- candidates: a read's best genes in the reference's ranking, with their numbers ---- */
+/* The reference holds, per read, a map gene -> (coverage, k-mer count) over every gene with at least one hit
+ * (ReadAnalyzer.hpp:64-88), picks the entries that reach the maximum (coverage first, then k-mer count; the map's ascending gene
+ * order among equals: ReadAnalyzer.hpp:90-102) and throws the rest away.  In candidates mode the first m entries of that map in
+ * the order in which :90-102 would pick them if each winner were removed in turn -- cov descending, then nk descending, then gene
+ * id ascending -- leave the device with the associations, whether or not the read then passes c * len or --single:
+ *   reads[i].len       valid characters of the joined string (ReadAnalyzer.hpp:46-49), as shk_read_evidence.len
+ *   reads[i].n_genes   size of the read's map: distinct gene ids with a hit (0 for a read shorter than k, without a valid k-mer or
+ *                      without a hit); may exceed m
+ *   entries[i*m + r]   the gene of rank r with its coverage and k-mer count; entry 0 is evidence mode's (cov, nk); the leading
+ *                      entries that share entry 0's (cov, nk) are, in order, the genes the ordinary result holds when the read
+ *                      passes; slots behind the last candidate are empty (all three 0: a candidate has nk >= 1)
+ * On an index of more than 65 536 records the entries are the reference's map entries: ids wrapped to 16 bits, cov and nk with the
+ * multiplicities of ReadAnalyzer.hpp:56-62, :79-86.  New: the reference has no counterpart beyond the lines named above.
+ *
+ * The price is evidence mode's (the full-probe kernels run: shk_last_kernel names "classify_fast_kernel<5, 3, false, candidates>",
+ * "classify_general_kernel<wrap, candidates>") plus 8 + 12 m bytes stored per read.  gene_off, gene_ids, n_assoc and
+ * shk_gene_counts are the same with the mode on and off; with it off nothing changes at all. */
+#define SHK_MAX_CANDIDATES 8
+typedef struct shk_candidate { uint32_t gene, cov, nk; } shk_candidate;          /* nk == 0: empty slot (all three 0) */
+typedef struct shk_read_candidates { uint32_t len, n_genes; } shk_read_candidates;
+typedef struct shk_candidates {
+  uint64_t                   n;        /* reads of that batch */
+  uint32_t                   m;        /* entries per read */
+  const shk_read_candidates *reads;    /* n */
+  const shk_candidate       *entries;  /* n * m, read i at entries[i*m .. i*m+m), rank order, empty slots last */
+} shk_candidates;
+/* Switches candidates mode on with m entries per read (1 .. SHK_MAX_CANDIDATES) or off (m = 0) for the batches submitted
+ * AFTERWARDS, through any of the four families; SHK_ERR_ARG for m > SHK_MAX_CANDIDATES, SHK_ERR_STATE while tickets are
+ * outstanding.  Independent of evidence mode: both may be on, then both _last calls answer and agree.  New: no counterpart. */
+int shk_candidates_enable(shk_ctx *ctx, uint32_t m);
+/* The candidates of the batch whose result was handed out LAST, with shk_evidence_last's rules: that result's lifetime and memory
+ * space (pinned host memory for host batches, DEVICE memory for resident ones); SHK_ERR_STATE if that batch was submitted with the
+ * mode off, if its wait returned an error, behind shk_count_work, or if no batch has been waited for yet.  New: no counterpart. */
+int shk_candidates_last(const shk_ctx *ctx, shk_candidates *out);
 
 /* Per-gene number of assigned reads accumulated over all classify calls (all
  * waited tickets) since the last reset (counts[g] for g in [0, 65536)); the quantity all-reduced

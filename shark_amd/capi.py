@@ -43,6 +43,10 @@ class ShkEvidence(C.Structure):
     _fields_ = [("n", C.c_uint64), ("reads", C.c_void_p)]
 
 
+class ShkCandidates(C.Structure):
+    _fields_ = [("n", C.c_uint64), ("m", C.c_uint32), ("reads", C.c_void_p), ("entries", C.c_void_p)]
+
+
 class ShkWorkCounters(C.Structure):
     _fields_ = [("n_kmers", C.c_uint64), ("n_hits", C.c_uint64), ("n_list_ids", C.c_uint64), ("n_bases", C.c_uint64)]
 
@@ -58,9 +62,11 @@ EXPORTS = [
     "shk_measure_valu_mix",
     "shk_measure_valu_mix_clock",
     "shk_evidence_enable", "shk_evidence_last",
+    "shk_candidates_enable", "shk_candidates_last",
 ]
 SHK_PIPE_DEPTH = 3
 SHK_DIST_ID_BYTES = 128
+SHK_MAX_CANDIDATES = 8
 
 _lib = None
 
@@ -119,6 +125,8 @@ def load():
         "shk_measure_valu_mix_clock": (C.c_int, [p, C.c_int, C.c_uint32, C.POINTER(C.c_double), C.POINTER(C.c_uint64), C.POINTER(C.c_double)]),
         "shk_evidence_enable": (C.c_int, [p, C.c_int]),
         "shk_evidence_last": (C.c_int, [p, C.POINTER(ShkEvidence)]),
+        "shk_candidates_enable": (C.c_int, [p, C.c_uint32]),
+        "shk_candidates_last": (C.c_int, [p, C.POINTER(ShkCandidates)]),
     }
     variant = bool(os.environ.get("SHK_LIB_PATH"))
     for name, (res, args) in later.items():
@@ -323,6 +331,29 @@ class SharkHip:
         if n == 0:
             return np.zeros((0, 3), dtype=np.uint32)
         return np.ctypeslib.as_array(C.cast(e.reads, C.POINTER(C.c_uint32)), shape=(n, 3)).copy()
+
+    # ---- candidates: per read its best m genes in the reference's ranking, with coverage and k-mer count --------
+    def candidates_enable(self, m=4):
+        """batches submitted from now on carry their reads' top m candidates (1 .. SHK_MAX_CANDIDATES; 0 switches the mode off) and
+        run the full-probe kernels; refused while tickets are outstanding"""
+        self._check(self.L.shk_candidates_enable(self.h, int(m)), "shk_candidates_enable")
+
+    def candidates_last(self):
+        """candidates of the batch whose result was handed out last: (reads, entries) -- an (n, 2) uint32 array (len, n_genes) and an
+        (n, m, 3) uint32 array (gene, cov, nk; rank order, empty slots all 0) copied from the context's pinned memory for a host
+        batch (classify, wait); for a resident one (classify_device, wait_device) (n, m, reads, entries) with the two DEVICE pointers
+        (8 bytes per read, 12 bytes per entry) -- read them back with hip_memcpy_dtoh.  Raises (SHK_ERR_STATE) when that batch
+        was submitted with candidates off"""
+        c = ShkCandidates()
+        self._check(self.L.shk_candidates_last(self.h, C.byref(c)), "shk_candidates_last")
+        n, m = int(c.n), int(c.m)
+        if not self._last_on_host:
+            return n, m, c.reads, c.entries
+        if n == 0:
+            return np.zeros((0, 2), dtype=np.uint32), np.zeros((0, m, 3), dtype=np.uint32)
+        reads = np.ctypeslib.as_array(C.cast(c.reads, C.POINTER(C.c_uint32)), shape=(n, 2)).copy()
+        entries = np.ctypeslib.as_array(C.cast(c.entries, C.POINTER(C.c_uint32)), shape=(n, m, 3)).copy()
+        return reads, entries
 
     def gene_counts(self, n=65536):
         a = np.zeros(n, dtype=np.uint64)

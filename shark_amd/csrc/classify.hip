@@ -52,7 +52,62 @@ namespace shk {
 // gene's coverage and k-mer count (ReadAnalyzer.hpp:90-102: the maximum over all genes, whether or not it then passes c * len or
 // --single) and the read's number of valid characters (:46-49), one shk_read_evidence per read next to count[read]; (0, 0, len)
 // for a read shorter than k, without a valid k-mer or without a hit.  len is then summed for every read, not only behind a hit.
-template <int U, int MODE, bool HASQ, bool FAST, bool EMIT, bool WRAP = false, bool EVID = false>
+//
+// (CAND) a read's ranked list of candidates, wave-uniform: an empty slot is (0, 0, 0), below every candidate (a gene with a hit
+// has nk >= 1).  The ordinary and the evidence instantiations hold the empty form and never touch it.
+template <bool CAND>
+struct CandidateList {};
+
+template <>
+struct CandidateList<true> {
+  static constexpr int NC = SHK_MAX_CANDIDATES;
+  uint32_t id[NC], cov[NC], nk[NC];
+  uint32_t n_genes;
+  __device__ __forceinline__ CandidateList() : n_genes(0)
+  {
+#pragma unroll
+    for (int i = 0; i < NC; ++i) { id[i] = 0; cov[i] = 0; nk[i] = 0; }
+  }
+  // Insertion in rank order, as selects on wave-uniform values for the reason given at process_read's arg-max.  keep[i]: entry i
+  // stays in front of g -- it ranks higher, or equal: the merge delivers ids in ascending order, so an equal entry is an earlier
+  // id and is not displaced.  The list is sorted, so keep[] is true up to g's place and false behind it; the entries behind it
+  // move down by one (walked from the end, each reads its old neighbour) and the last one drops out.
+  __device__ __forceinline__ void insert(const uint32_t g, const uint32_t g_cov, const uint32_t g_nk)
+  {
+    bool keep[NC];
+#pragma unroll
+    for (int i = 0; i < NC; ++i) keep[i] = (cov[i] > g_cov) | ((cov[i] == g_cov) & (nk[i] >= g_nk));
+#pragma unroll
+    for (int i = NC - 1; i >= 1; --i) {
+      const bool here = keep[i - 1];   // (and !keep[i]: g's place)
+      id[i] = keep[i] ? id[i] : (here ? g : id[i - 1]);
+      cov[i] = keep[i] ? cov[i] : (here ? g_cov : cov[i - 1]);
+      nk[i] = keep[i] ? nk[i] : (here ? g_nk : nk[i - 1]);
+    }
+    id[0] = keep[0] ? id[0] : g;
+    cov[0] = keep[0] ? cov[0] : g_cov;
+    nk[0] = keep[0] ? nk[0] : g_nk;
+    ++n_genes;   // (the size of the reference's map: the merge visits every id with a hit once)
+  }
+  // lane 0, vector stores: 8 bytes, then 12 bytes per stored entry
+  __device__ __forceinline__ void store(const ClassifyOut *O, const uint64_t read, const uint32_t len) const
+  {
+    const uint32_t m = O->cand_m;
+    O->cand_reads[read] = shk_read_candidates{len, n_genes};
+    shk_candidate *e = O->cand_entries + read * m;
+#pragma unroll
+    for (int i = 0; i < NC; ++i)
+      if ((uint32_t)i < m) e[i] = shk_candidate{id[i], cov[i], nk[i]};
+  }
+};
+
+// CAND (candidates mode, shk_candidates_enable; always with EVID): the reference's per-read map gene -> (cov, nk)
+// (ReadAnalyzer.hpp:64-88) is not collapsed into its maximum alone: the best SHK_MAX_CANDIDATES entries in the order in which
+// ReadAnalyzer.hpp:90-102 would pick them if each winner were removed in turn (cov descending, nk descending, gene id ascending)
+// are kept in wave-uniform registers beside the arg-max, the map's size is counted, and lane 0 stores one shk_read_candidates and
+// the first cand_m shk_candidate per read; a read shorter than k, without a valid k-mer or without a hit gets (len, 0) and empty
+// entries.  The evidence record is stored as well when the batch has a place for it (both modes on).
+template <int U, int MODE, bool HASQ, bool FAST, bool EMIT, bool WRAP = false, bool EVID = false, bool CAND = false>
 __device__ __forceinline__ void process_read(const ClassifyParams &P, const uint64_t read, const int lane, const WaveStore st,
                                              const uint32_t slot_cap, const uint32_t tie_cov, const uint32_t tie_nk,
                                              const uint32_t *lsum, const ReadMeta meta, const bool pre, const Raw8 pre_w, const Raw8 pre_q)
@@ -385,6 +440,7 @@ __device__ __forceinline__ void process_read(const ClassifyParams &P, const uint
   uint32_t best_id[SHK_INLINE_IDS] = {0, 0, 0, 0};
   uint32_t n_emit = 0;
   uint32_t len = 0;
+  CandidateList<CAND> cands;
   if (EVID) len = wave_sum_u32(my_valid);
   const uint32_t first_valid = WRAP ? wave_min_u32(my_first) : 0u;   // the read's first valid k-mer (ReadAnalyzer.hpp:51-62)
   if (any_hit && !SHK_ABL(P, 2u)) {   // ablation 2: skip the vote
@@ -501,6 +557,7 @@ __device__ __forceinline__ void process_read(const ClassifyParams &P, const uint
         n_best = gt ? 1u : (eq ? n_best + 1u : n_best);
         best_cov = gt ? cov : best_cov;
         best_nk = gt ? nk : best_nk;
+        if constexpr (CAND) cands.insert(g, cov, nk);
       }
     }
   }
@@ -514,7 +571,8 @@ __device__ __forceinline__ void process_read(const ClassifyParams &P, const uint
     // of `count`, the per-gene counts from gather_inline_kernel (wave-aggregated).
     const ClassifyOut *O = out_ptrs(P);
     O->count[read] = n_out;
-    if (EVID) O->evid[read] = shk_read_evidence{best_cov, best_nk, len};   // (12 bytes, one store)
+    if (EVID && (!CAND || O->evid)) O->evid[read] = shk_read_evidence{best_cov, best_nk, len};   // (12 bytes, one store)
+    if constexpr (CAND) cands.store(O, read, len);
     if (n_out > 0) {
       uint16_t *o = O->inl + read * SHK_INLINE_IDS;
 #pragma unroll
@@ -545,7 +603,8 @@ struct FastGeom {
 
 // EVID: the evidence instantiations (process_read's EVID).  Every batch submitted in evidence mode on an index of up to 65 536
 // genes runs there, whatever its lengths: classify_uni_kernel and anchor_verdict_kernel never compute a read's final coverage.
-template <int U, int MODE, bool HASQ, bool EVID = false>
+// CAND: the candidates instantiations (process_read's CAND, always with EVID), the same way.
+template <int U, int MODE, bool HASQ, bool EVID = false, bool CAND = false>
 __global__ __launch_bounds__((FastGeom<MODE, U>::THREADS), (FastGeom<MODE, U>::MIN_WAVES_PER_SIMD)) void classify_fast_kernel(const ClassifyParams P)
 {
   using G = FastGeom<MODE, U>;
@@ -595,7 +654,7 @@ __global__ __launch_bounds__((FastGeom<MODE, U>::THREADS), (FastGeom<MODE, U>::M
     if (have_nxt) fetch_group<HASQ>(P, m_nxt, (uint32_t)lane, w_nxt, q_nxt);
     const uint32_t nn = (have_nxt && n32 - nxt > stride) ? nxt + stride : n32;
     ReadMetaRaw r_nn = fetch_meta_issue(P, nn < n32 ? nn : read);          // clamped index
-    process_read<U, MODE, HASQ, true, false, false, EVID>(P, read, lane, st, S, 0u, 0u, lsum, m_cur, true, w_cur, q_cur);
+    process_read<U, MODE, HASQ, true, false, false, EVID, CAND>(P, read, lane, st, S, 0u, 0u, lsum, m_cur, true, w_cur, q_cur);
     if (!have_nxt) break;
     // The prefetched bases landed long ago.  Retire them HERE and hand the compiler plain register
     // values: otherwise it carries "a load may be pending" around the loop and, because the number of
@@ -941,7 +1000,8 @@ __global__ __launch_bounds__(1024) void class_scatter_kernel(const ClassifyParam
 // SHK_INLINE_IDS (EMIT).  Work items come from a queue.
 // ---------------------------------------------------------------------------
 // EVID: the evidence instantiations of the non-EMIT pass (whole batches on wrapped indices, the long-read queue)
-template <bool POW2, bool HASQ, bool EMIT, bool WRAP, bool EVID = false>
+// CAND: the candidates instantiations of the same pass
+template <bool POW2, bool HASQ, bool EMIT, bool WRAP, bool EVID = false, bool CAND = false>
 __global__ __launch_bounds__(CF_THREADS) void classify_general_kernel(const ClassifyParams P)
 {
   constexpr int U = 4;
@@ -972,7 +1032,7 @@ __global__ __launch_bounds__(CF_THREADS) void classify_general_kernel(const Clas
     } else if (P.work) {
       read = P.work[w];
     }
-    process_read<U, POW2 ? PM_BV : PM_BV_MOD, HASQ, false, EMIT, WRAP, EVID>(P, read, lane, st, S, tc, tn, nullptr, fetch_meta(P, read), false, Raw8{0u, 0u, 0u, 0u}, Raw8{0u, 0u, 0u, 0u});
+    process_read<U, POW2 ? PM_BV : PM_BV_MOD, HASQ, false, EMIT, WRAP, EVID, CAND>(P, read, lane, st, S, tc, tn, nullptr, fetch_meta(P, read), false, Raw8{0u, 0u, 0u, 0u}, Raw8{0u, 0u, 0u, 0u});
   }
 }
 
@@ -1170,9 +1230,10 @@ const char *probe_mode_name(const Ctx *ctx)
 }
 
 template <int U>
-static void launch_fast_u(const ClassifyParams &p, int mode, bool hasq, bool evidence, unsigned grid, hipStream_t s)
+static void launch_fast_u(const ClassifyParams &p, int mode, bool hasq, bool evidence, bool candidates, unsigned grid, hipStream_t s)
 {
-#define LF(M_, HQ_) do { if (evidence) hipLaunchKernelGGL((classify_fast_kernel<U, M_, HQ_, true>), dim3(grid), dim3(FastGeom<M_, U>::THREADS), 0, s, p); \
+#define LF(M_, HQ_) do { if (candidates) hipLaunchKernelGGL((classify_fast_kernel<U, M_, HQ_, true, true>), dim3(grid), dim3(FastGeom<M_, U>::THREADS), 0, s, p); \
+                         else if (evidence) hipLaunchKernelGGL((classify_fast_kernel<U, M_, HQ_, true>), dim3(grid), dim3(FastGeom<M_, U>::THREADS), 0, s, p); \
                          else hipLaunchKernelGGL((classify_fast_kernel<U, M_, HQ_>), dim3(grid), dim3(FastGeom<M_, U>::THREADS), 0, s, p); } while (0)
   switch (mode) {
   case PM_BV_MOD: if (hasq) LF(PM_BV_MOD, true); else LF(PM_BV_MOD, false); break;
@@ -1187,7 +1248,7 @@ static void launch_fast_u(const ClassifyParams &p, int mode, bool hasq, bool evi
 #undef LF
 }
 
-int launch_classify_fast(Ctx *ctx, const ClassifyParams &p, uint32_t max_slots, hipStream_t stream, bool evidence)
+int launch_classify_fast(Ctx *ctx, const ClassifyParams &p, uint32_t max_slots, hipStream_t stream, bool evidence, bool candidates)
 {
   if (p.n == 0) return SHK_OK;
   const bool hasq = p.hasq != 0;
@@ -1199,15 +1260,15 @@ int launch_classify_fast(Ctx *ctx, const ClassifyParams &p, uint32_t max_slots, 
   const uint64_t cap = pm_lds(mode) ? (u <= 5 ? 1024 : 768) : 4096;   // (u = 10 likewise 768: six waves per SIMD at most)   // LDS mode: exactly the resident workgroups
   const uint64_t want = (p.n + wpb - 1) / wpb;
   const unsigned grid = (unsigned)(want < cap ? want : cap);
-  if (u == 2) launch_fast_u<2>(p, mode, hasq, evidence, grid, stream);
-  else if (u == 3) launch_fast_u<3>(p, mode, hasq, evidence, grid, stream);
-  else if (u == 4) launch_fast_u<4>(p, mode, hasq, evidence, grid, stream);
-  else if (u == 5) launch_fast_u<5>(p, mode, hasq, evidence, grid, stream);
-  else if (u == 6) launch_fast_u<6>(p, mode, hasq, evidence, grid, stream);
-  else if (u == 8) launch_fast_u<8>(p, mode, hasq, evidence, grid, stream);
-  else launch_fast_u<10>(p, mode, hasq, evidence, grid, stream);
+  if (u == 2) launch_fast_u<2>(p, mode, hasq, evidence, candidates, grid, stream);
+  else if (u == 3) launch_fast_u<3>(p, mode, hasq, evidence, candidates, grid, stream);
+  else if (u == 4) launch_fast_u<4>(p, mode, hasq, evidence, candidates, grid, stream);
+  else if (u == 5) launch_fast_u<5>(p, mode, hasq, evidence, candidates, grid, stream);
+  else if (u == 6) launch_fast_u<6>(p, mode, hasq, evidence, candidates, grid, stream);
+  else if (u == 8) launch_fast_u<8>(p, mode, hasq, evidence, candidates, grid, stream);
+  else launch_fast_u<10>(p, mode, hasq, evidence, candidates, grid, stream);
   SHK_HIP(ctx, hipGetLastError());
-  snprintf(ctx->last_kernel, sizeof(ctx->last_kernel), "classify_fast_kernel<%u, %d, %s%s>", u, mode, hasq ? "true" : "false", evidence ? ", evidence" : "");
+  snprintf(ctx->last_kernel, sizeof(ctx->last_kernel), "classify_fast_kernel<%u, %d, %s%s>", u, mode, hasq ? "true" : "false", candidates ? ", candidates" : (evidence ? ", evidence" : ""));
   return SHK_OK;
 }
 
@@ -1402,11 +1463,20 @@ int launch_uniform_check(const ClassifyParams &p, uint32_t slot_cap, uint32_t *f
   return hipGetLastError() == hipSuccess ? SHK_OK : SHK_ERR_HIP;
 }
 
-int launch_classify_general(Ctx *ctx, const ClassifyParams &p, bool emit, unsigned n_waves, hipStream_t stream, bool evidence)
+int launch_classify_general(Ctx *ctx, const ClassifyParams &p, bool emit, unsigned n_waves, hipStream_t stream, bool evidence, bool candidates)
 {
   if (p.n_work == 0 && !p.work_count) return SHK_OK;
   const bool pow2 = ctx->idx.pow2, hasq = p.hasq != 0, wrap = ctx->idx.wrap;
   const unsigned grid = (n_waves + CF_WAVES - 1) / CF_WAVES;
+  if (candidates && !emit) {
+#define LGC(P2_, HQ_) do { if (wrap) hipLaunchKernelGGL((classify_general_kernel<P2_, HQ_, false, true, true, true>), dim3(grid), dim3(CF_THREADS), 0, stream, p); \
+                           else hipLaunchKernelGGL((classify_general_kernel<P2_, HQ_, false, false, true, true>), dim3(grid), dim3(CF_THREADS), 0, stream, p); } while (0)
+    if (pow2) { if (hasq) LGC(true, true); else LGC(true, false); }
+    else { if (hasq) LGC(false, true); else LGC(false, false); }
+#undef LGC
+    SHK_HIP(ctx, hipGetLastError());
+    return SHK_OK;
+  }
   if (evidence && !emit) {
 #define LGE(P2_, HQ_) do { if (wrap) hipLaunchKernelGGL((classify_general_kernel<P2_, HQ_, false, true, true>), dim3(grid), dim3(CF_THREADS), 0, stream, p); \
                            else hipLaunchKernelGGL((classify_general_kernel<P2_, HQ_, false, false, true>), dim3(grid), dim3(CF_THREADS), 0, stream, p); } while (0)
@@ -1477,6 +1547,14 @@ int launch_publish_evidence(const shk_read_evidence *evid, shk_read_evidence *h_
   const uint64_t want = (3 * n / 4 + 255) / 256;
   hipLaunchKernelGGL(publish_evidence_kernel, dim3((unsigned)(want < 1 ? 1 : (want < 512 ? want : 512))), dim3(256), 0, stream,
                      reinterpret_cast<const uint32_t *>(evid), reinterpret_cast<uint32_t *>(h_evid), 3 * n);
+  return hipGetLastError() == hipSuccess ? SHK_OK : SHK_ERR_HIP;
+}
+
+int launch_publish_words(const uint32_t *src, uint32_t *h_dst, uint64_t n_words, hipStream_t stream)
+{
+  if (n_words == 0) return SHK_OK;
+  const uint64_t want = (n_words / 4 + 255) / 256;
+  hipLaunchKernelGGL(publish_evidence_kernel, dim3((unsigned)(want < 1 ? 1 : (want < 512 ? want : 512))), dim3(256), 0, stream, src, h_dst, n_words);
   return hipGetLastError() == hipSuccess ? SHK_OK : SHK_ERR_HIP;
 }
 

@@ -72,6 +72,10 @@ const char *USAGE_MESSAGE =
     "          --evidence FILE               write <read> <coverage> <kmers> <valid bases> of every read (pair), in input order: the best\n"
     "                                        gene's figures, which pass iff kmers > 0 and coverage >= c * valid bases (slower: every\n"
     "                                        k-mer of every read is probed)\n"
+    "          --candidates FILE             write <read> <valid bases> <genes hit> and then <gene> <coverage> <kmers> of the read's best\n"
+    "                                        genes (coverage, then kmers, then the legend's order), one line per read (pair), in input\n"
+    "                                        order (as slow as --evidence; may be combined with it)\n"
+    "          --candidates-n M              genes per line of --candidates (default:4, 1 to 8)\n"
     "      -t N also sets the number of host threads that parse FASTQ / format output (default: up to 16)\n";
 
 struct Options {
@@ -91,6 +95,10 @@ struct Options {
   std::string gene_counts_path;
   std::string evidence_path;
   FILE *evidence_file = nullptr;   // (--evidence, opened by main() before any work is done)
+  std::string candidates_path;
+  FILE *candidates_file = nullptr; // (--candidates, likewise)
+  unsigned candidates_n = 4;
+  bool candidates_n_given = false;
 };
 
 // The command line is described by one table: option names, whether a value follows, and a handler that
@@ -170,6 +178,13 @@ const OptionRow OPTION_TABLE[] = {
     {1001, "batch", true, [](Options &o, const char *v) { o.batch = std::max<uint64_t>(1, value_of<uint64_t>(v)); o.batch_given = true; }},
     {1002, "gene-counts", true, [](Options &o, const char *v) { o.gene_counts_path = value_of<std::string>(v); }},
     {1004, "evidence", true, [](Options &o, const char *v) { o.evidence_path = value_of<std::string>(v); }},
+    {1005, "candidates", true, [](Options &o, const char *v) { o.candidates_path = value_of<std::string>(v); }},
+    {1006, "candidates-n", true,
+     [](Options &o, const char *v) {
+       o.candidates_n = value_of<unsigned>(v);
+       o.candidates_n_given = true;
+       if (o.candidates_n < 1 || o.candidates_n > SHK_MAX_CANDIDATES) reject(USAGE_MESSAGE, "shark: --candidates-n must be in the range [1, 8].");
+     }},
 };
 
 // Reads per device batch when --batch does not say.  A batch costs the device path 0.5-2 ms of launches, copies and bookkeeping
@@ -230,6 +245,7 @@ Options parse_arguments(int argc, char **argv)
     std::cerr << "shark : missing required files" << std::endl << "\n" << USAGE_MESSAGE;
     exit(EXIT_FAILURE);
   }
+  if (opt.candidates_n_given && opt.candidates_path.empty()) reject(USAGE_MESSAGE, "shark: --candidates-n needs --candidates FILE.");
   if (opt.out1_path.empty()) opt.out1_path = "sharked_sample.1";
   if (opt.out2_path.empty() && !opt.sample2_path.empty()) opt.out2_path = "sharked_sample.2";
   // --devices alone says how many workers there are; with --gpus N it has to name N devices
@@ -356,6 +372,9 @@ struct ReadBatch {
   std::vector<uint32_t> gene_off;
   std::vector<uint16_t> gene_ids;
   std::vector<shk_read_evidence> evidence;   // (--evidence) one record per read
+  std::vector<shk_read_candidates> cand_reads;   // (--candidates) one header per read ...
+  std::vector<shk_candidate> cand_entries;       // ... and cand_m entries
+  uint32_t cand_m = 0;
   int rc = 0;
   void reset()
   {
@@ -363,7 +382,7 @@ struct ReadBatch {
     qual_as_read1.clear(); qual_as_read2.clear();
     lean = false;
     text.reset();
-    gene_off.clear(); gene_ids.clear(); evidence.clear();
+    gene_off.clear(); gene_ids.clear(); evidence.clear(); cand_reads.clear(); cand_entries.clear(); cand_m = 0;
     rc = 0;
   }
 };
@@ -808,7 +827,7 @@ class GzCutter {
 // flight: the copies of the next batches overlap the kernels of the current one (shk_classify_submit / _wait).
 class ReadAnalyzer {
  public:
-  ReadAnalyzer(shk_ctx *ctx, bool need_qual, bool evidence) : ctx_(ctx), need_qual_(need_qual), evidence_(evidence) {}
+  ReadAnalyzer(shk_ctx *ctx, bool need_qual, bool evidence, bool candidates = false) : ctx_(ctx), need_qual_(need_qual), evidence_(evidence), candidates_(candidates) {}
   // false: the batch failed at once (b.rc is set) and is not in flight
   bool submit(std::unique_ptr<ReadBatch> b)
   {
@@ -849,13 +868,22 @@ class ReadAnalyzer {
         b->rc = shk_evidence_last(ctx_, &ev);
         if (b->rc == SHK_OK) b->evidence.assign(ev.reads, ev.reads + ev.n);
       }
+      if (candidates_ && b->rc == SHK_OK) {
+        shk_candidates cd{};
+        b->rc = shk_candidates_last(ctx_, &cd);
+        if (b->rc == SHK_OK) {
+          b->cand_m = cd.m;
+          b->cand_reads.assign(cd.reads, cd.reads + cd.n);
+          b->cand_entries.assign(cd.entries, cd.entries + cd.n * cd.m);
+        }
+      }
     }
     return b;
   }
 
  private:
   shk_ctx *ctx_;
-  bool need_qual_, evidence_;
+  bool need_qual_, evidence_, candidates_;
   std::deque<std::pair<uint64_t, std::unique_ptr<ReadBatch>>> flying_;
   std::unique_ptr<ReadBatch> failed_;
 };
@@ -964,12 +992,13 @@ class OffsetWriter {
 struct FormattedSegment {
   std::string ssv, fq1, fq2;        // fq: the FASTQ records behind the segment's first one
   std::string evd;                  // (--evidence) <id> <cov> <nk> <len> of every read of the segment
+  std::string cnd;                  // (--candidates) <id> <len> <n_genes> { <gene> <cov> <nk>} of every read of the segment
   std::string head1, head2;         // the first associated read's FASTQ records, printed unless its name equals the carried one
   std::string head_id, last_id;
   bool has_assoc = false, carries = false;
   void reset()
   {
-    ssv.clear(); fq1.clear(); fq2.clear(); evd.clear(); head1.clear(); head2.clear(); head_id.clear(); last_id.clear();
+    ssv.clear(); fq1.clear(); fq2.clear(); evd.clear(); cnd.clear(); head1.clear(); head2.clear(); head_id.clear(); last_id.clear();
     has_assoc = carries = false;
   }
 };
@@ -1019,7 +1048,7 @@ class TextPool {
             st->free.pop_back();
           }
           for (FormattedSegment &sg : q->segs)
-            for (std::string *x : {&sg.ssv, &sg.fq1, &sg.fq2, &sg.evd}) drop_pages(*x);
+            for (std::string *x : {&sg.ssv, &sg.fq1, &sg.fq2, &sg.evd, &sg.cnd}) drop_pages(*x);
           // (the object itself and its small strings are left to the process's end)
         }
       });
@@ -1057,10 +1086,11 @@ class TextPool {
 
 class ReadOutput {
  public:
-  ReadOutput(OffsetWriter *out1, OffsetWriter *out2, const std::vector<std::string> &legend, FILE *evidence = nullptr)
-      : out1_(out1), out2_(out2), legend_(legend), evidence_(evidence) {}
+  ReadOutput(OffsetWriter *out1, OffsetWriter *out2, const std::vector<std::string> &legend, FILE *evidence = nullptr, FILE *candidates = nullptr)
+      : out1_(out1), out2_(out2), legend_(legend), evidence_(evidence), candidates_(candidates), every_read_(evidence || candidates) {}
   bool failed() const { return failed_.load(); }
   bool evidence_write_failed() const { return failed_write_; }
+  bool candidates_write_failed() const { return failed_write_cand_; }
 
   // thread-safe; nothing is written
   void format(const ReadBatch &b, FormattedBatch &out) const
@@ -1081,7 +1111,7 @@ class ReadOutput {
       if (b.lean) {
         // many associated reads in this segment: its byte range in one read; few: one read per record
         const size_t n_assoc = b.gene_off[last] - b.gene_off[first];
-        if (n_assoc * 10 > last - first || evidence_) {     // (--evidence names every read)
+        if (n_assoc * 10 > last - first || every_read_) {     // (--evidence and --candidates name every read)
           f1.load_dense(b.part1, first, last);
           if (out2_) f2.load_dense(b.part2, first, last);
         } else {
@@ -1090,9 +1120,10 @@ class ReadOutput {
         }
       }
       if (evidence_) sg.evd.reserve((last - first) * 48);
+      if (candidates_) sg.cnd.reserve((last - first) * 64);
       for (size_t i = first; i < last; ++i) {
         const bool assoc = b.gene_off[i] != b.gene_off[i + 1];
-        if (!assoc && !evidence_) continue;
+        if (!assoc && !every_read_) continue;
         shk::RecordFetcher::View v1{nullptr, 0, nullptr, 0, nullptr}, v2{nullptr, 0, nullptr, 0, nullptr};
         const char *id;
         size_t id_len;
@@ -1112,6 +1143,26 @@ class ReadOutput {
           const int w = snprintf(num, sizeof(num), " %u %u %u\n", e.cov, e.nk, e.len);
           sg.evd.append(id, id_len);
           sg.evd.append(num, (size_t)w);
+        }
+        if (candidates_ && (b.cand_reads.size() != n || b.cand_entries.size() != n * b.cand_m)) failed_ = true;   // (likewise)
+        if (candidates_ && i < b.cand_reads.size() && (i + 1) * (size_t)b.cand_m <= b.cand_entries.size()) {
+          // the read's name as the ssv prints it, its valid length, the number of genes it hit, and the filled entries in rank
+          // order: the gene as the ssv names it, its coverage and its k-mer count
+          char num[48];
+          const shk_read_candidates &h = b.cand_reads[i];
+          int w = snprintf(num, sizeof(num), " %u %u", h.len, h.n_genes);
+          sg.cnd.append(id, id_len);
+          sg.cnd.append(num, (size_t)w);
+          for (uint32_t r = 0; r < b.cand_m; ++r) {
+            const shk_candidate &e = b.cand_entries[i * (size_t)b.cand_m + r];
+            if (e.nk == 0) break;
+            if (e.gene >= legend_.size()) { failed_ = true; break; }
+            sg.cnd.push_back(' ');
+            sg.cnd.append(legend_[e.gene]);
+            w = snprintf(num, sizeof(num), " %u %u", e.cov, e.nk);
+            sg.cnd.append(num, (size_t)w);
+          }
+          sg.cnd.push_back('\n');
         }
         if (!assoc) continue;
         for (uint32_t j = b.gene_off[i]; j < b.gene_off[i + 1]; ++j) {
@@ -1160,6 +1211,7 @@ class ReadOutput {
       const FormattedSegment &sg = f.segs[si];
       fwrite(sg.ssv.data(), 1, sg.ssv.size(), stdout);
       if (evidence_ && fwrite(sg.evd.data(), 1, sg.evd.size(), evidence_) != sg.evd.size()) failed_write_ = true;
+      if (candidates_ && fwrite(sg.cnd.data(), 1, sg.cnd.size(), candidates_) != sg.cnd.size()) failed_write_cand_ = true;
       // (ReadOutput.hpp:44-48: a read's FASTQ records are printed unless its name equals the one printed just before it)
       const bool head_repeats = sg.carries && sg.has_assoc && sg.head_id == carry_;
       if (out1_) {
@@ -1200,7 +1252,9 @@ class ReadOutput {
   OffsetWriter *out1_, *out2_;
   const std::vector<std::string> &legend_;
   FILE *evidence_;          // (--evidence) written by emit(), in input order
-  bool failed_write_ = false;
+  FILE *candidates_;        // (--candidates) likewise
+  bool every_read_;         // one of the two: every read is named, not only the associated ones
+  bool failed_write_ = false, failed_write_cand_ = false;
   mutable std::atomic<bool> failed_{false};   // a record could not be read back from its file (I/O error)
   std::string carry_;   // previd at the end of the previous batch (only used when a batch starts mid-chunk)
 };
@@ -1698,12 +1752,12 @@ void serial_feed(const Options &opt, const FeedPlan &plan, ParallelFeed &feed, B
 }
 
 // analyzers: one thread per worker, SHK_PIPE_DEPTH batches in flight each; t_gpu[g]: seconds inside shk_classify_submit / _wait
-std::vector<std::thread> start_analyzers(const std::vector<shk_ctx *> &ctxs, bool need_qual, bool evidence, BatchOrder &order, BatchOrder::Queue &to_format, std::vector<double> &t_gpu)
+std::vector<std::thread> start_analyzers(const std::vector<shk_ctx *> &ctxs, bool need_qual, bool evidence, bool candidates, BatchOrder &order, BatchOrder::Queue &to_format, std::vector<double> &t_gpu)
 {
   std::vector<std::thread> analyzers;
   for (int g = 0; g < (int)ctxs.size(); ++g) {
-    analyzers.emplace_back([&, g, need_qual, evidence] {
-      ReadAnalyzer ra(ctxs[(size_t)g], need_qual, evidence);
+    analyzers.emplace_back([&, g, need_qual, evidence, candidates] {
+      ReadAnalyzer ra(ctxs[(size_t)g], need_qual, evidence, candidates);
       BatchOrder::Queue &todo = order.input(g);
       bool open = true;
       while (open || ra.in_flight()) {
@@ -1758,7 +1812,7 @@ int run_sample(const Options &opt, GpuStart &gpu, BatchPool &pool, std::vector<s
   w1.open(opt.out1_path, write_helpers);
   if (opt.paired_flag && opt.out2_path != "") w2.open(opt.out2_path, write_helpers);
   OffsetWriter *out1 = w1.is_open() ? &w1 : nullptr, *out2 = w2.is_open() ? &w2 : nullptr;
-  ReadOutput ro(out1, out2, legend_ID, opt.evidence_file);
+  ReadOutput ro(out1, out2, legend_ID, opt.evidence_file, opt.candidates_file);
   setvbuf(stdout, nullptr, _IOFBF, 1 << 22);
 
   FeedPlan plan(opt, io_threads, need_qual);
@@ -1778,6 +1832,13 @@ int run_sample(const Options &opt, GpuStart &gpu, BatchPool &pool, std::vector<s
       if (const int rc = shk_evidence_enable(ctx, 1)) {
         feed.stop();
         std::cerr << "shark: evidence mode could not be switched on: " << shk_strerror(rc) << std::endl;
+        return EXIT_FAILURE;
+      }
+  if (opt.candidates_file)
+    for (shk_ctx *ctx : gpu.ctxs)
+      if (const int rc = shk_candidates_enable(ctx, opt.candidates_n)) {
+        feed.stop();
+        std::cerr << "shark: candidates mode could not be switched on: " << shk_strerror(rc) << std::endl;
         return EXIT_FAILURE;
       }
   std::unique_ptr<BatchSplitter> fs;
@@ -1806,7 +1867,7 @@ int run_sample(const Options &opt, GpuStart &gpu, BatchPool &pool, std::vector<s
       }
     });
   }
-  std::vector<std::thread> analyzers = start_analyzers(gpu.ctxs, need_qual, opt.evidence_file != nullptr, order, to_format, t_gpu);
+  std::vector<std::thread> analyzers = start_analyzers(gpu.ctxs, need_qual, opt.evidence_file != nullptr, opt.candidates_file != nullptr, order, to_format, t_gpu);
   // ordered drain
   int failed = 0;
   double t_out = 0;
@@ -1830,7 +1891,7 @@ int run_sample(const Options &opt, GpuStart &gpu, BatchPool &pool, std::vector<s
   fflush(stdout);
   timeline("pipeline threads joined");
   const char *error = serial_failed                                  ? "shark: cannot open the sample"
-                      : ro.failed()                                  ? "shark: cannot read the sample again for the output (or a batch came back without its evidence)"
+                      : ro.failed()                                  ? "shark: cannot read the sample again for the output (or a batch came back without its evidence or candidates)"
                       : shk::parallel_gunzip_out_of_memory().load() ? "shark: out of memory while inflating the sample"
                                                                      : nullptr;
   if (error) {
@@ -1850,6 +1911,7 @@ int run_sample(const Options &opt, GpuStart &gpu, BatchPool &pool, std::vector<s
   }
   bool written = true;
   const bool evidence_written = !opt.evidence_file || (fclose(opt.evidence_file) == 0 && !ro.evidence_write_failed());
+  const bool candidates_written = !opt.candidates_file || (fclose(opt.candidates_file) == 0 && !ro.candidates_write_failed());
   if (out1) written = w1.close() && written;
   if (out2) written = w2.close() && written;
   text_pool.finish();
@@ -1861,6 +1923,10 @@ int run_sample(const Options &opt, GpuStart &gpu, BatchPool &pool, std::vector<s
   }
   if (!evidence_written) {
     std::cerr << "shark: cannot write the evidence file " << opt.evidence_path << std::endl;
+    return EXIT_FAILURE;
+  }
+  if (!candidates_written) {
+    std::cerr << "shark: cannot write the candidates file " << opt.candidates_path << std::endl;
     return EXIT_FAILURE;
   }
   if (failed) {
@@ -1915,6 +1981,7 @@ int main(int argc, char *argv[])
   // (--evidence: the file is created only once the samples are known to be readable -- a run that fails on its inputs leaves an
   //  earlier evidence file alone)
   if (opt_parsed.evidence_path != "" && samples_can_be_opened(opt_parsed, false)) opt_parsed.evidence_file = fopen(opt_parsed.evidence_path.c_str(), "w");
+  if (opt_parsed.candidates_path != "" && samples_can_be_opened(opt_parsed, false)) opt_parsed.candidates_file = fopen(opt_parsed.candidates_path.c_str(), "w");   // (--candidates: likewise)
   const Options opt = opt_parsed;
   if (opt.verbose) timeline.on();
   timeline("arguments parsed");
@@ -1929,6 +1996,10 @@ int main(int argc, char *argv[])
   if (!samples_can_be_opened(opt)) return EXIT_FAILURE;
   if (opt.evidence_path != "" && !opt.evidence_file) {   // (the samples are there: it is the evidence file that could not be opened)
     std::cerr << "shark: cannot open the evidence file " << opt.evidence_path << std::endl;
+    return EXIT_FAILURE;
+  }
+  if (opt.candidates_path != "" && !opt.candidates_file) {
+    std::cerr << "shark: cannot open the candidates file " << opt.candidates_path << std::endl;
     return EXIT_FAILURE;
   }
 

@@ -112,6 +112,9 @@ static void slot_free(Slot &s)
   hipFree(s.d_seq1); hipFree(s.d_seq2); hipFree(s.d_qual1); hipFree(s.d_qual2); hipFree(s.d_off1); hipFree(s.d_off2);
   hipFree(s.d_count); hipFree(s.d_inl); hipFree(s.d_gene_off); hipFree(s.d_gene_ids);
   hipFree(s.d_long_queue); hipFree(s.d_tie_queue); hipFree(s.d_counters); hipFree(s.d_scan_temp); hipFree(s.d_out); hipFree(s.d_plan); hipFree(s.d_cls_entries); hipFree(s.d_cls_list); hipFree(s.d_cls_share); hipFree(s.d_cls_hist); hipFree(s.d_evid);
+  hipFree(s.d_cand_reads); hipFree(s.d_cand_entries);
+  if (s.h_cand_reads) (void)hipHostFree(s.h_cand_reads);
+  if (s.h_cand_entries) (void)hipHostFree(s.h_cand_entries);
   if (s.h_evid) (void)hipHostFree(s.h_evid);
   if (s.h_counters) (void)hipHostFree(s.h_counters);
   if (s.h_gene_off) (void)hipHostFree(s.h_gene_off);
@@ -137,8 +140,14 @@ static int slot_reserve(Ctx *ctx, Slot &s, uint64_t n)
   if ((rc = ensure_capacity(ctx, &s.d_gene_ids, &s.cap_gene_ids, 2 * n + 4096))) return rc;
   // (evidence mode only: 12 bytes per read that no other batch pays for)
   if (s.evidence && (rc = ensure_capacity(ctx, &s.d_evid, &s.cap_evid, n + 1))) return rc;
+  // (candidates mode only: 8 + 12 m bytes per read; the spare words keep publish_evidence_kernel's 16-byte copies inside)
+  if (s.cand_m && (rc = ensure_capacity(ctx, &s.d_cand_reads, &s.cap_cand_reads, n + 2))) return rc;
+  if (s.cand_m && (rc = ensure_capacity(ctx, &s.d_cand_entries, &s.cap_cand_entries, n * s.cand_m + 2))) return rc;
   ClassifyOut ho{};
   ho.evid = s.evidence ? s.d_evid : nullptr;
+  ho.cand_reads = s.cand_m ? s.d_cand_reads : nullptr;
+  ho.cand_entries = s.cand_m ? s.d_cand_entries : nullptr;
+  ho.cand_m = s.cand_m;
   ho.count = s.d_count; ho.inl = s.d_inl; ho.counters = s.d_counters; ho.long_queue = s.d_long_queue; ho.tie_queue = s.d_tie_queue;
   if (memcmp(&ho, &s.out_shadow, sizeof(ho)) != 0) {
     SHK_HIP(ctx, hipMemcpy(s.d_out, &ho, sizeof(ho), hipMemcpyHostToDevice));
@@ -217,7 +226,7 @@ static int run_long_reads(Ctx *ctx, Slot &s, uint32_t n_long)
   p.work = s.d_long_queue;
   p.n_work = n_long;
   p.work_count = nullptr;
-  return launch_classify_general(ctx, p, false, n_waves, ctx->stream, s.evidence);
+  return launch_classify_general(ctx, p, false, n_waves, ctx->stream, s.evidence, s.cand_m != 0);
 }
 
 // Everything behind the classify kernels, WITHOUT a host round trip: per-read counts -> offsets (scan), inline ids ->
@@ -259,6 +268,14 @@ static int enqueue_tail(Ctx *ctx, Slot &s, bool skip_hist_if_long, bool count_ge
     if ((rc = ensure_pinned(ctx, &s.h_evid, &s.cap_h_evid, n + 1))) return rc;
     if ((rc = launch_publish_evidence(s.d_evid, s.h_evid, n, st))) return rc;
   }
+  // (candidates mode: the headers and the entries, the same way)
+  if (s.cand_m && s.host_batch) {
+    if ((rc = ensure_pinned(ctx, &s.h_cand_reads, &s.cap_h_cand_reads, n + 2))) return rc;
+    if ((rc = ensure_pinned(ctx, &s.h_cand_entries, &s.cap_h_cand_entries, n * s.cand_m + 2))) return rc;
+    if ((rc = launch_publish_words(reinterpret_cast<const uint32_t *>(s.d_cand_reads), reinterpret_cast<uint32_t *>(s.h_cand_reads), 2 * n, st))) return rc;
+    if ((rc = launch_publish_words(reinterpret_cast<const uint32_t *>(s.d_cand_entries), reinterpret_cast<uint32_t *>(s.h_cand_entries), 3 * n * s.cand_m, st)))
+      return rc;
+  }
   SHK_HIP(ctx, hipEventRecord(s.ev_done, st));
   return SHK_OK;
 }
@@ -296,6 +313,7 @@ static int enqueue_classify(Ctx *ctx, Slot &s, const shk_batch *b, uint32_t max_
   const uint64_t n = b->n;
   int rc;
   s.evidence = ctx->evidence;
+  s.cand_m = ctx->cand_m;
   if ((rc = slot_reserve(ctx, s, n))) return rc;
   s.n = n;
   fill_params(ctx, s, b);
@@ -306,8 +324,9 @@ static int enqueue_classify(Ctx *ctx, Slot &s, const shk_batch *b, uint32_t max_
   // an index with a position table: classify_uni_kernel, uniform or not -- unless the batch is known to hold reads of more
   // than 64 staging groups (> 512 bases per pair), which only classify_fast_kernel stages without the general kernel's help
   // (evidence mode: never -- that kernel and anchor_verdict_kernel decide without a read's final coverage and k-mer count; the batch
-  //  takes the evidence instantiation of classify_fast_kernel, and none of the passes in front of the table kernels is made)
-  const bool table_kernel = uni_kernel_available(ctx) && n != 0 && groups_fit && !s.evidence;
+  //  takes the evidence instantiation of classify_fast_kernel, and none of the passes in front of the table kernels is made;
+  //  candidates mode: the same route for the same reason, through the candidates instantiation)
+  const bool table_kernel = uni_kernel_available(ctx) && n != 0 && groups_fit && !s.evidence && !s.cand_m;
   // a batch of mixed lengths on an index whose uniform batches take the exact table in LDS: sorted by the pairs' two lengths on
   // the device and classified class by class (classify_uni_kernel's CLS instantiation) -- when the classes are few enough for
   // the histogram (the caller's bound on the read length says) and, the device decides, full enough; also when the host knows
@@ -414,12 +433,13 @@ static int enqueue_classify(Ctx *ctx, Slot &s, const shk_batch *b, uint32_t max_
     p.work = nullptr;
     p.n_work = n;
     p.work_count = nullptr;
-    if ((rc = launch_classify_general(ctx, p, false, n_waves, st, s.evidence))) return rc;
-    snprintf(ctx->last_kernel, sizeof(ctx->last_kernel), s.evidence ? "classify_general_kernel<wrap, evidence>" : "classify_general_kernel<wrap>");
+    if ((rc = launch_classify_general(ctx, p, false, n_waves, st, s.evidence, s.cand_m != 0))) return rc;
+    snprintf(ctx->last_kernel, sizeof(ctx->last_kernel), s.cand_m ? "classify_general_kernel<wrap, candidates>"
+                                                                   : (s.evidence ? "classify_general_kernel<wrap, evidence>" : "classify_general_kernel<wrap>"));
   }
   if (!ctx->idx.wrap) {
     if (!table_kernel) {
-      if ((rc = launch_classify_fast(ctx, s.p, max_slots, st, s.evidence))) return rc;           // bit-vector probe chains; every index in evidence mode
+      if ((rc = launch_classify_fast(ctx, s.p, max_slots, st, s.evidence, s.cand_m != 0))) return rc;           // bit-vector probe chains; every index in evidence mode
     } else {
       // what the host knows decides the launch; when only the device knows, both are made and one returns at once
       if (uni_mode != UNI_NO && (rc = launch_classify_uni(ctx, s.p, max_slots, 1, st))) return rc;
@@ -479,6 +499,7 @@ static int classify_resident(Ctx *ctx, const shk_batch *b, uint32_t max_read_len
   Slot &s = ctx->slots[PIPE_DEPTH];
   const uint64_t n = b->n;
   ctx->last_evid_valid = false;   // (until this batch's result is handed out)
+  ctx->last_cand_valid = false;
   if (n >= 0xFFFFFFFFull) { ctx->last_error = "batch too large (n must be < 2^32-1)"; return SHK_ERR_ARG; }
   const bool paired = b->seq2 != nullptr;
   const uint32_t max_slots = max_read_len ? slots_for_len(max_read_len, ctx->prm.k, paired) : 0;
@@ -530,6 +551,10 @@ static int classify_resident(Ctx *ctx, const shk_batch *b, uint32_t max_read_len
   ctx->last_evid_valid = s.evidence && wc == nullptr;
   ctx->last_evid = s.d_evid;
   ctx->last_evid_n = n;
+  ctx->last_cand_valid = s.cand_m != 0 && wc == nullptr;
+  ctx->last_cand_m = s.cand_m;
+  ctx->last_cand_reads = s.d_cand_reads;
+  ctx->last_cand_entries = s.d_cand_entries;
   return SHK_OK;
 }
 
@@ -1020,6 +1045,7 @@ int shk_classify_wait(shk_ctx *ctx, uint64_t ticket, shk_result *result)
   Slot &s = ctx->slots[(ticket - 1) % PIPE_DEPTH];
   if (s.ticket != ticket || s.waited) { ctx->last_error = "unknown or already waited ticket"; return SHK_ERR_STATE; }
   ctx->last_evid_valid = false;   // (a batch that is refused below hands out no evidence either, and leaves none of an earlier batch behind)
+  ctx->last_cand_valid = false;
   SHK_HIP(ctx, hipEventSynchronize(s.ev_done));
   bool redone = false;
   int rc = finish_classify(ctx, s, s.long_speculative, true, &redone);
@@ -1046,6 +1072,10 @@ int shk_classify_wait(shk_ctx *ctx, uint64_t ticket, shk_result *result)
   ctx->last_evid_valid = s.evidence;
   ctx->last_evid = s.host_batch ? s.h_evid : s.d_evid;
   ctx->last_evid_n = n;
+  ctx->last_cand_valid = s.cand_m != 0;
+  ctx->last_cand_m = s.cand_m;
+  ctx->last_cand_reads = s.host_batch ? s.h_cand_reads : s.d_cand_reads;
+  ctx->last_cand_entries = s.host_batch ? s.h_cand_entries : s.d_cand_entries;
   return SHK_OK;
 }
 
@@ -1067,6 +1097,30 @@ int shk_evidence_last(const shk_ctx *ctx, shk_evidence *out)
   if (!ctx->last_evid_valid) return SHK_ERR_STATE;
   out->n = ctx->last_evid_n;
   out->reads = ctx->last_evid;
+  return SHK_OK;
+}
+
+int shk_candidates_enable(shk_ctx *ctx, uint32_t m)
+{
+  if (!ctx) return SHK_ERR_ARG;
+  if (m > SHK_MAX_CANDIDATES) { ctx->last_error = "shk_candidates_enable: m must be at most SHK_MAX_CANDIDATES"; return SHK_ERR_ARG; }
+  for (int i = 0; i < PIPE_DEPTH; ++i)
+    if (ctx->slots[i].ticket != 0 && !ctx->slots[i].waited) {
+      ctx->last_error = "shk_candidates_enable: tickets are outstanding (wait for them first)";
+      return SHK_ERR_STATE;
+    }
+  ctx->cand_m = m;
+  return SHK_OK;
+}
+
+int shk_candidates_last(const shk_ctx *ctx, shk_candidates *out)
+{
+  if (!ctx || !out) return SHK_ERR_ARG;
+  if (!ctx->last_cand_valid) return SHK_ERR_STATE;
+  out->n = ctx->last_evid_n;   // (the batch whose result was handed out last: one n for both kinds of record)
+  out->m = ctx->last_cand_m;
+  out->reads = ctx->last_cand_reads;
+  out->entries = ctx->last_cand_entries;
   return SHK_OK;
 }
 

@@ -134,6 +134,10 @@ struct ClassifyOut {
   uint32_t *long_queue;      // read indices that did not fit the fast kernel
   uint32_t *tie_queue;       // 3 words per entry: read index, best cov, best nk
   shk_read_evidence *evid;   // n : {best cov, best nk, valid length} per read -- written by the evidence instantiations only (nullptr otherwise)
+  // candidates mode (written by the candidates instantiations only; nullptr, nullptr, 0 otherwise)
+  shk_read_candidates *cand_reads;   // n : {valid length, genes with a hit}
+  shk_candidate *cand_entries;       // n * cand_m : read i's best cand_m genes in rank order, empty slots last
+  uint32_t cand_m;                   // 1 .. SHK_MAX_CANDIDATES: how many of the kernel's SHK_MAX_CANDIDATES entries are stored
 };
 
 // ---- classify kernel parameters (passed by value) --------------------------
@@ -263,6 +267,8 @@ struct Slot {
   uint32_t *d_gene_off = nullptr; size_t cap_gene_off = 0;
   uint16_t *d_gene_ids = nullptr; size_t cap_gene_ids = 0;
   shk_read_evidence *d_evid = nullptr; size_t cap_evid = 0;   // evidence mode: one record per read (allocated with the first such batch)
+  shk_read_candidates *d_cand_reads = nullptr; size_t cap_cand_reads = 0;   // candidates mode: one header per read and cand_m entries
+  shk_candidate *d_cand_entries = nullptr; size_t cap_cand_entries = 0;     //  (allocated with the first such batch)
   uint32_t *d_long_queue = nullptr; size_t cap_long_queue = 0;
   uint32_t *d_tie_queue = nullptr;  size_t cap_tie_queue = 0;
   uint32_t *d_counters = nullptr;
@@ -281,6 +287,8 @@ struct Slot {
   uint32_t *h_gene_off = nullptr;  size_t cap_h_gene_off = 0;
   uint16_t *h_gene_ids = nullptr;  size_t cap_h_gene_ids = 0;
   shk_read_evidence *h_evid = nullptr; size_t cap_h_evid = 0;   // (host batches in evidence mode; filled by publish_evidence_kernel)
+  shk_read_candidates *h_cand_reads = nullptr; size_t cap_h_cand_reads = 0;   // (host batches in candidates mode; filled by publish_evidence_kernel)
+  shk_candidate *h_cand_entries = nullptr; size_t cap_h_cand_entries = 0;
   hipEvent_t ev_h2d = nullptr, ev_done = nullptr, ev_d2h = nullptr;
   // the batch
   uint64_t ticket = 0;             // 0 = free
@@ -290,6 +298,7 @@ struct Slot {
   uint32_t fast_cap = 0, gen_slots = 0;
   bool host_batch = false;
   bool evidence = false;           // submitted in evidence mode: the evidence instantiations ran and d_evid (h_evid) hold its records
+  uint32_t cand_m = 0;             // submitted in candidates mode with this many entries per read (0: not): the candidates instantiations ran
   bool long_speculative = false;   // (device-resident submit) the caller's length bound was taken on trust: checked in wait
 };
 
@@ -299,9 +308,9 @@ struct Ctx;
 int build_index(Ctx *ctx);
 
 // classify.hip
-int launch_classify_fast(Ctx *ctx, const ClassifyParams &p, uint32_t max_slots, hipStream_t stream, bool evidence = false);
+int launch_classify_fast(Ctx *ctx, const ClassifyParams &p, uint32_t max_slots, hipStream_t stream, bool evidence = false, bool candidates = false);   // candidates: serves evidence too
 const char *probe_mode_name(const Ctx *ctx);
-int launch_classify_general(Ctx *ctx, const ClassifyParams &p, bool emit, unsigned n_waves, hipStream_t stream, bool evidence = false);   // evidence: the non-EMIT pass only
+int launch_classify_general(Ctx *ctx, const ClassifyParams &p, bool emit, unsigned n_waves, hipStream_t stream, bool evidence = false, bool candidates = false);   // evidence, candidates: the non-EMIT pass only
 int launch_gather_inline(const uint32_t *count, const uint16_t *inl, const uint32_t *gene_off, uint16_t *gene_ids, uint64_t n,
                          const uint32_t *counters, hipStream_t stream);
 int launch_finalize_total(const uint64_t *total, uint32_t *counters, uint64_t gene_ids_cap, hipStream_t stream);
@@ -312,6 +321,7 @@ int launch_vouch_check(const ClassifyParams &p, uint32_t L1, uint32_t L2, uint32
 int launch_publish_results(const uint32_t *counters, uint32_t *h_counters, const uint32_t *gene_off, uint32_t *h_gene_off, uint64_t n_off,
                            const uint16_t *gene_ids, uint16_t *h_gene_ids, uint64_t h_ids_cap, const uint32_t *uni_flag, hipStream_t stream);
 int launch_publish_evidence(const shk_read_evidence *evid, shk_read_evidence *h_evid, uint64_t n, hipStream_t stream);
+int launch_publish_words(const uint32_t *src, uint32_t *h_dst, uint64_t n_words, hipStream_t stream);   // the same kernel over any 16-byte aligned words (candidates)
 int launch_classify_uni(Ctx *ctx, const ClassifyParams &p, uint32_t max_slots, int rmode, hipStream_t stream);   // 0 ragged, 1 uniform, 2 by classes (CLS)
 int launch_class_prepass(const ClassifyParams &p, uint32_t slot_cap, uint32_t *flag, hipStream_t stream);   // behind launch_uniform_check: histogram, plan, scatter
 bool class_kernel_available(const Ctx *ctx, uint32_t max_slots);
@@ -377,6 +387,12 @@ struct Ctx {
   bool last_evid_valid = false;
   const shk_read_evidence *last_evid = nullptr;
   uint64_t last_evid_n = 0;
+  // candidates mode (shk_candidates_enable), the same way: cand_m entries per read for the batches submitted from now on (0: off)
+  uint32_t cand_m = 0;
+  bool last_cand_valid = false;
+  uint32_t last_cand_m = 0;
+  const shk_read_candidates *last_cand_reads = nullptr;
+  const shk_candidate *last_cand_entries = nullptr;
 
   // timing
   bool timing = false;
