@@ -261,6 +261,49 @@ int shk_candidates_enable(shk_ctx *ctx, uint32_t m);
  * mode off, if its wait returned an error, behind shk_count_work, or if no batch has been waited for yet.  New: no counterpart. */
 int shk_candidates_last(const shk_ctx *ctx, shk_candidates *out);
 
+/* ---- placement: where in its gene, and on which strand, an assigned read lies ---- */
+/* Per ASSOCIATION (read, gene g) and per mate: the diagonal of g's record that most of the mate's k-mers lie on.  Defined from
+ * sequences alone, never through the filter.  The record of g is the FASTA record whose k-mers pass 2 added under id g
+ * (main.cpp:160-187, numbering quirk included: at most one record per id); positions are 0-based offsets into its bytes.  A mate
+ * is the mate as the classifier sees it -- raw bytes behind the -q mask (FastqSplitter.hpp:70,:104-109), length L counting all
+ * bytes, the joiner 'N' belonging to neither mate.  A window of k characters is valid iff all are bases under to_int
+ * (kmer_utils.hpp:29-41); f is its k-mer, r the reverse complement (kmer_utils.hpp:47-55), min(f, r) its canonical k-mer and
+ * f <= r its orientation bit; a window with f == r takes no part, in the read or in the record.
+ *   votes    slot p of the mate (0 <= p <= L - k) votes iff its canonical k-mer is the canonical k-mer of EXACTLY ONE valid window x
+ *            of the record (k-mers compared in full; none: no vote; two or more: ambiguous, no vote).  The vote is (strand, pos):
+ *            strand = xor of the two orientation bits (0: same direction); pos = x - p for strand 0, x + p + k - L for strand 1 --
+ *            either way the record coordinate of the leftmost record base the whole mate would lie on along that diagonal.  pos may
+ *            be negative, and pos + L may pass the record's end.
+ *   result   the key with the most votes; ties go to strand 0, then to the smaller pos.  support = its votes.  No votes: (0, 0, 0);
+ *            mate 2 of a single-end batch: (0, 0, 0).  A read that reached g through filter false positives alone has support 0.
+ * Not an alignment: nothing is extended across an indel, which shows as lowered support.  New: the reference has no counterpart.
+ *
+ * The mode needs a table of its own, (gene, canonical k-mer) -> the unique x and its orientation, or "ambiguous", built on the
+ * device by shk_ref_finalize when shk_ref_keep_positions was called before (16 bytes per distinct (gene, k-mer) plus a directory
+ * of 4 bytes per bucket).  The classify kernels run unchanged; placement_kernel runs behind them over the reads
+ * that received associations.  gene_off, gene_ids, n_assoc, shk_last_kernel and shk_gene_counts are the same with the mode on
+ * and off; with it off nothing changes at all, and without shk_ref_keep_positions finalize does exactly what it always did. */
+typedef struct shk_mate_placement { int32_t pos; uint32_t support; uint32_t strand; } shk_mate_placement;
+typedef struct shk_placement { shk_mate_placement mate[2]; } shk_placement;   /* one per ASSOCIATION, parallel to gene_ids */
+typedef struct shk_placements {
+  uint64_t             n_assoc;   /* = that result's n_assoc */
+  const shk_placement *entries;   /* entries[j] belongs to gene_ids[j] */
+} shk_placements;
+/* Asks shk_ref_finalize to build the placement table as well.  Before shk_ref_finalize only; SHK_ERR_STATE afterwards.  Finalize
+ * then returns SHK_ERR_INDEX_TOO_LARGE for what the table cannot represent: a record of >= 2^31 bases, a reference of >= 2^32
+ * bases in all, or more than 2^30 distinct (gene, canonical k-mer) pairs.  New: no counterpart. */
+int shk_ref_keep_positions(shk_ctx *ctx);
+/* Switches placement mode on (enable != 0) or off for the batches submitted AFTERWARDS, through any of the four families.
+ * Switching it on returns SHK_ERR_STATE before shk_ref_finalize, on an index finalized without shk_ref_keep_positions, on an index
+ * of more than 65 536 records (ids wrap there and name several records) and, either way, while tickets are outstanding.
+ * Independent of evidence and candidates mode: all three may be on at once.  New: no counterpart. */
+int shk_placement_enable(shk_ctx *ctx, int enable);
+/* The placements of the batch whose result was handed out LAST, with shk_evidence_last's rules: that result's lifetime and memory
+ * space (pinned host memory for host batches, DEVICE memory for resident ones); computed from the final gene_off / gene_ids,
+ * whichever path produced them (batches repaired in shk_classify_wait included).  SHK_ERR_STATE if that batch was submitted with
+ * the mode off, if its wait returned an error, behind shk_count_work, or if no batch has been waited for yet.  New: no counterpart. */
+int shk_placement_last(const shk_ctx *ctx, shk_placements *out);
+
 /* Per-gene number of assigned reads accumulated over all classify calls (all
  * waited tickets) since the last reset (counts[g] for g in [0, 65536)); the quantity all-reduced
  * across GPUs.  n must be <= 65536. */

@@ -47,6 +47,10 @@ class ShkCandidates(C.Structure):
     _fields_ = [("n", C.c_uint64), ("m", C.c_uint32), ("reads", C.c_void_p), ("entries", C.c_void_p)]
 
 
+class ShkPlacements(C.Structure):
+    _fields_ = [("n_assoc", C.c_uint64), ("entries", C.c_void_p)]
+
+
 class ShkWorkCounters(C.Structure):
     _fields_ = [("n_kmers", C.c_uint64), ("n_hits", C.c_uint64), ("n_list_ids", C.c_uint64), ("n_bases", C.c_uint64)]
 
@@ -63,6 +67,7 @@ EXPORTS = [
     "shk_measure_valu_mix_clock",
     "shk_evidence_enable", "shk_evidence_last",
     "shk_candidates_enable", "shk_candidates_last",
+    "shk_ref_keep_positions", "shk_placement_enable", "shk_placement_last",
 ]
 SHK_PIPE_DEPTH = 3
 SHK_DIST_ID_BYTES = 128
@@ -127,6 +132,9 @@ def load():
         "shk_evidence_last": (C.c_int, [p, C.POINTER(ShkEvidence)]),
         "shk_candidates_enable": (C.c_int, [p, C.c_uint32]),
         "shk_candidates_last": (C.c_int, [p, C.POINTER(ShkCandidates)]),
+        "shk_ref_keep_positions": (C.c_int, [p]),
+        "shk_placement_enable": (C.c_int, [p, C.c_int]),
+        "shk_placement_last": (C.c_int, [p, C.POINTER(ShkPlacements)]),
     }
     variant = bool(os.environ.get("SHK_LIB_PATH"))
     for name, (res, args) in later.items():
@@ -191,7 +199,13 @@ class SharkHip:
     def ref_finalize(self):
         return self.L.shk_ref_finalize(self.h)
 
-    def build(self, seqs):
+    def keep_positions(self):
+        """ask ref_finalize / build to build placement mode's table as well (before the index is finalized only)"""
+        self._check(self.L.shk_ref_keep_positions(self.h), "shk_ref_keep_positions")
+
+    def build(self, seqs, keep_positions=False):
+        if keep_positions:
+            self.keep_positions()
         for s in seqs:
             self._check(self.ref_add(s), "shk_ref_add")
         self._check(self.ref_finalize(), "shk_ref_finalize")
@@ -355,6 +369,27 @@ class SharkHip:
         entries = np.ctypeslib.as_array(C.cast(c.entries, C.POINTER(C.c_uint32)), shape=(n, m, 3)).copy()
         return reads, entries
 
+    # ---- placement: per association and mate the best diagonal of the gene's record (strand, pos, support) --------
+    def placement_enable(self, on=True):
+        """batches submitted from now on carry one placement per association (the classify kernels run unchanged, placement_kernel
+        behind them); needs an index built with keep_positions; refused while tickets are outstanding"""
+        self._check(self.L.shk_placement_enable(self.h, int(bool(on))), "shk_placement_enable")
+
+    def placement_last(self):
+        """placements of the batch whose result was handed out last: an (n_assoc, 2, 3) int64 array -- per association (parallel to
+        gene_ids) and mate (strand, pos, support) -- copied from the context's pinned memory for a host batch (classify, wait); for a
+        resident one (classify_device, wait_device) (n_assoc, DEVICE pointer) of 24-byte records {pos i32, support u32, strand u32} x 2
+        -- placements_from_device reads them back.  Raises (SHK_ERR_STATE) when that batch was submitted with the mode off"""
+        pl = ShkPlacements()
+        self._check(self.L.shk_placement_last(self.h, C.byref(pl)), "shk_placement_last")
+        n = int(pl.n_assoc)
+        if not self._last_on_host:
+            return n, pl.entries
+        if n == 0:
+            return np.zeros((0, 2, 3), dtype=np.int64)
+        raw = np.ctypeslib.as_array(C.cast(pl.entries, C.POINTER(C.c_uint32)), shape=(n, 2, 3)).copy()
+        return placements_from_raw(raw)
+
     def gene_counts(self, n=65536):
         a = np.zeros(n, dtype=np.uint64)
         self._check(self.L.shk_gene_counts(self.h, _ptr(a), n), "shk_gene_counts")
@@ -450,6 +485,24 @@ class SharkHip:
         t = ShkTiming()
         self._check(self.L.shk_timing_get(self.h, C.byref(t)), "shk_timing_get")
         return {f: getattr(t, f) for f, _ in ShkTiming._fields_}
+
+
+def placements_from_raw(raw):
+    """(n, 2, 3) uint32 words {pos, support, strand} of shk_placement -> (n, 2, 3) int64 (strand, pos, support)"""
+    raw = np.asarray(raw, dtype=np.uint32).reshape(-1, 2, 3)
+    out = np.empty(raw.shape, dtype=np.int64)
+    out[:, :, 0] = raw[:, :, 2]
+    out[:, :, 1] = raw[:, :, 0].view(np.int32)
+    out[:, :, 2] = raw[:, :, 1]
+    return out
+
+
+def placements_from_device(n_assoc, ptr):
+    """read the records of a resident batch back: (n_assoc, 2, 3) int64 (strand, pos, support)"""
+    raw = np.zeros((n_assoc, 2, 3), dtype=np.uint32)
+    if n_assoc:
+        hip_memcpy_dtoh(raw, ptr, raw.nbytes)
+    return placements_from_raw(raw)
 
 
 _hip = None

@@ -31,15 +31,6 @@ namespace shk {
 enum { MODE_SET = 0, MODE_KEYS = 1 };
 constexpr int RK_THREADS = 256;
 
-// to_int (kmer_utils.hpp:29-41) for one byte: 0..3, or 4 = invalid
-__device__ __forceinline__ uint32_t base_code(uint32_t c)
-{
-  const uint32_t t = c & 0xDFu;
-  const uint32_t code = ((t >> 1) ^ (t >> 2)) & 3u;
-  const uint32_t expect = (0x54474341u >> (8 * code)) & 0xFFu;
-  return expect == t ? code : 4u;
-}
-
 // one thread per base position of the concatenated reference records
 template <int MODE>
 __global__ __launch_bounds__(RK_THREADS) void ref_kmer_kernel(const uint8_t *__restrict__ bytes, uint64_t total,
@@ -913,6 +904,13 @@ int build_index(Ctx *ctx)
     BI_HIP(hipGetLastError());
   }
   BI_HIP(hipStreamSynchronize(st));
+
+  // ---- placement mode's table (shk_ref_keep_positions; placement_build.hip): not a restatement of the filter, built for every index kind ----
+  if (ctx->keep_positions) {
+    if (total >= (1ull << 32)) { cleanup(); ctx->last_error = "reference has >= 2^32 bases"; return SHK_ERR_INDEX_TOO_LARGE; }
+    rc = build_placement_table(ctx, d_bytes, total, d_rec_off, n_rec, d_rec_nidx, d_keys, d_keys_alt);
+    if (rc != SHK_OK) { cleanup(); return rc; }
+  }
 
   cleanup();
 #undef BI_HIP

@@ -128,6 +128,15 @@ __device__ __forceinline__ void classify4(uint32_t w, uint32_t &code4, uint32_t 
   inv4 = x & 0x01010101u;
 }
 
+// the same for one byte: 0..3, or 4 = invalid (the index build and the placement table classify the reference byte by byte)
+__device__ __forceinline__ uint32_t base_code(uint32_t c)
+{
+  const uint32_t t = c & 0xDFu;
+  const uint32_t code = ((t >> 1) ^ (t >> 2)) & 3u;
+  const uint32_t expect = (0x54474341u >> (8 * code)) & 0xFFu;
+  return expect == t ? code : 4u;
+}
+
 // 4 x 2-bit codes (one per byte, first character in the LOW byte) -> 8 bits,
 // first character most significant (kmer_utils.hpp:67-69 packs MSB first).
 __device__ __forceinline__ uint32_t pack4(uint32_t code4) { return (code4 * 0x40100401u) >> 24; }

@@ -76,6 +76,10 @@ const char *USAGE_MESSAGE =
     "                                        genes (coverage, then kmers, then the legend's order), one line per read (pair), in input\n"
     "                                        order (as slow as --evidence; may be combined with it)\n"
     "          --candidates-n M              genes per line of --candidates (default:4, 1 to 8)\n"
+    "          --placements FILE             write <read> <gene> <strand> <pos> <support> per association (paired: the same three for mate 2\n"
+    "                                        behind them), in the order of the output's lines: where in the gene's record and on which\n"
+    "                                        strand each mate lies by its unique k-mers (may be combined with --evidence and\n"
+    "                                        --candidates; not for references of more than 65536 records)\n"
     "      -t N also sets the number of host threads that parse FASTQ / format output (default: up to 16)\n";
 
 struct Options {
@@ -99,6 +103,8 @@ struct Options {
   FILE *candidates_file = nullptr; // (--candidates, likewise)
   unsigned candidates_n = 4;
   bool candidates_n_given = false;
+  std::string placements_path;
+  FILE *placements_file = nullptr; // (--placements, likewise)
 };
 
 // The command line is described by one table: option names, whether a value follows, and a handler that
@@ -185,6 +191,7 @@ const OptionRow OPTION_TABLE[] = {
        o.candidates_n_given = true;
        if (o.candidates_n < 1 || o.candidates_n > SHK_MAX_CANDIDATES) reject(USAGE_MESSAGE, "shark: --candidates-n must be in the range [1, 8].");
      }},
+    {1007, "placements", true, [](Options &o, const char *v) { o.placements_path = value_of<std::string>(v); }},
 };
 
 // Reads per device batch when --batch does not say.  A batch costs the device path 0.5-2 ms of launches, copies and bookkeeping
@@ -375,6 +382,7 @@ struct ReadBatch {
   std::vector<shk_read_candidates> cand_reads;   // (--candidates) one header per read ...
   std::vector<shk_candidate> cand_entries;       // ... and cand_m entries
   uint32_t cand_m = 0;
+  std::vector<shk_placement> placements;         // (--placements) one record per association
   int rc = 0;
   void reset()
   {
@@ -382,7 +390,7 @@ struct ReadBatch {
     qual_as_read1.clear(); qual_as_read2.clear();
     lean = false;
     text.reset();
-    gene_off.clear(); gene_ids.clear(); evidence.clear(); cand_reads.clear(); cand_entries.clear(); cand_m = 0;
+    gene_off.clear(); gene_ids.clear(); evidence.clear(); cand_reads.clear(); cand_entries.clear(); cand_m = 0; placements.clear();
     rc = 0;
   }
 };
@@ -827,7 +835,8 @@ class GzCutter {
 // flight: the copies of the next batches overlap the kernels of the current one (shk_classify_submit / _wait).
 class ReadAnalyzer {
  public:
-  ReadAnalyzer(shk_ctx *ctx, bool need_qual, bool evidence, bool candidates = false) : ctx_(ctx), need_qual_(need_qual), evidence_(evidence), candidates_(candidates) {}
+  ReadAnalyzer(shk_ctx *ctx, bool need_qual, bool evidence, bool candidates = false, bool placements = false)
+      : ctx_(ctx), need_qual_(need_qual), evidence_(evidence), candidates_(candidates), placements_(placements) {}
   // false: the batch failed at once (b.rc is set) and is not in flight
   bool submit(std::unique_ptr<ReadBatch> b)
   {
@@ -877,13 +886,18 @@ class ReadAnalyzer {
           b->cand_entries.assign(cd.entries, cd.entries + cd.n * cd.m);
         }
       }
+      if (placements_ && b->rc == SHK_OK) {
+        shk_placements pl{};
+        b->rc = shk_placement_last(ctx_, &pl);
+        if (b->rc == SHK_OK) b->placements.assign(pl.entries, pl.entries + pl.n_assoc);
+      }
     }
     return b;
   }
 
  private:
   shk_ctx *ctx_;
-  bool need_qual_, evidence_, candidates_;
+  bool need_qual_, evidence_, candidates_, placements_;
   std::deque<std::pair<uint64_t, std::unique_ptr<ReadBatch>>> flying_;
   std::unique_ptr<ReadBatch> failed_;
 };
@@ -993,12 +1007,13 @@ struct FormattedSegment {
   std::string ssv, fq1, fq2;        // fq: the FASTQ records behind the segment's first one
   std::string evd;                  // (--evidence) <id> <cov> <nk> <len> of every read of the segment
   std::string cnd;                  // (--candidates) <id> <len> <n_genes> { <gene> <cov> <nk>} of every read of the segment
+  std::string plc;                  // (--placements) <id> <gene> <strand> <pos> <support> [mate 2's three] of every association of the segment
   std::string head1, head2;         // the first associated read's FASTQ records, printed unless its name equals the carried one
   std::string head_id, last_id;
   bool has_assoc = false, carries = false;
   void reset()
   {
-    ssv.clear(); fq1.clear(); fq2.clear(); evd.clear(); cnd.clear(); head1.clear(); head2.clear(); head_id.clear(); last_id.clear();
+    ssv.clear(); fq1.clear(); fq2.clear(); evd.clear(); cnd.clear(); plc.clear(); head1.clear(); head2.clear(); head_id.clear(); last_id.clear();
     has_assoc = carries = false;
   }
 };
@@ -1048,7 +1063,7 @@ class TextPool {
             st->free.pop_back();
           }
           for (FormattedSegment &sg : q->segs)
-            for (std::string *x : {&sg.ssv, &sg.fq1, &sg.fq2, &sg.evd, &sg.cnd}) drop_pages(*x);
+            for (std::string *x : {&sg.ssv, &sg.fq1, &sg.fq2, &sg.evd, &sg.cnd, &sg.plc}) drop_pages(*x);
           // (the object itself and its small strings are left to the process's end)
         }
       });
@@ -1086,11 +1101,14 @@ class TextPool {
 
 class ReadOutput {
  public:
-  ReadOutput(OffsetWriter *out1, OffsetWriter *out2, const std::vector<std::string> &legend, FILE *evidence = nullptr, FILE *candidates = nullptr)
-      : out1_(out1), out2_(out2), legend_(legend), evidence_(evidence), candidates_(candidates), every_read_(evidence || candidates) {}
+  ReadOutput(OffsetWriter *out1, OffsetWriter *out2, const std::vector<std::string> &legend, FILE *evidence = nullptr, FILE *candidates = nullptr,
+             FILE *placements = nullptr, bool paired = false)
+      : out1_(out1), out2_(out2), legend_(legend), evidence_(evidence), candidates_(candidates), placements_(placements), paired_(paired),
+        every_read_(evidence || candidates) {}
   bool failed() const { return failed_.load(); }
   bool evidence_write_failed() const { return failed_write_; }
   bool candidates_write_failed() const { return failed_write_cand_; }
+  bool placements_write_failed() const { return failed_write_plc_; }
 
   // thread-safe; nothing is written
   void format(const ReadBatch &b, FormattedBatch &out) const
@@ -1165,8 +1183,21 @@ class ReadOutput {
           sg.cnd.push_back('\n');
         }
         if (!assoc) continue;
+        if (placements_ && b.placements.size() != b.gene_ids.size()) failed_ = true;   // (a batch without a record per association: an error exit)
         for (uint32_t j = b.gene_off[i]; j < b.gene_off[i + 1]; ++j) {
           const std::string &gene = legend_[b.gene_ids[j]];
+          if (placements_ && j < b.placements.size()) {
+            // the ssv line's two fields, then per mate the strand, the record coordinate of the mate's leftmost base and the votes
+            char num[96];
+            const shk_placement &pl = b.placements[j];
+            const int w = paired_ ? snprintf(num, sizeof(num), " %u %d %u %u %d %u\n", pl.mate[0].strand, pl.mate[0].pos, pl.mate[0].support,
+                                             pl.mate[1].strand, pl.mate[1].pos, pl.mate[1].support)
+                                  : snprintf(num, sizeof(num), " %u %d %u\n", pl.mate[0].strand, pl.mate[0].pos, pl.mate[0].support);
+            sg.plc.append(id, id_len);
+            sg.plc.push_back(' ');
+            sg.plc.append(gene);
+            sg.plc.append(num, (size_t)w);
+          }
           sg.ssv.append(id, id_len);
           sg.ssv.push_back(' ');
           sg.ssv.append(gene);
@@ -1212,6 +1243,7 @@ class ReadOutput {
       fwrite(sg.ssv.data(), 1, sg.ssv.size(), stdout);
       if (evidence_ && fwrite(sg.evd.data(), 1, sg.evd.size(), evidence_) != sg.evd.size()) failed_write_ = true;
       if (candidates_ && fwrite(sg.cnd.data(), 1, sg.cnd.size(), candidates_) != sg.cnd.size()) failed_write_cand_ = true;
+      if (placements_ && fwrite(sg.plc.data(), 1, sg.plc.size(), placements_) != sg.plc.size()) failed_write_plc_ = true;
       // (ReadOutput.hpp:44-48: a read's FASTQ records are printed unless its name equals the one printed just before it)
       const bool head_repeats = sg.carries && sg.has_assoc && sg.head_id == carry_;
       if (out1_) {
@@ -1253,8 +1285,10 @@ class ReadOutput {
   const std::vector<std::string> &legend_;
   FILE *evidence_;          // (--evidence) written by emit(), in input order
   FILE *candidates_;        // (--candidates) likewise
+  FILE *placements_;        // (--placements) likewise, one line per association
+  bool paired_;             // (--placements) the sample has two files: mate 2's fields are printed
   bool every_read_;         // one of the two: every read is named, not only the associated ones
-  bool failed_write_ = false, failed_write_cand_ = false;
+  bool failed_write_ = false, failed_write_cand_ = false, failed_write_plc_ = false;
   mutable std::atomic<bool> failed_{false};   // a record could not be read back from its file (I/O error)
   std::string carry_;   // previd at the end of the previous batch (only used when a batch starts mid-chunk)
 };
@@ -1694,6 +1728,7 @@ std::string build_index(const Options &opt, GpuStart &gpu, std::vector<std::stri
     shk::FastxRecord rec;
     while (fa.read(rec) >= 0) {
       legend_ID.push_back(rec.name.c_str());
+      if (opt.placements_file && legend_ID.size() > 65536) return "shark: --placements is not available for a reference of more than 65536 records (gene ids wrap there).";
       const size_t len = strnlen(rec.seq.data(), rec.seq.size());  // C-string semantics (main.cpp:164)
       for (auto *ctx : gpu.ctxs) {
         const int rc = shk_ref_add(ctx, rec.seq.data(), len);
@@ -1703,6 +1738,9 @@ std::string build_index(const Options &opt, GpuStart &gpu, std::vector<std::stri
   }
   pelapsed("Transcript file processed");
   timeline("reference read");
+  if (opt.placements_file)
+    for (auto *ctx : gpu.ctxs)
+      if (const int rc = shk_ref_keep_positions(ctx)) return std::string("shark: ") + shk_strerror(rc);
   {
     const size_t n = gpu.ctxs.size();
     std::vector<std::thread> th;
@@ -1752,12 +1790,12 @@ void serial_feed(const Options &opt, const FeedPlan &plan, ParallelFeed &feed, B
 }
 
 // analyzers: one thread per worker, SHK_PIPE_DEPTH batches in flight each; t_gpu[g]: seconds inside shk_classify_submit / _wait
-std::vector<std::thread> start_analyzers(const std::vector<shk_ctx *> &ctxs, bool need_qual, bool evidence, bool candidates, BatchOrder &order, BatchOrder::Queue &to_format, std::vector<double> &t_gpu)
+std::vector<std::thread> start_analyzers(const std::vector<shk_ctx *> &ctxs, bool need_qual, bool evidence, bool candidates, bool placements, BatchOrder &order, BatchOrder::Queue &to_format, std::vector<double> &t_gpu)
 {
   std::vector<std::thread> analyzers;
   for (int g = 0; g < (int)ctxs.size(); ++g) {
-    analyzers.emplace_back([&, g, need_qual, evidence, candidates] {
-      ReadAnalyzer ra(ctxs[(size_t)g], need_qual, evidence, candidates);
+    analyzers.emplace_back([&, g, need_qual, evidence, candidates, placements] {
+      ReadAnalyzer ra(ctxs[(size_t)g], need_qual, evidence, candidates, placements);
       BatchOrder::Queue &todo = order.input(g);
       bool open = true;
       while (open || ra.in_flight()) {
@@ -1812,7 +1850,7 @@ int run_sample(const Options &opt, GpuStart &gpu, BatchPool &pool, std::vector<s
   w1.open(opt.out1_path, write_helpers);
   if (opt.paired_flag && opt.out2_path != "") w2.open(opt.out2_path, write_helpers);
   OffsetWriter *out1 = w1.is_open() ? &w1 : nullptr, *out2 = w2.is_open() ? &w2 : nullptr;
-  ReadOutput ro(out1, out2, legend_ID, opt.evidence_file, opt.candidates_file);
+  ReadOutput ro(out1, out2, legend_ID, opt.evidence_file, opt.candidates_file, opt.placements_file, opt.paired_flag);
   setvbuf(stdout, nullptr, _IOFBF, 1 << 22);
 
   FeedPlan plan(opt, io_threads, need_qual);
@@ -1841,6 +1879,13 @@ int run_sample(const Options &opt, GpuStart &gpu, BatchPool &pool, std::vector<s
         std::cerr << "shark: candidates mode could not be switched on: " << shk_strerror(rc) << std::endl;
         return EXIT_FAILURE;
       }
+  if (opt.placements_file)
+    for (shk_ctx *ctx : gpu.ctxs)
+      if (const int rc = shk_placement_enable(ctx, 1)) {
+        feed.stop();
+        std::cerr << "shark: placement mode could not be switched on: " << shk_strerror(rc) << " " << shk_last_error(ctx) << std::endl;
+        return EXIT_FAILURE;
+      }
   std::unique_ptr<BatchSplitter> fs;
   bool serial_failed = false;
   std::thread splitter([&] { serial_feed(opt, plan, feed, order, pool, fs, serial_failed); });
@@ -1867,7 +1912,7 @@ int run_sample(const Options &opt, GpuStart &gpu, BatchPool &pool, std::vector<s
       }
     });
   }
-  std::vector<std::thread> analyzers = start_analyzers(gpu.ctxs, need_qual, opt.evidence_file != nullptr, opt.candidates_file != nullptr, order, to_format, t_gpu);
+  std::vector<std::thread> analyzers = start_analyzers(gpu.ctxs, need_qual, opt.evidence_file != nullptr, opt.candidates_file != nullptr, opt.placements_file != nullptr, order, to_format, t_gpu);
   // ordered drain
   int failed = 0;
   double t_out = 0;
@@ -1912,6 +1957,7 @@ int run_sample(const Options &opt, GpuStart &gpu, BatchPool &pool, std::vector<s
   bool written = true;
   const bool evidence_written = !opt.evidence_file || (fclose(opt.evidence_file) == 0 && !ro.evidence_write_failed());
   const bool candidates_written = !opt.candidates_file || (fclose(opt.candidates_file) == 0 && !ro.candidates_write_failed());
+  const bool placements_written = !opt.placements_file || (fclose(opt.placements_file) == 0 && !ro.placements_write_failed());
   if (out1) written = w1.close() && written;
   if (out2) written = w2.close() && written;
   text_pool.finish();
@@ -1927,6 +1973,10 @@ int run_sample(const Options &opt, GpuStart &gpu, BatchPool &pool, std::vector<s
   }
   if (!candidates_written) {
     std::cerr << "shark: cannot write the candidates file " << opt.candidates_path << std::endl;
+    return EXIT_FAILURE;
+  }
+  if (!placements_written) {
+    std::cerr << "shark: cannot write the placements file " << opt.placements_path << std::endl;
     return EXIT_FAILURE;
   }
   if (failed) {
@@ -1982,6 +2032,7 @@ int main(int argc, char *argv[])
   //  earlier evidence file alone)
   if (opt_parsed.evidence_path != "" && samples_can_be_opened(opt_parsed, false)) opt_parsed.evidence_file = fopen(opt_parsed.evidence_path.c_str(), "w");
   if (opt_parsed.candidates_path != "" && samples_can_be_opened(opt_parsed, false)) opt_parsed.candidates_file = fopen(opt_parsed.candidates_path.c_str(), "w");   // (--candidates: likewise)
+  if (opt_parsed.placements_path != "" && samples_can_be_opened(opt_parsed, false)) opt_parsed.placements_file = fopen(opt_parsed.placements_path.c_str(), "w");   // (--placements: likewise)
   const Options opt = opt_parsed;
   if (opt.verbose) timeline.on();
   timeline("arguments parsed");
@@ -2000,6 +2051,10 @@ int main(int argc, char *argv[])
   }
   if (opt.candidates_path != "" && !opt.candidates_file) {
     std::cerr << "shark: cannot open the candidates file " << opt.candidates_path << std::endl;
+    return EXIT_FAILURE;
+  }
+  if (opt.placements_path != "" && !opt.placements_file) {
+    std::cerr << "shark: cannot open the placements file " << opt.placements_path << std::endl;
     return EXIT_FAILURE;
   }
 

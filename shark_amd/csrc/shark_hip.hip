@@ -30,6 +30,7 @@ int set_hip_error(Ctx *ctx, hipError_t e, const char *what)
 static void free_index(DeviceIndex &ix)
 {
   hipFree(ix.bf64); hipFree(ix.rank_w); hipFree(ix.ent); hipFree(ix.ids); hipFree(ix.sum32); hipFree(ix.tab); hipFree(ix.lsum32); hipFree(ix.lbig32); hipFree(ix.ltab); hipFree(ix.ref2); hipFree(ix.refpay); hipFree(ix.refext); hipFree(ix.refmul); hipFree(ix.atab); hipFree(ix.ktab);
+  hipFree(ix.ptab); hipFree(ix.pdir);
   ix = DeviceIndex{};
 }
 
@@ -113,6 +114,8 @@ static void slot_free(Slot &s)
   hipFree(s.d_count); hipFree(s.d_inl); hipFree(s.d_gene_off); hipFree(s.d_gene_ids);
   hipFree(s.d_long_queue); hipFree(s.d_tie_queue); hipFree(s.d_counters); hipFree(s.d_scan_temp); hipFree(s.d_out); hipFree(s.d_plan); hipFree(s.d_cls_entries); hipFree(s.d_cls_list); hipFree(s.d_cls_share); hipFree(s.d_cls_hist); hipFree(s.d_evid);
   hipFree(s.d_cand_reads); hipFree(s.d_cand_entries);
+  hipFree(s.d_place);
+  if (s.h_place) (void)hipHostFree(s.h_place);
   if (s.h_cand_reads) (void)hipHostFree(s.h_cand_reads);
   if (s.h_cand_entries) (void)hipHostFree(s.h_cand_entries);
   if (s.h_evid) (void)hipHostFree(s.h_evid);
@@ -276,6 +279,16 @@ static int enqueue_tail(Ctx *ctx, Slot &s, bool skip_hist_if_long, bool count_ge
     if ((rc = launch_publish_words(reinterpret_cast<const uint32_t *>(s.d_cand_entries), reinterpret_cast<uint32_t *>(s.h_cand_entries), 3 * n * s.cand_m, st)))
       return rc;
   }
+  // (placement mode: from the associations as they now stand in gene_off / gene_ids -- a redone batch comes through here again --, one
+  //  record per association; as many fit as gene_ids holds)
+  if (s.placement) {
+    if ((rc = ensure_capacity(ctx, &s.d_place, &s.cap_place, s.cap_gene_ids))) return rc;
+    if ((rc = launch_placement(ctx, s, st))) return rc;
+    if (s.host_batch) {
+      if ((rc = ensure_pinned(ctx, &s.h_place, &s.cap_h_place, s.cap_gene_ids))) return rc;
+      if ((rc = launch_publish_placements(s.d_counters, s.d_place, s.h_place, std::min<uint64_t>(s.cap_h_place, s.cap_place), st))) return rc;
+    }
+  }
   SHK_HIP(ctx, hipEventRecord(s.ev_done, st));
   return SHK_OK;
 }
@@ -314,6 +327,7 @@ static int enqueue_classify(Ctx *ctx, Slot &s, const shk_batch *b, uint32_t max_
   int rc;
   s.evidence = ctx->evidence;
   s.cand_m = ctx->cand_m;
+  s.placement = ctx->placement;
   if ((rc = slot_reserve(ctx, s, n))) return rc;
   s.n = n;
   fill_params(ctx, s, b);
@@ -500,6 +514,7 @@ static int classify_resident(Ctx *ctx, const shk_batch *b, uint32_t max_read_len
   const uint64_t n = b->n;
   ctx->last_evid_valid = false;   // (until this batch's result is handed out)
   ctx->last_cand_valid = false;
+  ctx->last_place_valid = false;
   if (n >= 0xFFFFFFFFull) { ctx->last_error = "batch too large (n must be < 2^32-1)"; return SHK_ERR_ARG; }
   const bool paired = b->seq2 != nullptr;
   const uint32_t max_slots = max_read_len ? slots_for_len(max_read_len, ctx->prm.k, paired) : 0;
@@ -555,6 +570,9 @@ static int classify_resident(Ctx *ctx, const shk_batch *b, uint32_t max_read_len
   ctx->last_cand_m = s.cand_m;
   ctx->last_cand_reads = s.d_cand_reads;
   ctx->last_cand_entries = s.d_cand_entries;
+  ctx->last_place_valid = s.placement && wc == nullptr;
+  ctx->last_place = s.d_place;
+  ctx->last_place_n = n_assoc;
   return SHK_OK;
 }
 
@@ -1046,6 +1064,7 @@ int shk_classify_wait(shk_ctx *ctx, uint64_t ticket, shk_result *result)
   if (s.ticket != ticket || s.waited) { ctx->last_error = "unknown or already waited ticket"; return SHK_ERR_STATE; }
   ctx->last_evid_valid = false;   // (a batch that is refused below hands out no evidence either, and leaves none of an earlier batch behind)
   ctx->last_cand_valid = false;
+  ctx->last_place_valid = false;
   SHK_HIP(ctx, hipEventSynchronize(s.ev_done));
   bool redone = false;
   int rc = finish_classify(ctx, s, s.long_speculative, true, &redone);
@@ -1076,6 +1095,10 @@ int shk_classify_wait(shk_ctx *ctx, uint64_t ticket, shk_result *result)
   ctx->last_cand_m = s.cand_m;
   ctx->last_cand_reads = s.host_batch ? s.h_cand_reads : s.d_cand_reads;
   ctx->last_cand_entries = s.host_batch ? s.h_cand_entries : s.d_cand_entries;
+  if (s.placement && s.host_batch && n_assoc > s.cap_h_place) { ctx->last_error = "placement publication failed"; return SHK_ERR_HIP; }
+  ctx->last_place_valid = s.placement;
+  ctx->last_place = s.host_batch ? s.h_place : s.d_place;
+  ctx->last_place_n = n_assoc;
   return SHK_OK;
 }
 
@@ -1121,6 +1144,40 @@ int shk_candidates_last(const shk_ctx *ctx, shk_candidates *out)
   out->m = ctx->last_cand_m;
   out->reads = ctx->last_cand_reads;
   out->entries = ctx->last_cand_entries;
+  return SHK_OK;
+}
+
+int shk_ref_keep_positions(shk_ctx *ctx)
+{
+  if (!ctx) return SHK_ERR_ARG;
+  if (ctx->mode != 0) { ctx->last_error = "shk_ref_keep_positions: the index is finalized already"; return SHK_ERR_STATE; }
+  ctx->keep_positions = true;
+  return SHK_OK;
+}
+
+int shk_placement_enable(shk_ctx *ctx, int enable)
+{
+  if (!ctx) return SHK_ERR_ARG;
+  for (int i = 0; i < PIPE_DEPTH; ++i)
+    if (ctx->slots[i].ticket != 0 && !ctx->slots[i].waited) {
+      ctx->last_error = "shk_placement_enable: tickets are outstanding (wait for them first)";
+      return SHK_ERR_STATE;
+    }
+  if (enable) {
+    if (ctx->mode != 2) { ctx->last_error = "shk_placement_enable: the index is not finalized"; return SHK_ERR_STATE; }
+    if (!ctx->idx.ptab_lg) { ctx->last_error = "shk_placement_enable: the index was finalized without shk_ref_keep_positions"; return SHK_ERR_STATE; }
+    if (ctx->n_records > 65536 || ctx->idx.wrap) { ctx->last_error = "shk_placement_enable: more than 65 536 records (gene ids wrap)"; return SHK_ERR_STATE; }
+  }
+  ctx->placement = enable != 0;
+  return SHK_OK;
+}
+
+int shk_placement_last(const shk_ctx *ctx, shk_placements *out)
+{
+  if (!ctx || !out) return SHK_ERR_ARG;
+  if (!ctx->last_place_valid) return SHK_ERR_STATE;
+  out->n_assoc = ctx->last_place_n;
+  out->entries = ctx->last_place;
   return SHK_OK;
 }
 

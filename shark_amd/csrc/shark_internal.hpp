@@ -106,7 +106,19 @@ struct DeviceIndex {
   uint32_t ktab_lg = 0;      // log2(buckets); 0 = not built
   uint32_t ktab_w = 0;       // w (the minimiser's length)
   uint64_t ktab_keys = 0;    // keys it holds (reference k-mers + false positives of the filter)
+  // ---- placement mode (shk_ref_keep_positions; placement_build.hip): (gene, canonical k-mer) -> its one window in the gene's record ----
+  //   ptab : one uint4 per DISTINCT (gene, canonical k-mer) of the reference, sorted by the 32-bit hash of the pair (pl_hash32), then
+  //          by the smallest global position of the pair: {k-mer low, k-mer high, x | orientation << 31, gene}; x = the offset of the
+  //          pair's only valid window in its record, orientation = 1 when that window's k-mer is its own canonical form;
+  //          PTAB_AMBIGUOUS in place of x | orientation when the pair has two or more windows.  Windows that are their own reverse
+  //          complement are left out.
+  //   pdir : pdir[b] = the first entry whose hash >> (32 - ptab_lg) is >= b, for b = 0 .. 2^ptab_lg (one more entry = ptab_n)
+  uint4 *ptab = nullptr;
+  uint32_t *pdir = nullptr;
+  uint32_t ptab_lg = 0;      // log2(buckets of pdir); 0 = not built
+  uint64_t ptab_n = 0;       // entries
 };
+constexpr uint32_t PTAB_AMBIGUOUS = 0xFFFFFFFFu;   // (no window has x = 2^31 - 1: a record has fewer than 2^31 bases)
 // Test-only read-back of the arrays above (tests/index_audit.py audits them entry by entry):
 //   extern "C" int shk_debug_index_array(const shk_ctx *, const char *name, void *dst, uint64_t dst_bytes, uint64_t *bytes_needed)
 // copies the named device array to the host exactly as allocated, padding included.  Names: rank_w, ent, ids, sum32, lsum32,
@@ -300,12 +312,23 @@ struct Slot {
   bool evidence = false;           // submitted in evidence mode: the evidence instantiations ran and d_evid (h_evid) hold its records
   uint32_t cand_m = 0;             // submitted in candidates mode with this many entries per read (0: not): the candidates instantiations ran
   bool long_speculative = false;   // (device-resident submit) the caller's length bound was taken on trust: checked in wait
+  // placement mode: one record per association, as many as d_gene_ids holds (allocated with the first such batch)
+  bool placement = false;          // submitted in placement mode: placement_kernel ran behind the assembly and d_place (h_place) hold its records
+  shk_placement *d_place = nullptr; size_t cap_place = 0;
+  shk_placement *h_place = nullptr; size_t cap_h_place = 0;   // (host batches; filled by publish_placements_kernel)
 };
 
 struct Ctx;
 
 // index_build.hip
 int build_index(Ctx *ctx);
+// placement_build.hip: DeviceIndex::ptab / pdir from the uploaded reference (called by build_index while its buffers live; keys_a, keys_b:
+// `total` words each, free for use)
+int build_placement_table(Ctx *ctx, const uint8_t *d_bytes, uint64_t total, const uint64_t *d_rec_off, uint32_t n_rec, const uint32_t *d_rec_nidx,
+                          uint64_t *keys_a, uint64_t *keys_b);
+// placement.hip: per association of the batch in `s` the best diagonal per mate, behind the kernels that wrote gene_off / gene_ids
+int launch_placement(Ctx *ctx, const Slot &s, hipStream_t stream);
+int launch_publish_placements(const uint32_t *counters, const shk_placement *src, shk_placement *h_dst, uint64_t h_cap, hipStream_t stream);
 
 // classify.hip
 int launch_classify_fast(Ctx *ctx, const ClassifyParams &p, uint32_t max_slots, hipStream_t stream, bool evidence = false, bool candidates = false);   // candidates: serves evidence too
@@ -393,6 +416,12 @@ struct Ctx {
   uint32_t last_cand_m = 0;
   const shk_read_candidates *last_cand_reads = nullptr;
   const shk_candidate *last_cand_entries = nullptr;
+  // placement mode (shk_ref_keep_positions, shk_placement_enable), the same way
+  bool keep_positions = false;      // finalize builds DeviceIndex::ptab
+  bool placement = false;
+  bool last_place_valid = false;
+  const shk_placement *last_place = nullptr;
+  uint64_t last_place_n = 0;
 
   // timing
   bool timing = false;
