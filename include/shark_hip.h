@@ -304,6 +304,68 @@ int shk_placement_enable(shk_ctx *ctx, int enable);
  * the mode off, if its wait returned an error, behind shk_count_work, or if no batch has been waited for yet.  New: no counterpart. */
 int shk_placement_last(const shk_ctx *ctx, shk_placements *out);
 
+/* ---- depth: per-base read depth along each gene, accumulated on the device over all batches ---- */
+/* Rests on placement (above) and inherits its definitions of mate, L, pos, strand and support.  For every association j = (read i,
+ * gene g) of a COUNTED batch and for each mate m of it whose placement has support >= min_support (min_support >= 1), the mate
+ * covers the record coordinates [pos, pos + L) n [0, len_g): L the mate's length in bytes, every byte counting; len_g the length
+ * in bytes of the FASTA record that pass 2 numbered g (main.cpp:160-187; an id without a record -- the numbering quirk -- has
+ * len_g = 0).  The strand plays no part: pos is the leftmost record base on either strand.
+ *   depth[g][x] = the number of such (association, mate) intervals that contain x, summed over all batches counted since the
+ *                 last shk_depth_reset.
+ * So: a pair whose mates overlap counts 2 on the overlap (depth counts mates, not fragments); a read tied over several genes
+ * counts in each of them; a mate with support 0 never counts (a placement reached through filter false positives alone, mate 2
+ * of a single-end batch, a mate shorter than k); an interval that clips to nothing counts nowhere (with support >= 1 at least k
+ * bases of the mate lie inside the record, so this does not arise).  Integer arithmetic, no tolerance anywhere.
+ *
+ * A batch is counted exactly once.  depth_accumulate_kernel runs in the batch's tail behind placement_kernel and skips itself
+ * under the conditions under which the per-gene counters (shk_gene_counts) skip: more associations than the result buffer holds,
+ * or reads beyond a length bound that was taken on trust -- the batch is then counted when shk_classify_wait / shk_classify_device
+ * runs the tail again.  A batch refused in wait is never counted: more than 2^32-1 associations (SHK_ERR_ARG), and a batch of
+ * shk_classify_device_submit whose caller vouched wrongly for its read lengths (the accumulation looks at the device's own verdict
+ * on the vouched lengths and returns; that path itself is unchanged, the per-gene counters of such a batch are what they always
+ * were).  shk_count_work is a measurement: its batch is not counted.
+ *
+ * The state is a difference array on the device, 4 bytes per base of the records that carry an id plus one entry (two atomic adds
+ * per counted mate: +1 at the interval's start, -1 at its end), and a 64-bit counter of counted mates; a read-out scans it into a
+ * second array of that size (allocated by the first read-out) and leaves the state as it is, so accumulation can go on.  Counters
+ * are 32 bits wide and wrap: once more than 2^31-1 mates have been counted since the last reset, every read-out returns
+ * SHK_ERR_INDEX_TOO_LARGE until shk_depth_reset (shk_depth_mates still stores the number).  New: the reference has no counterpart. */
+/* Switches depth mode on with this min_support (>= 1), or off (0), for the batches submitted AFTERWARDS, through any of the four
+ * families.  Switching it on returns SHK_ERR_STATE where shk_placement_enable(ctx, 1) does: before shk_ref_finalize, on an index
+ * finalized without shk_ref_keep_positions, on an index of more than 65 536 records; either way while tickets are outstanding.  The
+ * first enable allocates and clears the state; switching off keeps what has been accumulated, switching on again goes on from it.
+ * Independent of placement, evidence and candidates mode: with depth on and placement off placement_kernel runs all the same (depth
+ * needs its records), shk_placement_last answers SHK_ERR_STATE and no placement is published to pinned memory.  With the mode off
+ * no launch and no allocation is added.  New: no counterpart. */
+int shk_depth_enable(shk_ctx *ctx, uint32_t min_support);
+typedef struct shk_gene_depth {
+  uint32_t len;      /* len_g */
+  uint32_t covered;  /* number of x with depth >= 1 */
+  uint32_t max;      /* the largest depth in the gene */
+  uint32_t pad;
+  uint64_t sum;      /* sum of depth over the gene = the clipped bases of all counted mates */
+} shk_gene_depth;
+/* gene_start[0 .. n_genes] (n_genes + 1 entries, n_genes <= nidx of shk_index_info): the depth of gene g lies at
+ * [gene_start[g], gene_start[g+1]) of the full array, gene_start[g+1] - gene_start[g] = len_g.  A property of the index, not of
+ * the accumulated state: available from shk_ref_finalize on wherever shk_depth_enable can be switched on (SHK_ERR_STATE elsewhere),
+ * tickets outstanding or not.  New: no counterpart. */
+int shk_depth_layout(const shk_ctx *ctx, uint64_t *gene_start, uint32_t n_genes);
+/* The read-outs.  All return SHK_ERR_STATE if the mode was never enabled on this context or while tickets are outstanding, and
+ * SHK_ERR_INDEX_TOO_LARGE behind the overflow guard above; otherwise they run on the context's stream behind everything enqueued
+ * so far and leave the accumulated state untouched.  The scan is kept until a batch adds to the state or the state is reset: read-outs
+ * in a row (gene after gene, or get_all and then the summary) pay for one scan.  New: no counterpart.
+ *   shk_depth_get      depth[0 .. len_g) of one gene (gene < nidx) into host memory; cap (entries) must be at least len_g
+ *   shk_depth_get_all  the whole array, gene_start[nidx] entries (cap at least that): device == 0: `depth` is a host pointer;
+ *                      device != 0: a DEVICE pointer, the copy stays on the device
+ *   shk_depth_summary  out[g] for g < n_genes (n_genes <= nidx), host memory
+ *   shk_depth_mates    the number of counted mates since the last reset */
+int shk_depth_get(shk_ctx *ctx, uint32_t gene, uint32_t *depth, uint64_t cap);
+int shk_depth_get_all(shk_ctx *ctx, uint32_t *depth, uint64_t cap, int device);
+int shk_depth_summary(shk_ctx *ctx, shk_gene_depth *out, uint32_t n_genes);
+int shk_depth_mates(const shk_ctx *ctx, uint64_t *n_mates);
+/* Clears the accumulated depth and the mate counter (the mode stays as it is); the read-outs' state rules.  New: no counterpart. */
+int shk_depth_reset(shk_ctx *ctx);
+
 /* Per-gene number of assigned reads accumulated over all classify calls (all
  * waited tickets) since the last reset (counts[g] for g in [0, 65536)); the quantity all-reduced
  * across GPUs.  n must be <= 65536. */

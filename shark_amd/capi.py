@@ -51,6 +51,10 @@ class ShkPlacements(C.Structure):
     _fields_ = [("n_assoc", C.c_uint64), ("entries", C.c_void_p)]
 
 
+# shk_gene_depth as a numpy record (24 bytes)
+GENE_DEPTH_DTYPE = np.dtype([("len", np.uint32), ("covered", np.uint32), ("max", np.uint32), ("pad", np.uint32), ("sum", np.uint64)])
+
+
 class ShkWorkCounters(C.Structure):
     _fields_ = [("n_kmers", C.c_uint64), ("n_hits", C.c_uint64), ("n_list_ids", C.c_uint64), ("n_bases", C.c_uint64)]
 
@@ -68,6 +72,7 @@ EXPORTS = [
     "shk_evidence_enable", "shk_evidence_last",
     "shk_candidates_enable", "shk_candidates_last",
     "shk_ref_keep_positions", "shk_placement_enable", "shk_placement_last",
+    "shk_depth_enable", "shk_depth_layout", "shk_depth_get", "shk_depth_get_all", "shk_depth_summary", "shk_depth_mates", "shk_depth_reset",
 ]
 SHK_PIPE_DEPTH = 3
 SHK_DIST_ID_BYTES = 128
@@ -135,6 +140,13 @@ def load():
         "shk_ref_keep_positions": (C.c_int, [p]),
         "shk_placement_enable": (C.c_int, [p, C.c_int]),
         "shk_placement_last": (C.c_int, [p, C.POINTER(ShkPlacements)]),
+        "shk_depth_enable": (C.c_int, [p, C.c_uint32]),
+        "shk_depth_layout": (C.c_int, [p, p, C.c_uint32]),
+        "shk_depth_get": (C.c_int, [p, C.c_uint32, p, C.c_uint64]),
+        "shk_depth_get_all": (C.c_int, [p, p, C.c_uint64, C.c_int]),
+        "shk_depth_summary": (C.c_int, [p, p, C.c_uint32]),
+        "shk_depth_mates": (C.c_int, [p, C.POINTER(C.c_uint64)]),
+        "shk_depth_reset": (C.c_int, [p]),
     }
     variant = bool(os.environ.get("SHK_LIB_PATH"))
     for name, (res, args) in later.items():
@@ -389,6 +401,54 @@ class SharkHip:
             return np.zeros((0, 2, 3), dtype=np.int64)
         raw = np.ctypeslib.as_array(C.cast(pl.entries, C.POINTER(C.c_uint32)), shape=(n, 2, 3)).copy()
         return placements_from_raw(raw)
+
+    # ---- depth: per-base read depth along each gene, accumulated on the device over the batches counted since the last reset --------
+    def depth_enable(self, min_support=1):
+        """batches submitted from now on add their placed mates (support >= min_support) to the context's depth state; 0 switches
+        the mode off and keeps the state; needs an index built with keep_positions; refused while tickets are outstanding"""
+        self._check(self.L.shk_depth_enable(self.h, int(min_support)), "shk_depth_enable")
+
+    def depth_layout(self):
+        """gene_start[0 .. nidx] (uint64): the depth of gene g lies at [gene_start[g], gene_start[g + 1]) of depth_all()"""
+        gs = getattr(self, "_depth_layout", None)          # (a property of the finalized index: fetched once)
+        if gs is None:
+            gs = np.zeros(int(self.index_info()["nidx"]) + 1, dtype=np.uint64)
+            self._check(self.L.shk_depth_layout(self.h, _ptr(gs), len(gs) - 1), "shk_depth_layout")
+            self._depth_layout = gs
+        return gs.copy()
+
+    def depth(self, gene):
+        """the depth of one gene: uint32[len_g]"""
+        gs = self.depth_layout()
+        d = np.zeros(int(gs[gene + 1] - gs[gene]) if 0 <= gene < len(gs) - 1 else 0, dtype=np.uint32)     # (no such gene: the call says so)
+        self._check(self.L.shk_depth_get(self.h, int(gene), _ptr(d), len(d)), "shk_depth_get")
+        return d
+
+    def depth_all(self, device_ptr=None):
+        """the depth of every base, gene after gene (depth_layout): a uint32 array; with device_ptr (the address of a DEVICE buffer
+        of at least gene_start[nidx] uint32) the copy stays on the device and the number of entries is returned"""
+        total = int(self.depth_layout()[-1])
+        if device_ptr is not None:
+            self._check(self.L.shk_depth_get_all(self.h, C.c_void_p(device_ptr), total, 1), "shk_depth_get_all")
+            return total
+        d = np.zeros(total, dtype=np.uint32)
+        self._check(self.L.shk_depth_get_all(self.h, _ptr(d), total, 0), "shk_depth_get_all")
+        return d
+
+    def depth_summary(self):
+        """per gene (len, covered, max, pad, sum): a structured array of nidx records (GENE_DEPTH_DTYPE)"""
+        out = np.zeros(int(self.index_info()["nidx"]), dtype=GENE_DEPTH_DTYPE)
+        self._check(self.L.shk_depth_summary(self.h, _ptr(out), len(out)), "shk_depth_summary")
+        return out
+
+    def depth_mates(self):
+        """mates counted since the last reset"""
+        n = C.c_uint64()
+        self._check(self.L.shk_depth_mates(self.h, C.byref(n)), "shk_depth_mates")
+        return int(n.value)
+
+    def depth_reset(self):
+        self._check(self.L.shk_depth_reset(self.h), "shk_depth_reset")
 
     def gene_counts(self, n=65536):
         a = np.zeros(n, dtype=np.uint64)

@@ -910,6 +910,17 @@ int build_index(Ctx *ctx)
     if (total >= (1ull << 32)) { cleanup(); ctx->last_error = "reference has >= 2^32 bases"; return SHK_ERR_INDEX_TOO_LARGE; }
     rc = build_placement_table(ctx, d_bytes, total, d_rec_off, n_rec, d_rec_nidx, d_keys, d_keys_alt);
     if (rc != SHK_OK) { cleanup(); return rc; }
+    // depth mode's layout (depth.hip): where each id's record lies in one array over all bases; an id without a record has length 0.
+    // Only where the mode can be switched on (ids name one record each)
+    if (n_rec <= 65536 && !wrap) {
+      std::vector<uint64_t> gs(nidx + 1, 0);
+      for (uint32_t r = 0; r < n_rec; ++r)
+        if (h_has[r]) gs[h_nidx[r] + 1] = ctx->ref_off[r + 1] - ctx->ref_off[r];
+      for (uint64_t g = 0; g < nidx; ++g) gs[g + 1] += gs[g];
+      BI_HIP(hipMalloc((void **)&ix.gene_start, gs.size() * sizeof(uint64_t)));
+      BI_HIP(hipMemcpy(ix.gene_start, gs.data(), gs.size() * sizeof(uint64_t), hipMemcpyHostToDevice));
+      ctx->gene_start.swap(gs);
+    }
   }
 
   cleanup();

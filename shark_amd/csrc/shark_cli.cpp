@@ -80,6 +80,11 @@ const char *USAGE_MESSAGE =
     "                                        behind them), in the order of the output's lines: where in the gene's record and on which\n"
     "                                        strand each mate lies by its unique k-mers (may be combined with --evidence and\n"
     "                                        --candidates; not for references of more than 65536 records)\n"
+    "          --depth FILE                  write <gene> <start> <end> <depth> per run of equal depth >= 1 (0-based, half-open), genes in\n"
+    "                                        the legend's order: how many placed mates cover each base of each gene's record, summed\n"
+    "                                        over the whole sample on the GPUs (may be combined with --placements, --evidence and\n"
+    "                                        --candidates; not for references of more than 65536 records)\n"
+    "          --depth-min-support N         unique k-mers a mate's placement needs to be counted by --depth (default:1)\n"
     "      -t N also sets the number of host threads that parse FASTQ / format output (default: up to 16)\n";
 
 struct Options {
@@ -105,6 +110,9 @@ struct Options {
   bool candidates_n_given = false;
   std::string placements_path;
   FILE *placements_file = nullptr; // (--placements, likewise)
+  std::string depth_path;
+  FILE *depth_file = nullptr;      // (--depth, likewise; written once, after the last batch)
+  unsigned depth_min_support = 1;
 };
 
 // The command line is described by one table: option names, whether a value follows, and a handler that
@@ -192,6 +200,12 @@ const OptionRow OPTION_TABLE[] = {
        if (o.candidates_n < 1 || o.candidates_n > SHK_MAX_CANDIDATES) reject(USAGE_MESSAGE, "shark: --candidates-n must be in the range [1, 8].");
      }},
     {1007, "placements", true, [](Options &o, const char *v) { o.placements_path = value_of<std::string>(v); }},
+    {1008, "depth", true, [](Options &o, const char *v) { o.depth_path = value_of<std::string>(v); }},
+    {1009, "depth-min-support", true,
+     [](Options &o, const char *v) {
+       o.depth_min_support = value_of<unsigned>(v);
+       if (o.depth_min_support < 1) reject(USAGE_MESSAGE, "shark: --depth-min-support must be at least 1.");
+     }},
 };
 
 // Reads per device batch when --batch does not say.  A batch costs the device path 0.5-2 ms of launches, copies and bookkeeping
@@ -1729,6 +1743,7 @@ std::string build_index(const Options &opt, GpuStart &gpu, std::vector<std::stri
     while (fa.read(rec) >= 0) {
       legend_ID.push_back(rec.name.c_str());
       if (opt.placements_file && legend_ID.size() > 65536) return "shark: --placements is not available for a reference of more than 65536 records (gene ids wrap there).";
+      if (opt.depth_file && legend_ID.size() > 65536) return "shark: --depth is not available for a reference of more than 65536 records (gene ids wrap there).";
       const size_t len = strnlen(rec.seq.data(), rec.seq.size());  // C-string semantics (main.cpp:164)
       for (auto *ctx : gpu.ctxs) {
         const int rc = shk_ref_add(ctx, rec.seq.data(), len);
@@ -1738,7 +1753,7 @@ std::string build_index(const Options &opt, GpuStart &gpu, std::vector<std::stri
   }
   pelapsed("Transcript file processed");
   timeline("reference read");
-  if (opt.placements_file)
+  if (opt.placements_file || opt.depth_file)
     for (auto *ctx : gpu.ctxs)
       if (const int rc = shk_ref_keep_positions(ctx)) return std::string("shark: ") + shk_strerror(rc);
   {
@@ -1886,6 +1901,14 @@ int run_sample(const Options &opt, GpuStart &gpu, BatchPool &pool, std::vector<s
         std::cerr << "shark: placement mode could not be switched on: " << shk_strerror(rc) << " " << shk_last_error(ctx) << std::endl;
         return EXIT_FAILURE;
       }
+  // (--depth: every worker adds its batches' placed mates to its own depth state; write_depth sums the workers' arrays at the end)
+  if (opt.depth_file)
+    for (shk_ctx *ctx : gpu.ctxs)
+      if (const int rc = shk_depth_enable(ctx, opt.depth_min_support)) {
+        feed.stop();
+        std::cerr << "shark: depth mode could not be switched on: " << shk_strerror(rc) << " " << shk_last_error(ctx) << std::endl;
+        return EXIT_FAILURE;
+      }
   std::unique_ptr<BatchSplitter> fs;
   bool serial_failed = false;
   std::thread splitter([&] { serial_feed(opt, plan, feed, order, pool, fs, serial_failed); });
@@ -2022,6 +2045,61 @@ bool gene_counts(const Options &opt, std::vector<shk_ctx *> &ctxs, const std::ve
   return true;
 }
 
+// --depth: the workers' depth arrays (one per context, each over the batches that worker classified) summed on the host -- depth is
+// additive over contexts --, then one line per maximal run of equal depth >= 1: <gene> <start> <end> <depth>, genes in id order
+bool write_depth(const Options &opt, std::vector<shk_ctx *> &ctxs, const std::vector<std::string> &legend_ID)
+{
+  shk_index_info info{};
+  shk_index_info_get(ctxs[0], &info);
+  const uint32_t n_genes = (uint32_t)info.nidx;
+  std::vector<uint64_t> gene_start((size_t)n_genes + 1, 0);
+  int rc = shk_depth_layout(ctxs[0], gene_start.data(), n_genes);
+  if (rc != SHK_OK) {
+    std::cerr << "shark: the depth layout could not be read: " << shk_strerror(rc) << " " << shk_last_error(ctxs[0]) << std::endl;
+    fclose(opt.depth_file);
+    return false;
+  }
+  std::vector<uint32_t> depth((size_t)gene_start[n_genes], 0), part;
+  for (size_t g = 0; g < ctxs.size() && rc == SHK_OK; ++g) {
+    std::vector<uint32_t> &into = g == 0 ? depth : part;
+    into.assign(depth.size(), 0);
+    rc = shk_depth_get_all(ctxs[g], into.data(), into.size(), 0);
+    if (g != 0 && rc == SHK_OK)
+      for (size_t x = 0; x < depth.size(); ++x) depth[x] += part[x];
+    if (rc != SHK_OK) std::cerr << "shark: the depth of worker " << g << " could not be read: " << shk_strerror(rc) << " " << shk_last_error(ctxs[g]) << std::endl;
+  }
+  if (rc != SHK_OK) {
+    fclose(opt.depth_file);
+    return false;
+  }
+  std::string text;
+  bool ok = true;
+  for (uint32_t g = 0; g < n_genes; ++g) {
+    const uint32_t *d = depth.data() + gene_start[g];
+    const uint64_t len = gene_start[g + 1] - gene_start[g];
+    const std::string &name = g < legend_ID.size() ? legend_ID[g] : std::string();
+    for (uint64_t x = 0; x < len;) {
+      uint64_t e = x + 1;
+      while (e < len && d[e] == d[x]) ++e;
+      if (d[x]) {
+        text += name;
+        text += ' '; text += std::to_string(x);
+        text += ' '; text += std::to_string(e);
+        text += ' '; text += std::to_string(d[x]);
+        text += '\n';
+      }
+      x = e;
+    }
+    if (text.size() > (1u << 20) || g + 1 == n_genes) {
+      ok = ok && fwrite(text.data(), 1, text.size(), opt.depth_file) == text.size();
+      text.clear();
+    }
+  }
+  ok = (fclose(opt.depth_file) == 0) && ok;
+  if (!ok) std::cerr << "shark: cannot write the depth file " << opt.depth_path << std::endl;
+  return ok;
+}
+
 }  // namespace
 
 int main(int argc, char *argv[])
@@ -2033,6 +2111,7 @@ int main(int argc, char *argv[])
   if (opt_parsed.evidence_path != "" && samples_can_be_opened(opt_parsed, false)) opt_parsed.evidence_file = fopen(opt_parsed.evidence_path.c_str(), "w");
   if (opt_parsed.candidates_path != "" && samples_can_be_opened(opt_parsed, false)) opt_parsed.candidates_file = fopen(opt_parsed.candidates_path.c_str(), "w");   // (--candidates: likewise)
   if (opt_parsed.placements_path != "" && samples_can_be_opened(opt_parsed, false)) opt_parsed.placements_file = fopen(opt_parsed.placements_path.c_str(), "w");   // (--placements: likewise)
+  if (opt_parsed.depth_path != "" && samples_can_be_opened(opt_parsed, false)) opt_parsed.depth_file = fopen(opt_parsed.depth_path.c_str(), "w");   // (--depth: likewise)
   const Options opt = opt_parsed;
   if (opt.verbose) timeline.on();
   timeline("arguments parsed");
@@ -2058,12 +2137,18 @@ int main(int argc, char *argv[])
     return EXIT_FAILURE;
   }
 
+  if (opt.depth_path != "" && !opt.depth_file) {
+    std::cerr << "shark: cannot open the depth file " << opt.depth_path << std::endl;
+    return EXIT_FAILURE;
+  }
+
   BatchPool &pool = *new BatchPool;     // (never destroyed: the process leaves through _exit)
   GpuStart gpu(opt, pool);              // the contexts come up on a thread of their own from here on
   std::vector<std::string> legend_ID;   // gene names in file order (FastaSplitter.hpp:48); filled by build_index, read by the output stage
   if (const int rc = run_sample(opt, gpu, pool, legend_ID)) return rc;
   timeline("outputs closed");
   pelapsed("Sample completed");
+  if (opt.depth_file && !write_depth(opt, gpu.ctxs, legend_ID)) return EXIT_FAILURE;
 
   if ((opt.gene_counts_path != "" || (opt.verbose && opt.gpus > 1)) && !gene_counts(opt, gpu.ctxs, legend_ID)) return EXIT_FAILURE;
   if (opt.verbose) {

@@ -30,7 +30,7 @@ int set_hip_error(Ctx *ctx, hipError_t e, const char *what)
 static void free_index(DeviceIndex &ix)
 {
   hipFree(ix.bf64); hipFree(ix.rank_w); hipFree(ix.ent); hipFree(ix.ids); hipFree(ix.sum32); hipFree(ix.tab); hipFree(ix.lsum32); hipFree(ix.lbig32); hipFree(ix.ltab); hipFree(ix.ref2); hipFree(ix.refpay); hipFree(ix.refext); hipFree(ix.refmul); hipFree(ix.atab); hipFree(ix.ktab);
-  hipFree(ix.ptab); hipFree(ix.pdir);
+  hipFree(ix.ptab); hipFree(ix.pdir); hipFree(ix.gene_start);
   ix = DeviceIndex{};
 }
 
@@ -281,10 +281,13 @@ static int enqueue_tail(Ctx *ctx, Slot &s, bool skip_hist_if_long, bool count_ge
   }
   // (placement mode: from the associations as they now stand in gene_off / gene_ids -- a redone batch comes through here again --, one
   //  record per association; as many fit as gene_ids holds)
-  if (s.placement) {
+  // (depth mode needs the records as well: the kernel runs for either mode, only placement mode hands its records out; the batch is added
+  //  to the depth state behind it, under gene_hist_kernel's rule for a batch that comes through here again)
+  if (s.placement || s.depth) {
     if ((rc = ensure_capacity(ctx, &s.d_place, &s.cap_place, s.cap_gene_ids))) return rc;
     if ((rc = launch_placement(ctx, s, st))) return rc;
-    if (s.host_batch) {
+    if (s.depth && (rc = launch_depth_accumulate(ctx, s, skip_hist_if_long, st))) return rc;
+    if (s.placement && s.host_batch) {
       if ((rc = ensure_pinned(ctx, &s.h_place, &s.cap_h_place, s.cap_gene_ids))) return rc;
       if ((rc = launch_publish_placements(s.d_counters, s.d_place, s.h_place, std::min<uint64_t>(s.cap_h_place, s.cap_place), st))) return rc;
     }
@@ -328,6 +331,7 @@ static int enqueue_classify(Ctx *ctx, Slot &s, const shk_batch *b, uint32_t max_
   s.evidence = ctx->evidence;
   s.cand_m = ctx->cand_m;
   s.placement = ctx->placement;
+  s.depth = count_genes ? ctx->depth : 0u;   // (shk_count_work is a measurement: its batch is not counted)
   if ((rc = slot_reserve(ctx, s, n))) return rc;
   s.n = n;
   fill_params(ctx, s, b);
@@ -754,6 +758,7 @@ void shk_destroy(shk_ctx *ctx)
   free_index(ctx->idx);
   for (Slot &sl : ctx->slots) slot_free(sl);
   hipFree(ctx->d_scratch); hipFree(ctx->d_gene_counts); hipFree(ctx->d_gene_totals); hipFree(ctx->d_work_counters);
+  hipFree(ctx->d_depth_diff); hipFree(ctx->d_depth_mates); hipFree(ctx->d_depth_scan); hipFree(ctx->d_depth_scan_temp); hipFree(ctx->d_depth_summary);
   dist_release(ctx);
   for (auto e : ctx->ev_start) (void)hipEventDestroy(e);
   for (auto e : ctx->ev_stop) (void)hipEventDestroy(e);
@@ -1178,6 +1183,124 @@ int shk_placement_last(const shk_ctx *ctx, shk_placements *out)
   if (!ctx->last_place_valid) return SHK_ERR_STATE;
   out->n_assoc = ctx->last_place_n;
   out->entries = ctx->last_place;
+  return SHK_OK;
+}
+
+// ---- depth mode (depth.hip): the state lives in the context, the batches' tails add to it ----
+static bool tickets_outstanding(const shk_ctx *ctx)
+{
+  for (int i = 0; i < PIPE_DEPTH; ++i)
+    if (ctx->slots[i].ticket != 0 && !ctx->slots[i].waited) return true;
+  return false;
+}
+
+int shk_depth_enable(shk_ctx *ctx, uint32_t min_support)
+{
+  if (!ctx) return SHK_ERR_ARG;
+  if (tickets_outstanding(ctx)) { ctx->last_error = "shk_depth_enable: tickets are outstanding (wait for them first)"; return SHK_ERR_STATE; }
+  if (min_support) {
+    if (ctx->mode != 2) { ctx->last_error = "shk_depth_enable: the index is not finalized"; return SHK_ERR_STATE; }
+    if (!ctx->idx.ptab_lg) { ctx->last_error = "shk_depth_enable: the index was finalized without shk_ref_keep_positions"; return SHK_ERR_STATE; }
+    if (ctx->n_records > 65536 || ctx->idx.wrap || !ctx->idx.gene_start) { ctx->last_error = "shk_depth_enable: more than 65 536 records (gene ids wrap)"; return SHK_ERR_STATE; }
+    if (!ctx->d_depth_diff) {
+      SHK_HIP(ctx, hipSetDevice(ctx->prm.device));
+      const size_t bytes = (size_t)(ctx->gene_start.back() + 1) * sizeof(uint32_t);
+      uint32_t *diff = nullptr;
+      unsigned long long *mates = nullptr;
+      SHK_HIP(ctx, hipMalloc((void **)&diff, bytes));
+      if (hipError_t e = hipMalloc((void **)&mates, sizeof(unsigned long long))) { (void)hipFree(diff); return set_hip_error(ctx, e, "hipMalloc"); }
+      ctx->d_depth_diff = diff;
+      ctx->d_depth_mates = mates;
+      SHK_HIP(ctx, hipMemsetAsync(diff, 0, bytes, ctx->stream));
+      SHK_HIP(ctx, hipMemsetAsync(mates, 0, sizeof(unsigned long long), ctx->stream));
+    }
+  }
+  ctx->depth = min_support;
+  return SHK_OK;
+}
+
+int shk_depth_layout(const shk_ctx *ctx, uint64_t *gene_start, uint32_t n_genes)
+{
+  if (!ctx || !gene_start) return SHK_ERR_ARG;
+  if (ctx->mode != 2 || ctx->gene_start.empty()) return SHK_ERR_STATE;
+  if ((uint64_t)n_genes + 1 > ctx->gene_start.size()) return SHK_ERR_ARG;
+  memcpy(gene_start, ctx->gene_start.data(), ((size_t)n_genes + 1) * sizeof(uint64_t));
+  return SHK_OK;
+}
+
+// what every read-out starts with: the state rules, the stream drained behind everything enqueued so far, the mate counter and its guard
+static int depth_read_mates(shk_ctx *ctx, const char *who, uint64_t *n_mates)
+{
+  if (!ctx->d_depth_diff) { ctx->last_error = std::string(who) + ": depth mode was never enabled on this context"; return SHK_ERR_STATE; }
+  if (tickets_outstanding(ctx)) { ctx->last_error = std::string(who) + ": tickets are outstanding (wait for them first)"; return SHK_ERR_STATE; }
+  SHK_HIP(ctx, hipSetDevice(ctx->prm.device));
+  unsigned long long m = 0;
+  SHK_HIP(ctx, hipMemcpyAsync(&m, ctx->d_depth_mates, sizeof(m), hipMemcpyDeviceToHost, ctx->stream));
+  SHK_HIP(ctx, hipStreamSynchronize(ctx->stream));
+  if (n_mates) *n_mates = m;
+  if (m > 0x7FFFFFFFull) { ctx->last_error = std::string(who) + ": more than 2^31-1 mates counted since the last reset (32-bit depth counters)"; return SHK_ERR_INDEX_TOO_LARGE; }
+  return SHK_OK;
+}
+
+int shk_depth_mates(const shk_ctx *cctx, uint64_t *n_mates)
+{
+  if (!cctx || !n_mates) return SHK_ERR_ARG;
+  return depth_read_mates(const_cast<shk_ctx *>(cctx), "shk_depth_mates", n_mates);
+}
+
+int shk_depth_get_all(shk_ctx *ctx, uint32_t *depth, uint64_t cap, int device)
+{
+  if (!ctx) return SHK_ERR_ARG;
+  int rc = depth_read_mates(ctx, "shk_depth_get_all", nullptr);
+  if (rc) return rc;
+  const uint64_t total = ctx->gene_start.back();
+  if (cap < total || (!depth && total)) return SHK_ERR_ARG;
+  if (total == 0) return SHK_OK;
+  if ((rc = depth_scan(ctx))) return rc;
+  SHK_HIP(ctx, hipMemcpyAsync(depth, ctx->d_depth_scan + 1, total * sizeof(uint32_t), device ? hipMemcpyDeviceToDevice : hipMemcpyDeviceToHost, ctx->stream));
+  SHK_HIP(ctx, hipStreamSynchronize(ctx->stream));
+  return SHK_OK;
+}
+
+int shk_depth_get(shk_ctx *ctx, uint32_t gene, uint32_t *depth, uint64_t cap)
+{
+  if (!ctx) return SHK_ERR_ARG;
+  int rc = depth_read_mates(ctx, "shk_depth_get", nullptr);
+  if (rc) return rc;
+  if ((uint64_t)gene + 1 >= ctx->gene_start.size()) return SHK_ERR_ARG;
+  const uint64_t a = ctx->gene_start[gene], len = ctx->gene_start[gene + 1] - a;
+  if (cap < len || (!depth && len)) return SHK_ERR_ARG;
+  if (len == 0) return SHK_OK;
+  if ((rc = depth_scan(ctx))) return rc;
+  SHK_HIP(ctx, hipMemcpyAsync(depth, ctx->d_depth_scan + 1 + a, len * sizeof(uint32_t), hipMemcpyDeviceToHost, ctx->stream));
+  SHK_HIP(ctx, hipStreamSynchronize(ctx->stream));
+  return SHK_OK;
+}
+
+int shk_depth_summary(shk_ctx *ctx, shk_gene_depth *out, uint32_t n_genes)
+{
+  if (!ctx || (!out && n_genes)) return SHK_ERR_ARG;
+  int rc = depth_read_mates(ctx, "shk_depth_summary", nullptr);
+  if (rc) return rc;
+  if ((uint64_t)n_genes + 1 > ctx->gene_start.size()) return SHK_ERR_ARG;
+  if (n_genes == 0) return SHK_OK;
+  if ((rc = depth_scan(ctx))) return rc;
+  if ((rc = launch_depth_summary(ctx))) return rc;
+  SHK_HIP(ctx, hipMemcpyAsync(out, ctx->d_depth_summary, (size_t)n_genes * sizeof(shk_gene_depth), hipMemcpyDeviceToHost, ctx->stream));
+  SHK_HIP(ctx, hipStreamSynchronize(ctx->stream));
+  return SHK_OK;
+}
+
+int shk_depth_reset(shk_ctx *ctx)
+{
+  if (!ctx) return SHK_ERR_ARG;
+  if (!ctx->d_depth_diff) { ctx->last_error = "shk_depth_reset: depth mode was never enabled on this context"; return SHK_ERR_STATE; }
+  if (tickets_outstanding(ctx)) { ctx->last_error = "shk_depth_reset: tickets are outstanding (wait for them first)"; return SHK_ERR_STATE; }
+  SHK_HIP(ctx, hipSetDevice(ctx->prm.device));
+  SHK_HIP(ctx, hipMemsetAsync(ctx->d_depth_diff, 0, (size_t)(ctx->gene_start.back() + 1) * sizeof(uint32_t), ctx->stream));
+  SHK_HIP(ctx, hipMemsetAsync(ctx->d_depth_mates, 0, sizeof(unsigned long long), ctx->stream));
+  ctx->depth_scan_current = false;
+  SHK_HIP(ctx, hipStreamSynchronize(ctx->stream));
   return SHK_OK;
 }
 

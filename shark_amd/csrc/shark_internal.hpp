@@ -117,6 +117,9 @@ struct DeviceIndex {
   uint32_t *pdir = nullptr;
   uint32_t ptab_lg = 0;      // log2(buckets of pdir); 0 = not built
   uint64_t ptab_n = 0;       // entries
+  // ---- depth mode (depth.hip): gene_start[g] = bases of the records numbered below g, g = 0 .. nidx (nidx + 1 entries); built
+  //      with ptab for an index of at most 65 536 records (where the mode can be switched on), nullptr otherwise ----
+  uint64_t *gene_start = nullptr;
 };
 constexpr uint32_t PTAB_AMBIGUOUS = 0xFFFFFFFFu;   // (no window has x = 2^31 - 1: a record has fewer than 2^31 bases)
 // Test-only read-back of the arrays above (tests/index_audit.py audits them entry by entry):
@@ -316,6 +319,8 @@ struct Slot {
   bool placement = false;          // submitted in placement mode: placement_kernel ran behind the assembly and d_place (h_place) hold its records
   shk_placement *d_place = nullptr; size_t cap_place = 0;
   shk_placement *h_place = nullptr; size_t cap_h_place = 0;   // (host batches; filled by publish_placements_kernel)
+  // depth mode: submitted with this min_support (0: not): placement_kernel ran (d_place holds its records) and depth_accumulate_kernel behind it
+  uint32_t depth = 0;
 };
 
 struct Ctx;
@@ -329,6 +334,12 @@ int build_placement_table(Ctx *ctx, const uint8_t *d_bytes, uint64_t total, cons
 // placement.hip: per association of the batch in `s` the best diagonal per mate, behind the kernels that wrote gene_off / gene_ids
 int launch_placement(Ctx *ctx, const Slot &s, hipStream_t stream);
 int launch_publish_placements(const uint32_t *counters, const shk_placement *src, shk_placement *h_dst, uint64_t h_cap, hipStream_t stream);
+// depth.hip: the batch in `s` (its placements in s.d_place) into the context's difference array, behind launch_placement; skip_if_long: as launch_gene_hist
+int launch_depth_accumulate(Ctx *ctx, const Slot &s, bool skip_if_long, hipStream_t stream);
+// the read-out: Ctx::d_depth_scan[1 + x] = depth of base x of the full array (inclusive prefix sum of the difference array), on ctx->stream
+int depth_scan(Ctx *ctx);
+// per gene {len, covered, max, sum} of the scanned array into Ctx::d_depth_summary (nidx records), on ctx->stream behind depth_scan
+int launch_depth_summary(Ctx *ctx);
 
 // classify.hip
 int launch_classify_fast(Ctx *ctx, const ClassifyParams &p, uint32_t max_slots, hipStream_t stream, bool evidence = false, bool candidates = false);   // candidates: serves evidence too
@@ -422,6 +433,15 @@ struct Ctx {
   bool last_place_valid = false;
   const shk_placement *last_place = nullptr;
   uint64_t last_place_n = 0;
+  // depth mode (shk_depth_enable; depth.hip): the state outlives the mode's being switched off
+  std::vector<uint64_t> gene_start;            // host copy of DeviceIndex::gene_start (empty: the index carries none)
+  uint32_t depth = 0;                          // min_support for the batches submitted from now on (0: off)
+  uint32_t *d_depth_diff = nullptr;            // gene_start[nidx] + 1 entries: +1 at a counted mate's first base, -1 behind its last (allocated by the first enable)
+  unsigned long long *d_depth_mates = nullptr; // counted mates since the last reset
+  uint32_t *d_depth_scan = nullptr;            // read-out: exclusive scan of d_depth_diff over all its entries; depth of base x at [1 + x] (allocated by the first read-out)
+  uint64_t *d_depth_scan_temp = nullptr;
+  bool depth_scan_current = false;             // d_depth_scan holds the scan of the state as it stands (cleared by every launch that adds to it and by reset)
+  shk_gene_depth *d_depth_summary = nullptr;   // nidx records (allocated by the first shk_depth_summary)
 
   // timing
   bool timing = false;
