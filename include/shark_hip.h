@@ -304,6 +304,62 @@ int shk_placement_enable(shk_ctx *ctx, int enable);
  * the mode off, if its wait returned an error, behind shk_count_work, or if no batch has been waited for yet.  New: no counterpart. */
 int shk_placement_last(const shk_ctx *ctx, shk_placements *out);
 
+/* ---- segments: the several diagonals of its gene's record a mate lies on, and the slots that say so ---- */
+/* The references are gene loci -- genomic sequence, introns included -- and the reads are RNA-Seq: a mate that crosses an exon
+ * junction lies on two or more diagonals of its gene's record, an intron apart.  Placement (above) keeps the diagonal with the
+ * most votes; segments mode hands out the best m of them.  It rests on placement's definitions, unchanged: mate, L, window, vote
+ * and key (strand, pos).
+ *
+ * Per ASSOCIATION (read, gene g) and per mate let K be the set of distinct keys that received at least one vote.  Per key:
+ *   support   its votes
+ *   first     the smallest slot p that voted for it
+ *   last      the largest slot p that voted for it (first <= last <= L - k; votes need not be contiguous in between)
+ * The keys are ranked by support descending, then strand 0 first, then the smaller pos -- placement's tie rule, so rank 0 is
+ * exactly the mate's shk_mate_placement.  With m entries per mate (1 <= m <= SHK_MAX_SEGMENTS) the first m ranks leave the device
+ * together with n_keys = |K|, which may exceed m.  Slots behind the last key are empty (all five words 0: a segment has
+ * support >= 1).  No votes, a mate shorter than k, mate 2 of a single-end batch: n_keys = 0 and m empty slots.  Nothing is
+ * filtered on the device by strand or by a support floor: that is the consumer's choice.  Integers, no tolerance anywhere.
+ *
+ * Junctions are a pure function of the segments, computed by the consumer (shark --junctions, shark_amd.capi.junctions).  The
+ * record span [lo, hi) of a segment is the union of the record windows its first and last voting slots lie on:
+ *   strand 0: lo = pos + first,         hi = pos + last + k
+ *   strand 1: lo = pos + L - k - last,  hi = pos + L - first
+ * For one mate and a support floor s_min:
+ *   1. take its reported segments with support >= s_min and rank 0's strand (rank 0 itself included only if it reaches s_min);
+ *   2. sort them by (lo, hi);
+ *   3. every consecutive pair (A, B) with pos_B > pos_A is a junction
+ *        (g, donor = hi_A, acceptor = lo_B, intron = pos_B - pos_A, overlap = hi_A + intron - lo_B).
+ * overlap is signed: positive, read bases that both sides explain (microhomology at the junction: the breakpoint lies anywhere in
+ * it); negative, read bases that neither side explains (a substitution within k of the junction silences the windows over it).
+ * A table of junctions over many mates is keyed by (g, donor, acceptor) and counts the mates that show each; where mates disagree on
+ * the intron of one key (an indel in a read next to the junction moves its second diagonal) the key carries the smallest intron.
+ * Example (L = 100, k = 17): strand 1, pos 9653, slots 26..83 and strand 1, pos 10843, slots 0..14 give spans [9653, 9727) and
+ * [10912, 10943): donor 9727, acceptor 10912, intron 1190, overlap 5.
+ *
+ * The mode needs placement's table (shk_ref_keep_positions) and nothing else of placement mode: segments_kernel runs behind the
+ * classify kernels over the reads that received associations, from the final gene_off / gene_ids whichever path produced them
+ * (batches repaired in shk_classify_wait included), and stores 8 + 40 m bytes per association.  Independent of evidence,
+ * candidates, placement and depth mode: all may be on at once, then entry 0 equals shk_placement_last's record.  gene_off,
+ * gene_ids, n_assoc, shk_last_kernel, shk_gene_counts and the other modes' records are the same with the mode on and off; with it
+ * off no launch and no allocation is added.  New: the reference has no counterpart. */
+#define SHK_MAX_SEGMENTS 4
+typedef struct shk_segment { int32_t pos; uint32_t support, strand, first, last; } shk_segment;   /* support == 0: empty slot (all five 0) */
+typedef struct shk_segments {
+  uint64_t           n_assoc;  /* = that result's n_assoc */
+  uint32_t           m;        /* entries per mate */
+  const uint32_t    *n_keys;   /* n_assoc * 2:     [j*2 + mate],          j parallel to gene_ids */
+  const shk_segment *entries;  /* n_assoc * 2 * m: [(j*2 + mate)*m + r],  rank order, empty slots last */
+} shk_segments;
+/* Switches segments mode on with m entries per mate (1 .. SHK_MAX_SEGMENTS) or off (m = 0) for the batches submitted AFTERWARDS,
+ * through any of the four families.  SHK_ERR_ARG for m > SHK_MAX_SEGMENTS.  Switching it on returns SHK_ERR_STATE where
+ * shk_placement_enable(ctx, 1) does: before shk_ref_finalize, on an index finalized without shk_ref_keep_positions, on an index of
+ * more than 65 536 records; either way while tickets are outstanding.  New: no counterpart. */
+int shk_segments_enable(shk_ctx *ctx, uint32_t m);
+/* The segments of the batch whose result was handed out LAST, with shk_placement_last's rules: that result's lifetime and memory
+ * space (pinned host memory for host batches, DEVICE memory for resident ones).  SHK_ERR_STATE if that batch was submitted with
+ * the mode off, if its wait returned an error, behind shk_count_work, or if no batch has been waited for yet.  New: no counterpart. */
+int shk_segments_last(const shk_ctx *ctx, shk_segments *out);
+
 /* ---- depth: per-base read depth along each gene, accumulated on the device over all batches ---- */
 /* Rests on placement (above) and inherits its definitions of mate, L, pos, strand and support.  For every association j = (read i,
  * gene g) of a COUNTED batch and for each mate m of it whose placement has support >= min_support (min_support >= 1), the mate

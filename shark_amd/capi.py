@@ -51,6 +51,10 @@ class ShkPlacements(C.Structure):
     _fields_ = [("n_assoc", C.c_uint64), ("entries", C.c_void_p)]
 
 
+class ShkSegments(C.Structure):
+    _fields_ = [("n_assoc", C.c_uint64), ("m", C.c_uint32), ("n_keys", C.c_void_p), ("entries", C.c_void_p)]
+
+
 # shk_gene_depth as a numpy record (24 bytes)
 GENE_DEPTH_DTYPE = np.dtype([("len", np.uint32), ("covered", np.uint32), ("max", np.uint32), ("pad", np.uint32), ("sum", np.uint64)])
 
@@ -72,11 +76,13 @@ EXPORTS = [
     "shk_evidence_enable", "shk_evidence_last",
     "shk_candidates_enable", "shk_candidates_last",
     "shk_ref_keep_positions", "shk_placement_enable", "shk_placement_last",
+    "shk_segments_enable", "shk_segments_last",
     "shk_depth_enable", "shk_depth_layout", "shk_depth_get", "shk_depth_get_all", "shk_depth_summary", "shk_depth_mates", "shk_depth_reset",
 ]
 SHK_PIPE_DEPTH = 3
 SHK_DIST_ID_BYTES = 128
 SHK_MAX_CANDIDATES = 8
+SHK_MAX_SEGMENTS = 4
 
 _lib = None
 
@@ -140,6 +146,8 @@ def load():
         "shk_ref_keep_positions": (C.c_int, [p]),
         "shk_placement_enable": (C.c_int, [p, C.c_int]),
         "shk_placement_last": (C.c_int, [p, C.POINTER(ShkPlacements)]),
+        "shk_segments_enable": (C.c_int, [p, C.c_uint32]),
+        "shk_segments_last": (C.c_int, [p, C.POINTER(ShkSegments)]),
         "shk_depth_enable": (C.c_int, [p, C.c_uint32]),
         "shk_depth_layout": (C.c_int, [p, p, C.c_uint32]),
         "shk_depth_get": (C.c_int, [p, C.c_uint32, p, C.c_uint64]),
@@ -402,6 +410,30 @@ class SharkHip:
         raw = np.ctypeslib.as_array(C.cast(pl.entries, C.POINTER(C.c_uint32)), shape=(n, 2, 3)).copy()
         return placements_from_raw(raw)
 
+    # ---- segments: per association and mate the best m diagonals with their first and last voting slot --------
+    def segments_enable(self, m=SHK_MAX_SEGMENTS):
+        """batches submitted from now on carry, per association and mate, the m diagonals with the most votes (1 .. SHK_MAX_SEGMENTS;
+        0 switches the mode off); needs an index built with keep_positions; refused while tickets are outstanding"""
+        self._check(self.L.shk_segments_enable(self.h, int(m)), "shk_segments_enable")
+
+    def segments_last(self):
+        """segments of the batch whose result was handed out last: (n_keys, entries) -- an (n_assoc, 2) uint32 array and an
+        (n_assoc, 2, m, 5) int64 array (strand, pos, support, first, last; rank order, empty slots all 0), both parallel to gene_ids
+        -- copied from the context's pinned memory for a host batch (classify, wait); for a resident one (classify_device,
+        wait_device) (n_assoc, m, n_keys, entries) with the two DEVICE pointers (8 bytes per association, 20 bytes per entry
+        {pos i32, support, strand, first, last u32}) -- segments_from_device reads them back.  Raises (SHK_ERR_STATE) when that
+        batch was submitted with the mode off"""
+        sg = ShkSegments()
+        self._check(self.L.shk_segments_last(self.h, C.byref(sg)), "shk_segments_last")
+        n, m = int(sg.n_assoc), int(sg.m)
+        if not self._last_on_host:
+            return n, m, sg.n_keys, sg.entries
+        if n == 0:
+            return np.zeros((0, 2), dtype=np.uint32), np.zeros((0, 2, m, 5), dtype=np.int64)
+        keys = np.ctypeslib.as_array(C.cast(sg.n_keys, C.POINTER(C.c_uint32)), shape=(n, 2)).copy()
+        raw = np.ctypeslib.as_array(C.cast(sg.entries, C.POINTER(C.c_uint32)), shape=(n, 2, m, 5)).copy()
+        return keys, segments_from_raw(raw)
+
     # ---- depth: per-base read depth along each gene, accumulated on the device over the batches counted since the last reset --------
     def depth_enable(self, min_support=1):
         """batches submitted from now on add their placed mates (support >= min_support) to the context's depth state; 0 switches
@@ -563,6 +595,53 @@ def placements_from_device(n_assoc, ptr):
     if n_assoc:
         hip_memcpy_dtoh(raw, ptr, raw.nbytes)
     return placements_from_raw(raw)
+
+
+def segments_from_raw(raw):
+    """(n, 2, m, 5) uint32 words {pos, support, strand, first, last} of shk_segment -> int64 (strand, pos, support, first, last)"""
+    raw = np.asarray(raw, dtype=np.uint32)
+    out = np.empty(raw.shape, dtype=np.int64)
+    out[..., 0] = raw[..., 2]
+    out[..., 1] = raw[..., 0].view(np.int32)
+    out[..., 2] = raw[..., 1]
+    out[..., 3] = raw[..., 3]
+    out[..., 4] = raw[..., 4]
+    return out
+
+
+def segments_from_device(n_assoc, m, keys_ptr, entries_ptr):
+    """read the records of a resident batch back: ((n_assoc, 2) uint32, (n_assoc, 2, m, 5) int64) as segments_last gives them"""
+    keys = np.zeros((n_assoc, 2), dtype=np.uint32)
+    raw = np.zeros((n_assoc, 2, m, 5), dtype=np.uint32)
+    if n_assoc:
+        hip_memcpy_dtoh(keys, keys_ptr, keys.nbytes)
+        hip_memcpy_dtoh(raw, entries_ptr, raw.nbytes)
+    return keys, segments_from_raw(raw)
+
+
+def segment_span(seg, L, k):
+    """the record span [lo, hi) of one segment (strand, pos, support, first, last) of a mate of L bytes (include/shark_hip.h)"""
+    strand, pos, _, first, last = (int(v) for v in seg)
+    if strand == 0:
+        return pos + first, pos + last + k
+    return pos + L - k - last, pos + L - first
+
+
+def junctions(segments, L, k, s_min=8):
+    """the junctions of ONE mate of L bytes from its reported segments (rows (strand, pos, support, first, last), rank order), as
+    include/shark_hip.h defines them: [(donor, acceptor, intron, overlap)] in record order"""
+    segs = [tuple(int(v) for v in sg) for sg in segments]
+    segs = [sg for sg in segs if sg[2] >= 1]
+    if not segs:
+        return []
+    strand0 = segs[0][0]
+    kept = sorted((segment_span(sg, L, k) + (sg[1],) for sg in segs if sg[2] >= s_min and sg[0] == strand0), key=lambda t: (t[0], t[1]))
+    out = []
+    for (lo_a, hi_a, pos_a), (lo_b, hi_b, pos_b) in zip(kept, kept[1:]):
+        if pos_b > pos_a:
+            intron = pos_b - pos_a
+            out.append((hi_a, lo_b, intron, hi_a + intron - lo_b))
+    return out
 
 
 _hip = None

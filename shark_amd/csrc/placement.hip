@@ -30,10 +30,6 @@ namespace shk {
 
 namespace {
 
-constexpr int PL_THREADS = 256, PL_WAVES = PL_THREADS / 64;
-constexpr uint32_t PL_CACHED_CHUNKS = 8;        // 512 slots per mate in LDS: 2 x 4 KiB per wave
-constexpr uint64_t PL_NO_VOTE = ~0ull;
-
 struct PlaceParams {
   const uint32_t *gene_off;
   const uint16_t *gene_ids;
@@ -49,36 +45,6 @@ struct PlaceParams {
   uint32_t ptab_lg;
   shk_placement *out;
 };
-
-__device__ __forceinline__ uint64_t wave_min_u64(uint64_t v)
-{
-#pragma unroll
-  for (int o = 32; o >= 1; o >>= 1) {
-    const uint64_t t = __shfl_xor(v, o, 64);
-    v = t < v ? t : v;
-  }
-  return v;
-}
-
-// the vote of slot p of a mate of length L whose window is w (pl_window) for gene g, or PL_NO_VOTE
-__device__ __forceinline__ uint64_t pl_vote(const PlaceParams &P, uint32_t g, uint64_t w, uint32_t p, uint32_t L)
-{
-  if (w == PL_NO_KMER) return PL_NO_VOTE;
-  const uint64_t canon = w & ~(1ull << 63);
-  const uint32_t b = pl_hash32(g, canon) >> (32u - P.ptab_lg);
-  const uint32_t first = P.pdir[b], last = P.pdir[b + 1];
-  for (uint32_t j = first; j < last; ++j) {
-    const uint4 e = P.ptab[j];
-    if (e.x == (uint32_t)canon && e.y == (uint32_t)(canon >> 32) && e.w == g) {
-      if (e.z == PTAB_AMBIGUOUS) return PL_NO_VOTE;
-      const uint32_t x = e.z & 0x7FFFFFFFu;
-      const uint32_t strand = (e.z >> 31) ^ (uint32_t)(w >> 63);
-      const int32_t pos = strand ? (int32_t)(x + p + P.k - L) : (int32_t)(x - p);
-      return ((uint64_t)strand << 32) | ((uint32_t)pos ^ 0x80000000u);
-    }
-  }
-  return PL_NO_VOTE;
-}
 
 __global__ __launch_bounds__(PL_THREADS) void placement_kernel(const PlaceParams P)
 {

@@ -30,6 +30,7 @@
 #include <sstream>
 #include <string>
 #include <thread>
+#include <tuple>
 #include <utility>
 #include <vector>
 
@@ -85,6 +86,16 @@ const char *USAGE_MESSAGE =
     "                                        over the whole sample on the GPUs (may be combined with --placements, --evidence and\n"
     "                                        --candidates; not for references of more than 65536 records)\n"
     "          --depth-min-support N         unique k-mers a mate's placement needs to be counted by --depth (default:1)\n"
+    "          --segments FILE               write <read> <gene> and per mate <diagonals> and M x <strand> <pos> <support> <first> <last>\n"
+    "                                        per association, in the order of the output's lines: the M diagonals of the gene's record\n"
+    "                                        most of the mate's unique k-mers lie on, with the first and last k-mer slot on each (a\n"
+    "                                        spliced mate lies on several; empty entries are 0 0 0 0 0; not for references of more\n"
+    "                                        than 65536 records)\n"
+    "          --segments-max M              diagonals per mate of --segments and --junctions (default:4, 1 to 4)\n"
+    "          --junctions FILE              write <gene> <donor> <acceptor> <intron> <mates> per junction the sample's mates show, sorted\n"
+    "                                        by gene, donor, acceptor (record coordinates: the first base behind the left part, the\n"
+    "                                        first base of the right part; the same refusals as --segments)\n"
+    "          --junctions-min-support N     unique k-mers each side of a junction needs (default:8)\n"
     "      -t N also sets the number of host threads that parse FASTQ / format output (default: up to 16)\n";
 
 struct Options {
@@ -113,6 +124,12 @@ struct Options {
   std::string depth_path;
   FILE *depth_file = nullptr;      // (--depth, likewise; written once, after the last batch)
   unsigned depth_min_support = 1;
+  std::string segments_path;
+  FILE *segments_file = nullptr;   // (--segments, likewise)
+  unsigned segments_max = SHK_MAX_SEGMENTS;
+  std::string junctions_path;
+  FILE *junctions_file = nullptr;  // (--junctions, likewise; written once, after the last batch)
+  unsigned junctions_min_support = 8;
 };
 
 // The command line is described by one table: option names, whether a value follows, and a handler that
@@ -205,6 +222,18 @@ const OptionRow OPTION_TABLE[] = {
      [](Options &o, const char *v) {
        o.depth_min_support = value_of<unsigned>(v);
        if (o.depth_min_support < 1) reject(USAGE_MESSAGE, "shark: --depth-min-support must be at least 1.");
+     }},
+    {1010, "segments", true, [](Options &o, const char *v) { o.segments_path = value_of<std::string>(v); }},
+    {1011, "segments-max", true,
+     [](Options &o, const char *v) {
+       o.segments_max = value_of<unsigned>(v);
+       if (o.segments_max < 1 || o.segments_max > SHK_MAX_SEGMENTS) reject(USAGE_MESSAGE, "shark: --segments-max must be in the range [1, 4].");
+     }},
+    {1012, "junctions", true, [](Options &o, const char *v) { o.junctions_path = value_of<std::string>(v); }},
+    {1013, "junctions-min-support", true,
+     [](Options &o, const char *v) {
+       o.junctions_min_support = value_of<unsigned>(v);
+       if (o.junctions_min_support < 1) reject(USAGE_MESSAGE, "shark: --junctions-min-support must be at least 1.");
      }},
 };
 
@@ -397,6 +426,9 @@ struct ReadBatch {
   std::vector<shk_candidate> cand_entries;       // ... and cand_m entries
   uint32_t cand_m = 0;
   std::vector<shk_placement> placements;         // (--placements) one record per association
+  std::vector<uint32_t> seg_keys;                // (--segments, --junctions) two headers per association ...
+  std::vector<shk_segment> seg_entries;          // ... and 2 x seg_m entries
+  uint32_t seg_m = 0;
   int rc = 0;
   void reset()
   {
@@ -405,6 +437,7 @@ struct ReadBatch {
     lean = false;
     text.reset();
     gene_off.clear(); gene_ids.clear(); evidence.clear(); cand_reads.clear(); cand_entries.clear(); cand_m = 0; placements.clear();
+    seg_keys.clear(); seg_entries.clear(); seg_m = 0;
     rc = 0;
   }
 };
@@ -849,8 +882,8 @@ class GzCutter {
 // flight: the copies of the next batches overlap the kernels of the current one (shk_classify_submit / _wait).
 class ReadAnalyzer {
  public:
-  ReadAnalyzer(shk_ctx *ctx, bool need_qual, bool evidence, bool candidates = false, bool placements = false)
-      : ctx_(ctx), need_qual_(need_qual), evidence_(evidence), candidates_(candidates), placements_(placements) {}
+  ReadAnalyzer(shk_ctx *ctx, bool need_qual, bool evidence, bool candidates = false, bool placements = false, bool segments = false)
+      : ctx_(ctx), need_qual_(need_qual), evidence_(evidence), candidates_(candidates), placements_(placements), segments_(segments) {}
   // false: the batch failed at once (b.rc is set) and is not in flight
   bool submit(std::unique_ptr<ReadBatch> b)
   {
@@ -905,13 +938,22 @@ class ReadAnalyzer {
         b->rc = shk_placement_last(ctx_, &pl);
         if (b->rc == SHK_OK) b->placements.assign(pl.entries, pl.entries + pl.n_assoc);
       }
+      if (segments_ && b->rc == SHK_OK) {
+        shk_segments sg{};
+        b->rc = shk_segments_last(ctx_, &sg);
+        if (b->rc == SHK_OK) {
+          b->seg_m = sg.m;
+          b->seg_keys.assign(sg.n_keys, sg.n_keys + 2 * sg.n_assoc);
+          b->seg_entries.assign(sg.entries, sg.entries + 2 * sg.n_assoc * sg.m);
+        }
+      }
     }
     return b;
   }
 
  private:
   shk_ctx *ctx_;
-  bool need_qual_, evidence_, candidates_, placements_;
+  bool need_qual_, evidence_, candidates_, placements_, segments_;
   std::deque<std::pair<uint64_t, std::unique_ptr<ReadBatch>>> flying_;
   std::unique_ptr<ReadBatch> failed_;
 };
@@ -1017,17 +1059,20 @@ class OffsetWriter {
 // The text is produced per batch by any thread, in any order (format); the batches are then written in input order
 // (emit), which is also where the one thing that crosses a batch boundary is settled: whether the first associated read
 // of a batch that starts in the middle of a 50 000-read chunk repeats the previous batch's last read name.
+struct JunctionHit { uint32_t gene; int64_t donor, acceptor, intron; };   // (--junctions) one mate's one junction
 struct FormattedSegment {
   std::string ssv, fq1, fq2;        // fq: the FASTQ records behind the segment's first one
   std::string evd;                  // (--evidence) <id> <cov> <nk> <len> of every read of the segment
   std::string cnd;                  // (--candidates) <id> <len> <n_genes> { <gene> <cov> <nk>} of every read of the segment
   std::string plc;                  // (--placements) <id> <gene> <strand> <pos> <support> [mate 2's three] of every association of the segment
+  std::string sgm;                  // (--segments) <id> <gene> and per mate <n_keys> and m x <strand> <pos> <support> <first> <last>, per association
+  std::vector<JunctionHit> jnc;     // (--junctions) the junctions of the segment's mates, added to the run's table when the segment is written
   std::string head1, head2;         // the first associated read's FASTQ records, printed unless its name equals the carried one
   std::string head_id, last_id;
   bool has_assoc = false, carries = false;
   void reset()
   {
-    ssv.clear(); fq1.clear(); fq2.clear(); evd.clear(); cnd.clear(); plc.clear(); head1.clear(); head2.clear(); head_id.clear(); last_id.clear();
+    ssv.clear(); fq1.clear(); fq2.clear(); evd.clear(); cnd.clear(); plc.clear(); sgm.clear(); jnc.clear(); head1.clear(); head2.clear(); head_id.clear(); last_id.clear();
     has_assoc = carries = false;
   }
 };
@@ -1077,7 +1122,7 @@ class TextPool {
             st->free.pop_back();
           }
           for (FormattedSegment &sg : q->segs)
-            for (std::string *x : {&sg.ssv, &sg.fq1, &sg.fq2, &sg.evd, &sg.cnd, &sg.plc}) drop_pages(*x);
+            for (std::string *x : {&sg.ssv, &sg.fq1, &sg.fq2, &sg.evd, &sg.cnd, &sg.plc, &sg.sgm}) drop_pages(*x);
           // (the object itself and its small strings are left to the process's end)
         }
       });
@@ -1116,13 +1161,47 @@ class TextPool {
 class ReadOutput {
  public:
   ReadOutput(OffsetWriter *out1, OffsetWriter *out2, const std::vector<std::string> &legend, FILE *evidence = nullptr, FILE *candidates = nullptr,
-             FILE *placements = nullptr, bool paired = false)
+             FILE *placements = nullptr, bool paired = false, FILE *segments = nullptr, bool junctions = false, uint32_t k = 0, uint32_t junctions_min_support = 8)
       : out1_(out1), out2_(out2), legend_(legend), evidence_(evidence), candidates_(candidates), placements_(placements), paired_(paired),
-        every_read_(evidence || candidates) {}
+        every_read_(evidence || candidates), segments_(segments), junctions_(junctions), k_(k), s_min_(junctions_min_support) {}
   bool failed() const { return failed_.load(); }
   bool evidence_write_failed() const { return failed_write_; }
   bool candidates_write_failed() const { return failed_write_cand_; }
   bool placements_write_failed() const { return failed_write_plc_; }
+  bool segments_write_failed() const { return failed_write_sgm_; }
+
+  // The junctions of one mate of L bytes from its m reported segments (include/shark_hip.h, "segments"): the segments with at least
+  // s_min votes on rank 0's strand, sorted by their record span [lo, hi); every consecutive pair whose second diagonal lies further
+  // along the record is a junction (donor = hi of the first, acceptor = lo of the second, intron = the diagonals' distance).
+  static void mate_junctions(const shk_segment *e, uint32_t m, int64_t L, int64_t k, uint32_t s_min, uint32_t gene, std::vector<JunctionHit> &out)
+  {
+    struct Span { int64_t lo, hi, pos; } kept[SHK_MAX_SEGMENTS];
+    uint32_t n = 0;
+    for (uint32_t r = 0; r < m && r < SHK_MAX_SEGMENTS; ++r) {
+      if (e[r].support < 1 || e[r].support < s_min || e[r].strand != e[0].strand) continue;
+      const int64_t pos = e[r].pos, first = e[r].first, last = e[r].last;
+      kept[n++] = e[r].strand == 0 ? Span{pos + first, pos + last + k, pos} : Span{pos + L - k - last, pos + L - first, pos};
+    }
+    std::stable_sort(kept, kept + n, [](const Span &a, const Span &b) { return a.lo != b.lo ? a.lo < b.lo : a.hi < b.hi; });
+    for (uint32_t i = 0; i + 1 < n; ++i)
+      if (kept[i + 1].pos > kept[i].pos) out.push_back(JunctionHit{gene, kept[i].hi, kept[i + 1].lo, kept[i + 1].pos - kept[i].pos});
+  }
+  // --junctions: <gene> <donor> <acceptor> <intron> <mates>, sorted by gene index, donor, acceptor (mates that disagree on the intron
+  // of one (gene, donor, acceptor) -- an indel next to the junction --: the smallest)
+  bool write_junctions(FILE *f) const
+  {
+    std::string text;
+    for (const auto &kv : junction_table_) {
+      const uint32_t g = std::get<0>(kv.first);
+      text += g < legend_.size() ? legend_[g] : std::string();
+      text += ' '; text += std::to_string(std::get<1>(kv.first));
+      text += ' '; text += std::to_string(std::get<2>(kv.first));
+      text += ' '; text += std::to_string(kv.second.first);
+      text += ' '; text += std::to_string(kv.second.second);
+      text += '\n';
+    }
+    return fwrite(text.data(), 1, text.size(), f) == text.size();
+  }
 
   // thread-safe; nothing is written
   void format(const ReadBatch &b, FormattedBatch &out) const
@@ -1198,6 +1277,8 @@ class ReadOutput {
         }
         if (!assoc) continue;
         if (placements_ && b.placements.size() != b.gene_ids.size()) failed_ = true;   // (a batch without a record per association: an error exit)
+        const bool seg_mode = segments_ || junctions_;
+        if (seg_mode && (b.seg_m == 0 || b.seg_keys.size() != 2 * b.gene_ids.size() || b.seg_entries.size() != 2 * b.gene_ids.size() * b.seg_m)) failed_ = true;   // (likewise)
         for (uint32_t j = b.gene_off[i]; j < b.gene_off[i + 1]; ++j) {
           const std::string &gene = legend_[b.gene_ids[j]];
           if (placements_ && j < b.placements.size()) {
@@ -1211,6 +1292,30 @@ class ReadOutput {
             sg.plc.push_back(' ');
             sg.plc.append(gene);
             sg.plc.append(num, (size_t)w);
+          }
+          if (seg_mode && b.seg_m && 2 * (size_t)(j + 1) <= b.seg_keys.size() && 2 * (size_t)(j + 1) * b.seg_m <= b.seg_entries.size()) {
+            const shk_segment *e = b.seg_entries.data() + 2 * (size_t)j * b.seg_m;
+            if (segments_) {
+              // the ssv line's two fields, then per mate the number of diagonals and the reported ones in rank order
+              char num[96];
+              sg.sgm.append(id, id_len);
+              sg.sgm.push_back(' ');
+              sg.sgm.append(gene);
+              for (uint32_t t = 0; t < (paired_ ? 2u : 1u); ++t) {
+                int w = snprintf(num, sizeof(num), " %u", b.seg_keys[2 * (size_t)j + t]);
+                sg.sgm.append(num, (size_t)w);
+                for (uint32_t r = 0; r < b.seg_m; ++r) {
+                  const shk_segment &x = e[t * b.seg_m + r];
+                  w = snprintf(num, sizeof(num), " %u %d %u %u %u", x.strand, x.pos, x.support, x.first, x.last);
+                  sg.sgm.append(num, (size_t)w);
+                }
+              }
+              sg.sgm.push_back('\n');
+            }
+            if (junctions_) {
+              mate_junctions(e, b.seg_m, (int64_t)b.seq1.len(i), k_, s_min_, b.gene_ids[j], sg.jnc);
+              if (i < b.seq2.size()) mate_junctions(e + b.seg_m, b.seg_m, (int64_t)b.seq2.len(i), k_, s_min_, b.gene_ids[j], sg.jnc);
+            }
           }
           sg.ssv.append(id, id_len);
           sg.ssv.push_back(' ');
@@ -1258,6 +1363,12 @@ class ReadOutput {
       if (evidence_ && fwrite(sg.evd.data(), 1, sg.evd.size(), evidence_) != sg.evd.size()) failed_write_ = true;
       if (candidates_ && fwrite(sg.cnd.data(), 1, sg.cnd.size(), candidates_) != sg.cnd.size()) failed_write_cand_ = true;
       if (placements_ && fwrite(sg.plc.data(), 1, sg.plc.size(), placements_) != sg.plc.size()) failed_write_plc_ = true;
+      if (segments_ && fwrite(sg.sgm.data(), 1, sg.sgm.size(), segments_) != sg.sgm.size()) failed_write_sgm_ = true;
+      for (const JunctionHit &h : sg.jnc) {
+        auto it = junction_table_.emplace(std::make_tuple(h.gene, h.donor, h.acceptor), std::make_pair(h.intron, (uint64_t)0)).first;
+        it->second.first = std::min(it->second.first, h.intron);
+        ++it->second.second;
+      }
       // (ReadOutput.hpp:44-48: a read's FASTQ records are printed unless its name equals the one printed just before it)
       const bool head_repeats = sg.carries && sg.has_assoc && sg.head_id == carry_;
       if (out1_) {
@@ -1302,7 +1413,11 @@ class ReadOutput {
   FILE *placements_;        // (--placements) likewise, one line per association
   bool paired_;             // (--placements) the sample has two files: mate 2's fields are printed
   bool every_read_;         // one of the two: every read is named, not only the associated ones
-  bool failed_write_ = false, failed_write_cand_ = false, failed_write_plc_ = false;
+  FILE *segments_;          // (--segments) likewise, one line per association
+  bool junctions_;          // (--junctions) the mates' junctions are collected; write_junctions prints the table
+  uint32_t k_, s_min_;      // (--junctions) the k-mer length and the support either side needs
+  std::map<std::tuple<uint32_t, int64_t, int64_t>, std::pair<int64_t, uint64_t>> junction_table_;   // (gene, donor, acceptor) -> intron, mates
+  bool failed_write_ = false, failed_write_cand_ = false, failed_write_plc_ = false, failed_write_sgm_ = false;
   mutable std::atomic<bool> failed_{false};   // a record could not be read back from its file (I/O error)
   std::string carry_;   // previd at the end of the previous batch (only used when a batch starts mid-chunk)
 };
@@ -1744,6 +1859,8 @@ std::string build_index(const Options &opt, GpuStart &gpu, std::vector<std::stri
       legend_ID.push_back(rec.name.c_str());
       if (opt.placements_file && legend_ID.size() > 65536) return "shark: --placements is not available for a reference of more than 65536 records (gene ids wrap there).";
       if (opt.depth_file && legend_ID.size() > 65536) return "shark: --depth is not available for a reference of more than 65536 records (gene ids wrap there).";
+      if (opt.segments_file && legend_ID.size() > 65536) return "shark: --segments is not available for a reference of more than 65536 records (gene ids wrap there).";
+      if (opt.junctions_file && legend_ID.size() > 65536) return "shark: --junctions is not available for a reference of more than 65536 records (gene ids wrap there).";
       const size_t len = strnlen(rec.seq.data(), rec.seq.size());  // C-string semantics (main.cpp:164)
       for (auto *ctx : gpu.ctxs) {
         const int rc = shk_ref_add(ctx, rec.seq.data(), len);
@@ -1753,7 +1870,7 @@ std::string build_index(const Options &opt, GpuStart &gpu, std::vector<std::stri
   }
   pelapsed("Transcript file processed");
   timeline("reference read");
-  if (opt.placements_file || opt.depth_file)
+  if (opt.placements_file || opt.depth_file || opt.segments_file || opt.junctions_file)
     for (auto *ctx : gpu.ctxs)
       if (const int rc = shk_ref_keep_positions(ctx)) return std::string("shark: ") + shk_strerror(rc);
   {
@@ -1805,12 +1922,12 @@ void serial_feed(const Options &opt, const FeedPlan &plan, ParallelFeed &feed, B
 }
 
 // analyzers: one thread per worker, SHK_PIPE_DEPTH batches in flight each; t_gpu[g]: seconds inside shk_classify_submit / _wait
-std::vector<std::thread> start_analyzers(const std::vector<shk_ctx *> &ctxs, bool need_qual, bool evidence, bool candidates, bool placements, BatchOrder &order, BatchOrder::Queue &to_format, std::vector<double> &t_gpu)
+std::vector<std::thread> start_analyzers(const std::vector<shk_ctx *> &ctxs, bool need_qual, bool evidence, bool candidates, bool placements, bool segments, BatchOrder &order, BatchOrder::Queue &to_format, std::vector<double> &t_gpu)
 {
   std::vector<std::thread> analyzers;
   for (int g = 0; g < (int)ctxs.size(); ++g) {
-    analyzers.emplace_back([&, g, need_qual, evidence, candidates, placements] {
-      ReadAnalyzer ra(ctxs[(size_t)g], need_qual, evidence, candidates, placements);
+    analyzers.emplace_back([&, g, need_qual, evidence, candidates, placements, segments] {
+      ReadAnalyzer ra(ctxs[(size_t)g], need_qual, evidence, candidates, placements, segments);
       BatchOrder::Queue &todo = order.input(g);
       bool open = true;
       while (open || ra.in_flight()) {
@@ -1865,7 +1982,8 @@ int run_sample(const Options &opt, GpuStart &gpu, BatchPool &pool, std::vector<s
   w1.open(opt.out1_path, write_helpers);
   if (opt.paired_flag && opt.out2_path != "") w2.open(opt.out2_path, write_helpers);
   OffsetWriter *out1 = w1.is_open() ? &w1 : nullptr, *out2 = w2.is_open() ? &w2 : nullptr;
-  ReadOutput ro(out1, out2, legend_ID, opt.evidence_file, opt.candidates_file, opt.placements_file, opt.paired_flag);
+  ReadOutput ro(out1, out2, legend_ID, opt.evidence_file, opt.candidates_file, opt.placements_file, opt.paired_flag, opt.segments_file,
+                opt.junctions_file != nullptr, opt.k, opt.junctions_min_support);
   setvbuf(stdout, nullptr, _IOFBF, 1 << 22);
 
   FeedPlan plan(opt, io_threads, need_qual);
@@ -1899,6 +2017,14 @@ int run_sample(const Options &opt, GpuStart &gpu, BatchPool &pool, std::vector<s
       if (const int rc = shk_placement_enable(ctx, 1)) {
         feed.stop();
         std::cerr << "shark: placement mode could not be switched on: " << shk_strerror(rc) << " " << shk_last_error(ctx) << std::endl;
+        return EXIT_FAILURE;
+      }
+  // (--segments, --junctions: one mode of the library serves both; the junctions are computed from the segments on the host)
+  if (opt.segments_file || opt.junctions_file)
+    for (shk_ctx *ctx : gpu.ctxs)
+      if (const int rc = shk_segments_enable(ctx, opt.segments_max)) {
+        feed.stop();
+        std::cerr << "shark: segments mode could not be switched on: " << shk_strerror(rc) << " " << shk_last_error(ctx) << std::endl;
         return EXIT_FAILURE;
       }
   // (--depth: every worker adds its batches' placed mates to its own depth state; write_depth sums the workers' arrays at the end)
@@ -1935,7 +2061,8 @@ int run_sample(const Options &opt, GpuStart &gpu, BatchPool &pool, std::vector<s
       }
     });
   }
-  std::vector<std::thread> analyzers = start_analyzers(gpu.ctxs, need_qual, opt.evidence_file != nullptr, opt.candidates_file != nullptr, opt.placements_file != nullptr, order, to_format, t_gpu);
+  std::vector<std::thread> analyzers = start_analyzers(gpu.ctxs, need_qual, opt.evidence_file != nullptr, opt.candidates_file != nullptr, opt.placements_file != nullptr,
+                                                        opt.segments_file != nullptr || opt.junctions_file != nullptr, order, to_format, t_gpu);
   // ordered drain
   int failed = 0;
   double t_out = 0;
@@ -1981,6 +2108,12 @@ int run_sample(const Options &opt, GpuStart &gpu, BatchPool &pool, std::vector<s
   const bool evidence_written = !opt.evidence_file || (fclose(opt.evidence_file) == 0 && !ro.evidence_write_failed());
   const bool candidates_written = !opt.candidates_file || (fclose(opt.candidates_file) == 0 && !ro.candidates_write_failed());
   const bool placements_written = !opt.placements_file || (fclose(opt.placements_file) == 0 && !ro.placements_write_failed());
+  const bool segments_written = !opt.segments_file || (fclose(opt.segments_file) == 0 && !ro.segments_write_failed());
+  bool junctions_written = true;
+  if (opt.junctions_file) {
+    junctions_written = ro.write_junctions(opt.junctions_file);
+    junctions_written = fclose(opt.junctions_file) == 0 && junctions_written;
+  }
   if (out1) written = w1.close() && written;
   if (out2) written = w2.close() && written;
   text_pool.finish();
@@ -2000,6 +2133,14 @@ int run_sample(const Options &opt, GpuStart &gpu, BatchPool &pool, std::vector<s
   }
   if (!placements_written) {
     std::cerr << "shark: cannot write the placements file " << opt.placements_path << std::endl;
+    return EXIT_FAILURE;
+  }
+  if (!segments_written) {
+    std::cerr << "shark: cannot write the segments file " << opt.segments_path << std::endl;
+    return EXIT_FAILURE;
+  }
+  if (!junctions_written) {
+    std::cerr << "shark: cannot write the junctions file " << opt.junctions_path << std::endl;
     return EXIT_FAILURE;
   }
   if (failed) {
@@ -2112,6 +2253,8 @@ int main(int argc, char *argv[])
   if (opt_parsed.candidates_path != "" && samples_can_be_opened(opt_parsed, false)) opt_parsed.candidates_file = fopen(opt_parsed.candidates_path.c_str(), "w");   // (--candidates: likewise)
   if (opt_parsed.placements_path != "" && samples_can_be_opened(opt_parsed, false)) opt_parsed.placements_file = fopen(opt_parsed.placements_path.c_str(), "w");   // (--placements: likewise)
   if (opt_parsed.depth_path != "" && samples_can_be_opened(opt_parsed, false)) opt_parsed.depth_file = fopen(opt_parsed.depth_path.c_str(), "w");   // (--depth: likewise)
+  if (opt_parsed.segments_path != "" && samples_can_be_opened(opt_parsed, false)) opt_parsed.segments_file = fopen(opt_parsed.segments_path.c_str(), "w");   // (--segments: likewise)
+  if (opt_parsed.junctions_path != "" && samples_can_be_opened(opt_parsed, false)) opt_parsed.junctions_file = fopen(opt_parsed.junctions_path.c_str(), "w");   // (--junctions: likewise)
   const Options opt = opt_parsed;
   if (opt.verbose) timeline.on();
   timeline("arguments parsed");
@@ -2139,6 +2282,15 @@ int main(int argc, char *argv[])
 
   if (opt.depth_path != "" && !opt.depth_file) {
     std::cerr << "shark: cannot open the depth file " << opt.depth_path << std::endl;
+    return EXIT_FAILURE;
+  }
+
+  if (opt.segments_path != "" && !opt.segments_file) {
+    std::cerr << "shark: cannot open the segments file " << opt.segments_path << std::endl;
+    return EXIT_FAILURE;
+  }
+  if (opt.junctions_path != "" && !opt.junctions_file) {
+    std::cerr << "shark: cannot open the junctions file " << opt.junctions_path << std::endl;
     return EXIT_FAILURE;
   }
 

@@ -116,6 +116,9 @@ static void slot_free(Slot &s)
   hipFree(s.d_cand_reads); hipFree(s.d_cand_entries);
   hipFree(s.d_place);
   if (s.h_place) (void)hipHostFree(s.h_place);
+  hipFree(s.d_seg_keys); hipFree(s.d_seg_entries);
+  if (s.h_seg_keys) (void)hipHostFree(s.h_seg_keys);
+  if (s.h_seg_entries) (void)hipHostFree(s.h_seg_entries);
   if (s.h_cand_reads) (void)hipHostFree(s.h_cand_reads);
   if (s.h_cand_entries) (void)hipHostFree(s.h_cand_entries);
   if (s.h_evid) (void)hipHostFree(s.h_evid);
@@ -232,6 +235,12 @@ static int run_long_reads(Ctx *ctx, Slot &s, uint32_t n_long)
   return launch_classify_general(ctx, p, false, n_waves, ctx->stream, s.evidence, s.cand_m != 0);
 }
 
+// associations the pinned segment arrays of `s` hold at s.seg_m (segments_cap: the device's)
+static uint64_t segments_host_cap(const Slot &s)
+{
+  return s.seg_m ? std::min<uint64_t>(s.cap_h_seg_keys / 2, s.cap_h_seg_entries / (2ull * s.seg_m)) : 0;
+}
+
 // Everything behind the classify kernels, WITHOUT a host round trip: per-read counts -> offsets (scan), inline ids ->
 // CSR (gather), reads with more than SHK_INLINE_IDS genes (EMIT pass of the general kernel over the tie queue, whose
 // length stays on the device), per-gene histogram, counters -> pinned host memory, event.
@@ -292,6 +301,17 @@ static int enqueue_tail(Ctx *ctx, Slot &s, bool skip_hist_if_long, bool count_ge
       if ((rc = launch_publish_placements(s.d_counters, s.d_place, s.h_place, std::min<uint64_t>(s.cap_h_place, s.cap_place), st))) return rc;
     }
   }
+  // (segments mode: the same place in the tail for the same reason, its own kernel and its own arrays)
+  if (s.seg_m) {
+    if ((rc = ensure_capacity(ctx, &s.d_seg_keys, &s.cap_seg_keys, 2 * s.cap_gene_ids))) return rc;
+    if ((rc = ensure_capacity(ctx, &s.d_seg_entries, &s.cap_seg_entries, 2 * s.cap_gene_ids * s.seg_m))) return rc;
+    if ((rc = launch_segments(ctx, s, st))) return rc;
+    if (s.host_batch) {
+      if ((rc = ensure_pinned(ctx, &s.h_seg_keys, &s.cap_h_seg_keys, 2 * s.cap_gene_ids))) return rc;
+      if ((rc = ensure_pinned(ctx, &s.h_seg_entries, &s.cap_h_seg_entries, 2 * s.cap_gene_ids * s.seg_m))) return rc;
+      if ((rc = launch_publish_segments(s, std::min<uint64_t>(segments_host_cap(s), segments_cap(s)), st))) return rc;
+    }
+  }
   SHK_HIP(ctx, hipEventRecord(s.ev_done, st));
   return SHK_OK;
 }
@@ -331,6 +351,7 @@ static int enqueue_classify(Ctx *ctx, Slot &s, const shk_batch *b, uint32_t max_
   s.evidence = ctx->evidence;
   s.cand_m = ctx->cand_m;
   s.placement = ctx->placement;
+  s.seg_m = ctx->seg_m;
   s.depth = count_genes ? ctx->depth : 0u;   // (shk_count_work is a measurement: its batch is not counted)
   if ((rc = slot_reserve(ctx, s, n))) return rc;
   s.n = n;
@@ -519,6 +540,7 @@ static int classify_resident(Ctx *ctx, const shk_batch *b, uint32_t max_read_len
   ctx->last_evid_valid = false;   // (until this batch's result is handed out)
   ctx->last_cand_valid = false;
   ctx->last_place_valid = false;
+  ctx->last_seg_valid = false;
   if (n >= 0xFFFFFFFFull) { ctx->last_error = "batch too large (n must be < 2^32-1)"; return SHK_ERR_ARG; }
   const bool paired = b->seq2 != nullptr;
   const uint32_t max_slots = max_read_len ? slots_for_len(max_read_len, ctx->prm.k, paired) : 0;
@@ -577,6 +599,11 @@ static int classify_resident(Ctx *ctx, const shk_batch *b, uint32_t max_read_len
   ctx->last_place_valid = s.placement && wc == nullptr;
   ctx->last_place = s.d_place;
   ctx->last_place_n = n_assoc;
+  ctx->last_seg_valid = s.seg_m != 0 && wc == nullptr;
+  ctx->last_seg_m = s.seg_m;
+  ctx->last_seg_keys = s.d_seg_keys;
+  ctx->last_seg_entries = s.d_seg_entries;
+  ctx->last_seg_n = n_assoc;
   return SHK_OK;
 }
 
@@ -1070,6 +1097,7 @@ int shk_classify_wait(shk_ctx *ctx, uint64_t ticket, shk_result *result)
   ctx->last_evid_valid = false;   // (a batch that is refused below hands out no evidence either, and leaves none of an earlier batch behind)
   ctx->last_cand_valid = false;
   ctx->last_place_valid = false;
+  ctx->last_seg_valid = false;
   SHK_HIP(ctx, hipEventSynchronize(s.ev_done));
   bool redone = false;
   int rc = finish_classify(ctx, s, s.long_speculative, true, &redone);
@@ -1104,6 +1132,12 @@ int shk_classify_wait(shk_ctx *ctx, uint64_t ticket, shk_result *result)
   ctx->last_place_valid = s.placement;
   ctx->last_place = s.host_batch ? s.h_place : s.d_place;
   ctx->last_place_n = n_assoc;
+  if (s.seg_m && s.host_batch && n_assoc > segments_host_cap(s)) { ctx->last_error = "segments publication failed"; return SHK_ERR_HIP; }
+  ctx->last_seg_valid = s.seg_m != 0;
+  ctx->last_seg_m = s.seg_m;
+  ctx->last_seg_keys = s.host_batch ? s.h_seg_keys : s.d_seg_keys;
+  ctx->last_seg_entries = s.host_batch ? s.h_seg_entries : s.d_seg_entries;
+  ctx->last_seg_n = n_assoc;
   return SHK_OK;
 }
 
@@ -1183,6 +1217,35 @@ int shk_placement_last(const shk_ctx *ctx, shk_placements *out)
   if (!ctx->last_place_valid) return SHK_ERR_STATE;
   out->n_assoc = ctx->last_place_n;
   out->entries = ctx->last_place;
+  return SHK_OK;
+}
+
+int shk_segments_enable(shk_ctx *ctx, uint32_t m)
+{
+  if (!ctx) return SHK_ERR_ARG;
+  if (m > SHK_MAX_SEGMENTS) { ctx->last_error = "shk_segments_enable: m must be at most SHK_MAX_SEGMENTS"; return SHK_ERR_ARG; }
+  for (int i = 0; i < PIPE_DEPTH; ++i)
+    if (ctx->slots[i].ticket != 0 && !ctx->slots[i].waited) {
+      ctx->last_error = "shk_segments_enable: tickets are outstanding (wait for them first)";
+      return SHK_ERR_STATE;
+    }
+  if (m) {
+    if (ctx->mode != 2) { ctx->last_error = "shk_segments_enable: the index is not finalized"; return SHK_ERR_STATE; }
+    if (!ctx->idx.ptab_lg) { ctx->last_error = "shk_segments_enable: the index was finalized without shk_ref_keep_positions"; return SHK_ERR_STATE; }
+    if (ctx->n_records > 65536 || ctx->idx.wrap) { ctx->last_error = "shk_segments_enable: more than 65 536 records (gene ids wrap)"; return SHK_ERR_STATE; }
+  }
+  ctx->seg_m = m;
+  return SHK_OK;
+}
+
+int shk_segments_last(const shk_ctx *ctx, shk_segments *out)
+{
+  if (!ctx || !out) return SHK_ERR_ARG;
+  if (!ctx->last_seg_valid) return SHK_ERR_STATE;
+  out->n_assoc = ctx->last_seg_n;
+  out->m = ctx->last_seg_m;
+  out->n_keys = ctx->last_seg_keys;
+  out->entries = ctx->last_seg_entries;
   return SHK_OK;
 }
 

@@ -110,7 +110,7 @@ struct DeviceIndex {
   //   ptab : one uint4 per DISTINCT (gene, canonical k-mer) of the reference, sorted by the 32-bit hash of the pair (pl_hash32), then
   //          by the smallest global position of the pair: {k-mer low, k-mer high, x | orientation << 31, gene}; x = the offset of the
   //          pair's only valid window in its record, orientation = 1 when that window's k-mer is its own canonical form;
-  //          PTAB_AMBIGUOUS in place of x | orientation when the pair has two or more windows.  Windows that are their own reverse
+  //          PTAB_AMBIGUOUS (placement_common.hpp) in place of x | orientation when the pair has two or more windows.  Windows that are their own reverse
   //          complement are left out.
   //   pdir : pdir[b] = the first entry whose hash >> (32 - ptab_lg) is >= b, for b = 0 .. 2^ptab_lg (one more entry = ptab_n)
   uint4 *ptab = nullptr;
@@ -121,7 +121,6 @@ struct DeviceIndex {
   //      with ptab for an index of at most 65 536 records (where the mode can be switched on), nullptr otherwise ----
   uint64_t *gene_start = nullptr;
 };
-constexpr uint32_t PTAB_AMBIGUOUS = 0xFFFFFFFFu;   // (no window has x = 2^31 - 1: a record has fewer than 2^31 bases)
 // Test-only read-back of the arrays above (tests/index_audit.py audits them entry by entry):
 //   extern "C" int shk_debug_index_array(const shk_ctx *, const char *name, void *dst, uint64_t dst_bytes, uint64_t *bytes_needed)
 // copies the named device array to the host exactly as allocated, padding included.  Names: rank_w, ent, ids, sum32, lsum32,
@@ -321,6 +320,13 @@ struct Slot {
   shk_placement *h_place = nullptr; size_t cap_h_place = 0;   // (host batches; filled by publish_placements_kernel)
   // depth mode: submitted with this min_support (0: not): placement_kernel ran (d_place holds its records) and depth_accumulate_kernel behind it
   uint32_t depth = 0;
+  // segments mode: submitted with this many entries per mate (0: not): segments_kernel ran behind the assembly; per association two headers
+  // (d_seg_keys) and 2 x seg_m entries (d_seg_entries), allocated with the first such batch for as many associations as d_gene_ids holds
+  uint32_t seg_m = 0;
+  uint32_t *d_seg_keys = nullptr; size_t cap_seg_keys = 0;
+  shk_segment *d_seg_entries = nullptr; size_t cap_seg_entries = 0;
+  uint32_t *h_seg_keys = nullptr; size_t cap_h_seg_keys = 0;        // (host batches; filled by publish_segments_kernel)
+  shk_segment *h_seg_entries = nullptr; size_t cap_h_seg_entries = 0;
 };
 
 struct Ctx;
@@ -334,6 +340,10 @@ int build_placement_table(Ctx *ctx, const uint8_t *d_bytes, uint64_t total, cons
 // placement.hip: per association of the batch in `s` the best diagonal per mate, behind the kernels that wrote gene_off / gene_ids
 int launch_placement(Ctx *ctx, const Slot &s, hipStream_t stream);
 int launch_publish_placements(const uint32_t *counters, const shk_placement *src, shk_placement *h_dst, uint64_t h_cap, hipStream_t stream);
+// segments.hip: per association of the batch in `s` and per mate its best s.seg_m diagonals with their first and last voting slot
+int launch_segments(Ctx *ctx, const Slot &s, hipStream_t stream);
+uint64_t segments_cap(const Slot &s);   // associations d_seg_keys / d_seg_entries hold at s.seg_m
+int launch_publish_segments(const Slot &s, uint64_t h_cap, hipStream_t stream);   // h_cap: associations the pinned arrays (and the device's) hold
 // depth.hip: the batch in `s` (its placements in s.d_place) into the context's difference array, behind launch_placement; skip_if_long: as launch_gene_hist
 int launch_depth_accumulate(Ctx *ctx, const Slot &s, bool skip_if_long, hipStream_t stream);
 // the read-out: Ctx::d_depth_scan[1 + x] = depth of base x of the full array (inclusive prefix sum of the difference array), on ctx->stream
@@ -433,6 +443,13 @@ struct Ctx {
   bool last_place_valid = false;
   const shk_placement *last_place = nullptr;
   uint64_t last_place_n = 0;
+  // segments mode (shk_segments_enable; segments.hip), the same way: seg_m entries per mate for the batches submitted from now on (0: off)
+  uint32_t seg_m = 0;
+  bool last_seg_valid = false;
+  uint32_t last_seg_m = 0;
+  const uint32_t *last_seg_keys = nullptr;
+  const shk_segment *last_seg_entries = nullptr;
+  uint64_t last_seg_n = 0;
   // depth mode (shk_depth_enable; depth.hip): the state outlives the mode's being switched off
   std::vector<uint64_t> gene_start;            // host copy of DeviceIndex::gene_start (empty: the index carries none)
   uint32_t depth = 0;                          // min_support for the batches submitted from now on (0: off)

@@ -15,7 +15,7 @@ for blk in t.split("- .agpr_count:")[1:]:
         continue
     g = lambda k: re.search(r"\.%s:\s+(\d+)" % k, blk).group(1)
     dem = subprocess.run(["c++filt", name], capture_output=True, text=True).stdout.strip()
-    dem = re.sub(r"\(.*", "", dem).replace("void shk::", "")
+    dem = re.sub(r"\(.*", "", dem.replace("(anonymous namespace)::", "")).replace("void shk::", "")
     print("%-58s vgpr %3s sgpr %3s spill v%s s%s scratch %4s lds %6s" % (dem, g("vgpr_count"), g("sgpr_count"), g("vgpr_spill_count"), g("sgpr_spill_count"),
           g("private_segment_fixed_size"), g("group_segment_fixed_size")))
 PY
