@@ -422,6 +422,69 @@ int shk_depth_mates(const shk_ctx *ctx, uint64_t *n_mates);
 /* Clears the accumulated depth and the mate counter (the mode stays as it is); the read-outs' state rules.  New: no counterpart. */
 int shk_depth_reset(shk_ctx *ctx);
 
+/* ---- spliced depth and the junction table: the two consumers of segments mode, on the device ---- */
+/* Both rest on the segments section's definitions, unchanged: mate, L, key, support, first, last and the record span [lo, hi) of a
+ * segment.  Both consume one thing:
+ *
+ * KEPT SPANS of a mate at floor s_min (>= 1).  Take the mate's first SHK_MAX_SEGMENTS (4) ranked segments; keep those with
+ * support >= s_min and rank 0's strand (rank 0 itself only if it reaches s_min: ranks descend in support, so a rank 0 below the
+ * floor keeps nothing); sort the kept ones by (lo, hi), equal spans in rank order.  Steps 1 and 2 of the junction rule above at
+ * m = 4, whatever m segments mode itself runs at.  The result may be empty: the mate then contributes nothing anywhere.
+ *
+ * SPLICED DEPTH.  Depth mode (above) paints [pos, pos + L) along the mate's best diagonal -- straight over the intron of a mate
+ * that crosses a junction.  Here a counted mate covers the UNION of its kept spans, clipped to [0, len_g):
+ *   - a base counts once per mate, however many of its spans contain it (spans of one mate can overlap in record coordinates:
+ *     behind a short deletion, at an insertion in the read, over the microhomology of a junction);
+ *   - only explained bases count: nothing is extended to the mate's ends.  An overhang shorter than k past a junction holds no
+ *     whole window and cannot vote, so nothing says on which side of the intron it lies; extending the span by it would paint
+ *     it into the intron, the very error this mode removes.  A mate's ends behind its outermost voting windows are left out
+ *     for the same reason (a substitution there silences up to k windows): spliced depth is a lower bound base by base;
+ *   - depth[g][x], the counting of batches and every rule of depth mode are otherwise unchanged: mates are counted, not fragments;
+ *     a read tied over several genes counts in each; integers only; a batch is counted exactly once (a batch with more
+ *     associations than the result buffer holds or with reads beyond a length bound taken on trust is counted when the tail
+ *     runs again; a batch vouched for wrongly and a shk_count_work batch are not counted);
+ *   - a mate counts in shk_depth_mates iff it added at least one interval.
+ *
+ * JUNCTION TABLE.  For every counted mate, every consecutive pair (A, B) of its kept spans with pos_B > pos_A is one OBSERVATION
+ * of the key (g, donor = hi_A, acceptor = lo_B) -- step 3 of the junction rule.  Per key the table holds
+ *   mates    the observations since the last reset
+ *   intron   the smallest pos_B - pos_A among them
+ * which is `shark --junctions`' table, accumulated on the device over all counted batches (the same batches as depth's).
+ * Example (segments section): the mate with spans [9653, 9727) and [10912, 10943) covers those 74 + 31 bases and none of the 1185
+ * between them, and is one observation of (g, 9727, 10912) with intron 1190.
+ *
+ * State: spliced depth uses depth mode's state.  The table is an open-addressing array of `capacity` 16-byte entries on the device.
+ * New: the reference has no counterpart. */
+/* As shk_depth_enable, but the intervals of the batches submitted AFTERWARDS are the unions of kept spans at s_min = min_support.
+ * The state, its layout and every shk_depth_* read-out and reset are shared with plain depth, and one state holds one kind:
+ * switching between plain and spliced (either way) returns SHK_ERR_STATE if a depth batch of the other kind was submitted since
+ * the first enable or the last shk_depth_reset (the host keeps a flag; the device is not asked).  shk_depth_enable(ctx, 0) and
+ * shk_depth_enable_spliced(ctx, 0) switch either kind off.  placement_kernel does not run for spliced depth (unless placement
+ * mode asks for it); segments_kernel does, see below.  New: no counterpart. */
+int shk_depth_enable_spliced(shk_ctx *ctx, uint32_t min_support);
+/* Switches the junction table on with this min_support (>= 1) or off (0) for the batches submitted AFTERWARDS, through any of the
+ * four families.  capacity: table entries, rounded up to a power of two of at least 64; 16 bytes each; the table must hold every
+ * distinct key (keep it at most half full for short probe chains).  The first enable allocates and clears the table; a later
+ * enable with another capacity returns SHK_ERR_ARG unless no batch was submitted with the mode on since the first enable or the
+ * last shk_junctions_reset (the table is then allocated anew).  Switching off (capacity is ignored) keeps the table.  State rules
+ * are shk_segments_enable's: switching on returns SHK_ERR_STATE before shk_ref_finalize, without shk_ref_keep_positions, on an
+ * index of more than 65 536 records; either way while tickets are outstanding.  New: no counterpart.
+ *
+ * Both modes are independent of every other mode and of each other.  shk_segments_last hands out exactly what it does without
+ * them, at the caller's m.  With segments mode on at m = SHK_MAX_SEGMENTS its one segments_kernel launch serves them too;
+ * otherwise segments_kernel runs (once more) at m = 4 into arrays of the context's own, allocated with the first such batch and
+ * never handed out.  spliced_accumulate_kernel follows it.  With both off no launch and no allocation is added. */
+int shk_junctions_enable(shk_ctx *ctx, uint32_t min_support, uint64_t capacity);
+typedef struct shk_junction { uint32_t gene, donor, acceptor, intron; uint64_t mates; } shk_junction;
+/* The read-outs, with depth's rules: SHK_ERR_STATE if the mode was never enabled on this context or while tickets are
+ * outstanding; stream-ordered behind everything enqueued so far; the table is left untouched.  If any observation found the table
+ * full, every read-out returns SHK_ERR_INDEX_TOO_LARGE until shk_junctions_reset (nothing partial is handed out).
+ *   shk_junctions_get    *n = the number of distinct keys; out != NULL: the keys sorted by (gene, donor, acceptor) into out[0 .. *n)
+ *                        (host memory; SHK_ERR_ARG if cap < *n, *n is set all the same).  out == NULL: only *n
+ *   shk_junctions_reset  empties the table (the mode and the capacity stay as they are) */
+int shk_junctions_get(shk_ctx *ctx, shk_junction *out, uint64_t cap, uint64_t *n);
+int shk_junctions_reset(shk_ctx *ctx);
+
 /* Per-gene number of assigned reads accumulated over all classify calls (all
  * waited tickets) since the last reset (counts[g] for g in [0, 65536)); the quantity all-reduced
  * across GPUs.  n must be <= 65536. */

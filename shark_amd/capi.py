@@ -59,6 +59,11 @@ class ShkSegments(C.Structure):
 GENE_DEPTH_DTYPE = np.dtype([("len", np.uint32), ("covered", np.uint32), ("max", np.uint32), ("pad", np.uint32), ("sum", np.uint64)])
 
 
+# shk_junction as a numpy record (24 bytes)
+JUNCTION_DTYPE = np.dtype([("gene", np.uint32), ("donor", np.uint32), ("acceptor", np.uint32), ("intron", np.uint32), ("mates", np.uint64)])
+JUNCTIONS_DEFAULT_CAPACITY = 1 << 16
+
+
 class ShkWorkCounters(C.Structure):
     _fields_ = [("n_kmers", C.c_uint64), ("n_hits", C.c_uint64), ("n_list_ids", C.c_uint64), ("n_bases", C.c_uint64)]
 
@@ -78,6 +83,7 @@ EXPORTS = [
     "shk_ref_keep_positions", "shk_placement_enable", "shk_placement_last",
     "shk_segments_enable", "shk_segments_last",
     "shk_depth_enable", "shk_depth_layout", "shk_depth_get", "shk_depth_get_all", "shk_depth_summary", "shk_depth_mates", "shk_depth_reset",
+    "shk_depth_enable_spliced", "shk_junctions_enable", "shk_junctions_get", "shk_junctions_reset",
 ]
 SHK_PIPE_DEPTH = 3
 SHK_DIST_ID_BYTES = 128
@@ -155,6 +161,10 @@ def load():
         "shk_depth_summary": (C.c_int, [p, p, C.c_uint32]),
         "shk_depth_mates": (C.c_int, [p, C.POINTER(C.c_uint64)]),
         "shk_depth_reset": (C.c_int, [p]),
+        "shk_depth_enable_spliced": (C.c_int, [p, C.c_uint32]),
+        "shk_junctions_enable": (C.c_int, [p, C.c_uint32, C.c_uint64]),
+        "shk_junctions_get": (C.c_int, [p, p, C.c_uint64, C.POINTER(C.c_uint64)]),
+        "shk_junctions_reset": (C.c_int, [p]),
     }
     variant = bool(os.environ.get("SHK_LIB_PATH"))
     for name, (res, args) in later.items():
@@ -482,6 +492,30 @@ class SharkHip:
     def depth_reset(self):
         self._check(self.L.shk_depth_reset(self.h), "shk_depth_reset")
 
+    # ---- spliced depth and the junction table: segments mode's two consumers on the device --------
+    def depth_enable_spliced(self, min_support=8):
+        """as depth_enable, but a counted mate covers the union of its kept spans (kept_spans, span_union) instead of [pos, pos + L);
+        the state and every depth read-out are shared with plain depth, one kind at a time (switching on a state that holds the other
+        kind raises until depth_reset); 0 switches the mode off"""
+        self._check(self.L.shk_depth_enable_spliced(self.h, int(min_support)), "shk_depth_enable_spliced")
+
+    def junctions_enable(self, min_support=8, capacity=JUNCTIONS_DEFAULT_CAPACITY):
+        """batches submitted from now on add their mates' junctions (junctions() at m = 4 and s_min = min_support) to a table on the
+        device of `capacity` entries (rounded up to a power of two >= 64); 0 switches the mode off and keeps the table"""
+        self._check(self.L.shk_junctions_enable(self.h, int(min_support), int(capacity)), "shk_junctions_enable")
+
+    def junctions_get(self):
+        """the table: a structured array (JUNCTION_DTYPE: gene, donor, acceptor, intron, mates) sorted by (gene, donor, acceptor)"""
+        n = C.c_uint64()
+        self._check(self.L.shk_junctions_get(self.h, None, 0, C.byref(n)), "shk_junctions_get")
+        out = np.zeros(int(n.value), dtype=JUNCTION_DTYPE)
+        if len(out):
+            self._check(self.L.shk_junctions_get(self.h, _ptr(out), len(out), C.byref(n)), "shk_junctions_get")
+        return out[:int(n.value)]
+
+    def junctions_reset(self):
+        self._check(self.L.shk_junctions_reset(self.h), "shk_junctions_reset")
+
     def gene_counts(self, n=65536):
         a = np.zeros(n, dtype=np.uint64)
         self._check(self.L.shk_gene_counts(self.h, _ptr(a), n), "shk_gene_counts")
@@ -641,6 +675,32 @@ def junctions(segments, L, k, s_min=8):
         if pos_b > pos_a:
             intron = pos_b - pos_a
             out.append((hi_a, lo_b, intron, hi_a + intron - lo_b))
+    return out
+
+
+def kept_spans(segments, L, k, s_min):
+    """the kept spans of ONE mate of L bytes (include/shark_hip.h, "spliced depth and the junction table"): of its first
+    SHK_MAX_SEGMENTS reported segments (rows (strand, pos, support, first, last), rank order) those with support >= s_min on
+    rank 0's strand, as [(lo, hi, pos)] sorted by (lo, hi)"""
+    segs = [tuple(int(v) for v in sg) for sg in segments][:SHK_MAX_SEGMENTS]
+    segs = [sg for sg in segs if sg[2] >= 1]
+    if not segs:
+        return []
+    strand0 = segs[0][0]
+    return sorted((segment_span(sg, L, k) + (sg[1],) for sg in segs if sg[2] >= s_min and sg[0] == strand0), key=lambda t: (t[0], t[1]))
+
+
+def span_union(spans, len_g):
+    """the union of spans (rows whose first two fields are lo, hi) clipped to [0, len_g): disjoint [(lo, hi)] in ascending order,
+    touching and overlapping spans merged -- the bases spliced depth counts for one mate"""
+    out = []
+    for lo, hi in sorted((max(int(sp[0]), 0), min(int(sp[1]), int(len_g))) for sp in spans):
+        if hi <= lo:
+            continue
+        if out and lo <= out[-1][1]:
+            out[-1] = (out[-1][0], max(out[-1][1], hi))
+        else:
+            out.append((lo, hi))
     return out
 
 

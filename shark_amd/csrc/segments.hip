@@ -180,10 +180,10 @@ uint64_t segments_cap(const Slot &s)
   return std::min<uint64_t>(s.cap_seg_keys / 2, s.cap_seg_entries / (2ull * s.seg_m));
 }
 
-int launch_segments(Ctx *ctx, const Slot &s, hipStream_t stream)
+int launch_segments_into(Ctx *ctx, const Slot &s, uint32_t m, uint32_t *d_keys, shk_segment *d_entries, uint64_t cap_assoc, hipStream_t stream)
 {
   const DeviceIndex &ix = ctx->idx;
-  if (!ix.ptab_lg || !ix.ptab || !ix.pdir || !s.d_seg_keys || !s.d_seg_entries || !s.seg_m || s.seg_m > SHK_MAX_SEGMENTS) {
+  if (!ix.ptab_lg || !ix.ptab || !ix.pdir || !d_keys || !d_entries || !m || m > SHK_MAX_SEGMENTS) {
     ctx->last_error = "segments mode without its table";
     return SHK_ERR_STATE;
   }
@@ -193,7 +193,7 @@ int launch_segments(Ctx *ctx, const Slot &s, hipStream_t stream)
   P.gene_ids = s.d_gene_ids;
   P.counters = s.d_counters;
   P.n = s.n;
-  P.cap = std::min<uint64_t>(std::min<uint64_t>(s.cap_gene_ids, segments_cap(s)), 0xFFFFFFFFull);
+  P.cap = std::min<uint64_t>(std::min<uint64_t>(s.cap_gene_ids, cap_assoc), 0xFFFFFFFFull);
   P.seq[0] = s.p.seq1; P.off[0] = s.p.off1; P.qual[0] = s.p.hasq ? s.p.qual1 : nullptr;
   P.seq[1] = s.p.seq2; P.off[1] = s.p.off2; P.qual[1] = s.p.hasq ? s.p.qual2 : nullptr;
   P.mq = s.p.mq;
@@ -201,14 +201,19 @@ int launch_segments(Ctx *ctx, const Slot &s, hipStream_t stream)
   P.ptab = ix.ptab;
   P.pdir = ix.pdir;
   P.ptab_lg = ix.ptab_lg;
-  P.m = s.seg_m;
-  P.n_keys = s.d_seg_keys;
-  P.entries = reinterpret_cast<uint32_t *>(s.d_seg_entries);
+  P.m = m;
+  P.n_keys = d_keys;
+  P.entries = reinterpret_cast<uint32_t *>(d_entries);
   // one wave per read up to eight workgroups per CU's worth of them, persistent beyond (launch_placement's bound)
   const uint64_t want = (s.n + PL_WAVES - 1) / PL_WAVES;
   hipLaunchKernelGGL(segments_kernel, dim3((unsigned)std::min<uint64_t>(want, 2048)), dim3(PL_THREADS), 0, stream, P);
   const hipError_t e = hipGetLastError();
   return e == hipSuccess ? SHK_OK : set_hip_error(ctx, e, "segments_kernel");
+}
+
+int launch_segments(Ctx *ctx, const Slot &s, hipStream_t stream)
+{
+  return launch_segments_into(ctx, s, s.seg_m, s.d_seg_keys, s.d_seg_entries, segments_cap(s), stream);
 }
 
 int launch_publish_segments(const Slot &s, uint64_t h_cap, hipStream_t stream)

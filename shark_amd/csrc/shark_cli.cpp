@@ -86,6 +86,9 @@ const char *USAGE_MESSAGE =
     "                                        over the whole sample on the GPUs (may be combined with --placements, --evidence and\n"
     "                                        --candidates; not for references of more than 65536 records)\n"
     "          --depth-min-support N         unique k-mers a mate's placement needs to be counted by --depth (default:1)\n"
+    "          --depth-spliced               --depth counts, per mate, the record bases its diagonals explain (the union of the spans of\n"
+    "                                        its best 4 diagonals with at least --depth-min-support unique k-mers on the best one's\n"
+    "                                        strand) instead of one stretch of the mate's length: a spliced mate leaves its introns out\n"
     "          --segments FILE               write <read> <gene> and per mate <diagonals> and M x <strand> <pos> <support> <first> <last>\n"
     "                                        per association, in the order of the output's lines: the M diagonals of the gene's record\n"
     "                                        most of the mate's unique k-mers lie on, with the first and last k-mer slot on each (a\n"
@@ -96,6 +99,10 @@ const char *USAGE_MESSAGE =
     "                                        by gene, donor, acceptor (record coordinates: the first base behind the left part, the\n"
     "                                        first base of the right part; the same refusals as --segments)\n"
     "          --junctions-min-support N     unique k-mers each side of a junction needs (default:8)\n"
+    "          --junctions-device            the table of --junctions is accumulated on the GPUs instead of from the segments on the\n"
+    "                                        host (the same file; needs --segments-max 4, the default)\n"
+    "          --junctions-capacity N        entries of that table per worker, rounded up to a power of two (default:1048576, 16 bytes\n"
+    "                                        each; it must hold every distinct junction: a full table is an error, not a shorter file)\n"
     "      -t N also sets the number of host threads that parse FASTQ / format output (default: up to 16)\n";
 
 struct Options {
@@ -130,6 +137,10 @@ struct Options {
   std::string junctions_path;
   FILE *junctions_file = nullptr;  // (--junctions, likewise; written once, after the last batch)
   unsigned junctions_min_support = 8;
+  bool depth_spliced = false;             // (--depth-spliced)
+  bool junctions_device = false;          // (--junctions-device: the table comes from the library's junction table, not from ReadOutput's)
+  uint64_t junctions_capacity = 1u << 20; // (--junctions-capacity; entries per worker: 16 MiB, a thousand times the junctions of a human transcriptome's panel)
+  bool junctions_capacity_given = false;
 };
 
 // The command line is described by one table: option names, whether a value follows, and a handler that
@@ -235,6 +246,14 @@ const OptionRow OPTION_TABLE[] = {
        o.junctions_min_support = value_of<unsigned>(v);
        if (o.junctions_min_support < 1) reject(USAGE_MESSAGE, "shark: --junctions-min-support must be at least 1.");
      }},
+    {1014, "depth-spliced", false, [](Options &o, const char *) { o.depth_spliced = true; }},
+    {1015, "junctions-device", false, [](Options &o, const char *) { o.junctions_device = true; }},
+    {1016, "junctions-capacity", true,
+     [](Options &o, const char *v) {
+       o.junctions_capacity = value_of<uint64_t>(v);
+       o.junctions_capacity_given = true;
+       if (o.junctions_capacity < 1 || o.junctions_capacity > (1ull << 32)) reject(USAGE_MESSAGE, "shark: --junctions-capacity must be in the range [1, 4294967296].");
+     }},
 };
 
 // Reads per device batch when --batch does not say.  A batch costs the device path 0.5-2 ms of launches, copies and bookkeeping
@@ -296,6 +315,10 @@ Options parse_arguments(int argc, char **argv)
     exit(EXIT_FAILURE);
   }
   if (opt.candidates_n_given && opt.candidates_path.empty()) reject(USAGE_MESSAGE, "shark: --candidates-n needs --candidates FILE.");
+  if (opt.depth_spliced && opt.depth_path.empty()) reject(USAGE_MESSAGE, "shark: --depth-spliced needs --depth FILE.");
+  if (opt.junctions_device && opt.junctions_path.empty()) reject(USAGE_MESSAGE, "shark: --junctions-device needs --junctions FILE.");
+  if (opt.junctions_capacity_given && !opt.junctions_device) reject(USAGE_MESSAGE, "shark: --junctions-capacity needs --junctions-device.");
+  if (opt.junctions_device && opt.segments_max < SHK_MAX_SEGMENTS) reject(USAGE_MESSAGE, "shark: --junctions-device needs --segments-max 4 (the device's table is defined at 4 diagonals per mate).");
   if (opt.out1_path.empty()) opt.out1_path = "sharked_sample.1";
   if (opt.out2_path.empty() && !opt.sample2_path.empty()) opt.out2_path = "sharked_sample.2";
   // --devices alone says how many workers there are; with --gpus N it has to name N devices
@@ -1983,7 +2006,7 @@ int run_sample(const Options &opt, GpuStart &gpu, BatchPool &pool, std::vector<s
   if (opt.paired_flag && opt.out2_path != "") w2.open(opt.out2_path, write_helpers);
   OffsetWriter *out1 = w1.is_open() ? &w1 : nullptr, *out2 = w2.is_open() ? &w2 : nullptr;
   ReadOutput ro(out1, out2, legend_ID, opt.evidence_file, opt.candidates_file, opt.placements_file, opt.paired_flag, opt.segments_file,
-                opt.junctions_file != nullptr, opt.k, opt.junctions_min_support);
+                opt.junctions_file != nullptr && !opt.junctions_device, opt.k, opt.junctions_min_support);
   setvbuf(stdout, nullptr, _IOFBF, 1 << 22);
 
   FeedPlan plan(opt, io_threads, need_qual);
@@ -2020,7 +2043,8 @@ int run_sample(const Options &opt, GpuStart &gpu, BatchPool &pool, std::vector<s
         return EXIT_FAILURE;
       }
   // (--segments, --junctions: one mode of the library serves both; the junctions are computed from the segments on the host)
-  if (opt.segments_file || opt.junctions_file)
+  const bool host_junctions = opt.junctions_file && !opt.junctions_device;
+  if (opt.segments_file || host_junctions)
     for (shk_ctx *ctx : gpu.ctxs)
       if (const int rc = shk_segments_enable(ctx, opt.segments_max)) {
         feed.stop();
@@ -2030,9 +2054,17 @@ int run_sample(const Options &opt, GpuStart &gpu, BatchPool &pool, std::vector<s
   // (--depth: every worker adds its batches' placed mates to its own depth state; write_depth sums the workers' arrays at the end)
   if (opt.depth_file)
     for (shk_ctx *ctx : gpu.ctxs)
-      if (const int rc = shk_depth_enable(ctx, opt.depth_min_support)) {
+      if (const int rc = opt.depth_spliced ? shk_depth_enable_spliced(ctx, opt.depth_min_support) : shk_depth_enable(ctx, opt.depth_min_support)) {
         feed.stop();
         std::cerr << "shark: depth mode could not be switched on: " << shk_strerror(rc) << " " << shk_last_error(ctx) << std::endl;
+        return EXIT_FAILURE;
+      }
+  // (--junctions-device: every worker adds its batches' junctions to its own table; write_junctions_device merges the tables at the end)
+  if (opt.junctions_file && opt.junctions_device)
+    for (shk_ctx *ctx : gpu.ctxs)
+      if (const int rc = shk_junctions_enable(ctx, opt.junctions_min_support, opt.junctions_capacity)) {
+        feed.stop();
+        std::cerr << "shark: the junction table could not be switched on: " << shk_strerror(rc) << " " << shk_last_error(ctx) << std::endl;
         return EXIT_FAILURE;
       }
   std::unique_ptr<BatchSplitter> fs;
@@ -2062,7 +2094,7 @@ int run_sample(const Options &opt, GpuStart &gpu, BatchPool &pool, std::vector<s
     });
   }
   std::vector<std::thread> analyzers = start_analyzers(gpu.ctxs, need_qual, opt.evidence_file != nullptr, opt.candidates_file != nullptr, opt.placements_file != nullptr,
-                                                        opt.segments_file != nullptr || opt.junctions_file != nullptr, order, to_format, t_gpu);
+                                                        opt.segments_file != nullptr || host_junctions, order, to_format, t_gpu);
   // ordered drain
   int failed = 0;
   double t_out = 0;
@@ -2110,7 +2142,7 @@ int run_sample(const Options &opt, GpuStart &gpu, BatchPool &pool, std::vector<s
   const bool placements_written = !opt.placements_file || (fclose(opt.placements_file) == 0 && !ro.placements_write_failed());
   const bool segments_written = !opt.segments_file || (fclose(opt.segments_file) == 0 && !ro.segments_write_failed());
   bool junctions_written = true;
-  if (opt.junctions_file) {
+  if (host_junctions) {      // (--junctions-device: written by main() from the workers' tables, as --depth is)
     junctions_written = ro.write_junctions(opt.junctions_file);
     junctions_written = fclose(opt.junctions_file) == 0 && junctions_written;
   }
@@ -2241,6 +2273,46 @@ bool write_depth(const Options &opt, std::vector<shk_ctx *> &ctxs, const std::ve
   return ok;
 }
 
+// --junctions --junctions-device: the workers' tables (one per context, each over the batches that worker classified) merged on the
+// host -- mates add up, the intron is the smallest --, then --junctions' lines in its order.  A table that was full is an error and
+// leaves an empty file, never a shorter table
+bool write_junctions_device(const Options &opt, std::vector<shk_ctx *> &ctxs, const std::vector<std::string> &legend_ID)
+{
+  std::map<std::tuple<uint32_t, uint32_t, uint32_t>, std::pair<uint32_t, uint64_t>> table;   // (gene, donor, acceptor) -> intron, mates
+  std::vector<shk_junction> rows;
+  for (size_t g = 0; g < ctxs.size(); ++g) {
+    uint64_t n = 0;
+    int rc = shk_junctions_get(ctxs[g], nullptr, 0, &n);
+    rows.resize((size_t)n);
+    if (rc == SHK_OK && n) rc = shk_junctions_get(ctxs[g], rows.data(), n, &n);
+    if (rc != SHK_OK) {
+      std::cerr << "shark: the junction table of worker " << g << " could not be read: " << shk_strerror(rc) << " " << shk_last_error(ctxs[g])
+                << (rc == SHK_ERR_INDEX_TOO_LARGE ? " (run again with a larger --junctions-capacity)" : "") << std::endl;
+      fclose(opt.junctions_file);
+      return false;
+    }
+    for (const shk_junction &j : rows) {
+      auto it = table.emplace(std::make_tuple(j.gene, j.donor, j.acceptor), std::make_pair(j.intron, (uint64_t)0)).first;
+      it->second.first = std::min(it->second.first, j.intron);
+      it->second.second += j.mates;
+    }
+  }
+  std::string text;
+  for (const auto &kv : table) {
+    const uint32_t g = std::get<0>(kv.first);
+    text += g < legend_ID.size() ? legend_ID[g] : std::string();
+    text += ' '; text += std::to_string(std::get<1>(kv.first));
+    text += ' '; text += std::to_string(std::get<2>(kv.first));
+    text += ' '; text += std::to_string(kv.second.first);
+    text += ' '; text += std::to_string(kv.second.second);
+    text += '\n';
+  }
+  bool ok = fwrite(text.data(), 1, text.size(), opt.junctions_file) == text.size();
+  ok = (fclose(opt.junctions_file) == 0) && ok;
+  if (!ok) std::cerr << "shark: cannot write the junctions file " << opt.junctions_path << std::endl;
+  return ok;
+}
+
 }  // namespace
 
 int main(int argc, char *argv[])
@@ -2301,6 +2373,7 @@ int main(int argc, char *argv[])
   timeline("outputs closed");
   pelapsed("Sample completed");
   if (opt.depth_file && !write_depth(opt, gpu.ctxs, legend_ID)) return EXIT_FAILURE;
+  if (opt.junctions_file && opt.junctions_device && !write_junctions_device(opt, gpu.ctxs, legend_ID)) return EXIT_FAILURE;
 
   if ((opt.gene_counts_path != "" || (opt.verbose && opt.gpus > 1)) && !gene_counts(opt, gpu.ctxs, legend_ID)) return EXIT_FAILURE;
   if (opt.verbose) {

@@ -117,6 +117,7 @@ static void slot_free(Slot &s)
   hipFree(s.d_place);
   if (s.h_place) (void)hipHostFree(s.h_place);
   hipFree(s.d_seg_keys); hipFree(s.d_seg_entries);
+  hipFree(s.d_sp_keys); hipFree(s.d_sp_entries);
   if (s.h_seg_keys) (void)hipHostFree(s.h_seg_keys);
   if (s.h_seg_entries) (void)hipHostFree(s.h_seg_entries);
   if (s.h_cand_reads) (void)hipHostFree(s.h_cand_reads);
@@ -312,6 +313,21 @@ static int enqueue_tail(Ctx *ctx, Slot &s, bool skip_hist_if_long, bool count_ge
       if ((rc = launch_publish_segments(s, std::min<uint64_t>(segments_host_cap(s), segments_cap(s)), st))) return rc;
     }
   }
+  // (spliced depth, the junction table: behind segments_kernel's records at m = SHK_MAX_SEGMENTS -- segments mode's own where it runs at that
+  //  m, else a launch of that kernel into arrays nobody else sees --, under depth_accumulate_kernel's rule for a batch that comes through
+  //  here again)
+  if (s.sp_depth || s.sp_junc) {
+    const shk_segment *entries = s.d_seg_entries;
+    uint64_t cap_assoc = segments_cap(s);
+    if (s.seg_m != SHK_MAX_SEGMENTS) {
+      if ((rc = ensure_capacity(ctx, &s.d_sp_keys, &s.cap_sp_keys, 2 * s.cap_gene_ids))) return rc;
+      if ((rc = ensure_capacity(ctx, &s.d_sp_entries, &s.cap_sp_entries, 2 * s.cap_gene_ids * SHK_MAX_SEGMENTS))) return rc;
+      entries = s.d_sp_entries;
+      cap_assoc = std::min<uint64_t>(s.cap_sp_keys / 2, s.cap_sp_entries / (2ull * SHK_MAX_SEGMENTS));
+      if ((rc = launch_segments_into(ctx, s, SHK_MAX_SEGMENTS, s.d_sp_keys, s.d_sp_entries, cap_assoc, st))) return rc;
+    }
+    if ((rc = launch_spliced_accumulate(ctx, s, entries, cap_assoc, skip_hist_if_long, st))) return rc;
+  }
   SHK_HIP(ctx, hipEventRecord(s.ev_done, st));
   return SHK_OK;
 }
@@ -352,7 +368,11 @@ static int enqueue_classify(Ctx *ctx, Slot &s, const shk_batch *b, uint32_t max_
   s.cand_m = ctx->cand_m;
   s.placement = ctx->placement;
   s.seg_m = ctx->seg_m;
-  s.depth = count_genes ? ctx->depth : 0u;   // (shk_count_work is a measurement: its batch is not counted)
+  s.depth = count_genes && !ctx->depth_spliced ? ctx->depth : 0u;   // (shk_count_work is a measurement: its batch is not counted)
+  s.sp_depth = count_genes && ctx->depth_spliced ? ctx->depth : 0u;
+  s.sp_junc = count_genes ? ctx->junc : 0u;
+  if (s.depth || s.sp_depth) ctx->depth_dirty = true;
+  if (s.sp_junc) ctx->junc_dirty = true;
   if ((rc = slot_reserve(ctx, s, n))) return rc;
   s.n = n;
   fill_params(ctx, s, b);
@@ -786,6 +806,7 @@ void shk_destroy(shk_ctx *ctx)
   for (Slot &sl : ctx->slots) slot_free(sl);
   hipFree(ctx->d_scratch); hipFree(ctx->d_gene_counts); hipFree(ctx->d_gene_totals); hipFree(ctx->d_work_counters);
   hipFree(ctx->d_depth_diff); hipFree(ctx->d_depth_mates); hipFree(ctx->d_depth_scan); hipFree(ctx->d_depth_scan_temp); hipFree(ctx->d_depth_summary);
+  hipFree(ctx->d_junc_tab); hipFree(ctx->d_junc_dropped);
   dist_release(ctx);
   for (auto e : ctx->ev_start) (void)hipEventDestroy(e);
   for (auto e : ctx->ev_stop) (void)hipEventDestroy(e);
@@ -1257,14 +1278,19 @@ static bool tickets_outstanding(const shk_ctx *ctx)
   return false;
 }
 
-int shk_depth_enable(shk_ctx *ctx, uint32_t min_support)
+// both kinds of depth (plain intervals, unions of kept spans) over the one state
+static int depth_enable_kind(shk_ctx *ctx, uint32_t min_support, bool spliced, const char *who)
 {
   if (!ctx) return SHK_ERR_ARG;
-  if (tickets_outstanding(ctx)) { ctx->last_error = "shk_depth_enable: tickets are outstanding (wait for them first)"; return SHK_ERR_STATE; }
+  if (tickets_outstanding(ctx)) { ctx->last_error = std::string(who) + ": tickets are outstanding (wait for them first)"; return SHK_ERR_STATE; }
   if (min_support) {
-    if (ctx->mode != 2) { ctx->last_error = "shk_depth_enable: the index is not finalized"; return SHK_ERR_STATE; }
-    if (!ctx->idx.ptab_lg) { ctx->last_error = "shk_depth_enable: the index was finalized without shk_ref_keep_positions"; return SHK_ERR_STATE; }
-    if (ctx->n_records > 65536 || ctx->idx.wrap || !ctx->idx.gene_start) { ctx->last_error = "shk_depth_enable: more than 65 536 records (gene ids wrap)"; return SHK_ERR_STATE; }
+    if (ctx->mode != 2) { ctx->last_error = std::string(who) + ": the index is not finalized"; return SHK_ERR_STATE; }
+    if (!ctx->idx.ptab_lg) { ctx->last_error = std::string(who) + ": the index was finalized without shk_ref_keep_positions"; return SHK_ERR_STATE; }
+    if (ctx->n_records > 65536 || ctx->idx.wrap || !ctx->idx.gene_start) { ctx->last_error = std::string(who) + ": more than 65 536 records (gene ids wrap)"; return SHK_ERR_STATE; }
+    if (ctx->d_depth_diff && ctx->depth_dirty && spliced != ctx->depth_spliced) {
+      ctx->last_error = std::string(who) + ": the state holds depth of the other kind (plain / spliced): shk_depth_reset first";
+      return SHK_ERR_STATE;
+    }
     if (!ctx->d_depth_diff) {
       SHK_HIP(ctx, hipSetDevice(ctx->prm.device));
       const size_t bytes = (size_t)(ctx->gene_start.back() + 1) * sizeof(uint32_t);
@@ -1277,10 +1303,14 @@ int shk_depth_enable(shk_ctx *ctx, uint32_t min_support)
       SHK_HIP(ctx, hipMemsetAsync(diff, 0, bytes, ctx->stream));
       SHK_HIP(ctx, hipMemsetAsync(mates, 0, sizeof(unsigned long long), ctx->stream));
     }
+    ctx->depth_spliced = spliced;
   }
   ctx->depth = min_support;
   return SHK_OK;
 }
+
+int shk_depth_enable(shk_ctx *ctx, uint32_t min_support) { return depth_enable_kind(ctx, min_support, false, "shk_depth_enable"); }
+int shk_depth_enable_spliced(shk_ctx *ctx, uint32_t min_support) { return depth_enable_kind(ctx, min_support, true, "shk_depth_enable_spliced"); }
 
 int shk_depth_layout(const shk_ctx *ctx, uint64_t *gene_start, uint32_t n_genes)
 {
@@ -1363,6 +1393,88 @@ int shk_depth_reset(shk_ctx *ctx)
   SHK_HIP(ctx, hipMemsetAsync(ctx->d_depth_diff, 0, (size_t)(ctx->gene_start.back() + 1) * sizeof(uint32_t), ctx->stream));
   SHK_HIP(ctx, hipMemsetAsync(ctx->d_depth_mates, 0, sizeof(unsigned long long), ctx->stream));
   ctx->depth_scan_current = false;
+  ctx->depth_dirty = false;
+  SHK_HIP(ctx, hipStreamSynchronize(ctx->stream));
+  return SHK_OK;
+}
+
+// ---- the junction table (spliced.hip): the state lives in the context, the batches' tails add to it ----
+int shk_junctions_enable(shk_ctx *ctx, uint32_t min_support, uint64_t capacity)
+{
+  if (!ctx) return SHK_ERR_ARG;
+  if (tickets_outstanding(ctx)) { ctx->last_error = "shk_junctions_enable: tickets are outstanding (wait for them first)"; return SHK_ERR_STATE; }
+  if (min_support) {
+    if (ctx->mode != 2) { ctx->last_error = "shk_junctions_enable: the index is not finalized"; return SHK_ERR_STATE; }
+    if (!ctx->idx.ptab_lg) { ctx->last_error = "shk_junctions_enable: the index was finalized without shk_ref_keep_positions"; return SHK_ERR_STATE; }
+    if (ctx->n_records > 65536 || ctx->idx.wrap || !ctx->idx.gene_start) { ctx->last_error = "shk_junctions_enable: more than 65 536 records (gene ids wrap)"; return SHK_ERR_STATE; }
+    if (capacity > (1ull << 40)) { ctx->last_error = "shk_junctions_enable: capacity beyond 2^40 entries"; return SHK_ERR_ARG; }
+    uint64_t cap = 64;
+    while (cap < capacity) cap <<= 1;
+    if (ctx->d_junc_tab && cap != ctx->junc_cap) {
+      if (ctx->junc_dirty) { ctx->last_error = "shk_junctions_enable: another capacity than the table's (shk_junctions_reset first)"; return SHK_ERR_ARG; }
+      SHK_HIP(ctx, hipSetDevice(ctx->prm.device));
+      SHK_HIP(ctx, hipStreamSynchronize(ctx->stream));
+      (void)hipFree(ctx->d_junc_tab);
+      ctx->d_junc_tab = nullptr;
+      ctx->junc_cap = 0;
+    }
+    if (!ctx->d_junc_tab) {
+      SHK_HIP(ctx, hipSetDevice(ctx->prm.device));
+      if (!ctx->d_junc_dropped) SHK_HIP(ctx, hipMalloc((void **)&ctx->d_junc_dropped, sizeof(unsigned long long)));
+      SHK_HIP(ctx, hipMalloc((void **)&ctx->d_junc_tab, (size_t)cap * sizeof(JunctionEntry)));
+      ctx->junc_cap = cap;
+      ctx->junc_dirty = false;
+      if (const int rc = launch_junction_clear(ctx)) return rc;
+    }
+  }
+  ctx->junc = min_support;
+  return SHK_OK;
+}
+
+int shk_junctions_get(shk_ctx *ctx, shk_junction *out, uint64_t cap, uint64_t *n)
+{
+  if (!ctx || !n) return SHK_ERR_ARG;
+  if (!ctx->d_junc_tab) { ctx->last_error = "shk_junctions_get: the junction table was never enabled on this context"; return SHK_ERR_STATE; }
+  if (tickets_outstanding(ctx)) { ctx->last_error = "shk_junctions_get: tickets are outstanding (wait for them first)"; return SHK_ERR_STATE; }
+  SHK_HIP(ctx, hipSetDevice(ctx->prm.device));
+  // once per sample: the whole table to the host, the occupied entries ordered there.  Key order IS (gene, donor, acceptor) order: the
+  // genes' bases are numbered gene after gene and a donor is at least k, so within the reference donors ascend with (gene, donor)
+  std::vector<JunctionEntry> tab((size_t)ctx->junc_cap);
+  unsigned long long dropped = 0;
+  SHK_HIP(ctx, hipMemcpyAsync(&dropped, ctx->d_junc_dropped, sizeof(dropped), hipMemcpyDeviceToHost, ctx->stream));
+  SHK_HIP(ctx, hipMemcpyAsync(tab.data(), ctx->d_junc_tab, tab.size() * sizeof(JunctionEntry), hipMemcpyDeviceToHost, ctx->stream));
+  SHK_HIP(ctx, hipStreamSynchronize(ctx->stream));
+  if (dropped) {
+    ctx->last_error = "shk_junctions_get: the table was full for " + std::to_string(dropped) + " observations (shk_junctions_reset, then a larger capacity)";
+    return SHK_ERR_INDEX_TOO_LARGE;
+  }
+  tab.erase(std::remove_if(tab.begin(), tab.end(), [](const JunctionEntry &e) { return e.key == JUNCTION_EMPTY; }), tab.end());
+  *n = tab.size();
+  if (!out) return SHK_OK;
+  if (cap < tab.size()) return SHK_ERR_ARG;
+  std::sort(tab.begin(), tab.end(), [](const JunctionEntry &a, const JunctionEntry &b) { return a.key < b.key; });
+  const std::vector<uint64_t> &gs = ctx->gene_start;
+  for (size_t i = 0; i < tab.size(); ++i) {
+    const uint64_t donor = tab[i].key >> 32, acceptor = tab[i].key & 0xFFFFFFFFull;
+    // acceptor < len_g strictly: the last gene that starts at or in front of it (genes without a record have no bases)
+    const size_t g = (size_t)(std::upper_bound(gs.begin(), gs.end(), acceptor) - gs.begin()) - 1;
+    out[i].gene = (uint32_t)g;
+    out[i].donor = (uint32_t)(donor - gs[g]);
+    out[i].acceptor = (uint32_t)(acceptor - gs[g]);
+    out[i].intron = tab[i].intron;
+    out[i].mates = tab[i].mates;
+  }
+  return SHK_OK;
+}
+
+int shk_junctions_reset(shk_ctx *ctx)
+{
+  if (!ctx) return SHK_ERR_ARG;
+  if (!ctx->d_junc_tab) { ctx->last_error = "shk_junctions_reset: the junction table was never enabled on this context"; return SHK_ERR_STATE; }
+  if (tickets_outstanding(ctx)) { ctx->last_error = "shk_junctions_reset: tickets are outstanding (wait for them first)"; return SHK_ERR_STATE; }
+  SHK_HIP(ctx, hipSetDevice(ctx->prm.device));
+  if (const int rc = launch_junction_clear(ctx)) return rc;
+  ctx->junc_dirty = false;
   SHK_HIP(ctx, hipStreamSynchronize(ctx->stream));
   return SHK_OK;
 }

@@ -327,9 +327,24 @@ struct Slot {
   shk_segment *d_seg_entries = nullptr; size_t cap_seg_entries = 0;
   uint32_t *h_seg_keys = nullptr; size_t cap_h_seg_keys = 0;        // (host batches; filled by publish_segments_kernel)
   shk_segment *h_seg_entries = nullptr; size_t cap_h_seg_entries = 0;
+  // spliced depth and the junction table (spliced.hip): submitted with these floors (0: not).  They read segments_kernel's records at
+  // m = SHK_MAX_SEGMENTS: segments mode's own when it runs at that m, else arrays of their own (allocated with the first such batch,
+  // never handed out) that a second launch of segments_kernel fills
+  uint32_t sp_depth = 0, sp_junc = 0;
+  uint32_t *d_sp_keys = nullptr; size_t cap_sp_keys = 0;
+  shk_segment *d_sp_entries = nullptr; size_t cap_sp_entries = 0;
 };
 
 struct Ctx;
+
+// one entry of the junction table (spliced.hip): key = (gene_start[g] + donor) << 32 | (gene_start[g] + acceptor)
+struct JunctionEntry {
+  unsigned long long key;   // JUNCTION_EMPTY: free
+  uint32_t mates;           // observations since the last reset
+  uint32_t intron;          // the smallest seen (all ones in a free entry)
+};
+static_assert(sizeof(JunctionEntry) == 16, "16-byte entries");
+constexpr unsigned long long JUNCTION_EMPTY = ~0ull;   // (no key: its acceptor half would be base 2^32 - 1 of a reference of fewer than 2^32 bases)
 
 // index_build.hip
 int build_index(Ctx *ctx);
@@ -342,10 +357,16 @@ int launch_placement(Ctx *ctx, const Slot &s, hipStream_t stream);
 int launch_publish_placements(const uint32_t *counters, const shk_placement *src, shk_placement *h_dst, uint64_t h_cap, hipStream_t stream);
 // segments.hip: per association of the batch in `s` and per mate its best s.seg_m diagonals with their first and last voting slot
 int launch_segments(Ctx *ctx, const Slot &s, hipStream_t stream);
+// the same kernel at m entries per mate into other arrays (cap_assoc: associations they hold): what spliced.hip reads when segments mode is off or narrower
+int launch_segments_into(Ctx *ctx, const Slot &s, uint32_t m, uint32_t *d_keys, shk_segment *d_entries, uint64_t cap_assoc, hipStream_t stream);
 uint64_t segments_cap(const Slot &s);   // associations d_seg_keys / d_seg_entries hold at s.seg_m
 int launch_publish_segments(const Slot &s, uint64_t h_cap, hipStream_t stream);   // h_cap: associations the pinned arrays (and the device's) hold
 // depth.hip: the batch in `s` (its placements in s.d_place) into the context's difference array, behind launch_placement; skip_if_long: as launch_gene_hist
 int launch_depth_accumulate(Ctx *ctx, const Slot &s, bool skip_if_long, hipStream_t stream);
+// spliced.hip: the batch in `s` from its segments at m = SHK_MAX_SEGMENTS (`entries`, cap_assoc associations) into the depth state (s.sp_depth)
+// and / or the junction table (s.sp_junc), behind segments_kernel; skip_if_long: as launch_gene_hist
+int launch_spliced_accumulate(Ctx *ctx, const Slot &s, const shk_segment *entries, uint64_t cap_assoc, bool skip_if_long, hipStream_t stream);
+int launch_junction_clear(Ctx *ctx);   // every entry of Ctx::d_junc_tab empty, Ctx::d_junc_dropped 0, on ctx->stream
 // the read-out: Ctx::d_depth_scan[1 + x] = depth of base x of the full array (inclusive prefix sum of the difference array), on ctx->stream
 int depth_scan(Ctx *ctx);
 // per gene {len, covered, max, sum} of the scanned array into Ctx::d_depth_summary (nidx records), on ctx->stream behind depth_scan
@@ -459,6 +480,15 @@ struct Ctx {
   uint64_t *d_depth_scan_temp = nullptr;
   bool depth_scan_current = false;             // d_depth_scan holds the scan of the state as it stands (cleared by every launch that adds to it and by reset)
   shk_gene_depth *d_depth_summary = nullptr;   // nidx records (allocated by the first shk_depth_summary)
+  // (shk_depth_enable_spliced) one state holds one kind: plain intervals or the unions of kept spans
+  bool depth_spliced = false;                  // the kind `depth` stands for
+  bool depth_dirty = false;                    // a depth batch of either kind was submitted since the first enable / the last reset
+  // junction table (shk_junctions_enable; spliced.hip): like the depth state it outlives the mode's being switched off
+  uint32_t junc = 0;                           // min_support for the batches submitted from now on (0: off)
+  uint64_t junc_cap = 0;                       // entries, a power of two >= 64 (0: never enabled)
+  JunctionEntry *d_junc_tab = nullptr;
+  unsigned long long *d_junc_dropped = nullptr;   // observations that found the table full since the last reset
+  bool junc_dirty = false;                     // a junction batch was submitted since the first enable / the last reset
 
   // timing
   bool timing = false;
