@@ -485,6 +485,74 @@ typedef struct shk_junction { uint32_t gene, donor, acceptor, intron; uint64_t m
 int shk_junctions_get(shk_ctx *ctx, shk_junction *out, uint64_t cap, uint64_t *n);
 int shk_junctions_reset(shk_ctx *ctx);
 
+/* ---- pileup: per record base, how many counted mates show A, C, G or T there -- the third consumer of segments mode ---- */
+/* Placement, depth, segments, spliced depth and the junction table say WHERE a mate lies; pileup says what it READS there.  It
+ * rests on definitions this header already has, unchanged: the mate as the classifier sees it (its raw bytes behind the -q mask:
+ * a byte whose quality is below min_quality is the byte minus 64), L, segment, record span [lo, hi), and the KEPT SPANS of a mate
+ * at floor s_min (the first four ranked segments with support >= s_min on rank 0's strand, sorted by (lo, hi), equal spans in
+ * rank order).
+ *
+ * OWNERSHIP.  For every association (read, gene g) of a COUNTED batch and each mate of it, walk the kept spans in sorted order
+ * with spliced depth's `reach`, 0 at first:
+ *     span r owns the record coordinates [max(lo_r, reach), min(hi_r, len_g));   then reach = max(reach, hi_r).
+ * A record base is therefore owned by at most one span of a mate -- the earliest in sorted order that contains it --, and the owned
+ * pieces are exactly the pieces spliced depth adds.
+ *
+ * OBSERVATION.  An owned coordinate x on the diagonal (strand, pos) of its span reads one byte of the mate, at index
+ *     strand 0: i = x - pos;        strand 1: i = pos + L - 1 - x.
+ * A span lies inside [pos, pos + L) (first <= last <= L - k), so 0 <= i < L: every owned coordinate has its byte.  Let
+ * c = to_int[byte] (kmer_utils.hpp:29-41: A, C, G, T and their lower case are 1 .. 4, every other byte 0).
+ *     c == 0 (an N, any other non-base, a byte masked by -q): the base makes NO observation;
+ *     otherwise the observed base ON THE RECORD'S STRAND is b = c - 1 on strand 0 and b = 3 - (c - 1) on strand 1: with the codes
+ *     A, C, G, T = 0 .. 3 that is the complement (the fact reverse_char states).
+ *   counts[g][x][b] = the number of observations of b at x, summed over all batches counted since the last shk_pileup_reset.
+ * A mate is a PILEUP MATE iff it owned at least one coordinate (spliced depth's rule for shk_depth_mates), whatever its bytes there.
+ * Example (segments section): the mate with spans [9653, 9727) and [10912, 10943) on strand 1 makes 74 + 31 observations (if all
+ * its bytes there are bases) and none at the 1185 bases between them.
+ *
+ * Consequences:
+ *   - a base counts at most once per mate, so every counter is at most the number of pileup mates; a 64-bit device counter of
+ *     pileup mates guards the 32-bit counters: beyond 2^32 - 1 pileup mates since the last reset every read-out returns
+ *     SHK_ERR_INDEX_TOO_LARGE until shk_pileup_reset (shk_pileup_mates still stores the number);
+ *   - with the same s_min over the same batches,
+ *         sum_b counts[g][x][b] + (observations lost to c == 0 at x) == spliced depth[g][x]:
+ *     equality where no read byte is a non-base, and never more;
+ *   - nothing is compared with the reference sequence and the device does not keep it: the caller holds the FASTA, the reference
+ *     allele is the caller's to look up;
+ *   - a read tied over several genes counts in each of them; mates are counted, not fragments;
+ *   - a batch is counted exactly once, by depth mode's rules word for word: a batch with more associations than the result buffer
+ *     holds, or with reads beyond a length bound taken on trust, is counted when the tail runs again (shk_classify_wait /
+ *     shk_classify_device); a batch vouched for wrongly and a shk_count_work batch are never counted;
+ *   - integers only, no tolerance anywhere.
+ *
+ * State: uint32 counts[gene_start[nidx]][4] on the device, interleaved -- entry [x * 4 + b] of gene g at (gene_start[g] + x) * 4 + b,
+ * shk_depth_layout's gene_start, which answers wherever this mode can be switched on --, 16 bytes per record base (four times
+ * depth's), and the 64-bit counter.  The counters are the answer: a read-out is one copy, no scan.
+ *
+ * Independent of every other mode: gene_off, gene_ids, n_assoc, shk_last_kernel, shk_gene_counts and every other mode's records
+ * and state are the same with the mode on and off.  With segments mode on at m = SHK_MAX_SEGMENTS its one segments_kernel launch
+ * serves pileup too; otherwise segments_kernel runs at m = 4 into the arrays of the context's own that spliced depth and the
+ * junction table use (one launch serves all three).  pileup_kernel follows.  With the mode off no launch and no allocation is
+ * added.  New: the reference has no counterpart. */
+/* Switches pileup mode on with s_min = min_support (>= 1) or off (0) for the batches submitted AFTERWARDS, through any of the four
+ * families.  State rules are shk_junctions_enable's: switching on returns SHK_ERR_STATE before shk_ref_finalize, without
+ * shk_ref_keep_positions, on an index of more than 65 536 records; either way while tickets are outstanding.  The first enable
+ * allocates and clears the state (SHK_ERR_NOMEM if it cannot: the mode is left off); switching off keeps what has been accumulated,
+ * switching on again goes on from it.  New: no counterpart. */
+int shk_pileup_enable(shk_ctx *ctx, uint32_t min_support);
+/* The read-outs, with depth's rules: SHK_ERR_STATE if the mode was never enabled on this context or while tickets are outstanding,
+ * SHK_ERR_INDEX_TOO_LARGE behind the guard above; otherwise they run on the context's stream behind everything enqueued so far and
+ * leave the state untouched.  New: no counterpart.
+ *   shk_pileup_get      the 4 * len_g entries [x * 4 + b] of one gene (gene < nidx) into host memory; cap (entries) at least that
+ *   shk_pileup_get_all  all 4 * gene_start[nidx] entries (cap at least that): device == 0: `counts` is a host pointer; device != 0:
+ *                       a DEVICE pointer, the copy stays on the device
+ *   shk_pileup_mates    the pileup mates since the last reset
+ *   shk_pileup_reset    clears the counters and the mate counter (the mode stays as it is) */
+int shk_pileup_get(shk_ctx *ctx, uint32_t gene, uint32_t *counts, uint64_t cap);
+int shk_pileup_get_all(shk_ctx *ctx, uint32_t *counts, uint64_t cap, int device);
+int shk_pileup_mates(const shk_ctx *ctx, uint64_t *n);
+int shk_pileup_reset(shk_ctx *ctx);
+
 /* Per-gene number of assigned reads accumulated over all classify calls (all
  * waited tickets) since the last reset (counts[g] for g in [0, 65536)); the quantity all-reduced
  * across GPUs.  n must be <= 65536. */

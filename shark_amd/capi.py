@@ -84,6 +84,7 @@ EXPORTS = [
     "shk_segments_enable", "shk_segments_last",
     "shk_depth_enable", "shk_depth_layout", "shk_depth_get", "shk_depth_get_all", "shk_depth_summary", "shk_depth_mates", "shk_depth_reset",
     "shk_depth_enable_spliced", "shk_junctions_enable", "shk_junctions_get", "shk_junctions_reset",
+    "shk_pileup_enable", "shk_pileup_get", "shk_pileup_get_all", "shk_pileup_mates", "shk_pileup_reset",
 ]
 SHK_PIPE_DEPTH = 3
 SHK_DIST_ID_BYTES = 128
@@ -165,6 +166,11 @@ def load():
         "shk_junctions_enable": (C.c_int, [p, C.c_uint32, C.c_uint64]),
         "shk_junctions_get": (C.c_int, [p, p, C.c_uint64, C.POINTER(C.c_uint64)]),
         "shk_junctions_reset": (C.c_int, [p]),
+        "shk_pileup_enable": (C.c_int, [p, C.c_uint32]),
+        "shk_pileup_get": (C.c_int, [p, C.c_uint32, p, C.c_uint64]),
+        "shk_pileup_get_all": (C.c_int, [p, p, C.c_uint64, C.c_int]),
+        "shk_pileup_mates": (C.c_int, [p, C.POINTER(C.c_uint64)]),
+        "shk_pileup_reset": (C.c_int, [p]),
     }
     variant = bool(os.environ.get("SHK_LIB_PATH"))
     for name, (res, args) in later.items():
@@ -515,6 +521,39 @@ class SharkHip:
 
     def junctions_reset(self):
         self._check(self.L.shk_junctions_reset(self.h), "shk_junctions_reset")
+
+    # ---- pileup: per record base the counted mates that show A, C, G or T there -- segments mode's third consumer on the device --------
+    def pileup_enable(self, min_support=8):
+        """batches submitted from now on add, per mate, the bases under its kept spans (kept_spans at s_min = min_support; a base owned
+        by the earliest span that holds it) to the context's pileup state; 0 switches the mode off and keeps the state"""
+        self._check(self.L.shk_pileup_enable(self.h, int(min_support)), "shk_pileup_enable")
+
+    def pileup(self, gene):
+        """the counts of one gene: uint32 (len_g, 4), columns A, C, G, T on the record's strand"""
+        gs = self.depth_layout()
+        d = np.zeros((int(gs[gene + 1] - gs[gene]) if 0 <= gene < len(gs) - 1 else 0, 4), dtype=np.uint32)     # (no such gene: the call says so)
+        self._check(self.L.shk_pileup_get(self.h, int(gene), _ptr(d), d.size), "shk_pileup_get")
+        return d
+
+    def pileup_all(self, device_ptr=None):
+        """the counts of every base, gene after gene (depth_layout): uint32 (n_bases, 4); with device_ptr (the address of a DEVICE buffer
+        of at least 4 * gene_start[nidx] uint32) the copy stays on the device and the number of entries is returned"""
+        total = int(self.depth_layout()[-1])
+        if device_ptr is not None:
+            self._check(self.L.shk_pileup_get_all(self.h, C.c_void_p(device_ptr), 4 * total, 1), "shk_pileup_get_all")
+            return 4 * total
+        d = np.zeros((total, 4), dtype=np.uint32)
+        self._check(self.L.shk_pileup_get_all(self.h, _ptr(d), d.size, 0), "shk_pileup_get_all")
+        return d
+
+    def pileup_mates(self):
+        """mates that owned at least one record base since the last reset"""
+        n = C.c_uint64()
+        self._check(self.L.shk_pileup_mates(self.h, C.byref(n)), "shk_pileup_mates")
+        return int(n.value)
+
+    def pileup_reset(self):
+        self._check(self.L.shk_pileup_reset(self.h), "shk_pileup_reset")
 
     def gene_counts(self, n=65536):
         a = np.zeros(n, dtype=np.uint64)

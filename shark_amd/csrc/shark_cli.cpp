@@ -103,6 +103,11 @@ const char *USAGE_MESSAGE =
     "                                        host (the same file; needs --segments-max 4, the default)\n"
     "          --junctions-capacity N        entries of that table per worker, rounded up to a power of two (default:1048576, 16 bytes\n"
     "                                        each; it must hold every distinct junction: a full table is an error, not a shorter file)\n"
+    "          --pileup FILE                 write <gene> <x> <A> <C> <G> <T> per record base (0-based) at least one mate shows a base at:\n"
+    "                                        how many mates show each base there, on the record's strand, under the spans --depth-spliced\n"
+    "                                        counts, summed over the whole sample on the GPUs; genes in the legend's order (combines with\n"
+    "                                        --depth, --junctions and --segments; not for references of more than 65536 records)\n"
+    "          --pileup-min-support N        unique k-mers a diagonal of a mate needs to be read by --pileup (default:8)\n"
     "      -t N also sets the number of host threads that parse FASTQ / format output (default: up to 16)\n";
 
 struct Options {
@@ -141,6 +146,10 @@ struct Options {
   bool junctions_device = false;          // (--junctions-device: the table comes from the library's junction table, not from ReadOutput's)
   uint64_t junctions_capacity = 1u << 20; // (--junctions-capacity; entries per worker: 16 MiB, a thousand times the junctions of a human transcriptome's panel)
   bool junctions_capacity_given = false;
+  std::string pileup_path;
+  FILE *pileup_file = nullptr;     // (--pileup, likewise; written once, after the last batch)
+  unsigned pileup_min_support = 8;
+  bool pileup_min_support_given = false;
 };
 
 // The command line is described by one table: option names, whether a value follows, and a handler that
@@ -254,6 +263,13 @@ const OptionRow OPTION_TABLE[] = {
        o.junctions_capacity_given = true;
        if (o.junctions_capacity < 1 || o.junctions_capacity > (1ull << 32)) reject(USAGE_MESSAGE, "shark: --junctions-capacity must be in the range [1, 4294967296].");
      }},
+    {1017, "pileup", true, [](Options &o, const char *v) { o.pileup_path = value_of<std::string>(v); }},
+    {1018, "pileup-min-support", true,
+     [](Options &o, const char *v) {
+       o.pileup_min_support = value_of<unsigned>(v);
+       o.pileup_min_support_given = true;
+       if (o.pileup_min_support < 1) reject(USAGE_MESSAGE, "shark: --pileup-min-support must be at least 1.");
+     }},
 };
 
 // Reads per device batch when --batch does not say.  A batch costs the device path 0.5-2 ms of launches, copies and bookkeeping
@@ -319,6 +335,7 @@ Options parse_arguments(int argc, char **argv)
   if (opt.junctions_device && opt.junctions_path.empty()) reject(USAGE_MESSAGE, "shark: --junctions-device needs --junctions FILE.");
   if (opt.junctions_capacity_given && !opt.junctions_device) reject(USAGE_MESSAGE, "shark: --junctions-capacity needs --junctions-device.");
   if (opt.junctions_device && opt.segments_max < SHK_MAX_SEGMENTS) reject(USAGE_MESSAGE, "shark: --junctions-device needs --segments-max 4 (the device's table is defined at 4 diagonals per mate).");
+  if (opt.pileup_min_support_given && opt.pileup_path.empty()) reject(USAGE_MESSAGE, "shark: --pileup-min-support needs --pileup FILE.");
   if (opt.out1_path.empty()) opt.out1_path = "sharked_sample.1";
   if (opt.out2_path.empty() && !opt.sample2_path.empty()) opt.out2_path = "sharked_sample.2";
   // --devices alone says how many workers there are; with --gpus N it has to name N devices
@@ -1884,6 +1901,7 @@ std::string build_index(const Options &opt, GpuStart &gpu, std::vector<std::stri
       if (opt.depth_file && legend_ID.size() > 65536) return "shark: --depth is not available for a reference of more than 65536 records (gene ids wrap there).";
       if (opt.segments_file && legend_ID.size() > 65536) return "shark: --segments is not available for a reference of more than 65536 records (gene ids wrap there).";
       if (opt.junctions_file && legend_ID.size() > 65536) return "shark: --junctions is not available for a reference of more than 65536 records (gene ids wrap there).";
+      if (opt.pileup_file && legend_ID.size() > 65536) return "shark: --pileup is not available for a reference of more than 65536 records (gene ids wrap there).";
       const size_t len = strnlen(rec.seq.data(), rec.seq.size());  // C-string semantics (main.cpp:164)
       for (auto *ctx : gpu.ctxs) {
         const int rc = shk_ref_add(ctx, rec.seq.data(), len);
@@ -1893,7 +1911,7 @@ std::string build_index(const Options &opt, GpuStart &gpu, std::vector<std::stri
   }
   pelapsed("Transcript file processed");
   timeline("reference read");
-  if (opt.placements_file || opt.depth_file || opt.segments_file || opt.junctions_file)
+  if (opt.placements_file || opt.depth_file || opt.segments_file || opt.junctions_file || opt.pileup_file)
     for (auto *ctx : gpu.ctxs)
       if (const int rc = shk_ref_keep_positions(ctx)) return std::string("shark: ") + shk_strerror(rc);
   {
@@ -2065,6 +2083,14 @@ int run_sample(const Options &opt, GpuStart &gpu, BatchPool &pool, std::vector<s
       if (const int rc = shk_junctions_enable(ctx, opt.junctions_min_support, opt.junctions_capacity)) {
         feed.stop();
         std::cerr << "shark: the junction table could not be switched on: " << shk_strerror(rc) << " " << shk_last_error(ctx) << std::endl;
+        return EXIT_FAILURE;
+      }
+  // (--pileup: every worker adds its batches' bases to its own pileup state; write_pileup sums the workers' arrays at the end)
+  if (opt.pileup_file)
+    for (shk_ctx *ctx : gpu.ctxs)
+      if (const int rc = shk_pileup_enable(ctx, opt.pileup_min_support)) {
+        feed.stop();
+        std::cerr << "shark: pileup mode could not be switched on: " << shk_strerror(rc) << " " << shk_last_error(ctx) << std::endl;
         return EXIT_FAILURE;
       }
   std::unique_ptr<BatchSplitter> fs;
@@ -2313,6 +2339,58 @@ bool write_junctions_device(const Options &opt, std::vector<shk_ctx *> &ctxs, co
   return ok;
 }
 
+// --pileup: the workers' counters (one array per context, each over the batches that worker classified) summed on the host -- the
+// counts are additive over contexts --, then one line per record base with at least one observation: <gene> <x> <A> <C> <G> <T>,
+// genes in id order, x ascending
+bool write_pileup(const Options &opt, std::vector<shk_ctx *> &ctxs, const std::vector<std::string> &legend_ID)
+{
+  shk_index_info info{};
+  shk_index_info_get(ctxs[0], &info);
+  const uint32_t n_genes = (uint32_t)info.nidx;
+  std::vector<uint64_t> gene_start((size_t)n_genes + 1, 0);
+  int rc = shk_depth_layout(ctxs[0], gene_start.data(), n_genes);
+  if (rc != SHK_OK) {
+    std::cerr << "shark: the pileup layout could not be read: " << shk_strerror(rc) << " " << shk_last_error(ctxs[0]) << std::endl;
+    fclose(opt.pileup_file);
+    return false;
+  }
+  std::vector<uint32_t> counts((size_t)gene_start[n_genes] * 4, 0), part;
+  for (size_t g = 0; g < ctxs.size() && rc == SHK_OK; ++g) {
+    std::vector<uint32_t> &into = g == 0 ? counts : part;
+    into.assign(counts.size(), 0);
+    rc = shk_pileup_get_all(ctxs[g], into.data(), into.size(), 0);
+    if (g != 0 && rc == SHK_OK)
+      for (size_t x = 0; x < counts.size(); ++x) counts[x] += part[x];
+    if (rc != SHK_OK) std::cerr << "shark: the pileup of worker " << g << " could not be read: " << shk_strerror(rc) << " " << shk_last_error(ctxs[g]) << std::endl;
+  }
+  if (rc != SHK_OK) {
+    fclose(opt.pileup_file);
+    return false;
+  }
+  std::string text;
+  bool ok = true;
+  for (uint32_t g = 0; g < n_genes; ++g) {
+    const uint32_t *c = counts.data() + gene_start[g] * 4;
+    const uint64_t len = gene_start[g + 1] - gene_start[g];
+    const std::string &name = g < legend_ID.size() ? legend_ID[g] : std::string();
+    for (uint64_t x = 0; x < len; ++x) {
+      const uint32_t *b = c + x * 4;
+      if (!(b[0] | b[1] | b[2] | b[3])) continue;
+      text += name;
+      text += ' '; text += std::to_string(x);
+      for (int i = 0; i < 4; ++i) { text += ' '; text += std::to_string(b[i]); }
+      text += '\n';
+    }
+    if (text.size() > (1u << 20) || g + 1 == n_genes) {
+      ok = ok && fwrite(text.data(), 1, text.size(), opt.pileup_file) == text.size();
+      text.clear();
+    }
+  }
+  ok = (fclose(opt.pileup_file) == 0) && ok;
+  if (!ok) std::cerr << "shark: cannot write the pileup file " << opt.pileup_path << std::endl;
+  return ok;
+}
+
 }  // namespace
 
 int main(int argc, char *argv[])
@@ -2327,6 +2405,7 @@ int main(int argc, char *argv[])
   if (opt_parsed.depth_path != "" && samples_can_be_opened(opt_parsed, false)) opt_parsed.depth_file = fopen(opt_parsed.depth_path.c_str(), "w");   // (--depth: likewise)
   if (opt_parsed.segments_path != "" && samples_can_be_opened(opt_parsed, false)) opt_parsed.segments_file = fopen(opt_parsed.segments_path.c_str(), "w");   // (--segments: likewise)
   if (opt_parsed.junctions_path != "" && samples_can_be_opened(opt_parsed, false)) opt_parsed.junctions_file = fopen(opt_parsed.junctions_path.c_str(), "w");   // (--junctions: likewise)
+  if (opt_parsed.pileup_path != "" && samples_can_be_opened(opt_parsed, false)) opt_parsed.pileup_file = fopen(opt_parsed.pileup_path.c_str(), "w");   // (--pileup: likewise)
   const Options opt = opt_parsed;
   if (opt.verbose) timeline.on();
   timeline("arguments parsed");
@@ -2365,6 +2444,10 @@ int main(int argc, char *argv[])
     std::cerr << "shark: cannot open the junctions file " << opt.junctions_path << std::endl;
     return EXIT_FAILURE;
   }
+  if (opt.pileup_path != "" && !opt.pileup_file) {
+    std::cerr << "shark: cannot open the pileup file " << opt.pileup_path << std::endl;
+    return EXIT_FAILURE;
+  }
 
   BatchPool &pool = *new BatchPool;     // (never destroyed: the process leaves through _exit)
   GpuStart gpu(opt, pool);              // the contexts come up on a thread of their own from here on
@@ -2374,6 +2457,7 @@ int main(int argc, char *argv[])
   pelapsed("Sample completed");
   if (opt.depth_file && !write_depth(opt, gpu.ctxs, legend_ID)) return EXIT_FAILURE;
   if (opt.junctions_file && opt.junctions_device && !write_junctions_device(opt, gpu.ctxs, legend_ID)) return EXIT_FAILURE;
+  if (opt.pileup_file && !write_pileup(opt, gpu.ctxs, legend_ID)) return EXIT_FAILURE;
 
   if ((opt.gene_counts_path != "" || (opt.verbose && opt.gpus > 1)) && !gene_counts(opt, gpu.ctxs, legend_ID)) return EXIT_FAILURE;
   if (opt.verbose) {

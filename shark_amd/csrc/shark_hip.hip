@@ -315,8 +315,8 @@ static int enqueue_tail(Ctx *ctx, Slot &s, bool skip_hist_if_long, bool count_ge
   }
   // (spliced depth, the junction table: behind segments_kernel's records at m = SHK_MAX_SEGMENTS -- segments mode's own where it runs at that
   //  m, else a launch of that kernel into arrays nobody else sees --, under depth_accumulate_kernel's rule for a batch that comes through
-  //  here again)
-  if (s.sp_depth || s.sp_junc) {
+  //  here again; pileup mode: the third reader of the same records, its own kernel behind theirs)
+  if (s.sp_depth || s.sp_junc || s.pileup) {
     const shk_segment *entries = s.d_seg_entries;
     uint64_t cap_assoc = segments_cap(s);
     if (s.seg_m != SHK_MAX_SEGMENTS) {
@@ -326,7 +326,8 @@ static int enqueue_tail(Ctx *ctx, Slot &s, bool skip_hist_if_long, bool count_ge
       cap_assoc = std::min<uint64_t>(s.cap_sp_keys / 2, s.cap_sp_entries / (2ull * SHK_MAX_SEGMENTS));
       if ((rc = launch_segments_into(ctx, s, SHK_MAX_SEGMENTS, s.d_sp_keys, s.d_sp_entries, cap_assoc, st))) return rc;
     }
-    if ((rc = launch_spliced_accumulate(ctx, s, entries, cap_assoc, skip_hist_if_long, st))) return rc;
+    if ((s.sp_depth || s.sp_junc) && (rc = launch_spliced_accumulate(ctx, s, entries, cap_assoc, skip_hist_if_long, st))) return rc;
+    if (s.pileup && (rc = launch_pileup(ctx, s, entries, cap_assoc, skip_hist_if_long, st))) return rc;
   }
   SHK_HIP(ctx, hipEventRecord(s.ev_done, st));
   return SHK_OK;
@@ -371,6 +372,7 @@ static int enqueue_classify(Ctx *ctx, Slot &s, const shk_batch *b, uint32_t max_
   s.depth = count_genes && !ctx->depth_spliced ? ctx->depth : 0u;   // (shk_count_work is a measurement: its batch is not counted)
   s.sp_depth = count_genes && ctx->depth_spliced ? ctx->depth : 0u;
   s.sp_junc = count_genes ? ctx->junc : 0u;
+  s.pileup = count_genes ? ctx->pileup : 0u;
   if (s.depth || s.sp_depth) ctx->depth_dirty = true;
   if (s.sp_junc) ctx->junc_dirty = true;
   if ((rc = slot_reserve(ctx, s, n))) return rc;
@@ -807,6 +809,7 @@ void shk_destroy(shk_ctx *ctx)
   hipFree(ctx->d_scratch); hipFree(ctx->d_gene_counts); hipFree(ctx->d_gene_totals); hipFree(ctx->d_work_counters);
   hipFree(ctx->d_depth_diff); hipFree(ctx->d_depth_mates); hipFree(ctx->d_depth_scan); hipFree(ctx->d_depth_scan_temp); hipFree(ctx->d_depth_summary);
   hipFree(ctx->d_junc_tab); hipFree(ctx->d_junc_dropped);
+  hipFree(ctx->d_pileup); hipFree(ctx->d_pileup_mates);
   dist_release(ctx);
   for (auto e : ctx->ev_start) (void)hipEventDestroy(e);
   for (auto e : ctx->ev_stop) (void)hipEventDestroy(e);
@@ -1475,6 +1478,95 @@ int shk_junctions_reset(shk_ctx *ctx)
   SHK_HIP(ctx, hipSetDevice(ctx->prm.device));
   if (const int rc = launch_junction_clear(ctx)) return rc;
   ctx->junc_dirty = false;
+  SHK_HIP(ctx, hipStreamSynchronize(ctx->stream));
+  return SHK_OK;
+}
+
+// ---- pileup mode (pileup.hip): the state lives in the context, the batches' tails add to it ----
+// the counters: four per record base, and at least one allocation's worth for an index without a base
+static size_t pileup_bytes(const shk_ctx *ctx) { return std::max<size_t>((size_t)ctx->gene_start.back() * 4 * sizeof(uint32_t), 16); }
+
+int shk_pileup_enable(shk_ctx *ctx, uint32_t min_support)
+{
+  if (!ctx) return SHK_ERR_ARG;
+  if (tickets_outstanding(ctx)) { ctx->last_error = "shk_pileup_enable: tickets are outstanding (wait for them first)"; return SHK_ERR_STATE; }
+  if (min_support) {
+    if (ctx->mode != 2) { ctx->last_error = "shk_pileup_enable: the index is not finalized"; return SHK_ERR_STATE; }
+    if (!ctx->idx.ptab_lg) { ctx->last_error = "shk_pileup_enable: the index was finalized without shk_ref_keep_positions"; return SHK_ERR_STATE; }
+    if (ctx->n_records > 65536 || ctx->idx.wrap || !ctx->idx.gene_start) { ctx->last_error = "shk_pileup_enable: more than 65 536 records (gene ids wrap)"; return SHK_ERR_STATE; }
+    if (!ctx->d_pileup_mates) {
+      SHK_HIP(ctx, hipSetDevice(ctx->prm.device));
+      const size_t bytes = pileup_bytes(ctx);
+      uint32_t *counts = nullptr;
+      unsigned long long *mates = nullptr;
+      SHK_HIP(ctx, hipMalloc((void **)&counts, bytes));          // (out of memory: SHK_ERR_NOMEM, the mode stays off)
+      if (hipError_t e = hipMalloc((void **)&mates, sizeof(unsigned long long))) { (void)hipFree(counts); return set_hip_error(ctx, e, "hipMalloc"); }
+      ctx->d_pileup = counts;
+      ctx->d_pileup_mates = mates;
+      SHK_HIP(ctx, hipMemsetAsync(counts, 0, bytes, ctx->stream));
+      SHK_HIP(ctx, hipMemsetAsync(mates, 0, sizeof(unsigned long long), ctx->stream));
+    }
+  }
+  ctx->pileup = min_support;
+  return SHK_OK;
+}
+
+// what every read-out starts with: the state rules, the stream drained behind everything enqueued so far, the mate counter and its guard
+static int pileup_read_mates(shk_ctx *ctx, const char *who, uint64_t *n_mates)
+{
+  if (!ctx->d_pileup_mates) { ctx->last_error = std::string(who) + ": pileup mode was never enabled on this context"; return SHK_ERR_STATE; }
+  if (tickets_outstanding(ctx)) { ctx->last_error = std::string(who) + ": tickets are outstanding (wait for them first)"; return SHK_ERR_STATE; }
+  SHK_HIP(ctx, hipSetDevice(ctx->prm.device));
+  unsigned long long m = 0;
+  SHK_HIP(ctx, hipMemcpyAsync(&m, ctx->d_pileup_mates, sizeof(m), hipMemcpyDeviceToHost, ctx->stream));
+  SHK_HIP(ctx, hipStreamSynchronize(ctx->stream));
+  if (n_mates) *n_mates = m;
+  if (m > 0xFFFFFFFFull) { ctx->last_error = std::string(who) + ": more than 2^32-1 pileup mates since the last reset (32-bit counters)"; return SHK_ERR_INDEX_TOO_LARGE; }
+  return SHK_OK;
+}
+
+int shk_pileup_mates(const shk_ctx *cctx, uint64_t *n)
+{
+  if (!cctx || !n) return SHK_ERR_ARG;
+  return pileup_read_mates(const_cast<shk_ctx *>(cctx), "shk_pileup_mates", n);
+}
+
+int shk_pileup_get_all(shk_ctx *ctx, uint32_t *counts, uint64_t cap, int device)
+{
+  if (!ctx) return SHK_ERR_ARG;
+  const int rc = pileup_read_mates(ctx, "shk_pileup_get_all", nullptr);
+  if (rc) return rc;
+  const uint64_t total = 4 * ctx->gene_start.back();
+  if (cap < total || (!counts && total)) return SHK_ERR_ARG;
+  if (total == 0) return SHK_OK;
+  // (the counters are the answer: no scan, one copy)
+  SHK_HIP(ctx, hipMemcpyAsync(counts, ctx->d_pileup, total * sizeof(uint32_t), device ? hipMemcpyDeviceToDevice : hipMemcpyDeviceToHost, ctx->stream));
+  SHK_HIP(ctx, hipStreamSynchronize(ctx->stream));
+  return SHK_OK;
+}
+
+int shk_pileup_get(shk_ctx *ctx, uint32_t gene, uint32_t *counts, uint64_t cap)
+{
+  if (!ctx) return SHK_ERR_ARG;
+  const int rc = pileup_read_mates(ctx, "shk_pileup_get", nullptr);
+  if (rc) return rc;
+  if ((uint64_t)gene + 1 >= ctx->gene_start.size()) return SHK_ERR_ARG;
+  const uint64_t a = 4 * ctx->gene_start[gene], len = 4 * ctx->gene_start[gene + 1] - a;
+  if (cap < len || (!counts && len)) return SHK_ERR_ARG;
+  if (len == 0) return SHK_OK;
+  SHK_HIP(ctx, hipMemcpyAsync(counts, ctx->d_pileup + a, len * sizeof(uint32_t), hipMemcpyDeviceToHost, ctx->stream));
+  SHK_HIP(ctx, hipStreamSynchronize(ctx->stream));
+  return SHK_OK;
+}
+
+int shk_pileup_reset(shk_ctx *ctx)
+{
+  if (!ctx) return SHK_ERR_ARG;
+  if (!ctx->d_pileup_mates) { ctx->last_error = "shk_pileup_reset: pileup mode was never enabled on this context"; return SHK_ERR_STATE; }
+  if (tickets_outstanding(ctx)) { ctx->last_error = "shk_pileup_reset: tickets are outstanding (wait for them first)"; return SHK_ERR_STATE; }
+  SHK_HIP(ctx, hipSetDevice(ctx->prm.device));
+  SHK_HIP(ctx, hipMemsetAsync(ctx->d_pileup, 0, pileup_bytes(ctx), ctx->stream));
+  SHK_HIP(ctx, hipMemsetAsync(ctx->d_pileup_mates, 0, sizeof(unsigned long long), ctx->stream));
   SHK_HIP(ctx, hipStreamSynchronize(ctx->stream));
   return SHK_OK;
 }

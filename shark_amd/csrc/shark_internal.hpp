@@ -333,6 +333,9 @@ struct Slot {
   uint32_t sp_depth = 0, sp_junc = 0;
   uint32_t *d_sp_keys = nullptr; size_t cap_sp_keys = 0;
   shk_segment *d_sp_entries = nullptr; size_t cap_sp_entries = 0;
+  // pileup mode (pileup.hip): submitted with this floor (0: not).  The third reader of those records at m = SHK_MAX_SEGMENTS, from the same
+  // arrays: segments mode's own at that m, else d_sp_*, which are filled when ANY of spliced depth, the junction table and pileup is on
+  uint32_t pileup = 0;
 };
 
 struct Ctx;
@@ -366,6 +369,8 @@ int launch_depth_accumulate(Ctx *ctx, const Slot &s, bool skip_if_long, hipStrea
 // spliced.hip: the batch in `s` from its segments at m = SHK_MAX_SEGMENTS (`entries`, cap_assoc associations) into the depth state (s.sp_depth)
 // and / or the junction table (s.sp_junc), behind segments_kernel; skip_if_long: as launch_gene_hist
 int launch_spliced_accumulate(Ctx *ctx, const Slot &s, const shk_segment *entries, uint64_t cap_assoc, bool skip_if_long, hipStream_t stream);
+// pileup.hip: the batch in `s` from the same records into Ctx::d_pileup at floor s.pileup, behind segments_kernel; skip_if_long: as launch_gene_hist
+int launch_pileup(Ctx *ctx, const Slot &s, const shk_segment *entries, uint64_t cap_assoc, bool skip_if_long, hipStream_t stream);
 int launch_junction_clear(Ctx *ctx);   // every entry of Ctx::d_junc_tab empty, Ctx::d_junc_dropped 0, on ctx->stream
 // the read-out: Ctx::d_depth_scan[1 + x] = depth of base x of the full array (inclusive prefix sum of the difference array), on ctx->stream
 int depth_scan(Ctx *ctx);
@@ -489,6 +494,10 @@ struct Ctx {
   JunctionEntry *d_junc_tab = nullptr;
   unsigned long long *d_junc_dropped = nullptr;   // observations that found the table full since the last reset
   bool junc_dirty = false;                     // a junction batch was submitted since the first enable / the last reset
+  // pileup mode (shk_pileup_enable; pileup.hip): like the depth state it outlives the mode's being switched off
+  uint32_t pileup = 0;                         // min_support for the batches submitted from now on (0: off)
+  uint32_t *d_pileup = nullptr;                // gene_start[nidx] x 4 counters, [x * 4 + b]: the observations of base b at x (allocated by the first enable)
+  unsigned long long *d_pileup_mates = nullptr;   // pileup mates since the last reset (not null: the mode was enabled once)
 
   // timing
   bool timing = false;
