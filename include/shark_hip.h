@@ -518,7 +518,7 @@ int shk_junctions_reset(shk_ctx *ctx);
  *         sum_b counts[g][x][b] + (observations lost to c == 0 at x) == spliced depth[g][x]:
  *     equality where no read byte is a non-base, and never more;
  *   - nothing is compared with the reference sequence and the device does not keep it: the caller holds the FASTA, the reference
- *     allele is the caller's to look up;
+ *     allele is the caller's to look up (unless shk_ref_keep_bases was asked for: the variants section below);
  *   - a read tied over several genes counts in each of them; mates are counted, not fragments;
  *   - a batch is counted exactly once, by depth mode's rules word for word: a batch with more associations than the result buffer
  *     holds, or with reads beyond a length bound taken on trust, is counted when the tail runs again (shk_classify_wait /
@@ -552,6 +552,63 @@ int shk_pileup_get(shk_ctx *ctx, uint32_t gene, uint32_t *counts, uint64_t cap);
 int shk_pileup_get_all(shk_ctx *ctx, uint32_t *counts, uint64_t cap, int device);
 int shk_pileup_mates(const shk_ctx *ctx, uint64_t *n);
 int shk_pileup_reset(shk_ctx *ctx);
+/* Adds an array in the pileup layout, element by element (modulo 2^32), to the context's pileup state and `mates` to the 64-bit
+ * counter of pileup mates: what sums the states of N workers or N ranks (a variant call, below, is not linear in the counters, so
+ * the states are summed BEFORE the call), and what loads a hand-made state.  device == 0: `counts` is a host pointer; device != 0: a
+ * DEVICE pointer, 16-byte aligned.  n_entries must be 4 * gene_start[nidx] (SHK_ERR_ARG otherwise; SHK_ERR_ARG for counts == NULL
+ * with entries to add and for a device pointer that is not aligned).  The caller vouches that no counter in `counts` exceeds `mates` -- true of every state this library accumulated --; it is
+ * not checked, and with it the guard of the mate counter (2^32 - 1) keeps guarding the 32-bit counters behind the call.
+ * shk_pileup_reset's state rules: SHK_ERR_STATE if the mode was never enabled on this context or while tickets are outstanding; the
+ * mode may be on or off.  Runs on the context's stream behind everything enqueued so far and returns when it is done.  New: no
+ * counterpart. */
+int shk_pileup_add(shk_ctx *ctx, const uint32_t *counts, uint64_t n_entries, uint64_t mates, int device);
+
+/* ---- variants: the record positions where the pileup shows another base than the record -- pileup's read-out against the reference ---- */
+/* Pileup (above) counts what the mates read at every record base; variants mode holds that against the record itself, on the
+ * device, and hands out the positions that differ.  It adds nothing to a batch: the state is pileup's, the call is a read-out.
+ *
+ * RECORD BASES.  shk_ref_keep_bases asks shk_ref_finalize to keep the records' bases on the device: one byte per record base in
+ * shk_depth_layout's order -- base x of gene g at gene_start[g] + x, the records that carry an id and no others -- holding
+ * r = to_int[byte] - 1 (kmer_utils.hpp:29-41): A, C, G, T and their lower case are 0 .. 3, every other byte is 4.
+ *
+ * THE CALL.  For record base x of gene g let n[b] = counts[g][x][b] (b = 0 .. 3 = A, C, G, T), T = n[0] + n[1] + n[2] + n[3] as a
+ * 64-bit sum, and r the record's base there.
+ *   - a position with r == 4 takes no part in anything below: it is no site and adds to no sum;
+ *   - otherwise alt is the b != r with the largest n[b]; ties go to the smallest b;
+ *   - x is a SITE iff all three hold:
+ *         T >= min_depth,     n[alt] >= min_alt,     (uint64) n[alt] * frac_den >= (uint64) frac_num * T
+ *     (the allele fraction n[alt] / T is at least frac_num / frac_den, compared without a division).
+ * Parameters: min_depth >= 1, min_alt >= 1, 1 <= frac_den <= 65535, frac_num <= frac_den; anything else is SHK_ERR_ARG.  Within
+ * these bounds both products stay below 2^51.  Integers only, no tolerance anywhere.
+ * Per gene, over its positions with r < 4:
+ *   observed     sum of T
+ *   mismatches   sum of (T - n[r]): the observations that differ from the record
+ *   covered      the number of x with T >= min_depth
+ *   sites        the number of sites
+ * mismatches / observed is the gene's error rate: what a site's allele fraction is held against to tell a variant from noise.  (The
+ * two sums are 64 bits wide and wrap; a state this library accumulated stays far below that.)
+ * Example: r = A, n = (12, 0, 5, 0), defaults of the command (depth 8, alt 3, frac 1/5): T = 17, alt = G, 5 * 5 >= 1 * 17: a site
+ * {ref 0, alt 2}.  With n = (14, 0, 3, 0): 3 * 5 = 15 < 17: none.
+ *
+ * Kernels (variants.hip): two streaming passes over the state (16 bytes per base) and the record bases (1 byte per base) -- count
+ * the sites per wavefront, scan the counts, write the records at their final places, so the order is (gene, x) without a sort --
+ * and one pass for the summary.  Scratch memory is allocated by the first call, kept, and only grows.  New: no counterpart. */
+/* Asks shk_ref_finalize to keep the record bases as well.  Implies shk_ref_keep_positions (the array only exists where gene_start
+ * does).  Before shk_ref_finalize only; SHK_ERR_STATE afterwards.  Costs one byte per record base; without the call finalize does
+ * exactly what it did: no allocation, no launch.  New: no counterpart. */
+int shk_ref_keep_bases(shk_ctx *ctx);
+typedef struct shk_variant_params { uint32_t min_depth, min_alt, frac_num, frac_den; } shk_variant_params;
+typedef struct shk_variant { uint32_t gene, x, ref, alt, n[4]; } shk_variant;            /* 32 bytes; ref, alt: 0 .. 3 = A, C, G, T */
+typedef struct shk_gene_variants { uint64_t observed, mismatches; uint32_t covered, sites; } shk_gene_variants;
+/* The read-outs.  SHK_ERR_STATE if pileup mode was never enabled on this context, if the index was finalized without
+ * shk_ref_keep_bases, or while tickets are outstanding; SHK_ERR_INDEX_TOO_LARGE behind pileup's mate guard; SHK_ERR_ARG for
+ * parameters outside the bounds above.  Both run on the context's stream behind everything enqueued so far and leave the pileup
+ * state untouched, so accumulation can go on.
+ *   shk_variants_get      *n = the number of sites; out != NULL: the sites sorted by (gene, x) into out[0 .. *n) (host memory;
+ *                         SHK_ERR_ARG if cap < *n, *n is set all the same).  out == NULL: only *n (shk_junctions_get's conventions)
+ *   shk_variants_summary  out[g] for g < n_genes (n_genes <= nidx), host memory */
+int shk_variants_get(shk_ctx *ctx, const shk_variant_params *p, shk_variant *out, uint64_t cap, uint64_t *n);
+int shk_variants_summary(shk_ctx *ctx, const shk_variant_params *p, shk_gene_variants *out, uint32_t n_genes);
 
 /* Per-gene number of assigned reads accumulated over all classify calls (all
  * waited tickets) since the last reset (counts[g] for g in [0, 65536)); the quantity all-reduced

@@ -64,6 +64,15 @@ JUNCTION_DTYPE = np.dtype([("gene", np.uint32), ("donor", np.uint32), ("acceptor
 JUNCTIONS_DEFAULT_CAPACITY = 1 << 16
 
 
+class ShkVariantParams(C.Structure):
+    _fields_ = [("min_depth", C.c_uint32), ("min_alt", C.c_uint32), ("frac_num", C.c_uint32), ("frac_den", C.c_uint32)]
+
+
+# shk_variant (32 bytes) and shk_gene_variants (24 bytes) as numpy records
+VARIANT_DTYPE = np.dtype([("gene", np.uint32), ("x", np.uint32), ("ref", np.uint32), ("alt", np.uint32), ("n", np.uint32, (4,))])
+GENE_VARIANTS_DTYPE = np.dtype([("observed", np.uint64), ("mismatches", np.uint64), ("covered", np.uint32), ("sites", np.uint32)])
+
+
 class ShkWorkCounters(C.Structure):
     _fields_ = [("n_kmers", C.c_uint64), ("n_hits", C.c_uint64), ("n_list_ids", C.c_uint64), ("n_bases", C.c_uint64)]
 
@@ -85,6 +94,7 @@ EXPORTS = [
     "shk_depth_enable", "shk_depth_layout", "shk_depth_get", "shk_depth_get_all", "shk_depth_summary", "shk_depth_mates", "shk_depth_reset",
     "shk_depth_enable_spliced", "shk_junctions_enable", "shk_junctions_get", "shk_junctions_reset",
     "shk_pileup_enable", "shk_pileup_get", "shk_pileup_get_all", "shk_pileup_mates", "shk_pileup_reset",
+    "shk_pileup_add", "shk_ref_keep_bases", "shk_variants_get", "shk_variants_summary",
 ]
 SHK_PIPE_DEPTH = 3
 SHK_DIST_ID_BYTES = 128
@@ -171,6 +181,10 @@ def load():
         "shk_pileup_get_all": (C.c_int, [p, p, C.c_uint64, C.c_int]),
         "shk_pileup_mates": (C.c_int, [p, C.POINTER(C.c_uint64)]),
         "shk_pileup_reset": (C.c_int, [p]),
+        "shk_pileup_add": (C.c_int, [p, p, C.c_uint64, C.c_uint64, C.c_int]),
+        "shk_ref_keep_bases": (C.c_int, [p]),
+        "shk_variants_get": (C.c_int, [p, C.POINTER(ShkVariantParams), p, C.c_uint64, C.POINTER(C.c_uint64)]),
+        "shk_variants_summary": (C.c_int, [p, C.POINTER(ShkVariantParams), p, C.c_uint32]),
     }
     variant = bool(os.environ.get("SHK_LIB_PATH"))
     for name, (res, args) in later.items():
@@ -239,9 +253,16 @@ class SharkHip:
         """ask ref_finalize / build to build placement mode's table as well (before the index is finalized only)"""
         self._check(self.L.shk_ref_keep_positions(self.h), "shk_ref_keep_positions")
 
-    def build(self, seqs, keep_positions=False):
+    def keep_bases(self):
+        """ask ref_finalize / build to keep the records' bases on the device as well (variants, variants_summary); implies
+        keep_positions; before the index is finalized only"""
+        self._check(self.L.shk_ref_keep_bases(self.h), "shk_ref_keep_bases")
+
+    def build(self, seqs, keep_positions=False, keep_bases=False):
         if keep_positions:
             self.keep_positions()
+        if keep_bases:
+            self.keep_bases()
         for s in seqs:
             self._check(self.ref_add(s), "shk_ref_add")
         self._check(self.ref_finalize(), "shk_ref_finalize")
@@ -275,7 +296,7 @@ class SharkHip:
     # ---- test-only read-back of the derived index arrays (shk_debug_index_array: exported, not in the header, not in EXPORTS) ----
     DEBUG_ARRAYS = {"rank_w": np.uint32, "ent": np.uint32, "ids": np.uint16, "sum32": np.uint32, "lsum32": np.uint32,
                     "lbig32": np.uint32, "tab": np.uint64, "atab": np.uint64, "ltab": np.uint32, "ref2": np.uint32,
-                    "refpay": np.uint32, "refext": np.uint32, "refmul": np.uint32}
+                    "refpay": np.uint32, "refext": np.uint32, "refmul": np.uint32, "recbase": np.uint8}
     DEBUG_META = ("tab_lg", "sum_shift", "lsum_shift", "lbig_shift", "ltab_mul", "ref_total", "n_set", "tot_idx", "pow2", "wrap",
                   "ent_len", "ids_len", "bf_bits", "bf_words64", "sum_bits", "ktab_lg")
 
@@ -554,6 +575,36 @@ class SharkHip:
 
     def pileup_reset(self):
         self._check(self.L.shk_pileup_reset(self.h), "shk_pileup_reset")
+
+    def pileup_add(self, counts, mates, device_ptr=None):
+        """adds an array in pileup_all()'s layout -- uint32 (n_bases, 4), or flat -- element by element to the state and `mates` to the
+        mate counter (the caller vouches that no counter exceeds `mates`); with device_ptr (the address of a DEVICE buffer of
+        4 * gene_start[nidx] uint32) `counts` is ignored and the buffer is added"""
+        total = 4 * int(self.depth_layout()[-1])
+        if device_ptr is not None:
+            self._check(self.L.shk_pileup_add(self.h, C.c_void_p(device_ptr), total, int(mates), 1), "shk_pileup_add")
+            return
+        a = np.ascontiguousarray(counts, dtype=np.uint32)
+        self._check(self.L.shk_pileup_add(self.h, _ptr(a), a.size, int(mates), 0), "shk_pileup_add")
+
+    # ---- variants: the record positions where the pileup shows another base than the record (needs an index built with keep_bases) --------
+    def variants(self, min_depth=8, min_alt=3, frac=(1, 5)):
+        """the sites of the pileup state at these thresholds (include/shark_hip.h, "variants"): a structured array (VARIANT_DTYPE: gene,
+        x, ref, alt, n[4]) sorted by (gene, x)"""
+        prm = ShkVariantParams(int(min_depth), int(min_alt), int(frac[0]), int(frac[1]))
+        n = C.c_uint64()
+        self._check(self.L.shk_variants_get(self.h, C.byref(prm), None, 0, C.byref(n)), "shk_variants_get")
+        out = np.zeros(int(n.value), dtype=VARIANT_DTYPE)
+        if len(out):
+            self._check(self.L.shk_variants_get(self.h, C.byref(prm), _ptr(out), len(out), C.byref(n)), "shk_variants_get")
+        return out[:int(n.value)]
+
+    def variants_summary(self, min_depth=8, min_alt=3, frac=(1, 5)):
+        """per gene (observed, mismatches, covered, sites): a structured array of nidx records (GENE_VARIANTS_DTYPE)"""
+        prm = ShkVariantParams(int(min_depth), int(min_alt), int(frac[0]), int(frac[1]))
+        out = np.zeros(int(self.index_info()["nidx"]), dtype=GENE_VARIANTS_DTYPE)
+        self._check(self.L.shk_variants_summary(self.h, C.byref(prm), _ptr(out), len(out)), "shk_variants_summary")
+        return out
 
     def gene_counts(self, n=65536):
         a = np.zeros(n, dtype=np.uint64)

@@ -919,6 +919,22 @@ int build_index(Ctx *ctx)
       for (uint64_t g = 0; g < nidx; ++g) gs[g + 1] += gs[g];
       BI_HIP(hipMalloc((void **)&ix.gene_start, gs.size() * sizeof(uint64_t)));
       BI_HIP(hipMemcpy(ix.gene_start, gs.data(), gs.size() * sizeof(uint64_t), hipMemcpyHostToDevice));
+      // variants mode's record bases (shk_ref_keep_bases; variants.hip), in that layout: built here from the records' bytes while the host
+      // still holds them -- once per index, one byte per base, not hot.  Padded with 4 ("no base") to a dword and one more
+      if (ctx->keep_bases) {
+        static const struct ToCode { uint8_t t[256]; ToCode() { for (int c = 0; c < 256; ++c) t[c] = 4; t['A'] = t['a'] = 0; t['C'] = t['c'] = 1; t['G'] = t['g'] = 2; t['T'] = t['t'] = 3; } } code;
+        const uint64_t bases = gs[nidx], bytes = (bases + 3) / 4 * 4 + 4;
+        std::vector<uint8_t> rb(bytes, 4);
+        for (uint32_t r = 0; r < n_rec; ++r)
+          if (h_has[r]) {
+            const uint8_t *src = reinterpret_cast<const uint8_t *>(ctx->ref_bytes.data()) + ctx->ref_off[r];
+            uint8_t *dst = rb.data() + gs[h_nidx[r]];
+            for (uint64_t i = 0, len = ctx->ref_off[r + 1] - ctx->ref_off[r]; i < len; ++i) dst[i] = code.t[src[i]];
+          }
+        BI_HIP(hipMalloc((void **)&ix.recbase, bytes));
+        BI_HIP(hipMemcpy(ix.recbase, rb.data(), bytes, hipMemcpyHostToDevice));
+        ix.recbase_bytes = bytes;
+      }
       ctx->gene_start.swap(gs);
     }
   }

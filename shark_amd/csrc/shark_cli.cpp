@@ -15,6 +15,7 @@
 #include <sys/stat.h>
 
 #include <algorithm>
+#include <cctype>
 #include <chrono>
 #include <fstream>
 #include <condition_variable>
@@ -108,6 +109,14 @@ const char *USAGE_MESSAGE =
     "                                        counts, summed over the whole sample on the GPUs; genes in the legend's order (combines with\n"
     "                                        --depth, --junctions and --segments; not for references of more than 65536 records)\n"
     "          --pileup-min-support N        unique k-mers a diagonal of a mate needs to be read by --pileup (default:8)\n"
+    "          --variants FILE               write <gene> <x> <ref> <alt> <A> <C> <G> <T> per record base (0-based) where the sample's pileup\n"
+    "                                        shows another base than the record: the counts of --pileup held against the record on the\n"
+    "                                        GPU; ref and alt as letters, genes in the legend's order (the same refusals as --pileup)\n"
+    "          --variants-min-support N      unique k-mers a diagonal of a mate needs to be read by --variants (default:8; with --pileup\n"
+    "                                        the two must agree: there is one pileup)\n"
+    "          --variants-min-depth N        mates that must show a base at a site (default:8)\n"
+    "          --variants-min-alt N          mates that must show the alternative base (default:3)\n"
+    "          --variants-min-frac P/Q       the alternative base's share of those mates, at least P/Q (default:1/5; P <= Q <= 65535)\n"
     "      -t N also sets the number of host threads that parse FASTQ / format output (default: up to 16)\n";
 
 struct Options {
@@ -150,6 +159,12 @@ struct Options {
   FILE *pileup_file = nullptr;     // (--pileup, likewise; written once, after the last batch)
   unsigned pileup_min_support = 8;
   bool pileup_min_support_given = false;
+  std::string variants_path;
+  FILE *variants_file = nullptr;   // (--variants, likewise; written once, after the last batch and after --pileup's file)
+  unsigned variants_min_support = 8;
+  shk_variant_params variants_params{8, 3, 1, 5};   // (--variants-min-depth, -min-alt, -min-frac)
+  bool variants_sub_flag_given = false;
+  bool variants_min_support_given = false;
 };
 
 // The command line is described by one table: option names, whether a value follows, and a handler that
@@ -270,6 +285,36 @@ const OptionRow OPTION_TABLE[] = {
        o.pileup_min_support_given = true;
        if (o.pileup_min_support < 1) reject(USAGE_MESSAGE, "shark: --pileup-min-support must be at least 1.");
      }},
+    {1019, "variants", true, [](Options &o, const char *v) { o.variants_path = value_of<std::string>(v); }},
+    {1020, "variants-min-support", true,
+     [](Options &o, const char *v) {
+       o.variants_min_support = value_of<unsigned>(v);
+       o.variants_sub_flag_given = o.variants_min_support_given = true;
+       if (o.variants_min_support < 1) reject(USAGE_MESSAGE, "shark: --variants-min-support must be at least 1.");
+     }},
+    {1021, "variants-min-depth", true,
+     [](Options &o, const char *v) {
+       o.variants_params.min_depth = value_of<unsigned>(v);
+       o.variants_sub_flag_given = true;
+       if (o.variants_params.min_depth < 1) reject(USAGE_MESSAGE, "shark: --variants-min-depth must be at least 1.");
+     }},
+    {1022, "variants-min-alt", true,
+     [](Options &o, const char *v) {
+       o.variants_params.min_alt = value_of<unsigned>(v);
+       o.variants_sub_flag_given = true;
+       if (o.variants_params.min_alt < 1) reject(USAGE_MESSAGE, "shark: --variants-min-alt must be at least 1.");
+     }},
+    {1023, "variants-min-frac", true,
+     [](Options &o, const char *v) {
+       // P/Q, both decimal, nothing else
+       unsigned long long num = 0, den = 0;
+       int used = 0;
+       const bool parsed = sscanf(v, "%llu/%llu%n", &num, &den, &used) == 2 && v[used] == '\0' && isdigit((unsigned char)v[0]);
+       o.variants_sub_flag_given = true;
+       if (!parsed || den < 1 || den > 65535 || num > den) reject(USAGE_MESSAGE, "shark: --variants-min-frac must be P/Q with P <= Q and Q in the range [1, 65535].");
+       o.variants_params.frac_num = (uint32_t)num;
+       o.variants_params.frac_den = (uint32_t)den;
+     }},
 };
 
 // Reads per device batch when --batch does not say.  A batch costs the device path 0.5-2 ms of launches, copies and bookkeeping
@@ -336,6 +381,9 @@ Options parse_arguments(int argc, char **argv)
   if (opt.junctions_capacity_given && !opt.junctions_device) reject(USAGE_MESSAGE, "shark: --junctions-capacity needs --junctions-device.");
   if (opt.junctions_device && opt.segments_max < SHK_MAX_SEGMENTS) reject(USAGE_MESSAGE, "shark: --junctions-device needs --segments-max 4 (the device's table is defined at 4 diagonals per mate).");
   if (opt.pileup_min_support_given && opt.pileup_path.empty()) reject(USAGE_MESSAGE, "shark: --pileup-min-support needs --pileup FILE.");
+  if (opt.variants_sub_flag_given && opt.variants_path.empty()) reject(USAGE_MESSAGE, "shark: --variants-min-support, --variants-min-depth, --variants-min-alt and --variants-min-frac need --variants FILE.");
+  if (!opt.variants_path.empty() && !opt.pileup_path.empty() && opt.variants_min_support != opt.pileup_min_support)
+    reject(USAGE_MESSAGE, "shark: --variants-min-support and --pileup-min-support must be equal (there is one pileup).");
   if (opt.out1_path.empty()) opt.out1_path = "sharked_sample.1";
   if (opt.out2_path.empty() && !opt.sample2_path.empty()) opt.out2_path = "sharked_sample.2";
   // --devices alone says how many workers there are; with --gpus N it has to name N devices
@@ -1902,6 +1950,7 @@ std::string build_index(const Options &opt, GpuStart &gpu, std::vector<std::stri
       if (opt.segments_file && legend_ID.size() > 65536) return "shark: --segments is not available for a reference of more than 65536 records (gene ids wrap there).";
       if (opt.junctions_file && legend_ID.size() > 65536) return "shark: --junctions is not available for a reference of more than 65536 records (gene ids wrap there).";
       if (opt.pileup_file && legend_ID.size() > 65536) return "shark: --pileup is not available for a reference of more than 65536 records (gene ids wrap there).";
+      if (opt.variants_file && legend_ID.size() > 65536) return "shark: --variants is not available for a reference of more than 65536 records (gene ids wrap there).";
       const size_t len = strnlen(rec.seq.data(), rec.seq.size());  // C-string semantics (main.cpp:164)
       for (auto *ctx : gpu.ctxs) {
         const int rc = shk_ref_add(ctx, rec.seq.data(), len);
@@ -1911,9 +1960,13 @@ std::string build_index(const Options &opt, GpuStart &gpu, std::vector<std::stri
   }
   pelapsed("Transcript file processed");
   timeline("reference read");
-  if (opt.placements_file || opt.depth_file || opt.segments_file || opt.junctions_file || opt.pileup_file)
+  if (opt.placements_file || opt.depth_file || opt.segments_file || opt.junctions_file || opt.pileup_file || opt.variants_file)
     for (auto *ctx : gpu.ctxs)
       if (const int rc = shk_ref_keep_positions(ctx)) return std::string("shark: ") + shk_strerror(rc);
+  // (--variants: the records' bases stay on the device; only worker 0 is asked for the sites, but every replica is built alike)
+  if (opt.variants_file)
+    for (auto *ctx : gpu.ctxs)
+      if (const int rc = shk_ref_keep_bases(ctx)) return std::string("shark: ") + shk_strerror(rc);
   {
     const size_t n = gpu.ctxs.size();
     std::vector<std::thread> th;
@@ -2086,9 +2139,10 @@ int run_sample(const Options &opt, GpuStart &gpu, BatchPool &pool, std::vector<s
         return EXIT_FAILURE;
       }
   // (--pileup: every worker adds its batches' bases to its own pileup state; write_pileup sums the workers' arrays at the end)
-  if (opt.pileup_file)
+  // (--variants reads the same state, at the same floor: parse_arguments saw to that)
+  if (opt.pileup_file || opt.variants_file)
     for (shk_ctx *ctx : gpu.ctxs)
-      if (const int rc = shk_pileup_enable(ctx, opt.pileup_min_support)) {
+      if (const int rc = shk_pileup_enable(ctx, opt.pileup_file ? opt.pileup_min_support : opt.variants_min_support)) {
         feed.stop();
         std::cerr << "shark: pileup mode could not be switched on: " << shk_strerror(rc) << " " << shk_last_error(ctx) << std::endl;
         return EXIT_FAILURE;
@@ -2391,6 +2445,53 @@ bool write_pileup(const Options &opt, std::vector<shk_ctx *> &ctxs, const std::v
   return ok;
 }
 
+// --variants: a variant call is not linear in the counters, so the workers' states are summed first -- every other worker's array and
+// mate counter added into worker 0's on its device (shk_pileup_get_all, shk_pileup_add) -- and worker 0 is asked once.  One line per
+// site: <gene> <x> <ref> <alt> <A> <C> <G> <T>, genes in id order, x ascending (the order the library hands them out in).  Runs behind
+// write_pileup: what it does to worker 0's state nobody reads afterwards
+bool write_variants(const Options &opt, std::vector<shk_ctx *> &ctxs, const std::vector<std::string> &legend_ID)
+{
+  shk_index_info info{};
+  shk_index_info_get(ctxs[0], &info);
+  std::vector<uint64_t> gene_start((size_t)info.nidx + 1, 0);
+  int rc = ctxs.size() > 1 ? shk_depth_layout(ctxs[0], gene_start.data(), (uint32_t)info.nidx) : SHK_OK;
+  std::vector<uint32_t> part;
+  for (size_t g = 1; g < ctxs.size() && rc == SHK_OK; ++g) {
+    uint64_t mates = 0;
+    part.assign((size_t)gene_start[info.nidx] * 4, 0);
+    // (shk_pileup_mates stores the number even behind its guard; get_all refuses there, and so would the sum)
+    rc = shk_pileup_get_all(ctxs[g], part.data(), part.size(), 0);
+    if (rc == SHK_OK) rc = shk_pileup_mates(ctxs[g], &mates);
+    if (rc != SHK_OK) { std::cerr << "shark: the pileup of worker " << g << " could not be read: " << shk_strerror(rc) << " " << shk_last_error(ctxs[g]) << std::endl; break; }
+    rc = shk_pileup_add(ctxs[0], part.data(), part.size(), mates, 0);
+  }
+  uint64_t n = 0;
+  std::vector<shk_variant> sites;
+  if (rc == SHK_OK) rc = shk_variants_get(ctxs[0], &opt.variants_params, nullptr, 0, &n);
+  if (rc == SHK_OK && n) {
+    sites.resize((size_t)n);
+    rc = shk_variants_get(ctxs[0], &opt.variants_params, sites.data(), sites.size(), &n);
+  }
+  if (rc != SHK_OK) {
+    std::cerr << "shark: the variants could not be read: " << shk_strerror(rc) << " " << shk_last_error(ctxs[0]) << std::endl;
+    fclose(opt.variants_file);
+    return false;
+  }
+  std::string text;
+  for (const shk_variant &v : sites) {
+    text += v.gene < legend_ID.size() ? legend_ID[v.gene] : std::string();
+    text += ' '; text += std::to_string(v.x);
+    text += ' '; text += "ACGT"[v.ref & 3u];
+    text += ' '; text += "ACGT"[v.alt & 3u];
+    for (int i = 0; i < 4; ++i) { text += ' '; text += std::to_string(v.n[i]); }
+    text += '\n';
+  }
+  bool ok = fwrite(text.data(), 1, text.size(), opt.variants_file) == text.size();
+  ok = (fclose(opt.variants_file) == 0) && ok;
+  if (!ok) std::cerr << "shark: cannot write the variants file " << opt.variants_path << std::endl;
+  return ok;
+}
+
 }  // namespace
 
 int main(int argc, char *argv[])
@@ -2406,6 +2507,7 @@ int main(int argc, char *argv[])
   if (opt_parsed.segments_path != "" && samples_can_be_opened(opt_parsed, false)) opt_parsed.segments_file = fopen(opt_parsed.segments_path.c_str(), "w");   // (--segments: likewise)
   if (opt_parsed.junctions_path != "" && samples_can_be_opened(opt_parsed, false)) opt_parsed.junctions_file = fopen(opt_parsed.junctions_path.c_str(), "w");   // (--junctions: likewise)
   if (opt_parsed.pileup_path != "" && samples_can_be_opened(opt_parsed, false)) opt_parsed.pileup_file = fopen(opt_parsed.pileup_path.c_str(), "w");   // (--pileup: likewise)
+  if (opt_parsed.variants_path != "" && samples_can_be_opened(opt_parsed, false)) opt_parsed.variants_file = fopen(opt_parsed.variants_path.c_str(), "w");   // (--variants: likewise)
   const Options opt = opt_parsed;
   if (opt.verbose) timeline.on();
   timeline("arguments parsed");
@@ -2448,6 +2550,10 @@ int main(int argc, char *argv[])
     std::cerr << "shark: cannot open the pileup file " << opt.pileup_path << std::endl;
     return EXIT_FAILURE;
   }
+  if (opt.variants_path != "" && !opt.variants_file) {
+    std::cerr << "shark: cannot open the variants file " << opt.variants_path << std::endl;
+    return EXIT_FAILURE;
+  }
 
   BatchPool &pool = *new BatchPool;     // (never destroyed: the process leaves through _exit)
   GpuStart gpu(opt, pool);              // the contexts come up on a thread of their own from here on
@@ -2458,6 +2564,7 @@ int main(int argc, char *argv[])
   if (opt.depth_file && !write_depth(opt, gpu.ctxs, legend_ID)) return EXIT_FAILURE;
   if (opt.junctions_file && opt.junctions_device && !write_junctions_device(opt, gpu.ctxs, legend_ID)) return EXIT_FAILURE;
   if (opt.pileup_file && !write_pileup(opt, gpu.ctxs, legend_ID)) return EXIT_FAILURE;
+  if (opt.variants_file && !write_variants(opt, gpu.ctxs, legend_ID)) return EXIT_FAILURE;
 
   if ((opt.gene_counts_path != "" || (opt.verbose && opt.gpus > 1)) && !gene_counts(opt, gpu.ctxs, legend_ID)) return EXIT_FAILURE;
   if (opt.verbose) {

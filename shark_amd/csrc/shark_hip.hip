@@ -30,7 +30,7 @@ int set_hip_error(Ctx *ctx, hipError_t e, const char *what)
 static void free_index(DeviceIndex &ix)
 {
   hipFree(ix.bf64); hipFree(ix.rank_w); hipFree(ix.ent); hipFree(ix.ids); hipFree(ix.sum32); hipFree(ix.tab); hipFree(ix.lsum32); hipFree(ix.lbig32); hipFree(ix.ltab); hipFree(ix.ref2); hipFree(ix.refpay); hipFree(ix.refext); hipFree(ix.refmul); hipFree(ix.atab); hipFree(ix.ktab);
-  hipFree(ix.ptab); hipFree(ix.pdir); hipFree(ix.gene_start);
+  hipFree(ix.ptab); hipFree(ix.pdir); hipFree(ix.gene_start); hipFree(ix.recbase);
   ix = DeviceIndex{};
 }
 
@@ -810,6 +810,7 @@ void shk_destroy(shk_ctx *ctx)
   hipFree(ctx->d_depth_diff); hipFree(ctx->d_depth_mates); hipFree(ctx->d_depth_scan); hipFree(ctx->d_depth_scan_temp); hipFree(ctx->d_depth_summary);
   hipFree(ctx->d_junc_tab); hipFree(ctx->d_junc_dropped);
   hipFree(ctx->d_pileup); hipFree(ctx->d_pileup_mates);
+  hipFree(ctx->d_var_waves); hipFree(ctx->d_var_temp); hipFree(ctx->d_var_out); hipFree(ctx->d_var_summary);
   dist_release(ctx);
   for (auto e : ctx->ev_start) (void)hipEventDestroy(e);
   for (auto e : ctx->ev_stop) (void)hipEventDestroy(e);
@@ -928,6 +929,7 @@ int shk_debug_index_array(const shk_ctx *cctx, const char *name, void *dst, uint
   else if (what == "ref2") { src = total ? ix.ref2 : nullptr; bytes = ((total + 15) / 16 + 4) * sizeof(uint32_t); }
   else if (what == "refpay") { src = total ? ix.refpay : nullptr; bytes = (total + 8) * sizeof(uint32_t); }
   else if (what == "refext") { src = total ? ix.refext : nullptr; bytes = (total + 8) * sizeof(uint32_t); }
+  else if (what == "recbase") { src = ix.recbase; bytes = ix.recbase_bytes; }
   else if (what == "refmul") { src = total ? ix.refmul : nullptr; bytes = ((total + 31) / 32 + 2) * sizeof(uint32_t); }
   else return SHK_ERR_ARG;
   if (!src) bytes = 0;
@@ -1215,6 +1217,15 @@ int shk_ref_keep_positions(shk_ctx *ctx)
   if (!ctx) return SHK_ERR_ARG;
   if (ctx->mode != 0) { ctx->last_error = "shk_ref_keep_positions: the index is finalized already"; return SHK_ERR_STATE; }
   ctx->keep_positions = true;
+  return SHK_OK;
+}
+
+int shk_ref_keep_bases(shk_ctx *ctx)
+{
+  if (!ctx) return SHK_ERR_ARG;
+  if (ctx->mode != 0) { ctx->last_error = "shk_ref_keep_bases: the index is finalized already"; return SHK_ERR_STATE; }
+  ctx->keep_positions = true;   // (the bases lie in gene_start's order, which the placement table's build provides)
+  ctx->keep_bases = true;
   return SHK_OK;
 }
 
@@ -1567,6 +1578,57 @@ int shk_pileup_reset(shk_ctx *ctx)
   SHK_HIP(ctx, hipSetDevice(ctx->prm.device));
   SHK_HIP(ctx, hipMemsetAsync(ctx->d_pileup, 0, pileup_bytes(ctx), ctx->stream));
   SHK_HIP(ctx, hipMemsetAsync(ctx->d_pileup_mates, 0, sizeof(unsigned long long), ctx->stream));
+  SHK_HIP(ctx, hipStreamSynchronize(ctx->stream));
+  return SHK_OK;
+}
+
+int shk_pileup_add(shk_ctx *ctx, const uint32_t *counts, uint64_t n_entries, uint64_t mates, int device)
+{
+  if (!ctx) return SHK_ERR_ARG;
+  if (!ctx->d_pileup_mates) { ctx->last_error = "shk_pileup_add: pileup mode was never enabled on this context"; return SHK_ERR_STATE; }
+  if (tickets_outstanding(ctx)) { ctx->last_error = "shk_pileup_add: tickets are outstanding (wait for them first)"; return SHK_ERR_STATE; }
+  if (n_entries != 4 * ctx->gene_start.back() || (!counts && n_entries)) { ctx->last_error = "shk_pileup_add: n_entries is not 4 * gene_start[nidx]"; return SHK_ERR_ARG; }
+  SHK_HIP(ctx, hipSetDevice(ctx->prm.device));
+  uint32_t *staged = nullptr;
+  if (!device && n_entries) {
+    // (once per worker or rank and sample: a buffer for the length of the call)
+    SHK_HIP(ctx, hipMalloc((void **)&staged, n_entries * sizeof(uint32_t)));
+    if (hipError_t e = hipMemcpyAsync(staged, counts, n_entries * sizeof(uint32_t), hipMemcpyHostToDevice, ctx->stream)) { (void)hipFree(staged); return set_hip_error(ctx, e, "hipMemcpyAsync"); }
+  }
+  int rc = launch_pileup_add(ctx, staged ? staged : counts, n_entries, mates);
+  const hipError_t e = hipStreamSynchronize(ctx->stream);
+  if (staged) (void)hipFree(staged);
+  if (rc == SHK_OK && e != hipSuccess) rc = set_hip_error(ctx, e, "hipStreamSynchronize");
+  return rc;
+}
+
+// ---- variants mode (variants.hip): read-outs of the pileup state against DeviceIndex::recbase ----
+static int variants_check(shk_ctx *ctx, const char *who, const shk_variant_params *p)
+{
+  if (!p || p->min_depth < 1 || p->min_alt < 1 || p->frac_den < 1 || p->frac_den > 65535 || p->frac_num > p->frac_den) {
+    ctx->last_error = std::string(who) + ": parameters outside min_depth >= 1, min_alt >= 1, 1 <= frac_den <= 65535, frac_num <= frac_den";
+    return SHK_ERR_ARG;
+  }
+  if (!ctx->d_pileup_mates) { ctx->last_error = std::string(who) + ": pileup mode was never enabled on this context"; return SHK_ERR_STATE; }
+  if (!ctx->idx.recbase) { ctx->last_error = std::string(who) + ": the index was finalized without shk_ref_keep_bases"; return SHK_ERR_STATE; }
+  return pileup_read_mates(ctx, who, nullptr);   // (tickets, the stream drained, the mate guard)
+}
+
+int shk_variants_get(shk_ctx *ctx, const shk_variant_params *p, shk_variant *out, uint64_t cap, uint64_t *n)
+{
+  if (!ctx || !n) return SHK_ERR_ARG;
+  if (const int rc = variants_check(ctx, "shk_variants_get", p)) return rc;
+  return variants_call(ctx, *p, out, cap, n);
+}
+
+int shk_variants_summary(shk_ctx *ctx, const shk_variant_params *p, shk_gene_variants *out, uint32_t n_genes)
+{
+  if (!ctx) return SHK_ERR_ARG;
+  if (const int rc = variants_check(ctx, "shk_variants_summary", p)) return rc;
+  if ((uint64_t)n_genes + 1 > ctx->gene_start.size() || (!out && n_genes)) return SHK_ERR_ARG;
+  if (n_genes == 0) return SHK_OK;
+  if (const int rc = launch_variants_summary(ctx, *p)) return rc;
+  SHK_HIP(ctx, hipMemcpyAsync(out, ctx->d_var_summary, (size_t)n_genes * sizeof(shk_gene_variants), hipMemcpyDeviceToHost, ctx->stream));
   SHK_HIP(ctx, hipStreamSynchronize(ctx->stream));
   return SHK_OK;
 }

@@ -120,11 +120,16 @@ struct DeviceIndex {
   // ---- depth mode (depth.hip): gene_start[g] = bases of the records numbered below g, g = 0 .. nidx (nidx + 1 entries); built
   //      with ptab for an index of at most 65 536 records (where the mode can be switched on), nullptr otherwise ----
   uint64_t *gene_start = nullptr;
+  // ---- variants mode (shk_ref_keep_bases; variants.hip): recbase[gene_start[g] + x] = to_int[byte] - 1 of base x of gene g's record
+  //      (0 .. 3, every other byte 4), in gene_start's order; recbase_bytes = gene_start[nidx] rounded up to a dword plus one dword, the padding 4:
+  //      a lane may load an aligned dword behind the end.  nullptr / 0 = not built ----
+  uint8_t *recbase = nullptr;
+  uint64_t recbase_bytes = 0;
 };
 // Test-only read-back of the arrays above (tests/index_audit.py audits them entry by entry):
 //   extern "C" int shk_debug_index_array(const shk_ctx *, const char *name, void *dst, uint64_t dst_bytes, uint64_t *bytes_needed)
 // copies the named device array to the host exactly as allocated, padding included.  Names: rank_w, ent, ids, sum32, lsum32,
-// lbig32, tab, atab, ltab, ref2, refpay, refext, refmul.  dst == NULL only reports the size; the size is 0 when this index does
+// lbig32, tab, atab, ltab, ref2, refpay, refext, refmul, recbase.  dst == NULL only reports the size; the size is 0 when this index does
 // not carry the array.  "meta" gives SHK_DEBUG_META_WORDS uint64_t scalars in this order: tab_lg, sum_shift, lsum_shift,
 // lbig_shift, ltab_mul, ref_total, n_set, tot_idx, pow2, wrap, ent_len, ids_len, bf_bits, bf_words64, sum_bits, ktab_lg.
 // Exported from the library but deliberately not declared in include/shark_hip.h; no classify path uses it.
@@ -371,6 +376,13 @@ int launch_depth_accumulate(Ctx *ctx, const Slot &s, bool skip_if_long, hipStrea
 int launch_spliced_accumulate(Ctx *ctx, const Slot &s, const shk_segment *entries, uint64_t cap_assoc, bool skip_if_long, hipStream_t stream);
 // pileup.hip: the batch in `s` from the same records into Ctx::d_pileup at floor s.pileup, behind segments_kernel; skip_if_long: as launch_gene_hist
 int launch_pileup(Ctx *ctx, const Slot &s, const shk_segment *entries, uint64_t cap_assoc, bool skip_if_long, hipStream_t stream);
+// variants.hip: d_pileup[i] += d_add[i] over n_entries counters (d_add 16-byte aligned: SHK_ERR_ARG otherwise), *d_pileup_mates += mates, on ctx->stream
+int launch_pileup_add(Ctx *ctx, const uint32_t *d_add, uint64_t n_entries, uint64_t mates);
+// variants.hip: the sites of the pileup state against DeviceIndex::recbase: their number into *n_sites (host; the stream is drained) and, with
+// out != nullptr, the records in (gene, x) order into out[0 .. *n_sites) (host; SHK_ERR_ARG if cap is smaller, *n_sites set all the same)
+int variants_call(Ctx *ctx, const shk_variant_params &prm, shk_variant *out, uint64_t cap, uint64_t *n_sites);
+// variants.hip: per gene {observed, mismatches, covered, sites} into Ctx::d_var_summary (nidx records), on ctx->stream
+int launch_variants_summary(Ctx *ctx, const shk_variant_params &prm);
 int launch_junction_clear(Ctx *ctx);   // every entry of Ctx::d_junc_tab empty, Ctx::d_junc_dropped 0, on ctx->stream
 // the read-out: Ctx::d_depth_scan[1 + x] = depth of base x of the full array (inclusive prefix sum of the difference array), on ctx->stream
 int depth_scan(Ctx *ctx);
@@ -498,6 +510,12 @@ struct Ctx {
   uint32_t pileup = 0;                         // min_support for the batches submitted from now on (0: off)
   uint32_t *d_pileup = nullptr;                // gene_start[nidx] x 4 counters, [x * 4 + b]: the observations of base b at x (allocated by the first enable)
   unsigned long long *d_pileup_mates = nullptr;   // pileup mates since the last reset (not null: the mode was enabled once)
+  // variants mode (shk_ref_keep_bases, shk_variants_get / _summary; variants.hip): read-outs of the pileup state; scratch only grows
+  bool keep_bases = false;                     // finalize builds DeviceIndex::recbase
+  uint32_t *d_var_waves = nullptr;             // sites per wavefront of 256 positions, then their exclusive scan
+  uint64_t *d_var_temp = nullptr;              // exclusive_scan_u32's temp over d_var_waves (allocated with it)
+  shk_variant *d_var_out = nullptr;   size_t cap_var_out = 0;   // records
+  shk_gene_variants *d_var_summary = nullptr;  // nidx records
 
   // timing
   bool timing = false;
