@@ -296,7 +296,9 @@ class SharkHip:
     # ---- test-only read-back of the derived index arrays (shk_debug_index_array: exported, not in the header, not in EXPORTS) ----
     DEBUG_ARRAYS = {"rank_w": np.uint32, "ent": np.uint32, "ids": np.uint16, "sum32": np.uint32, "lsum32": np.uint32,
                     "lbig32": np.uint32, "tab": np.uint64, "atab": np.uint64, "ltab": np.uint32, "ref2": np.uint32,
-                    "refpay": np.uint32, "refext": np.uint32, "refmul": np.uint32, "recbase": np.uint8}
+                    "refpay": np.uint32, "refext": np.uint32, "refmul": np.uint32, "recbase": np.uint8,
+                    "ptab": np.uint32, "pdir": np.uint32, "pmeta": np.uint64}      # (ptab: 4 words per entry; pmeta: DEBUG_PMETA)
+    DEBUG_PMETA = ("ptab_lg", "ptab_n")
     DEBUG_META = ("tab_lg", "sum_shift", "lsum_shift", "lbig_shift", "ltab_mul", "ref_total", "n_set", "tot_idx", "pow2", "wrap",
                   "ent_len", "ids_len", "bf_bits", "bf_words64", "sum_bits", "ktab_lg")
 

@@ -915,6 +915,14 @@ int shk_debug_index_array(const shk_ctx *cctx, const char *name, void *dst, uint
     memcpy(dst, meta, sizeof(meta));
     return SHK_OK;
   }
+  if (what == "pmeta") {   // (a name of its own: `meta` keeps its 16 words)
+    const uint64_t pmeta[SHK_DEBUG_PMETA_WORDS] = {ix.ptab_lg, ix.ptab_n};
+    *bytes_needed = ix.ptab_lg ? sizeof(pmeta) : 0;
+    if (!dst || !ix.ptab_lg) return SHK_OK;
+    if (dst_bytes < sizeof(pmeta)) return SHK_ERR_ARG;
+    memcpy(dst, pmeta, sizeof(pmeta));
+    return SHK_OK;
+  }
   const void *src = nullptr;
   uint64_t bytes = 0;
   if (what == "rank_w") { src = ix.rank_w; bytes = (ix.bf_words64 + 2) * sizeof(uint32_t); }
@@ -931,6 +939,8 @@ int shk_debug_index_array(const shk_ctx *cctx, const char *name, void *dst, uint
   else if (what == "refext") { src = total ? ix.refext : nullptr; bytes = (total + 8) * sizeof(uint32_t); }
   else if (what == "recbase") { src = ix.recbase; bytes = ix.recbase_bytes; }
   else if (what == "refmul") { src = total ? ix.refmul : nullptr; bytes = ((total + 31) / 32 + 2) * sizeof(uint32_t); }
+  else if (what == "ptab") { src = ix.ptab_lg ? ix.ptab : nullptr; bytes = (ix.ptab_n + 1) * sizeof(uint4); }
+  else if (what == "pdir") { src = ix.ptab_lg ? ix.pdir : nullptr; bytes = ((1ull << ix.ptab_lg) + 2) * sizeof(uint32_t); }
   else return SHK_ERR_ARG;
   if (!src) bytes = 0;
   *bytes_needed = bytes;

@@ -132,8 +132,12 @@ struct DeviceIndex {
 // lbig32, tab, atab, ltab, ref2, refpay, refext, refmul, recbase.  dst == NULL only reports the size; the size is 0 when this index does
 // not carry the array.  "meta" gives SHK_DEBUG_META_WORDS uint64_t scalars in this order: tab_lg, sum_shift, lsum_shift,
 // lbig_shift, ltab_mul, ref_total, n_set, tot_idx, pow2, wrap, ent_len, ids_len, bf_bits, bf_words64, sum_bits, ktab_lg.
+// The placement table (tests/placement_audit.py audits it): ptab = ptab_n + 1 entries of 16 bytes as allocated (the last one is
+// spare and never written), pdir = 2^ptab_lg + 2 words, "pmeta" = SHK_DEBUG_PMETA_WORDS uint64_t scalars in this order: ptab_lg,
+// ptab_n.  All three have size 0 on an index finalized without shk_ref_keep_positions.  (gene_start: shk_depth_layout.)
 // Exported from the library but deliberately not declared in include/shark_hip.h; no classify path uses it.
 constexpr uint32_t SHK_DEBUG_META_WORDS = 16;
+constexpr uint32_t SHK_DEBUG_PMETA_WORDS = 2;
 constexpr uint32_t REFEXT_NONE = 0xFFFFFFFFu, REFEXT_CLIP = 254u;   // (an extent never reads 255: no entry looks like REFEXT_NONE)
 constexpr uint32_t REFPAY_NONE = 0xFFFFFFFFu;   // (multi with payload 2^30-1: not a rank, n_set <= 2^30-1 entries have ranks below that)
 
