@@ -78,6 +78,16 @@ int shk_ref_add(shk_ctx *ctx, const char *seq, uint64_t len);
  * (set bit -> ascending unique gene id list) CSR. */
 int shk_ref_finalize(shk_ctx *ctx);
 
+/* THE K-MER KEYED TABLE of a one-gene index (k <= 17).  The reference's answer for a k-mer depends only on its
+ * filter position, so the canonical k-mers whose position is a set bit -- the gene's own and the ones that collide with them in the
+ * filter -- decide every probe exactly.  shk_ref_finalize enumerates them on the device (all 4^k / 2 canonical k-mers against the
+ * index's exact table: tens of milliseconds at k = 17) and builds a second exact table keyed by the k-mer itself, which the
+ * classify kernels then probe without XXH64: the same results, a sixth less kernel time.  On by default; shk_ref_kmer_table(ctx, 0)
+ * before shk_ref_finalize (SHK_ERR_STATE afterwards) or SHK_NO_KMER_TABLE=1 in the environment leaves it out -- for a context that
+ * classifies fewer pairs than repay the enumeration.  Where it does not apply (several genes, k > 17, more keys than the table
+ * holds: beyond one gene of about 21 kb at k = 17 and 2^33 bits) nothing is built and nothing changes.  New: no counterpart. */
+int shk_ref_kmer_table(shk_ctx *ctx, int on);
+
 typedef struct shk_index_info {
   uint64_t n_records;    /* FASTA records added (= legend_ID.size(), FastaSplitter.hpp:48) */
   uint64_t nidx;         /* final gene counter (main.cpp:191) */

@@ -95,6 +95,7 @@ EXPORTS = [
     "shk_depth_enable_spliced", "shk_junctions_enable", "shk_junctions_get", "shk_junctions_reset",
     "shk_pileup_enable", "shk_pileup_get", "shk_pileup_get_all", "shk_pileup_mates", "shk_pileup_reset",
     "shk_pileup_add", "shk_ref_keep_bases", "shk_variants_get", "shk_variants_summary",
+    "shk_ref_kmer_table",
 ]
 SHK_PIPE_DEPTH = 3
 SHK_DIST_ID_BYTES = 128
@@ -183,6 +184,7 @@ def load():
         "shk_pileup_reset": (C.c_int, [p]),
         "shk_pileup_add": (C.c_int, [p, p, C.c_uint64, C.c_uint64, C.c_int]),
         "shk_ref_keep_bases": (C.c_int, [p]),
+        "shk_ref_kmer_table": (C.c_int, [p, C.c_int]),
         "shk_variants_get": (C.c_int, [p, C.POINTER(ShkVariantParams), p, C.c_uint64, C.POINTER(C.c_uint64)]),
         "shk_variants_summary": (C.c_int, [p, C.POINTER(ShkVariantParams), p, C.c_uint32]),
     }
@@ -258,6 +260,11 @@ class SharkHip:
         keep_positions; before the index is finalized only"""
         self._check(self.L.shk_ref_keep_bases(self.h), "shk_ref_keep_bases")
 
+    def kmer_table(self, on):
+        """whether ref_finalize / build may build the one-gene index's table keyed by the canonical k-mer (on by default; before the
+        index is finalized only)"""
+        self._check(self.L.shk_ref_kmer_table(self.h, 1 if on else 0), "shk_ref_kmer_table")
+
     def build(self, seqs, keep_positions=False, keep_bases=False):
         if keep_positions:
             self.keep_positions()
@@ -297,10 +304,12 @@ class SharkHip:
     DEBUG_ARRAYS = {"rank_w": np.uint32, "ent": np.uint32, "ids": np.uint16, "sum32": np.uint32, "lsum32": np.uint32,
                     "lbig32": np.uint32, "tab": np.uint64, "atab": np.uint64, "ltab": np.uint32, "ref2": np.uint32,
                     "refpay": np.uint32, "refext": np.uint32, "refmul": np.uint32, "recbase": np.uint8,
+                    "kxtab": np.uint8, "kxkeys": np.uint64, "kxmeta": np.uint64,
                     "ptab": np.uint32, "pdir": np.uint32, "pmeta": np.uint64}      # (ptab: 4 words per entry; pmeta: DEBUG_PMETA)
     DEBUG_PMETA = ("ptab_lg", "ptab_n")
     DEBUG_META = ("tab_lg", "sum_shift", "lsum_shift", "lbig_shift", "ltab_mul", "ref_total", "n_set", "tot_idx", "pow2", "wrap",
                   "ent_len", "ids_len", "bf_bits", "bf_words64", "sum_bits", "ktab_lg")
+    DEBUG_KXMETA = ("kx_in_use", "kx_m1", "kx_m2", "kx_keys", "kx_enum_us", "kx_build_us")
 
     def _debug_read(self, name, dtype):
         fn = self.L.shk_debug_index_array
@@ -321,6 +330,10 @@ class SharkHip:
     def debug_index_meta(self):
         """the scalars that decode the arrays"""
         return dict(zip(self.DEBUG_META, (int(x) for x in self._debug_read("meta", np.uint64))))
+
+    def debug_kx_meta(self):
+        """the k-mer keyed table of a one-gene index (kmer_table.hpp): is it in use, its multipliers, its key count, what building it took"""
+        return dict(zip(self.DEBUG_KXMETA, (int(x) for x in self._debug_read("kxmeta", np.uint64))))
 
     # ---- classification --------------------------------------------------------
     def _host_batch(self, seq1, off1, seq2, off2, qual1, qual2):

@@ -1368,6 +1368,14 @@ int launch_classify_uni(Ctx *ctx, const ClassifyParams &p_in, uint32_t max_slots
     p.lsum_shift = ctx->idx.ltab_mul;   // (no summary in this mode: the field carries the table's slot multiplier)
     p.lx_gene = ctx->idx.ltab_gene;
     p.lx_multi = (uni && ctx->idx.ltab_sparse && ctx->idx.ltab_gene == 0xFFFFFFFFu) ? 1u : 0u;
+    // a one-gene index that carries the table keyed by the canonical k-mer (kmer_table.hpp): the KX instantiations probe that one --
+    // the same answers without XXH64
+    if (ctx->idx.kxtab && ctx->idx.ltab_gene != 0xFFFFFFFFu) {
+      p.lsum32 = reinterpret_cast<const uint32_t *>(ctx->idx.kxtab);
+      p.lsum_shift = ctx->idx.kx_m1;
+      p.kx_m2 = ctx->idx.kx_m2;
+      p.kx = 1u;
+    }
     // three pairs per staging pass (classify_uni.hpp, TRI): uniform batches without qualities, U = 3 ... 5 (SHK_NO_TRI=1: not)
     p.tri = ((rmode == 1 || rmode == 3) && !hasq && u >= 3 && u <= 5 && !ctx->env_no_tri) ? 1u : 0u;
     // ... with a round of disjoint k-mers for the three pairs together in front (classify_uni.hpp, TF: an instantiation of its own)

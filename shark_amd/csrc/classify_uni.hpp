@@ -229,10 +229,15 @@ __host__ __device__ inline bool tri_applies(const uint32_t L1, const uint32_t L2
 // The plan's structure (rounds, tiles) is the layout's for every pair; its bounds -- what the slots behind a stop cover, the threshold --
 // are computed from the pair's own two lengths (see per_pair).  No sorting by length, no pass over the offsets but
 // uniform_check_kernel's.
-template <int U, int MODE, bool HASQ, int LSL, bool UNI, bool CLS = false, bool LXM = false, bool TRI = false, bool TFK = false, bool TRO = false>
+// KX (exact-table instantiations of a ONE-gene index, k <= 17): the workgroup's table is keyed by the canonical k-mer itself
+// (kmer_table.hpp, DeviceIndex::kxtab) instead of by its filter position -- the same bytes of LDS, the same answers, no XXH64 in a
+// probe.  A compile-time form like LXM; control flow, plans and bounds are the hashed instantiation's.
+template <int U, int MODE, bool HASQ, int LSL, bool UNI, bool CLS = false, bool LXM = false, bool TRI = false, bool TFK = false, bool TRO = false, bool KX = false>
 __global__ __launch_bounds__((UniGeom<U, MODE, LSL>::THREADS), (UniGeom<U, MODE, LSL>::MIN_WAVES)) void classify_uni_kernel(const ClassifyParams P)
 {
   static_assert(!TRO || TRI, "TRO is a form of the three-pairs instantiation");
+  static_assert(!KX || (pm_lds(MODE) && LSL == 21 && !LXM), "KX is a form of the one-gene exact-table instantiations");
+  static_assert(KXTAB_BYTES <= LTAB_BYTES, "the k-mer keyed image has to fit the LDS the exact table reserves");
   static_assert(!CLS || UNI, "CLS is a form of the uniform instantiation");
   static_assert(!LXM || (UNI && !CLS && pm_lds(MODE) && LSL == 21), "LXM is a form of the uniform exact-table instantiation");
   static_assert(!TRI || (UNI && !CLS && !HASQ && pm_lds(MODE) && LSL == 21 && U <= 8), "TRI is a form of the uniform exact-table instantiation without qualities");
@@ -753,7 +758,10 @@ static void launch_uni_u(const ClassifyParams &p, int mode, bool hasq, bool big,
 {
   if (rmode == 2) {
     if constexpr (U <= 5 || U == 10) {
-      if (lx && mode == PM_LDS_TAB) {
+      if (lx && mode == PM_LDS_TAB && p.kx) {
+        if (hasq) hipLaunchKernelGGL((classify_uni_kernel<U, PM_LDS_TAB, true, 21, true, true, false, false, false, false, true>), dim3(grid), dim3(UniGeom<U, PM_LDS_TAB, 21>::THREADS), 0, s, p);
+        else hipLaunchKernelGGL((classify_uni_kernel<U, PM_LDS_TAB, false, 21, true, true, false, false, false, false, true>), dim3(grid), dim3(UniGeom<U, PM_LDS_TAB, 21>::THREADS), 0, s, p);
+      } else if (lx && mode == PM_LDS_TAB) {
         if (hasq) hipLaunchKernelGGL((classify_uni_kernel<U, PM_LDS_TAB, true, 21, true, true>), dim3(grid), dim3(UniGeom<U, PM_LDS_TAB, 21>::THREADS), 0, s, p);
         else hipLaunchKernelGGL((classify_uni_kernel<U, PM_LDS_TAB, false, 21, true, true>), dim3(grid), dim3(UniGeom<U, PM_LDS_TAB, 21>::THREADS), 0, s, p);
       }
@@ -764,7 +772,9 @@ static void launch_uni_u(const ClassifyParams &p, int mode, bool hasq, bool big,
   if (rmode == 3) {
     if constexpr (U >= 3 && U <= 5) {
       if (lx && mode == PM_LDS_TAB && !hasq) {
-        if (p.lx_multi) hipLaunchKernelGGL((classify_uni_kernel<U, PM_LDS_TAB, false, 21, true, false, true, true, false, true>), dim3(grid), dim3(UniGeom<U, PM_LDS_TAB, 21>::THREADS), 0, s, p);
+        if (p.kx && p.tile_first) hipLaunchKernelGGL((classify_uni_kernel<U, PM_LDS_TAB, false, 21, true, false, false, true, true, true, true>), dim3(grid), dim3(UniGeom<U, PM_LDS_TAB, 21>::THREADS), 0, s, p);
+        else if (p.kx) hipLaunchKernelGGL((classify_uni_kernel<U, PM_LDS_TAB, false, 21, true, false, false, true, false, true, true>), dim3(grid), dim3(UniGeom<U, PM_LDS_TAB, 21>::THREADS), 0, s, p);
+        else if (p.lx_multi) hipLaunchKernelGGL((classify_uni_kernel<U, PM_LDS_TAB, false, 21, true, false, true, true, false, true>), dim3(grid), dim3(UniGeom<U, PM_LDS_TAB, 21>::THREADS), 0, s, p);
         else if (p.tile_first) hipLaunchKernelGGL((classify_uni_kernel<U, PM_LDS_TAB, false, 21, true, false, false, true, true, true>), dim3(grid), dim3(UniGeom<U, PM_LDS_TAB, 21>::THREADS), 0, s, p);
         else hipLaunchKernelGGL((classify_uni_kernel<U, PM_LDS_TAB, false, 21, true, false, false, true, false, true>), dim3(grid), dim3(UniGeom<U, PM_LDS_TAB, 21>::THREADS), 0, s, p);
       }
@@ -779,7 +789,9 @@ static void launch_uni_u(const ClassifyParams &p, int mode, bool hasq, bool big,
       const bool host_knows = p.uni_flag == nullptr;
       const bool applies = host_knows && tri_applies(p.uni_L1, p.uni_L2, p.k, 64u * U);
       if (!host_knows || applies) {
-        if (p.lx_multi) hipLaunchKernelGGL((classify_uni_kernel<U, PM_LDS_TAB, false, 21, true, false, true, true>), dim3(grid), dim3(UniGeom<U, PM_LDS_TAB, 21>::THREADS), 0, s, p);
+        if (p.kx && p.tile_first) hipLaunchKernelGGL((classify_uni_kernel<U, PM_LDS_TAB, false, 21, true, false, false, true, true, false, true>), dim3(grid), dim3(UniGeom<U, PM_LDS_TAB, 21>::THREADS), 0, s, p);
+        else if (p.kx) hipLaunchKernelGGL((classify_uni_kernel<U, PM_LDS_TAB, false, 21, true, false, false, true, false, false, true>), dim3(grid), dim3(UniGeom<U, PM_LDS_TAB, 21>::THREADS), 0, s, p);
+        else if (p.lx_multi) hipLaunchKernelGGL((classify_uni_kernel<U, PM_LDS_TAB, false, 21, true, false, true, true>), dim3(grid), dim3(UniGeom<U, PM_LDS_TAB, 21>::THREADS), 0, s, p);
         else if (p.tile_first) hipLaunchKernelGGL((classify_uni_kernel<U, PM_LDS_TAB, false, 21, true, false, false, true, true>), dim3(grid), dim3(UniGeom<U, PM_LDS_TAB, 21>::THREADS), 0, s, p);
         else hipLaunchKernelGGL((classify_uni_kernel<U, PM_LDS_TAB, false, 21, true, false, false, true>), dim3(grid), dim3(UniGeom<U, PM_LDS_TAB, 21>::THREADS), 0, s, p);
         if (applies) return;
@@ -798,7 +810,15 @@ static void launch_uni_u(const ClassifyParams &p, int mode, bool hasq, bool big,
                         else if (L_ != 20) { if (hasq) LU4(M_, L_, true, false); else LU4(M_, L_, false, false); } } while (0)
   switch (mode) {
   case PM_LDS_TAB:
-    if (lx) { if constexpr (U <= 5 || U == 10) LU(PM_LDS_TAB, 21); }   // (launch_classify_uni asks for it only where it is compiled)
+    if (lx && p.kx) {   // (the one-gene index's k-mer keyed table)
+      if constexpr (U <= 5 || U == 10) {
+#define LK(HQ_, UN_) hipLaunchKernelGGL((classify_uni_kernel<U, PM_LDS_TAB, HQ_, 21, UN_, false, false, false, false, false, true>), dim3(grid), dim3(UniGeom<U, PM_LDS_TAB, 21>::THREADS), 0, s, p)
+        if (uni) { if (hasq) LK(true, true); else LK(false, true); }
+        else { if (hasq) LK(true, false); else LK(false, false); }
+#undef LK
+      }
+    }
+    else if (lx) { if constexpr (U <= 5 || U == 10) LU(PM_LDS_TAB, 21); }   // (launch_classify_uni asks for it only where it is compiled)
     else if (big) LU(PM_LDS_TAB, 20);
     else LU(PM_LDS_TAB, 18);
     break;

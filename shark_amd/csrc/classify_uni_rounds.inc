@@ -71,6 +71,7 @@
           continue;
         }
         const uint64_t canon = fwd < rc ? fwd : rc;         // KmerBuilder.hpp:49, ReadAnalyzer.hpp:55
+        if (KX) { pos[j] = canon; continue; }               // (the table is keyed by the k-mer itself: no XXH64)
         const uint64_t hsh = xxh64_u64(canon);
         // (LDS-summary mode with a power-of-two size keeps the raw hash: every use below masks the bits it needs)
         pos[j] = POW2 ? (LSUM ? hsh : (hsh & P.bf_mask)) : bf_pos_np(hsh, P);
@@ -95,6 +96,18 @@
 #pragma unroll
         for (int j = JLO; j < JHI; ++j) { okm[j] = ok[j] ? 0xFFFFFFFFu : 0u; any |= ok[j]; }
         something = __ballot(any) != 0ull;
+      } else if (KX) {
+        // the exact table in LDS keyed by the canonical k-mer (kmer_table.hpp; pos[] is the k-mer): every entry is the one gene's,
+        // none escapes to the position table
+        bool any = false;
+#pragma unroll
+        for (int j = JLO; j < JHI; ++j) {
+          mt[j] = kxtab_lookup(reinterpret_cast<const uint8_t *>(lsum), P.lsum_shift, P.kx_m2, pos[j]);
+          slo[j] = P.lx_gene;
+          okm[j] = mt[j] ? 0xFFFFFFFFu : 0u;
+          any |= mt[j];
+        }
+        lane_any |= any;
       } else if (LX) {
         // the exact table in LDS: displacement of the position's group, then the slot (shark_internal.hpp)
         const uint32_t *T = lsum;

@@ -13,6 +13,11 @@
       const uint64_t x = ((uint64_t)__builtin_amdgcn_alignbit(d2, d1, af) << 32) | __builtin_amdgcn_alignbit(d1, d0, af);
       const uint64_t y = ((uint64_t)__builtin_amdgcn_alignbit(e2, e1, ar) << 32) | __builtin_amdgcn_alignbit(e1, e0, ar);
       const uint64_t fwd = y & kmer_mask, rc = ~x & kmer_mask;
+      if constexpr (KX) {
+        // the table keyed by the canonical k-mer itself (kmer_table.hpp): no XXH64; every entry is the one gene's (P.lx_gene), none escapes
+        payload = 0u;
+        return kxtab_lookup(reinterpret_cast<const uint8_t *>(lsum), P.lsum_shift, P.kx_m2, fwd < rc ? fwd : rc);
+      }
       const uint64_t h = xxh64_u64(fwd < rc ? fwd : rc);
       const uint32_t *T = lsum;
       const char *D = reinterpret_cast<const char *>(lsum + LTAB_T_WORDS);

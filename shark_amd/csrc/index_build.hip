@@ -16,6 +16,7 @@
 #include <hip/hip_runtime.h>
 
 #include <algorithm>
+#include <chrono>
 #include <cmath>
 #include <cstdio>
 #include <cstdlib>
@@ -455,6 +456,84 @@ static bool build_lds_table(const std::vector<uint64_t> &tab, uint32_t tab_lg, s
   return ltab_build(keys, img, mul);
 }
 
+// ---- the keys of the k-mer keyed exact table of a one-gene index (kmer_table.hpp): every canonical k-mer whose filter position is a set bit ----
+// All 4^k k-mers are walked, less the ones that cannot be canonical: a k-mer is smaller than its reverse complement when its first
+// base is smaller than the complement of its last (t + l < 3 in codes: six of the sixteen (t, l)), larger when t + l > 3 (six: never
+// visited), and only the four ties t + l = 3 need the comparison (half of them pass: those lanes idle through one hash).  An item is
+// (one of the ten (t, l), the k - 2 bases between them); a wave's 64 consecutive items share their (t, l) for k >= 5, so on the sure
+// ones every lane hashes.  Each k-mer is visited once -- a k-mer that is its own reverse complement (even k) too -- and "is its
+// position a set bit" is answered by the index's exact table held in LDS (ltab_lookup, the rule classify_uni_kernel applies), not by
+// the filter in memory: the pass is arithmetic only.  Hits go to a bounded buffer in any order (the host sorts them); *count says how
+// many there were, beyond `cap` they are dropped and the caller gives up.
+constexpr int KE_THREADS = 1024;
+__global__ __launch_bounds__(KE_THREADS) void kmer_enum_kernel(const uint32_t *__restrict__ ltab, const uint32_t mul, const uint64_t bf_mask, const uint32_t k,
+                                                               uint64_t *__restrict__ out, const uint32_t cap, uint32_t *__restrict__ count)
+{
+  __shared__ uint32_t img[LTAB_BYTES / 4];
+  for (uint32_t i = threadIdx.x; i < LTAB_BYTES / 16; i += KE_THREADS) reinterpret_cast<uint4 *>(img)[i] = reinterpret_cast<const uint4 *>(ltab)[i];
+  __syncthreads();
+  const uint32_t mid_bits = 2u * k - 4u;
+  const uint64_t items = 10ull << mid_bits;
+  for (uint64_t i = (uint64_t)blockIdx.x * KE_THREADS + threadIdx.x; i < items; i += (uint64_t)gridDim.x * KE_THREADS) {
+    const uint32_t combo = (uint32_t)(i >> mid_bits);
+    // (t << 2 | l) of combo 0 .. 9: the six sure ones (0,0) (0,1) (0,2) (1,0) (1,1) (2,0), then the ties (0,3) (1,2) (2,1) (3,0)
+    const uint32_t tl = (uint32_t)(0xC963854210ull >> (4u * combo)) & 15u;
+    const uint64_t v = ((uint64_t)(tl >> 2) << (2u * k - 2u)) | ((i & ((1ull << mid_bits) - 1ull)) << 2) | (tl & 3u);
+    bool canon = true;
+    if (combo >= 6u) canon = v <= revcomp_left_aligned(v << (64u - 2u * k), k);
+    if (!canon) continue;
+    uint32_t payload;
+    if (ltab_lookup(img, mul, xxh64_u64(v), bf_mask, &payload)) {
+      const uint32_t at = atomicAdd(count, 1u);
+      if (at < cap) out[at] = v;
+    }
+  }
+}
+
+// ... and the table from them.  Optional: whatever fails in here -- memory, a launch, more keys than the table holds, no pair of
+// multipliers that works -- leaves ix.kxtab unset, and the hashed table serves with the same results.
+static void build_kmer_table(DeviceIndex &ix, const uint32_t k, hipStream_t st)
+{
+  const uint32_t cap = 2u * KXTAB_MAX_KEYS;
+  uint64_t *d_keys = nullptr;
+  uint32_t *d_count = nullptr;
+  uint8_t *d_img = nullptr;
+  const bool ok = [&]() -> bool {
+#define KX_HIP(call) do { if ((call) != hipSuccess) return false; } while (0)
+    KX_HIP(hipMalloc((void **)&d_keys, cap * sizeof(uint64_t)));
+    KX_HIP(hipMalloc((void **)&d_count, sizeof(uint32_t)));
+    KX_HIP(hipMalloc((void **)&d_img, LTAB_BYTES));
+    KX_HIP(hipMemsetAsync(d_count, 0, sizeof(uint32_t), st));
+    KX_HIP(hipMemsetAsync(d_img, 0, LTAB_BYTES, st));
+    KX_HIP(hipStreamSynchronize(st));
+    const auto t0 = std::chrono::steady_clock::now();
+    hipLaunchKernelGGL(kmer_enum_kernel, dim3(256), dim3(KE_THREADS), 0, st, (const uint32_t *)ix.ltab, ix.ltab_mul, ix.bf_bits - 1, k, d_keys, cap, d_count);
+    KX_HIP(hipGetLastError());
+    uint32_t n = 0;
+    KX_HIP(hipMemcpyAsync(&n, d_count, sizeof(uint32_t), hipMemcpyDeviceToHost, st));
+    KX_HIP(hipStreamSynchronize(st));
+    const auto t1 = std::chrono::steady_clock::now();
+    ix.kx_enum_us = (uint64_t)std::chrono::duration<double, std::micro>(t1 - t0).count();
+    if (n == 0 || n > KXTAB_MAX_KEYS) return false;
+    std::vector<uint64_t> keys(n);
+    KX_HIP(hipMemcpy(keys.data(), d_keys, n * sizeof(uint64_t), hipMemcpyDeviceToHost));
+    std::sort(keys.begin(), keys.end());     // (the same image on every rank and in every run)
+    std::vector<uint8_t> img;
+    if (!kxtab_build(keys, img, &ix.kx_m1, &ix.kx_m2)) return false;
+    ix.kx_build_us = (uint64_t)std::chrono::duration<double, std::micro>(std::chrono::steady_clock::now() - t1).count();
+    KX_HIP(hipMemcpy(d_img, img.data(), KXTAB_BYTES, hipMemcpyHostToDevice));
+    KX_HIP(hipMemcpy(d_keys, keys.data(), n * sizeof(uint64_t), hipMemcpyHostToDevice));
+    ix.kx_nkeys = n;
+    return true;
+#undef KX_HIP
+  }();
+  (void)hipFree(d_count);
+  if (ok) { ix.kxtab = d_img; ix.kxkeys = d_keys; return; }
+  (void)hipFree(d_keys); (void)hipFree(d_img);
+  (void)hipGetLastError();   // (optional: a failure in here is not the build's)
+  ix.kx_nkeys = 0; ix.kx_m1 = ix.kx_m2 = 0;
+}
+
 static unsigned grid_for(uint64_t n, unsigned threads) { return (unsigned)((n + threads - 1) / threads); }
 
 int build_index(Ctx *ctx)
@@ -682,6 +761,7 @@ int build_index(Ctx *ctx)
         // tiny indices (a gene or a few): the whole table fits the LDS of a CU as a perfect hash -- uniform batches then
         // touch no memory but their own bases (classify_uni.hpp LSL = 21); the chains above stay for trimmed reads
         if (ix.ltab) { (void)hipFree(ix.ltab); ix.ltab = nullptr; }
+        if (ix.kxtab) { (void)hipFree(ix.kxtab); (void)hipFree(ix.kxkeys); ix.kxtab = nullptr; ix.kxkeys = nullptr; ix.kx_nkeys = 0; }
         ix.ltab_gene = 0xFFFFFFFFu;
         ix.ltab_sparse = false;
         if (ix.pow2 && ix.lsum_shift && lgB >= 24 && lgB <= LTAB_MAX_POS_LG && n_set <= LTAB_MAX_KEYS && !getenv("SHK_NO_LDS_TABLE")) {
@@ -696,6 +776,13 @@ int build_index(Ctx *ctx)
             BI_HIP(hipMalloc((void **)&ix.ltab, LTAB_BYTES));
             BI_HIP(hipMemcpyAsync(ix.ltab, img.data(), LTAB_BYTES, hipMemcpyHostToDevice, st));
             BI_HIP(hipStreamSynchronize(st));
+            // a one-gene index, k <= 17: the same table keyed by the canonical k-mer itself (kmer_table.hpp), which the KX instantiations
+            // of classify_uni_kernel probe without XXH64 -- when the keys can be expected to fit: the n_set positions' own k-mers and, of
+            // the 4^k / 2 canonical k-mers, the share n_set / 2^lgB that collide with them (k = 17, 2^33 bits: twice n_set).  Costs an
+            // enumeration of all canonical k-mers on the device (shk_ref_kmer_table(ctx, 0) / SHK_NO_KMER_TABLE=1: not built)
+            if (ctx->kmer_table && !getenv("SHK_NO_KMER_TABLE") && ix.ltab_gene != 0xFFFFFFFFu && k >= 2 && k <= 17 &&
+                (double)n_set + std::ldexp((double)n_set, (int)(2 * k) - 1 - (int)lgB) <= (double)KXTAB_MAX_KEYS)
+              build_kmer_table(ix, k, st);
           }
         }
         table_bytes = slots * sizeof(uint64_t);

@@ -18,6 +18,13 @@
 #include <algorithm>
 #include <vector>
 
+// (the lookup rule also runs on the device: the index build's enumeration of the k-mer keyed table's keys, kmer_table.hpp)
+#if defined(__HIPCC__)
+#define SHK_LTAB_FN __host__ __device__ inline
+#else
+#define SHK_LTAB_FN inline
+#endif
+
 namespace shk {
 
 constexpr uint32_t LTAB_SLOT_LG = 15, LTAB_GROUP_LG = 13;
@@ -83,7 +90,7 @@ inline bool ltab_build(const std::vector<LtabKey> &keys, std::vector<uint32_t> &
 
 // The lookup rule, as classify_uni_kernel applies it to the raw 64-bit hash `h` of a filter with 2^lgB bits (bf_mask =
 // 2^lgB - 1): true = the position is a key, *payload = its entry's payload.
-inline bool ltab_lookup(const uint32_t *img, uint32_t mul, uint64_t h, uint64_t bf_mask, uint32_t *payload)
+SHK_LTAB_FN bool ltab_lookup(const uint32_t *img, uint32_t mul, uint64_t h, uint64_t bf_mask, uint32_t *payload)
 {
   const uint32_t tagmask = (uint32_t)(bf_mask >> LTAB_SLOT_LG);
   const uint32_t gmask = tagmask & ((1u << LTAB_GROUP_LG) - 1u);

@@ -67,6 +67,10 @@ __global__ __launch_bounds__(256) void random_lookup_kernel(const uint8_t *__res
 // measured VALU rate by this kernel's (instructions from the same counter pass, time from here): how far the classify kernel is
 // from what the SIMDs can issue of THIS mix -- 15 of XXH64's 38 instructions are quarter-rate multiplies -- rather than from the
 // 2-cycle peak no integer code reaches.
+// KX: the probe of the table keyed by the canonical k-mer (kmer_table.hpp) in place of XXH64 and the hashed table's rule -- what the
+// classify kernel of a one-gene index runs when that table is built; shk_measure_valu_mix picks the form the context's index uses,
+// shk_measure_valu_mix_xxh64 is always the hashed one, so both ceilings can be read.
+template <bool KX>
 __global__ __launch_bounds__(256) void valu_mix_kernel(const uint32_t iters, const uint32_t k, uint32_t *__restrict__ out)
 {
   const uint32_t tid = blockIdx.x * blockDim.x + threadIdx.x;
@@ -95,14 +99,29 @@ __global__ __launch_bounds__(256) void valu_mix_kernel(const uint32_t iters, con
     const uint64_t x = ((uint64_t)__builtin_amdgcn_alignbit(f2, f1, sf) << 32) | __builtin_amdgcn_alignbit(f1, f0, sf);
     const uint64_t y = ((uint64_t)__builtin_amdgcn_alignbit(e2, e1, sr) << 32) | __builtin_amdgcn_alignbit(e1, e0, sr);
     const uint64_t fwd = y & kmer_mask, rc = ~x & kmer_mask;
-    const uint64_t h = xxh64_u64(fwd < rc ? fwd : rc);
-    // the exact table's probe (`lx_hit_at`: addresses and compare; the two LDS reads themselves are not VALU work)
-    const uint32_t di = ((uint32_t)h >> 14) & gmask2;
-    const uint32_t tg = __builtin_amdgcn_alignbit((uint32_t)(h >> 32), (uint32_t)h, 15) & tagmask;
-    const uint32_t base = (uint32_t)h + (tg >> 13) * 40503u;
-    const uint32_t ti = ((base + di) << 2) & ((32768u - 1u) << 2);
-    const uint32_t ee = ti ^ d1;
-    const bool hit = (ee >> 13) == ((tg << 1) | 1u);
+    uint64_t h;
+    uint32_t ti;
+    bool hit;
+    if constexpr (KX) {
+      // the k-mer keyed table's probe (kxtab_lookup: mixing, addresses, compare; its three LDS reads are not VALU work)
+      uint32_t tag, base;
+      kxtab_mix(fwd < rc ? fwd : rc, 0x9E3779u | (iters << 24), 0x85EBCBu | (iters << 24), tag, base);
+      const uint32_t dd = (((tag << 1) & ((2u << KXTAB_GROUP_LG) - 2u)) ^ d1) & 0xFFFFu;
+      ti = ((base + dd) << 1) & ((2u << KXTAB_RING_LG) - 2u);
+      const uint32_t t16 = (ti ^ d2) & 0xFFFFu, t2 = ((ti >> 3) ^ d0) & 0xFFu;
+      const uint32_t e = t16 | (((t2 >> (ti & 6u)) & 3u) << 16);
+      hit = (ti < 2u * KXTAB_SLOTS) & (e == tag) & (tag != 0u);
+      h = ((uint64_t)tag << 32) | base;
+    } else {
+      h = xxh64_u64(fwd < rc ? fwd : rc);
+      // the exact table's probe (`lx_hit_at`: addresses and compare; the two LDS reads themselves are not VALU work)
+      const uint32_t di = ((uint32_t)h >> 14) & gmask2;
+      const uint32_t tg = __builtin_amdgcn_alignbit((uint32_t)(h >> 32), (uint32_t)h, 15) & tagmask;
+      const uint32_t base = (uint32_t)h + (tg >> 13) * 40503u;
+      ti = ((base + di) << 2) & ((32768u - 1u) << 2);
+      const uint32_t ee = ti ^ d1;
+      hit = (ee >> 13) == ((tg << 1) | 1u);
+    }
     // validity window and coverage step of a matched slot (`slot_valid`, `sparse_first`)
     const uint64_t v0 = ((uint64_t)d2 << 32) | inv8, v1 = ((uint64_t)d0 << 32) | lsb;
     const uint32_t vs = lane;
@@ -129,12 +148,26 @@ __global__ __launch_bounds__(256) void valu_mix_kernel(const uint32_t iters, con
 
 using namespace shk;
 
+static int measure_valu_mix(shk_ctx *cctx, bool kx, int waves_per_simd, uint32_t iters, double *ms_out, uint64_t *wave_iterations, double *shader_ghz);
+
 extern "C" int shk_measure_valu_mix(shk_ctx *cctx, int waves_per_simd, uint32_t iters, double *ms_out, uint64_t *wave_iterations)
 {
   return shk_measure_valu_mix_clock(cctx, waves_per_simd, iters, ms_out, wave_iterations, nullptr);
 }
 
+// (the form the context's own exact-table kernel runs: with the k-mer keyed table when its index carries one)
 extern "C" int shk_measure_valu_mix_clock(shk_ctx *cctx, int waves_per_simd, uint32_t iters, double *ms_out, uint64_t *wave_iterations, double *shader_ghz)
+{
+  return measure_valu_mix(cctx, cctx && cctx->idx.kxtab != nullptr, waves_per_simd, iters, ms_out, wave_iterations, shader_ghz);
+}
+
+// (always the form with XXH64 and the hashed table's rule; exported, not declared in shark_hip.h: a measurement's control)
+extern "C" int shk_measure_valu_mix_xxh64(shk_ctx *cctx, int waves_per_simd, uint32_t iters, double *ms_out, uint64_t *wave_iterations, double *shader_ghz)
+{
+  return measure_valu_mix(cctx, false, waves_per_simd, iters, ms_out, wave_iterations, shader_ghz);
+}
+
+static int measure_valu_mix(shk_ctx *cctx, const bool kx, int waves_per_simd, uint32_t iters, double *ms_out, uint64_t *wave_iterations, double *shader_ghz)
 {
   Ctx *ctx = cctx;
   if (!ctx || !ms_out || !wave_iterations || waves_per_simd < 1 || waves_per_simd > 8 || iters == 0) return SHK_ERR_ARG;
@@ -155,11 +188,13 @@ extern "C" int shk_measure_valu_mix_clock(shk_ctx *cctx, int waves_per_simd, uin
   MS_HIP(hipEventCreate(&e1));
   // one 256-thread workgroup puts a wave on each of a CU's four SIMDs: W workgroups per CU are W waves per SIMD, all resident at once
   const unsigned grid = (unsigned)prop.multiProcessorCount * (unsigned)waves_per_simd;
-  hipLaunchKernelGGL(valu_mix_kernel, dim3(grid), dim3(256), 0, ctx->stream, 64u, ctx->prm.k, out);
+  if (kx) hipLaunchKernelGGL(valu_mix_kernel<true>, dim3(grid), dim3(256), 0, ctx->stream, 64u, ctx->prm.k, out);
+  else hipLaunchKernelGGL(valu_mix_kernel<false>, dim3(grid), dim3(256), 0, ctx->stream, 64u, ctx->prm.k, out);
   MS_HIP(hipGetLastError());
   MS_HIP(hipMemsetAsync(out + 1024, 0, 64, ctx->stream));
   MS_HIP(hipEventRecord(e0, ctx->stream));
-  hipLaunchKernelGGL(valu_mix_kernel, dim3(grid), dim3(256), 0, ctx->stream, iters, ctx->prm.k, out);
+  if (kx) hipLaunchKernelGGL(valu_mix_kernel<true>, dim3(grid), dim3(256), 0, ctx->stream, iters, ctx->prm.k, out);
+  else hipLaunchKernelGGL(valu_mix_kernel<false>, dim3(grid), dim3(256), 0, ctx->stream, iters, ctx->prm.k, out);
   MS_HIP(hipGetLastError());
   MS_HIP(hipEventRecord(e1, ctx->stream));
   MS_HIP(hipEventSynchronize(e1));

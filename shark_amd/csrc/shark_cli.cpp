@@ -117,6 +117,9 @@ const char *USAGE_MESSAGE =
     "          --variants-min-depth N        mates that must show a base at a site (default:8)\n"
     "          --variants-min-alt N          mates that must show the alternative base (default:3)\n"
     "          --variants-min-frac P/Q       the alternative base's share of those mates, at least P/Q (default:1/5; P <= Q <= 65535)\n"
+    "          --kmer-table                  one gene, k <= 17: also build the exact table keyed by the k-mer itself (no XXH64 per probe; the\n"
+    "                                        same output).  Costs tens of milliseconds when the index is built and pays on the GPU\n"
+    "                                        alone, so it is off here, where the host and the link bound a run\n"
     "      -t N also sets the number of host threads that parse FASTQ / format output (default: up to 16)\n";
 
 struct Options {
@@ -162,6 +165,7 @@ struct Options {
   std::string variants_path;
   FILE *variants_file = nullptr;   // (--variants, likewise; written once, after the last batch and after --pileup's file)
   unsigned variants_min_support = 8;
+  bool kmer_table = false;         // (--kmer-table: the one-gene index's table keyed by the k-mer, shk_ref_kmer_table; off here unless asked for)
   shk_variant_params variants_params{8, 3, 1, 5};   // (--variants-min-depth, -min-alt, -min-frac)
   bool variants_sub_flag_given = false;
   bool variants_min_support_given = false;
@@ -270,6 +274,7 @@ const OptionRow OPTION_TABLE[] = {
        o.junctions_min_support = value_of<unsigned>(v);
        if (o.junctions_min_support < 1) reject(USAGE_MESSAGE, "shark: --junctions-min-support must be at least 1.");
      }},
+    {1024, "kmer-table", false, [](Options &o, const char *) { o.kmer_table = true; }},
     {1014, "depth-spliced", false, [](Options &o, const char *) { o.depth_spliced = true; }},
     {1015, "junctions-device", false, [](Options &o, const char *) { o.junctions_device = true; }},
     {1016, "junctions-capacity", true,
@@ -1963,6 +1968,9 @@ std::string build_index(const Options &opt, GpuStart &gpu, std::vector<std::stri
   if (opt.placements_file || opt.depth_file || opt.segments_file || opt.junctions_file || opt.pileup_file || opt.variants_file)
     for (auto *ctx : gpu.ctxs)
       if (const int rc = shk_ref_keep_positions(ctx)) return std::string("shark: ") + shk_strerror(rc);
+  // (the k-mer keyed table repays its enumeration behind several hundred million pairs classified at the GPU's speed: not in a run of this command)
+  for (auto *ctx : gpu.ctxs)
+    if (const int rc = shk_ref_kmer_table(ctx, opt.kmer_table ? 1 : 0)) return std::string("shark: ") + shk_strerror(rc);
   // (--variants: the records' bases stay on the device; only worker 0 is asked for the sites, but every replica is built alike)
   if (opt.variants_file)
     for (auto *ctx : gpu.ctxs)

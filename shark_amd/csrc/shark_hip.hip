@@ -29,7 +29,7 @@ int set_hip_error(Ctx *ctx, hipError_t e, const char *what)
 
 static void free_index(DeviceIndex &ix)
 {
-  hipFree(ix.bf64); hipFree(ix.rank_w); hipFree(ix.ent); hipFree(ix.ids); hipFree(ix.sum32); hipFree(ix.tab); hipFree(ix.lsum32); hipFree(ix.lbig32); hipFree(ix.ltab); hipFree(ix.ref2); hipFree(ix.refpay); hipFree(ix.refext); hipFree(ix.refmul); hipFree(ix.atab); hipFree(ix.ktab);
+  hipFree(ix.bf64); hipFree(ix.rank_w); hipFree(ix.ent); hipFree(ix.ids); hipFree(ix.sum32); hipFree(ix.tab); hipFree(ix.lsum32); hipFree(ix.lbig32); hipFree(ix.ltab); hipFree(ix.kxtab); hipFree(ix.kxkeys); hipFree(ix.ref2); hipFree(ix.refpay); hipFree(ix.refext); hipFree(ix.refmul); hipFree(ix.atab); hipFree(ix.ktab);
   hipFree(ix.ptab); hipFree(ix.pdir); hipFree(ix.gene_start); hipFree(ix.recbase);
   ix = DeviceIndex{};
 }
@@ -915,6 +915,14 @@ int shk_debug_index_array(const shk_ctx *cctx, const char *name, void *dst, uint
     memcpy(dst, meta, sizeof(meta));
     return SHK_OK;
   }
+  if (what == "kxmeta") {   // (the k-mer keyed table's scalars, on every index; a name of its own: `meta` keeps its 16 words)
+    const uint64_t kxmeta[SHK_DEBUG_KXMETA_WORDS] = {ix.kxtab ? 1u : 0u, ix.kx_m1, ix.kx_m2, ix.kx_nkeys, ix.kx_enum_us, ix.kx_build_us};
+    *bytes_needed = sizeof(kxmeta);
+    if (!dst) return SHK_OK;
+    if (dst_bytes < sizeof(kxmeta)) return SHK_ERR_ARG;
+    memcpy(dst, kxmeta, sizeof(kxmeta));
+    return SHK_OK;
+  }
   if (what == "pmeta") {   // (a name of its own: `meta` keeps its 16 words)
     const uint64_t pmeta[SHK_DEBUG_PMETA_WORDS] = {ix.ptab_lg, ix.ptab_n};
     *bytes_needed = ix.ptab_lg ? sizeof(pmeta) : 0;
@@ -934,6 +942,8 @@ int shk_debug_index_array(const shk_ctx *cctx, const char *name, void *dst, uint
   else if (what == "tab") { src = slots ? ix.tab : nullptr; bytes = (slots + 2) * sizeof(uint64_t); }
   else if (what == "atab") { src = slots && total ? ix.atab : nullptr; bytes = (slots + 2) * sizeof(uint64_t); }
   else if (what == "ltab") { src = ix.ltab; bytes = LTAB_BYTES; }
+  else if (what == "kxtab") { src = ix.kxtab; bytes = LTAB_BYTES; }
+  else if (what == "kxkeys") { src = ix.kxtab ? ix.kxkeys : nullptr; bytes = ix.kx_nkeys * sizeof(uint64_t); }
   else if (what == "ref2") { src = total ? ix.ref2 : nullptr; bytes = ((total + 15) / 16 + 4) * sizeof(uint32_t); }
   else if (what == "refpay") { src = total ? ix.refpay : nullptr; bytes = (total + 8) * sizeof(uint32_t); }
   else if (what == "refext") { src = total ? ix.refext : nullptr; bytes = (total + 8) * sizeof(uint32_t); }
@@ -1227,6 +1237,14 @@ int shk_ref_keep_positions(shk_ctx *ctx)
   if (!ctx) return SHK_ERR_ARG;
   if (ctx->mode != 0) { ctx->last_error = "shk_ref_keep_positions: the index is finalized already"; return SHK_ERR_STATE; }
   ctx->keep_positions = true;
+  return SHK_OK;
+}
+
+int shk_ref_kmer_table(shk_ctx *ctx, int on)
+{
+  if (!ctx) return SHK_ERR_ARG;
+  if (ctx->mode != 0) { ctx->last_error = "shk_ref_kmer_table: the index is finalized already"; return SHK_ERR_STATE; }
+  ctx->kmer_table = on != 0;
   return SHK_OK;
 }
 

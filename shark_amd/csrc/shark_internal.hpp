@@ -9,6 +9,7 @@
 
 #include "../../include/shark_hip.h"
 #include "lds_table.hpp"   // LTAB_*: the LDS-resident exact table of a tiny index
+#include "kmer_table.hpp"  // KXTAB_*: the same for a one-gene index, keyed by the canonical k-mer itself
 
 namespace shk {
 
@@ -69,6 +70,15 @@ struct DeviceIndex {
   uint32_t ltab_mul = 0;      //   the multiplier its slots were computed with
   uint32_t ltab_gene = 0xFFFFFFFFu;   //   the ONE gene every key of that table answers with (a one-gene index), else 0xFFFFFFFF
   bool ltab_sparse = false;           //   the sparse first rounds are allowed on it (not SHK_NO_SPARSE=1 at build time)
+  // the exact table of a ONE-gene index a second time, keyed by the canonical k-mer itself (kmer_table.hpp; k <= 17): its keys are every
+  // canonical k-mer whose filter position is a set bit -- the gene's own and the ones that collide with them --, enumerated on the device
+  // when the index is built (kmer_enum_kernel), so a probe needs no XXH64.  nullptr = not built (switched off, several genes, too many
+  // keys, the builder gave up): the hashed table serves, results are the same
+  uint8_t *kxtab = nullptr;           // LTAB_BYTES as allocated (the image is KXTAB_BYTES, the rest zero)
+  uint64_t *kxkeys = nullptr;         // the keys, sorted (kx_nkeys of them)
+  uint64_t kx_nkeys = 0;
+  uint32_t kx_m1 = 0, kx_m2 = 0;      // the image's multipliers
+  uint64_t kx_enum_us = 0, kx_build_us = 0;   // what the enumeration on the device and the construction on the host took
   uint64_t *tab = nullptr;   // 2 slots per bucket
   uint32_t tab_lg = 0;       // log2(number of buckets); 0 = no table
   bool tab_with_summary = false;
@@ -132,11 +142,15 @@ struct DeviceIndex {
 // lbig32, tab, atab, ltab, ref2, refpay, refext, refmul, recbase.  dst == NULL only reports the size; the size is 0 when this index does
 // not carry the array.  "meta" gives SHK_DEBUG_META_WORDS uint64_t scalars in this order: tab_lg, sum_shift, lsum_shift,
 // lbig_shift, ltab_mul, ref_total, n_set, tot_idx, pow2, wrap, ent_len, ids_len, bf_bits, bf_words64, sum_bits, ktab_lg.
+// The k-mer keyed table: "kxmeta" = SHK_DEBUG_KXMETA_WORDS uint64_t scalars on every index, in this order: kx_in_use (1 = built: the
+// one-gene exact-table kernels probe it), kx_m1, kx_m2, kx_keys, kx_enum_us, kx_build_us (a name of its own, as pmeta: `meta` keeps
+// its 16 words); kxtab = its image (LTAB_BYTES as allocated), kxkeys = its sorted keys (uint64_t), both of size 0 when it is not built.
 // The placement table (tests/placement_audit.py audits it): ptab = ptab_n + 1 entries of 16 bytes as allocated (the last one is
 // spare and never written), pdir = 2^ptab_lg + 2 words, "pmeta" = SHK_DEBUG_PMETA_WORDS uint64_t scalars in this order: ptab_lg,
 // ptab_n.  All three have size 0 on an index finalized without shk_ref_keep_positions.  (gene_start: shk_depth_layout.)
 // Exported from the library but deliberately not declared in include/shark_hip.h; no classify path uses it.
 constexpr uint32_t SHK_DEBUG_META_WORDS = 16;
+constexpr uint32_t SHK_DEBUG_KXMETA_WORDS = 6;
 constexpr uint32_t SHK_DEBUG_PMETA_WORDS = 2;
 constexpr uint32_t REFEXT_NONE = 0xFFFFFFFFu, REFEXT_CLIP = 254u;   // (an extent never reads 255: no entry looks like REFEXT_NONE)
 constexpr uint32_t REFPAY_NONE = 0xFFFFFFFFu;   // (multi with payload 2^30-1: not a rank, n_set <= 2^30-1 entries have ranks below that)
@@ -185,6 +199,8 @@ struct ClassifyParams {
   uint32_t tri;              // 1 = the three-pairs-per-pass instantiation (classify_uni.hpp, TRI) is launched beside the ordinary uniform one: the one whose lengths qualify works
   uint32_t tile_first;       // (with tri, one-gene index) 1 = a round of disjoint k-mers for the three staged pairs together in front of the pairs' own rounds (classify_uni.hpp, TF)
   uint32_t lx_multi;         // exact table in LDS of an index of SEVERAL genes: the sparse first rounds with the early decision's argument (classify_uni.hpp)
+  uint32_t kx;               // 1 = lsum32 is the one-gene index's table keyed by the canonical k-mer (kmer_table.hpp; classify_uni.hpp, KX): lsum_shift carries its m1,
+  uint32_t kx_m2;            //   this its m2
   uint64_t bf_bits;
   uint64_t bf_mask;
   // options
@@ -481,6 +497,7 @@ struct Ctx {
   const shk_candidate *last_cand_entries = nullptr;
   // placement mode (shk_ref_keep_positions, shk_placement_enable), the same way
   bool keep_positions = false;      // finalize builds DeviceIndex::ptab
+  bool kmer_table = true;           // finalize builds DeviceIndex::kxtab where it applies (shk_ref_kmer_table; SHK_NO_KMER_TABLE=1: never)
   bool placement = false;
   bool last_place_valid = false;
   const shk_placement *last_place = nullptr;
