@@ -160,6 +160,11 @@ __device__ unsigned long long shk_stamp_waves[2 * 4096];   // per wave of the la
 #ifndef SHK_NO_SPARSE
 #define SHK_NO_SPARSE 0
 #endif
+// KX probes (kmer_table.hpp) of the sparse rounds and of probe_rounds: the 16-bit candidate stage on every lane, the confirm stage
+// behind a ballot (-DSHK_KX_ONE_STAGE=1: the one-call kxtab_lookup on every lane there too, as in the tiles' round; for A/B timing)
+#ifndef SHK_KX_ONE_STAGE
+#define SHK_KX_ONE_STAGE 0
+#endif
 // (-DSHK_NO_PARTIAL=1: the round between the cut's two stops is always probed whole, for A/B timing)
 #ifndef SHK_NO_PARTIAL
 #define SHK_NO_PARTIAL 0

@@ -99,13 +99,35 @@
       } else if (KX) {
         // the exact table in LDS keyed by the canonical k-mer (kmer_table.hpp; pos[] is the k-mer): every entry is the one gene's,
         // none escapes to the position table
+        // -- the candidate stage for every slot of the call, ONE ballot over them, the confirm stage behind it (see lx_probe)
+        const uint8_t *img = reinterpret_cast<const uint8_t *>(lsum);
         bool any = false;
+#if SHK_KX_ONE_STAGE
 #pragma unroll
         for (int j = JLO; j < JHI; ++j) {
-          mt[j] = kxtab_lookup(reinterpret_cast<const uint8_t *>(lsum), P.lsum_shift, P.kx_m2, pos[j]);
+          mt[j] = kxtab_lookup(img, P.lsum_shift, P.kx_m2, pos[j]);
+          any |= mt[j];
+        }
+#else
+        uint32_t tg[U], s2[U];
+#pragma unroll
+        for (int j = JLO; j < JHI; ++j) {
+          mt[j] = kxtab_candidate(img, P.lsum_shift, P.kx_m2, pos[j], tg[j], s2[j]);
+          any |= mt[j];
+        }
+        if (__ballot(any)) {
+          any = false;
+#pragma unroll
+          for (int j = JLO; j < JHI; ++j) {
+            mt[j] = mt[j] & kxtab_confirm(img, tg[j], s2[j]);
+            any |= mt[j];
+          }
+        }
+#endif
+#pragma unroll
+        for (int j = JLO; j < JHI; ++j) {
           slo[j] = P.lx_gene;
           okm[j] = mt[j] ? 0xFFFFFFFFu : 0u;
-          any |= mt[j];
         }
         lane_any |= any;
       } else if (LX) {

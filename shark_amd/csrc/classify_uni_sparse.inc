@@ -13,8 +13,10 @@
       return per_gene && gene_cover(j_const) < thr_r - ub;
     };
     // the slot ss of the read as a probe of the exact LDS table (LX): is its k-mer in the filter?  (`want` false: no probe)
-    auto lx_hit_at = [&](const uint32_t ss_in, const bool want, uint32_t &payload) -> bool {
-      return want & lx_probe(fw, rv, want ? ss_in : 0u, payload);
+    // (KX: the candidate stage's answer; the caller confirms behind its ballot with lx_confirm(tag, s2) -- the sparse rounds' reads
+    //  are nearly all from elsewhere behind the tiles' round)
+    auto lx_hit_at = [&](const uint32_t ss_in, const bool want, uint32_t &payload, uint32_t &tag, uint32_t &s2) -> bool {
+      return want & lx_probe(fw, rv, want ? ss_in : 0u, payload, std::true_type{}, tag, s2);
     };
     // the first two rounds of a one-gene index in the sparse order (see spT above).  true: the read is settled.  false: mt / slo of
     // the rounds 0 and 1 are what probe_rounds would have left (matches validated), the read goes on behind the cut's first stop.
@@ -42,13 +44,13 @@
       };
       const bool tile = ln >= nA;
       const uint32_t sA = tile ? spLast - (ln - nA) * k : 2u * ln;
-      uint32_t pA = 0u, pB = 0u;
+      uint32_t pA = 0u, pB = 0u, tgA = 0u, tgB = 0u, s2A = 0u, s2B = 0u;
       SHK_STAMP(2);
-      bool hA = lx_hit_at(sA, true, pA);
+      bool hA = lx_hit_at(sA, true, pA, tgA, s2A);
       uint64_t HA = __ballot(hA);
       SHK_STAMP(3);
       if (HA) {
-        hA = hA && slot_valid(sA);   // (the slot has to exist and be a valid k-mer)
+        hA = hA && lx_confirm(tgA, s2A) && slot_valid(sA);   // (the entry's other bits; the slot has to exist and be a valid k-mer)
         HA = __ballot(hA);
       }
       if (HA && sp_one) {
@@ -65,11 +67,11 @@
       }
       SHK_STAMP(4);
       const uint32_t sB = ln < nA - 1u ? 2u * ln + 1u : ln + nA;
-      bool hB = lx_hit_at(sB, true, pB);
+      bool hB = lx_hit_at(sB, true, pB, tgB, s2B);
       uint64_t HB = __ballot(hB);
       SHK_STAMP(5);
       if (HB) {
-        hB = hB && slot_valid(sB);
+        hB = hB && lx_confirm(tgB, s2B) && slot_valid(sB);
         HB = __ballot(hB);
       }
       if (!(HA | HB) && spUb < thr_r) return 1;   // the bound cut: nothing of the prefix is in the filter
@@ -111,8 +113,9 @@
         }
       }
       // ... then the displaced slots, and on behind the cut's first stop as ever
-      uint32_t pF = 0u;
-      const bool hF = lx_hit_at(128u - T + ln, ln < T, pF) && slot_valid(ln < T ? 128u - T + ln : 0u);
+      uint32_t pF = 0u, tgF = 0u, s2F = 0u;
+      bool hF = lx_hit_at(128u - T + ln, ln < T, pF, tgF, s2F);
+      if (__ballot(hF)) hF = hF && lx_confirm(tgF, s2F) && slot_valid(ln < T ? 128u - T + ln : 0u);
       if (!sp_one && __ballot(hF & (pF == LTAB_ESC))) return 2;
       settle_round(1, vAB | (hF ? 4u : 0u));
       if (!sp_one) {

@@ -3,7 +3,10 @@
     // the slot ss of a staged pair (its two code streams at fwp / rvp) as a probe of the exact LDS table (LX): is its k-mer in the
     // filter?  payload = the gene of the matched entry's single-gene list, or the escape value.  (Not validated: the caller looks
     // at the slot when something matched.)
-    auto lx_probe = [&](const uint32_t *fwp, const uint32_t *rvp, const uint32_t ss, uint32_t &payload) -> bool {
+    // `sparse` (a constant; KX): the probe is one of a round in which a miss is the expected answer -- what comes back is then the
+    // CANDIDATE stage's answer (kmer_table.hpp) with `tag` and `s2` for the confirm stage, which the caller runs behind the ballot it
+    // takes over the round's hits anyway (lx_confirm); otherwise tag and s2 are not touched and the answer is final
+    auto lx_probe = [&](const uint32_t *fwp, const uint32_t *rvp, const uint32_t ss, uint32_t &payload, auto sparse, uint32_t &tag, uint32_t &s2) -> bool {
       const uint32_t q = rcap - k - ss;
       const uint32_t *f = fwp + (ss >> 4);
       const uint32_t *r = rvp + (q >> 4);
@@ -14,9 +17,14 @@
       const uint64_t y = ((uint64_t)__builtin_amdgcn_alignbit(e2, e1, ar) << 32) | __builtin_amdgcn_alignbit(e1, e0, ar);
       const uint64_t fwd = y & kmer_mask, rc = ~x & kmer_mask;
       if constexpr (KX) {
-        // the table keyed by the canonical k-mer itself (kmer_table.hpp): no XXH64; every entry is the one gene's (P.lx_gene), none escapes
+        // the table keyed by the canonical k-mer itself (kmer_table.hpp): no XXH64; every entry is the one gene's (P.lx_gene), none escapes.
+        // Where misses are expected every lane compares the tag's low 16 bits only; the entry's other two bits and the two guards are
+        // looked at when some lane of the wave passed that -- one probe stream in a thousand among reads from elsewhere, and every
+        // hit's.  The tiles' round, where nearly every probe is a hit, asks the whole rule at once
         payload = 0u;
-        return kxtab_lookup(reinterpret_cast<const uint8_t *>(lsum), P.lsum_shift, P.kx_m2, fwd < rc ? fwd : rc);
+        const uint8_t *img = reinterpret_cast<const uint8_t *>(lsum);
+        if constexpr (decltype(sparse)::value && !SHK_KX_ONE_STAGE) return kxtab_candidate(img, P.lsum_shift, P.kx_m2, fwd < rc ? fwd : rc, tag, s2);
+        else return kxtab_lookup(img, P.lsum_shift, P.kx_m2, fwd < rc ? fwd : rc);
       }
       const uint64_t h = xxh64_u64(fwd < rc ? fwd : rc);
       const uint32_t *T = lsum;
@@ -30,6 +38,11 @@
       payload = ee & LTAB_ESC;
       return (ee >> 13) == ((tg << 1) | 1u);
     };
+    // the confirm stage of a sparse-round candidate (true where lx_probe's answer was final already)
+    auto lx_confirm = [&](const uint32_t tag, const uint32_t s2) -> bool {
+      if constexpr (KX && !SHK_KX_ONE_STAGE) return kxtab_confirm(reinterpret_cast<const uint8_t *>(lsum), tag, s2);
+      else return true;
+    };
     // (TRI) does pair p of the triple hold an invalid character (N)?  -- its threshold is then lower than the plan's, and its slots need
     // their validity windows: per_pair's business
     bool inv3[3] = {false, false, false};
@@ -41,9 +54,9 @@
     uint32_t tf_done = 0u;
     if constexpr (TF) {
       if (tf_on) {
-        uint32_t pay;
+        uint32_t pay, tg_ = 0u, s2_ = 0u;
         const uint32_t *fwp = reinterpret_cast<const uint32_t *>(wbase + tf_area * WORDS);
-        bool hit = tf_want & lx_probe(fwp, fwp + code_dwords_for(S), tf_slot, pay);
+        bool hit = tf_want & lx_probe(fwp, fwp + code_dwords_for(S), tf_slot, pay, std::false_type{}, tg_, s2_);
         if (inv3[0] | inv3[1] | inv3[2] | (TRO && tro_short != 0u)) {   // (TRO: a tile behind a short mate's end is no k-mer of the pair; the staging marked those bases invalid)
           // a pair with invalid characters: a tile counts when its k characters are valid (slot_valid's window); the pair's threshold
           // is at most the plan's (fewer valid bases), so the plan's is the safe one to pass

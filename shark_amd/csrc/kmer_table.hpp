@@ -58,7 +58,8 @@ SHK_KX_FN void kxtab_mix(const uint64_t c, const uint32_t m1, const uint32_t m2,
   base = lo ^ ((tag * (m2 & 0xFFFFFFu)) >> 16);
 }
 
-// The lookup rule: is c (< 2^34) a key of the image?  The kernel, the builder's check and the host tool all go through this.
+// The lookup rule: is c (< 2^34) a key of the image?  The builder's check, the host tool and the tests go through this, and so do the
+// kernels where a hit is the expected answer (the tiles' round).
 // (Every read stays inside the image whatever c is: a slot number that does not exist reads T2's and D's bytes and is a miss.)
 SHK_KX_FN bool kxtab_lookup(const uint8_t *img, const uint32_t m1, const uint32_t m2, const uint64_t c)
 {
@@ -70,6 +71,30 @@ SHK_KX_FN bool kxtab_lookup(const uint8_t *img, const uint32_t m1, const uint32_
   const uint32_t t2 = img[KXTAB_T2_OFF + (s2 >> 3)];
   const uint32_t e = t16 | (((t2 >> (s2 & 6u)) & 3u) << 16);
   return (s2 < 2u * KXTAB_SLOTS) & (e == tag) & (tag != 0u);
+}
+
+// The same rule in two stages, for the kernels' probes of reads from elsewhere, where a miss is the expected answer: every lane runs
+// the first, the second runs behind a ballot that a wave of misses does not pass (classify_uni_tiles.inc).
+// THE CANDIDATE STAGE: mixing, D, the slot, T16, and the compare of the tag's low 16 bits -- a key of the image always passes it (all
+// 18 bits of its entry agree), and a value that is no key passes it about 2 in 100 000 times: an occupied slot of its group whose
+// entry differs in the bits 16 and 17 only, an empty slot under a tag whose low half is 0, a slot number that does not exist whose
+// two bytes (T2's or D's) happen to agree.  `tag` and `s2` (twice the slot number) are what the confirm stage needs.
+SHK_KX_FN bool kxtab_candidate(const uint8_t *img, const uint32_t m1, const uint32_t m2, const uint64_t c, uint32_t &tag, uint32_t &s2)
+{
+  uint32_t base;
+  kxtab_mix(c, m1, m2, tag, base);
+  const uint32_t d = *reinterpret_cast<const uint16_t *>(img + KXTAB_D_OFF + ((tag << 1) & ((2u << KXTAB_GROUP_LG) - 2u)));
+  s2 = ((base + d) << 1) & ((2u << KXTAB_RING_LG) - 2u);
+  const uint16_t t16 = *reinterpret_cast<const uint16_t *>(img + s2);
+  return t16 == (uint16_t)tag;
+}
+
+// THE CONFIRM STAGE, for a candidate: the entry's two high bits (T2), the slot number exists, the tag is not the empty entry's.
+// candidate && confirm == kxtab_lookup for every c.
+SHK_KX_FN bool kxtab_confirm(const uint8_t *img, const uint32_t tag, const uint32_t s2)
+{
+  const uint32_t t2 = img[KXTAB_T2_OFF + (s2 >> 3)];
+  return (s2 < 2u * KXTAB_SLOTS) & (((t2 >> (s2 & 6u)) & 3u) == (tag >> 16)) & (tag != 0u);
 }
 
 // The image (KXTAB_BYTES) for a sorted set of distinct keys and a pair of multipliers.  The displacement search tests 64

@@ -2,7 +2,9 @@
 // with the lookup rule the kernel uses, that every key is found, that M random 34-bit values are answered exactly as a std::set of
 // the keys answers them, and that the adversarial non-keys of every key are not found: the key with any one of its 34 bits
 // flipped, and the other values that share its slot before the displacement and its group (they differ in the tag's bits above the
-// group, land on the key's own slot and have to be told apart by the stored tag alone).
+// group, land on the key's own slot and have to be told apart by the stored tag alone).  `candidate_non_keys` counts the non-keys among
+// all these probes that pass the first of the lookup's two stages (kxtab_candidate: the tag's low 16 bits) and are turned down by the
+// second; `two_stage_diff` the probes, keys included, for which the two stages and the one-call rule disagree (none).
 // usage: shark-kxtab-check KIND N SEED [M [SHUFFLE]]   -> one JSON object
 //   KIND random: N distinct random 34-bit keys;  polya / repeat: the canonical 17-mers of N + 16 bases of poly-A / of an AC repeat
 //   with a substitution every few dozen bases (low complexity: few distinct keys, close to one another)
@@ -55,7 +57,15 @@ int main(int argc, char **argv)
   const auto t0 = std::chrono::steady_clock::now();
   const bool built = shk::kxtab_build(keys, img, &m1, &m2, &attempts);
   const double build_us = std::chrono::duration<double, std::micro>(std::chrono::steady_clock::now() - t0).count();
-  unsigned long long missing = 0, false_pos = 0, false_neg = 0, used = 0, flip_fp = 0, flip_probes = 0, slot_fp = 0, slot_probes = 0, hash = 1469598103934665603ull;
+  unsigned long long missing = 0, false_pos = 0, false_neg = 0, used = 0, flip_fp = 0, flip_probes = 0, slot_fp = 0, slot_probes = 0, cand_non_keys = 0, two_stage_diff = 0, hash = 1469598103934665603ull;
+  // (the two stages against the one-call rule, for every probe; a non-key: did it pass the candidate stage?)
+  auto lookup = [&](const uint64_t v, const bool is_key) -> bool {
+    uint32_t tag, s2;
+    const bool cand = shk::kxtab_candidate(img.data(), m1, m2, v, tag, s2), got = shk::kxtab_lookup(img.data(), m1, m2, v);
+    if (!is_key && cand) ++cand_non_keys;
+    if ((cand && shk::kxtab_confirm(img.data(), tag, s2)) != got) ++two_stage_diff;
+    return got;
+  };
   if (built) {
     for (uint32_t s = 0; s < shk::KXTAB_SLOTS; ++s) {
       uint16_t t16;
@@ -64,12 +74,12 @@ int main(int argc, char **argv)
     }
     for (const uint8_t b : img) hash = (hash ^ b) * 1099511628211ull;
     for (const uint64_t c : keys) {
-      if (!shk::kxtab_lookup(img.data(), m1, m2, c)) ++missing;
+      if (!lookup(c, true)) ++missing;
       for (uint32_t bit = 0; bit < shk::KXTAB_KEY_BITS; ++bit) {
         const uint64_t v = c ^ (1ull << bit);
         if (set.count(v)) continue;
         ++flip_probes;
-        flip_fp += shk::kxtab_lookup(img.data(), m1, m2, v);
+        flip_fp += lookup(v, false);
       }
       uint32_t tag, base;
       shk::kxtab_mix(c, m1, m2, tag, base);
@@ -77,20 +87,20 @@ int main(int argc, char **argv)
         const uint64_t v = unmix(tag ^ (h << shk::KXTAB_GROUP_LG), base, m1, m2);
         if (set.count(v)) continue;
         ++slot_probes;
-        slot_fp += shk::kxtab_lookup(img.data(), m1, m2, v);
+        slot_fp += lookup(v, false);
       }
     }
     for (uint64_t i = 0; i < m; ++i) {
       const uint64_t v = rng() & mask;
-      const bool got = shk::kxtab_lookup(img.data(), m1, m2, v), want = set.count(v) != 0;
+      const bool want = set.count(v) != 0, got = lookup(v, want);
       false_pos += got && !want;
       false_neg += !got && want;
     }
   }
   printf("{\"built\": %s, \"m1\": %u, \"m2\": %u, \"attempts\": %u, \"keys\": %zu, \"capacity\": %u, \"bytes\": %u, \"slots_used\": %llu, \"missing\": %llu, "
          "\"false_pos\": %llu, \"false_neg\": %llu, \"probes\": %llu, \"flip_false_pos\": %llu, \"flip_probes\": %llu, \"slot_false_pos\": %llu, "
-         "\"slot_probes\": %llu, \"image_hash\": \"%016llx\", \"build_us\": %.0f}\n",
+         "\"slot_probes\": %llu, \"candidate_non_keys\": %llu, \"two_stage_diff\": %llu, \"image_hash\": \"%016llx\", \"build_us\": %.0f}\n",
          built ? "true" : "false", m1, m2, attempts, keys.size(), shk::KXTAB_MAX_KEYS, shk::KXTAB_BYTES, used, missing, false_pos, false_neg,
-         (unsigned long long)m, flip_fp, flip_probes, slot_fp, slot_probes, built ? hash : 0ull, build_us);
+         (unsigned long long)m, flip_fp, flip_probes, slot_fp, slot_probes, cand_non_keys, two_stage_diff, built ? hash : 0ull, build_us);
   return 0;
 }

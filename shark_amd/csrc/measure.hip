@@ -11,6 +11,9 @@
 
 #include "kmer_device.hpp"
 #include "shark_internal.hpp"
+#ifndef SHK_KX_ONE_STAGE
+#define SHK_KX_ONE_STAGE 0   // (classify_uni.hpp: 1 = the one-call lookup on every lane; the mix below follows the kernel's form)
+#endif
 
 namespace shk {
 
@@ -103,14 +106,20 @@ __global__ __launch_bounds__(256) void valu_mix_kernel(const uint32_t iters, con
     uint32_t ti;
     bool hit;
     if constexpr (KX) {
-      // the k-mer keyed table's probe (kxtab_lookup: mixing, addresses, compare; its three LDS reads are not VALU work)
+      // the k-mer keyed table's probe as the kernel's fast path runs it (kxtab_candidate: mixing, addresses, the 16-bit compare; its two
+      // LDS reads are not VALU work; the confirm stage runs behind a ballot that a wave of misses does not pass)
       uint32_t tag, base;
       kxtab_mix(fwd < rc ? fwd : rc, 0x9E3779u | (iters << 24), 0x85EBCBu | (iters << 24), tag, base);
       const uint32_t dd = (((tag << 1) & ((2u << KXTAB_GROUP_LG) - 2u)) ^ d1) & 0xFFFFu;
       ti = ((base + dd) << 1) & ((2u << KXTAB_RING_LG) - 2u);
-      const uint32_t t16 = (ti ^ d2) & 0xFFFFu, t2 = ((ti >> 3) ^ d0) & 0xFFu;
+      const uint32_t t16 = (ti ^ d2) & 0xFFFFu;
+#if SHK_KX_ONE_STAGE
+      const uint32_t t2 = ((ti >> 3) ^ d0) & 0xFFu;
       const uint32_t e = t16 | (((t2 >> (ti & 6u)) & 3u) << 16);
       hit = (ti < 2u * KXTAB_SLOTS) & (e == tag) & (tag != 0u);
+#else
+      hit = (uint16_t)t16 == (uint16_t)tag;
+#endif
       h = ((uint64_t)tag << 32) | base;
     } else {
       h = xxh64_u64(fwd < rc ? fwd : rc);
