@@ -620,6 +620,79 @@ typedef struct shk_gene_variants { uint64_t observed, mismatches; uint32_t cover
 int shk_variants_get(shk_ctx *ctx, const shk_variant_params *p, shk_variant *out, uint64_t cap, uint64_t *n);
 int shk_variants_summary(shk_ctx *ctx, const shk_variant_params *p, shk_gene_variants *out, uint32_t n_genes);
 
+/* ---- alignments: each placed mate's gapped alignment to its gene's record -- the per-read product, the fourth consumer of segments mode ---- */
+/* Depth, the junction table, pileup and variants hand out aggregates; alignments mode hands out, per ASSOCIATION (read, gene g) and per
+ * mate, where the mate's bases lie on g's record: at most SHK_MAX_SEGMENTS gap-free BLOCKS, and how many of their bases agree with the
+ * record.  It rests on definitions this header already has, unchanged: mate, L, the -q mask, to_int, segment, record span [lo, hi), the
+ * KEPT SPANS of a mate at floor s_min, pileup's OWNERSHIP walk with `reach`, len_g, and the record's code r of shk_ref_keep_bases
+ * (0 .. 3, every other byte 4).  Everything below is per association and per mate.
+ *
+ * READ COORDINATE.  q = x - pos is the index of the read base under record coordinate x on the diagonal (strand, pos), counted in the
+ * record's orientation on either strand: on strand 0 the mate's byte q, on strand 1 its byte L - 1 - q, complemented (pileup's two
+ * index formulas read as one).  A block {x, q, len} says: read bases q .. q + len - 1 lie on record bases x .. x + len - 1.
+ *
+ * 1. PIECES.  Pileup's owned pieces [a_r, b_r) = [max(lo_r, reach), min(hi_r, len_g)) of the kept spans in sorted order, word for
+ *    word; empty ones are dropped.  They ascend and are disjoint in x.
+ * 2. TRIMMING.  Consecutive pieces can overlap in the READ (microhomology at a junction: overlap > 0).  Walk the pieces with a read
+ *    cursor c, 0 at first:  t = max(0, c - (a_r - pos_r)),  a' = a_r + t.  If a' >= b_r the piece yields no block (and c stays);
+ *    otherwise it yields the block {x = a', q = a' - pos_r, len = b_r - a'} and c = q + len.  The left side keeps the shared read
+ *    bases.  The blocks ascend and are disjoint in both x and q; the first piece always yields a block.
+ * 3. GAP CLOSURE.  Between consecutive blocks A and B let R = q_B - (q_A + len_A), the read bases neither explains, and
+ *    G = x_B - (x_A + len_A).  Closure applies iff 1 <= R <= 64 and G >= R (typically a substitution within k of a junction, which
+ *    silenced the windows over it).  For every split s in 0 .. R the read bases q_A + len_A + t with t < s go on A's diagonal, at
+ *    record x_A + len_A + t, and the remaining R - s on B's diagonal, at the record bases directly left of x_B (read base
+ *    q_A + len_A + t at x_B - R + t).  cost(s) = the number of those R bases that are NOT A MATCH (step 4).  Take the s of smallest
+ *    cost, ties to the LARGEST s; then  len_A += s;  x_B -= R - s;  q_B -= R - s;  len_B += R - s.  G >= R keeps the record
+ *    intervals disjoint and inside [0, len_g).  A gap consumes only its own bases, so the gaps are independent of each other.  Every
+ *    other gap stays open: R > 64, or G < R (an insertion in the read).
+ * 4. COUNTING, over the final blocks.  For the read byte's c = to_int[byte behind the -q mask] and the record's code r at a block base:
+ *    c == 0 or r == 4: neither a match nor a mismatch; otherwise b = c - 1 on strand 0 and 3 - (c - 1) on strand 1, and b == r is a
+ *    match, anything else a mismatch.  (For a split's cost a base that is neither counts as not a match.)
+ * 5. RECORD.  shk_mate_alignment, 64 bytes per mate, 128 per association, parallel to gene_ids: n_blocks, strand (rank 0's), matches,
+ *    mismatches, and the blocks in ascending order; unused blocks are zero.  A mate without a block -- no kept span: support below
+ *    s_min, a mate shorter than k, mate 2 of a single-end batch -- is all zero.
+ * Example (segments section; L = 100, k = 17): strand 1, spans [9653, 9727) at pos 9653 and [10912, 10943) at pos 10843.  Blocks
+ * {9653, 0, 74} and, trimmed by the overlap of 5, {10917, 74, 26}: R = 0, nothing is clipped, and the gap is G = 1190 record bases;
+ * at min_intron <= 1190 the text form is 74M1190N26M.
+ *
+ * What the mode does NOT do:
+ *   - the mate's ends outside its outermost blocks are not extended: they become soft clips, for spliced depth's reason (nothing
+ *     says on which side of an intron an overhang shorter than k lies);
+ *   - no pair-level claim is made: no proper-pair flag, no template length;
+ *   - there is no mapping quality.
+ *
+ * Independent of every other mode: gene_off, gene_ids, n_assoc, shk_last_kernel, shk_gene_counts and every other mode's records and
+ * state are the same with the mode on and off.  It reads segments_kernel's records at m = SHK_MAX_SEGMENTS as spliced depth, the
+ * junction table and pileup do (one launch of that kernel serves all four); align_kernel follows pileup_kernel in the batch's tail,
+ * from the final gene_off / gene_ids whichever path produced them (batches repaired in shk_classify_wait included).  With the mode
+ * off no launch and no allocation is added.  Integers only, no tolerance anywhere.  New: the reference has no counterpart. */
+typedef struct shk_mate_alignment {
+  uint32_t n_blocks, strand, matches, mismatches;
+  struct { uint32_t x, q, len; } block[4];     /* SHK_MAX_SEGMENTS of them */
+} shk_mate_alignment;                          /* 64 bytes */
+typedef struct shk_alignments {
+  uint64_t                  n_assoc;           /* = that result's n_assoc */
+  const shk_mate_alignment *entries;           /* n_assoc * 2: [j*2 + mate], j parallel to gene_ids */
+} shk_alignments;
+/* Switches alignments mode on with s_min = min_support (>= 1) or off (0) for the batches submitted AFTERWARDS, through any of the four
+ * families.  State rules are shk_pileup_enable's: switching on returns SHK_ERR_STATE before shk_ref_finalize, without
+ * shk_ref_keep_positions, on an index of more than 65 536 records; either way while tickets are outstanding.  Switching on also
+ * returns SHK_ERR_STATE on an index finalized without shk_ref_keep_bases.  New: no counterpart. */
+int shk_alignments_enable(shk_ctx *ctx, uint32_t min_support);
+/* The alignments of the batch whose result was handed out LAST, with shk_segments_last's rules: that result's lifetime and memory
+ * space (pinned host memory for host batches, DEVICE memory for resident ones).  SHK_ERR_STATE if that batch was submitted with
+ * the mode off, if its wait returned an error, behind shk_count_work, or if no batch has been waited for yet.  New: no counterpart. */
+int shk_alignments_last(const shk_ctx *ctx, shk_alignments *out);
+/* The text form of one record: its CIGAR string (NUL-terminated) into buf[0 .. cap) and the edit distance into *nm (nm may be NULL).
+ * A pure host function -- no context, no device -- and the single definition of the text form.  L: the mate's length in bytes.  Walk:
+ * q_0 as S; per block its len as M; between consecutive blocks R as I if R > 0, then G as N if G >= min_intron, else G as D if G > 0;
+ * finally L - (q + len) of the last block as S.  Operations of length 0 are left out, adjacent equal operations are merged.
+ *     *nm = mismatches + sum of R + sum of G over the gaps written as D.
+ * n_blocks == 0 gives "*" and nm 0.  SHK_ERR_ARG if buf is NULL or too small (the text and its NUL must fit), or if the record is
+ * inconsistent: more than 4 blocks, a block of length 0, blocks that do not ascend without overlap in x and in q, a block that ends
+ * behind L.  New: no counterpart. */
+int shk_alignment_cigar(const shk_mate_alignment *a, uint32_t L, uint32_t min_intron, char *buf, size_t cap, uint32_t *nm);
+
 /* Per-gene number of assigned reads accumulated over all classify calls (all
  * waited tickets) since the last reset (counts[g] for g in [0, 65536)); the quantity all-reduced
  * across GPUs.  n must be <= 65536. */

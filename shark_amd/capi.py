@@ -64,6 +64,17 @@ JUNCTION_DTYPE = np.dtype([("gene", np.uint32), ("donor", np.uint32), ("acceptor
 JUNCTIONS_DEFAULT_CAPACITY = 1 << 16
 
 
+class ShkAlignments(C.Structure):
+    _fields_ = [("n_assoc", C.c_uint64), ("entries", C.c_void_p)]
+
+
+# shk_mate_alignment as a numpy record (64 bytes): n_blocks, strand, matches, mismatches and four blocks {x, q, len}
+ALIGNMENT_DTYPE = np.dtype([("n_blocks", np.uint32), ("strand", np.uint32), ("matches", np.uint32), ("mismatches", np.uint32),
+                            ("block", np.uint32, (4, 3))])
+assert ALIGNMENT_DTYPE.itemsize == 64
+SAM_DEFAULT_MIN_INTRON = 20
+
+
 class ShkVariantParams(C.Structure):
     _fields_ = [("min_depth", C.c_uint32), ("min_alt", C.c_uint32), ("frac_num", C.c_uint32), ("frac_den", C.c_uint32)]
 
@@ -96,6 +107,7 @@ EXPORTS = [
     "shk_pileup_enable", "shk_pileup_get", "shk_pileup_get_all", "shk_pileup_mates", "shk_pileup_reset",
     "shk_pileup_add", "shk_ref_keep_bases", "shk_variants_get", "shk_variants_summary",
     "shk_ref_kmer_table",
+    "shk_alignments_enable", "shk_alignments_last", "shk_alignment_cigar",
 ]
 SHK_PIPE_DEPTH = 3
 SHK_DIST_ID_BYTES = 128
@@ -187,6 +199,9 @@ def load():
         "shk_ref_kmer_table": (C.c_int, [p, C.c_int]),
         "shk_variants_get": (C.c_int, [p, C.POINTER(ShkVariantParams), p, C.c_uint64, C.POINTER(C.c_uint64)]),
         "shk_variants_summary": (C.c_int, [p, C.POINTER(ShkVariantParams), p, C.c_uint32]),
+        "shk_alignments_enable": (C.c_int, [p, C.c_uint32]),
+        "shk_alignments_last": (C.c_int, [p, C.POINTER(ShkAlignments)]),
+        "shk_alignment_cigar": (C.c_int, [p, C.c_uint32, C.c_uint32, C.c_char_p, C.c_size_t, C.POINTER(C.c_uint32)]),
     }
     variant = bool(os.environ.get("SHK_LIB_PATH"))
     for name, (res, args) in later.items():
@@ -602,6 +617,28 @@ class SharkHip:
         a = np.ascontiguousarray(counts, dtype=np.uint32)
         self._check(self.L.shk_pileup_add(self.h, _ptr(a), a.size, int(mates), 0), "shk_pileup_add")
 
+    # ---- alignments: per association and mate the blocks of the mate on its gene's record -- segments mode's fourth consumer on the device --------
+    def alignments_enable(self, min_support=8):
+        """batches submitted from now on carry, per association and mate, the mate's gapped alignment to the gene's record (at most four
+        blocks from its kept spans at s_min = min_support, with match and mismatch counts); 0 switches the mode off; needs an index
+        built with keep_bases; refused while tickets are outstanding"""
+        self._check(self.L.shk_alignments_enable(self.h, int(min_support)), "shk_alignments_enable")
+
+    def alignments_last(self):
+        """alignments of the batch whose result was handed out last: an (n_assoc, 2) array of ALIGNMENT_DTYPE records, parallel to
+        gene_ids, copied from the context's pinned memory for a host batch (classify, wait); for a resident one (classify_device,
+        wait_device) (n_assoc, DEVICE pointer) of 64-byte records, two per association -- alignments_from_device reads them back.
+        Raises (SHK_ERR_STATE) when that batch was submitted with the mode off"""
+        al = ShkAlignments()
+        self._check(self.L.shk_alignments_last(self.h, C.byref(al)), "shk_alignments_last")
+        n = int(al.n_assoc)
+        if not self._last_on_host:
+            return n, al.entries
+        if n == 0:
+            return np.zeros((0, 2), dtype=ALIGNMENT_DTYPE)
+        raw = np.ctypeslib.as_array(C.cast(al.entries, C.POINTER(C.c_uint32)), shape=(n, 2, 16)).copy()
+        return alignments_from_raw(raw)
+
     # ---- variants: the record positions where the pileup shows another base than the record (needs an index built with keep_bases) --------
     def variants(self, min_depth=8, min_alt=3, frac=(1, 5)):
         """the sites of the pileup state at these thresholds (include/shark_hip.h, "variants"): a structured array (VARIANT_DTYPE: gene,
@@ -756,6 +793,34 @@ def segments_from_device(n_assoc, m, keys_ptr, entries_ptr):
         hip_memcpy_dtoh(keys, keys_ptr, keys.nbytes)
         hip_memcpy_dtoh(raw, entries_ptr, raw.nbytes)
     return keys, segments_from_raw(raw)
+
+
+def alignments_from_raw(raw):
+    """(n, 2, 16) uint32 words of shk_mate_alignment -> (n, 2) records of ALIGNMENT_DTYPE"""
+    raw = np.ascontiguousarray(raw, dtype=np.uint32).reshape(-1, 2, 16)
+    return raw.view(ALIGNMENT_DTYPE).reshape(-1, 2)
+
+
+def alignments_from_device(n_assoc, ptr):
+    """read the records of a resident batch back: (n_assoc, 2) records of ALIGNMENT_DTYPE as alignments_last gives them"""
+    raw = np.zeros((n_assoc, 2, 16), dtype=np.uint32)
+    if n_assoc:
+        hip_memcpy_dtoh(raw, ptr, raw.nbytes)
+    return alignments_from_raw(raw)
+
+
+def cigar(rec, L, min_intron=SAM_DEFAULT_MIN_INTRON):
+    """(CIGAR string, NM) of one ALIGNMENT_DTYPE record of a mate of L bytes: shk_alignment_cigar, the single definition of the text form
+    (a host function: no context, no device).  Raises ValueError for a record that is inconsistent with L"""
+    lib = load()
+    one = np.zeros(1, dtype=ALIGNMENT_DTYPE)
+    one[0] = rec
+    buf = C.create_string_buffer(256)
+    nm = C.c_uint32()
+    rc = lib.shk_alignment_cigar(_ptr(one), int(L), int(min_intron), buf, len(buf), C.byref(nm))
+    if rc != 0:
+        raise ValueError("shk_alignment_cigar: %s" % lib.shk_strerror(rc).decode())
+    return buf.value.decode(), int(nm.value)
 
 
 def segment_span(seg, L, k):

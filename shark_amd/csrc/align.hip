@@ -1,0 +1,265 @@
+// align.hip -- alignments mode's kernel (gfx950): per association and mate the gapped alignment of the mate to its gene's record as at most
+// four blocks, with its match and mismatch counts against the record (include/shark_hip.h, "alignments").  The fourth
+// consumer of segments mode on the device and the first reader of DeviceIndex::recbase inside a batch: it runs behind segments_kernel's
+// records at m = SHK_MAX_SEGMENTS and behind pileup_kernel in the batch's tail.
+//
+// pileup_kernel's outer shape: one wavefront per read with associations, persistent beyond 2 048 workgroups, its three early returns
+// and its guard for a read whose associations the buffers do not hold.  A mate's kept spans (kept_spans.hpp), the ownership walk with
+// `reach` and the trimming with the read cursor are wave-uniform: scalar work.  The blocks of a mate are never held as an array: the walk
+// keeps ONE open block A; when the next block B appears the gap between them is closed (both ends it can move are A's right and B's
+// left), A is final, is counted and goes into the lanes that will store it, and B becomes the open block.  The walk itself always reads
+// span 0 and moves the others down.  So no index into registers is ever a run-time value: no scratch memory.
+//
+// Closure of a gap of R <= 64 read bases: lane t < R loads its read byte and the record bases under it on A's and on B's diagonal, two
+// ballots give the not-a-match masks, lane s < R prices split s with two popcounts, split R (all on A) is priced by the wave, and one
+// wave minimum over cost << 7 | (64 - s) settles the split and the tie.  Counting: 64 block coordinates per pass, ballot and popcount
+// into scalar counters.  A mate's record is one aligned 64-byte line: lanes 0 .. 15 store one dword each.  No LDS.
+#include <hip/hip_runtime.h>
+
+#include <algorithm>
+
+#include "kept_spans.hpp"
+#include "placement_common.hpp"
+#include "shark_internal.hpp"
+
+namespace shk {
+
+static_assert(sizeof(shk_mate_alignment) == 64, "a mate's record is one 64-byte line");
+
+namespace {
+
+constexpr uint32_t AL_WORDS = sizeof(shk_mate_alignment) / 4;   // 16: one per storing lane
+constexpr uint32_t AL_MAX_CLOSE = 64;                           // the widest gap closure prices: one read base per lane
+
+struct AlignParams {
+  const uint32_t *gene_off;
+  const uint16_t *gene_ids;
+  const uint32_t *counters;
+  uint64_t n;                      // reads
+  const uint8_t *seq[2];           // nullptr: the batch has no such mate
+  const uint64_t *off[2];
+  const uint8_t *qual[2];          // nullptr: no masking
+  int32_t mq;
+  uint32_t k;
+  const shk_segment *entries;      // [(j * 2 + mate) * SHK_MAX_SEGMENTS + r]
+  const uint64_t *gene_start;
+  const uint8_t *recbase;          // [gene_start[g] + x]: 0 .. 3, every other byte 4
+  uint32_t n_genes;                // entries of gene_start - 1
+  uint32_t skip_if_long;
+  uint32_t s_min;
+  uint32_t n_waves;                // of the launch: a wave's step through the reads (a kernel argument costs no register between its uses)
+  uint32_t cap;                    // associations `entries` and `out` hold (at most 2^32 - 1: a batch has no more)
+  uint32_t *out;                   // [(j * 2 + mate) * AL_WORDS + w]
+};
+
+// one mate's bytes behind the -q mask, read in the record's orientation
+struct Mate {
+  const uint8_t *seq, *qual;
+  int32_t mq;
+  uint32_t L, strand;
+};
+
+// The read base of read coordinate q (the header's "read coordinate") on the record's strand: 0 .. 3, or 4 for a byte that is no base, a
+// masked one, and a q outside the mate (no block or gap holds one: the compare keeps a lane inside the mate whatever the records hold).
+__device__ __forceinline__ uint32_t read_base(const Mate &M, int32_t q)
+{
+  const uint32_t idx = M.strand ? M.L - 1u - (uint32_t)q : (uint32_t)q;
+  if (idx >= M.L) return 4u;
+  uint32_t ch = M.seq[idx];
+  if (M.qual && (int32_t)(int8_t)M.qual[idx] < M.mq) ch = (ch - 64u) & 0xFFu;
+  const uint32_t c = base_code(ch);
+  return c < 4u ? (M.strand ? 3u - c : c) : 4u;
+}
+
+// the record's code at x of a record of len_g bases that starts at rec (4 outside it: nothing reads there, as above)
+__device__ __forceinline__ uint32_t record_base(const uint8_t *__restrict__ rec, int32_t len_g, int32_t x)
+{
+  return (uint32_t)x < (uint32_t)len_g ? (uint32_t)rec[x] : 4u;
+}
+
+__device__ __forceinline__ uint32_t wave_min_u32(uint32_t v)
+{
+#pragma unroll
+  for (int o = 32; o >= 1; o >>= 1) {
+    const uint32_t t = (uint32_t)__shfl_xor((int)v, o, 64);
+    v = t < v ? t : v;
+  }
+  return v;
+}
+
+// The split of a gap of R read bases (1 <= R <= 64) that start at read coordinate q0, between a block that ends at record coordinate xa
+// and one that starts at xb: the number s of them that go on the left block's diagonal.  Smallest cost, ties to the largest s.
+__device__ __forceinline__ uint32_t close_gap(const Mate &M, const uint8_t *__restrict__ rec, int32_t len_g, int32_t q0, int32_t xa, int32_t xb, uint32_t R,
+                                              uint32_t lane)
+{
+  bool not_a = false, not_b = false;
+  if (lane < R) {
+    const uint32_t b = read_base(M, q0 + (int32_t)lane);
+    not_a = !(b < 4u && b == record_base(rec, len_g, xa + (int32_t)lane));
+    not_b = !(b < 4u && b == record_base(rec, len_g, xb - (int32_t)R + (int32_t)lane));
+  }
+  const uint64_t mask_a = __ballot(not_a), mask_b = __ballot(not_b);   // (bits R .. 63 are 0)
+  // split s = lane < R: the low s bits of A's mask and the bits from s on of B's (a shift by lane <= 63); split R: all of A's mask
+  uint32_t key = 0xFFFFFFFFu;
+  if (lane < R) key = ((uint32_t)(__popcll(mask_a & ((1ull << lane) - 1ull)) + __popcll(mask_b >> lane)) << 7) | (AL_MAX_CLOSE - lane);
+  const uint32_t key_r = ((uint32_t)__popcll(mask_a) << 7) | (AL_MAX_CLOSE - R);
+  const uint32_t best = std::min(wave_min_u32(key), key_r);
+  return __builtin_amdgcn_readfirstlane(AL_MAX_CLOSE - (best & 127u));
+}
+
+__global__ __launch_bounds__(PL_THREADS) void align_kernel(const AlignParams P)
+{
+  // the batch will be assembled again and comes through here again; or it will be refused in wait (pileup_kernel's rule)
+  if (P.counters[CTR_OVERFLOW] || (P.skip_if_long && P.counters[CTR_LONG]) || P.counters[CTR_VOUCH_BAD]) return;
+  const uint32_t lane = threadIdx.x & 63u;
+  const uint32_t wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);   // (the same in every lane: what follows from it is scalar)
+  // all ones in the lane that stores header word w, as vector values: the same as sixteen compares of the lane id against constants would
+  // be kept as 64-bit lane masks in scalar registers across every loop, which the scalar file has no room for.
+  // The record's layout over the lanes, lane w holding dword w (`word` below): lanes 0 .. 3 n_blocks, strand, matches, mismatches;
+  // lanes 4 + 3 b + {0, 1, 2} block b's x, q, len (b = 0 .. 3); so hdr[w] is 0xFFFFFFFF in lane w and 0 elsewhere, hdr_any is all
+  // ones in lanes 0 .. 3, and a finished block reaches its three lanes through `lane - (4 + 3 n_blocks)` being 0, 1 or 2.
+  uint32_t hdr[4];
+#pragma unroll
+  for (uint32_t w = 0; w < 4; ++w) hdr[w] = 0u - (((lane ^ w) - 1u) >> 31);   // (lane == w: 0 - 1 has the top bit)
+  const uint32_t hdr_any = hdr[0] | hdr[1] | hdr[2] | hdr[3];
+  for (uint64_t i = (uint64_t)blockIdx.x * PL_WAVES + wave; i < P.n; i += P.n_waves) {
+    const uint32_t o0 = P.gene_off[i], o1 = P.gene_off[i + 1];
+    if (o1 <= o0 || o1 > P.cap) continue;
+    for (uint32_t m = 0; m < 2; ++m) {
+      if (!P.seq[m]) continue;
+      // (a single-end batch: mate 2's records are all zero, and they lie behind mate 1's -- lanes 16 .. 31 store them with mate 1's)
+      const uint32_t n_store = m == 0u && !P.seq[1] ? 2u * AL_WORDS : AL_WORDS;
+      Mate M{};
+      const uint64_t a = P.off[m][i], len = P.off[m][i + 1] - a;
+      M.L = len > 0x7FFFFFFFull ? 0x7FFFFFFFu : (uint32_t)len;   // (segments_kernel's L)
+      M.seq = P.seq[m] + a;
+      M.qual = P.qual[m] ? P.qual[m] + a : nullptr;
+      M.mq = P.mq;
+      for (uint32_t j = o0; j < o1; ++j) {
+        const uint32_t g = P.gene_ids[j];
+        uint32_t word = 0;                        // this lane's dword of the record (lanes 0 .. 15)
+        uint32_t n_blocks = 0, matches = 0, mismatches = 0;
+        if (g < P.n_genes) {
+          const uint64_t start = P.gene_start[g];
+          const int32_t len_g = (int32_t)(P.gene_start[g + 1] - start);   // (a record has fewer than 2^31 bases: the placement table's bound)
+          const uint8_t *const rec = P.recbase + start;
+          const shk_segment *e = P.entries + ((uint64_t)j * 2u + m) * SHK_MAX_SEGMENTS;
+          M.strand = e[0].strand;   // (rank 0's: every kept span lies on it)
+          KeptSpans S = kept_spans(e, M.L, P.k, P.s_min);
+          int32_t reach = 0, cursor = 0;
+          int32_t ax = 0, aq = 0, al = 0;         // the open block (al == 0: none yet)
+          // One pass per kept span and a last one that only closes the open block.  The pass always reads span 0 and then moves the
+          // others down, so the loop needs no unrolling to keep its indices constant, and the code that finishes a block exists once.
+#pragma nounroll
+          for (uint32_t r = 0; r <= S.n; ++r) {
+            int32_t bx = 0, bq = 0, bl = 0;       // the block of this pass (bl == 0: none)
+            if (r < S.n) {
+              // pileup's owned piece
+              const int32_t lo = S.lo[0] > reach ? S.lo[0] : reach;
+              const int32_t hi = S.hi[0] < len_g ? S.hi[0] : len_g;
+              const int32_t pos = S.pos[0];
+              reach = S.hi[0] > reach ? S.hi[0] : reach;
+              S.lo[0] = S.lo[1]; S.lo[1] = S.lo[2]; S.lo[2] = S.lo[3];
+              S.hi[0] = S.hi[1]; S.hi[1] = S.hi[2]; S.hi[2] = S.hi[3];
+              S.pos[0] = S.pos[1]; S.pos[1] = S.pos[2]; S.pos[2] = S.pos[3];
+              // trimmed by the read bases the blocks before it have explained
+              const int32_t over = cursor - (lo - pos);
+              const int32_t from = lo + (over > 0 ? over : 0);
+              if (hi > lo && from < hi) {
+                bx = from; bq = from - pos; bl = hi - from;
+                cursor = bq + bl;
+              }
+              if (!bl) continue;
+            }
+            if (al) {
+              if (bl) {
+                const int32_t R = bq - (aq + al), G = bx - (ax + al);
+                if (R >= 1 && R <= (int32_t)AL_MAX_CLOSE && G >= R) {
+                  const int32_t s = (int32_t)close_gap(M, rec, len_g, aq + al, ax + al, bx, (uint32_t)R, lane);
+                  al += s;
+                  bx -= R - s; bq -= R - s; bl += R - s;
+                }
+              }
+              // A is final: counted over its bases, 64 per pass, and handed to the three lanes that store it
+              for (int32_t t0 = 0; t0 < al; t0 += 64) {
+                const int32_t t = t0 + (int32_t)lane;
+                bool is_m = false, is_x = false;
+                if (t < al) {
+                  const uint32_t b = read_base(M, aq + t), rb = record_base(rec, len_g, ax + t);
+                  is_m = b < 4u && b == rb;
+                  is_x = b < 4u && rb < 4u && b != rb;
+                }
+                matches += (uint32_t)__popcll(__ballot(is_m));
+                mismatches += (uint32_t)__popcll(__ballot(is_x));
+              }
+              const uint32_t w = lane - (4u + 3u * n_blocks);
+              word = w == 0u ? (uint32_t)ax : (w == 1u ? (uint32_t)aq : (w == 2u ? (uint32_t)al : word));
+              ++n_blocks;
+            }
+            ax = bx; aq = bq; al = bl;
+          }
+        }
+        if (n_blocks) {
+          word = (word & ~hdr_any) | (n_blocks & hdr[0]) | (M.strand & hdr[1]) | (matches & hdr[2]) | (mismatches & hdr[3]);
+        }
+        if (lane < n_store) P.out[((uint64_t)j * 2u + m) * AL_WORDS + lane] = word;
+      }
+    }
+  }
+}
+
+// publish_segments_kernel's copy for this mode's records: the associations the batch has, as far as both arrays hold them
+__global__ __launch_bounds__(256) void publish_alignments_kernel(const uint32_t *__restrict__ counters, const uint4 *__restrict__ src, uint4 *__restrict__ h_dst,
+                                                                 uint64_t h_cap)
+{
+  if (counters[CTR_OVERFLOW]) return;
+  const uint64_t total = ((uint64_t)counters[CTR_ASSOC_HI] << 32) | counters[CTR_ASSOC_LO];
+  const uint64_t n4 = (total < h_cap ? total : h_cap) * (2u * AL_WORDS / 4u);
+  const uint64_t tid = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x, nth = (uint64_t)gridDim.x * blockDim.x;
+  for (uint64_t i = tid; i < n4; i += nth) h_dst[i] = src[i];
+}
+
+}  // namespace
+
+int launch_alignments(Ctx *ctx, const Slot &s, const shk_segment *entries, uint64_t cap_assoc, bool skip_if_long, hipStream_t stream)
+{
+  const DeviceIndex &ix = ctx->idx;
+  if (!ix.gene_start || !ix.recbase || !entries || !s.align || !s.d_align) {
+    ctx->last_error = "alignments mode without its state";
+    return SHK_ERR_STATE;
+  }
+  if (s.n == 0) return SHK_OK;
+  AlignParams P{};
+  P.gene_off = s.d_gene_off;
+  P.gene_ids = s.d_gene_ids;
+  P.counters = s.d_counters;
+  P.n = s.n;
+  P.cap = (uint32_t)std::min<uint64_t>(std::min<uint64_t>(std::min<uint64_t>(s.cap_gene_ids, cap_assoc), s.cap_align / 2), 0xFFFFFFFFull);   // (launch_segments')
+  P.seq[0] = s.p.seq1; P.off[0] = s.p.off1; P.qual[0] = s.p.hasq ? s.p.qual1 : nullptr;
+  P.seq[1] = s.p.seq2; P.off[1] = s.p.off2; P.qual[1] = s.p.hasq ? s.p.qual2 : nullptr;
+  P.mq = s.p.mq;
+  P.k = s.p.k;
+  P.entries = entries;
+  P.gene_start = ix.gene_start;
+  P.recbase = ix.recbase;
+  P.n_genes = (uint32_t)(ctx->gene_start.size() - 1);
+  P.skip_if_long = skip_if_long ? 1u : 0u;
+  P.s_min = s.align;
+  P.out = reinterpret_cast<uint32_t *>(s.d_align);
+  // one wave per read up to 2 048 workgroups, persistent beyond (launch_segments' bound)
+  const unsigned blocks = (unsigned)std::min<uint64_t>((s.n + PL_WAVES - 1) / PL_WAVES, 2048);
+  P.n_waves = blocks * PL_WAVES;
+  hipLaunchKernelGGL(align_kernel, dim3(blocks), dim3(PL_THREADS), 0, stream, P);
+  const hipError_t e = hipGetLastError();
+  return e == hipSuccess ? SHK_OK : set_hip_error(ctx, e, "align_kernel");
+}
+
+int launch_publish_alignments(const Slot &s, uint64_t h_cap, hipStream_t stream)
+{
+  const uint64_t want = (h_cap * (2u * AL_WORDS / 4u) + 255) / 256;
+  hipLaunchKernelGGL(publish_alignments_kernel, dim3((unsigned)(want < 1 ? 1 : (want < 512 ? want : 512))), dim3(256), 0, stream, s.d_counters,
+                     reinterpret_cast<const uint4 *>(s.d_align), reinterpret_cast<uint4 *>(s.h_align), h_cap);
+  return hipGetLastError() == hipSuccess ? SHK_OK : SHK_ERR_HIP;
+}
+
+}  // namespace shk

@@ -117,6 +117,12 @@ const char *USAGE_MESSAGE =
     "          --variants-min-depth N        mates that must show a base at a site (default:8)\n"
     "          --variants-min-alt N          mates that must show the alternative base (default:3)\n"
     "          --variants-min-frac P/Q       the alternative base's share of those mates, at least P/Q (default:1/5; P <= Q <= 65535)\n"
+    "          --sam FILE                    write the gapped alignment of every placed mate to its gene's record as SAM: one line per\n"
+    "                                        association and mate with at least one block, in input order (header: @HD, one @SQ per gene;\n"
+    "                                        MAPQ 255, TLEN 0, NM:i: from the record's bases; the mate's ends outside its blocks are soft\n"
+    "                                        clips; the same refusals as --segments; combines with every other output)\n"
+    "          --sam-min-support N           unique k-mers a diagonal of a mate needs to become a block of --sam (default:8)\n"
+    "          --sam-min-intron N            record bases a gap between two blocks needs to be written as N, not D (default:20)\n"
     "          --kmer-table                  one gene, k <= 17: also build the exact table keyed by the k-mer itself (no XXH64 per probe; the\n"
     "                                        same output).  Costs tens of milliseconds when the index is built and pays on the GPU\n"
     "                                        alone, so it is off here, where the host and the link bound a run\n"
@@ -165,6 +171,10 @@ struct Options {
   std::string variants_path;
   FILE *variants_file = nullptr;   // (--variants, likewise; written once, after the last batch and after --pileup's file)
   unsigned variants_min_support = 8;
+  std::string sam_path;
+  FILE *sam_file = nullptr;        // (--sam, likewise; the header is written once the reference is read, the lines per batch)
+  unsigned sam_min_support = 8, sam_min_intron = 20;
+  bool sam_sub_flag_given = false;
   bool kmer_table = false;         // (--kmer-table: the one-gene index's table keyed by the k-mer, shk_ref_kmer_table; off here unless asked for)
   shk_variant_params variants_params{8, 3, 1, 5};   // (--variants-min-depth, -min-alt, -min-frac)
   bool variants_sub_flag_given = false;
@@ -320,6 +330,18 @@ const OptionRow OPTION_TABLE[] = {
        o.variants_params.frac_num = (uint32_t)num;
        o.variants_params.frac_den = (uint32_t)den;
      }},
+    {1024, "sam", true, [](Options &o, const char *v) { o.sam_path = value_of<std::string>(v); }},
+    {1025, "sam-min-support", true,
+     [](Options &o, const char *v) {
+       o.sam_min_support = value_of<unsigned>(v);
+       o.sam_sub_flag_given = true;
+       if (o.sam_min_support < 1) reject(USAGE_MESSAGE, "shark: --sam-min-support must be at least 1.");
+     }},
+    {1026, "sam-min-intron", true,
+     [](Options &o, const char *v) {
+       o.sam_min_intron = value_of<unsigned>(v);
+       o.sam_sub_flag_given = true;
+     }},
 };
 
 // Reads per device batch when --batch does not say.  A batch costs the device path 0.5-2 ms of launches, copies and bookkeeping
@@ -389,6 +411,7 @@ Options parse_arguments(int argc, char **argv)
   if (opt.variants_sub_flag_given && opt.variants_path.empty()) reject(USAGE_MESSAGE, "shark: --variants-min-support, --variants-min-depth, --variants-min-alt and --variants-min-frac need --variants FILE.");
   if (!opt.variants_path.empty() && !opt.pileup_path.empty() && opt.variants_min_support != opt.pileup_min_support)
     reject(USAGE_MESSAGE, "shark: --variants-min-support and --pileup-min-support must be equal (there is one pileup).");
+  if (opt.sam_sub_flag_given && opt.sam_path.empty()) reject(USAGE_MESSAGE, "shark: --sam-min-support and --sam-min-intron need --sam FILE.");
   if (opt.out1_path.empty()) opt.out1_path = "sharked_sample.1";
   if (opt.out2_path.empty() && !opt.sample2_path.empty()) opt.out2_path = "sharked_sample.2";
   // --devices alone says how many workers there are; with --gpus N it has to name N devices
@@ -522,6 +545,7 @@ struct ReadBatch {
   std::vector<uint32_t> seg_keys;                // (--segments, --junctions) two headers per association ...
   std::vector<shk_segment> seg_entries;          // ... and 2 x seg_m entries
   uint32_t seg_m = 0;
+  std::vector<shk_mate_alignment> alignments;    // (--sam) two records per association
   int rc = 0;
   void reset()
   {
@@ -531,6 +555,7 @@ struct ReadBatch {
     text.reset();
     gene_off.clear(); gene_ids.clear(); evidence.clear(); cand_reads.clear(); cand_entries.clear(); cand_m = 0; placements.clear();
     seg_keys.clear(); seg_entries.clear(); seg_m = 0;
+    alignments.clear();
     rc = 0;
   }
 };
@@ -975,8 +1000,8 @@ class GzCutter {
 // flight: the copies of the next batches overlap the kernels of the current one (shk_classify_submit / _wait).
 class ReadAnalyzer {
  public:
-  ReadAnalyzer(shk_ctx *ctx, bool need_qual, bool evidence, bool candidates = false, bool placements = false, bool segments = false)
-      : ctx_(ctx), need_qual_(need_qual), evidence_(evidence), candidates_(candidates), placements_(placements), segments_(segments) {}
+  ReadAnalyzer(shk_ctx *ctx, bool need_qual, bool evidence, bool candidates = false, bool placements = false, bool segments = false, bool alignments = false)
+      : ctx_(ctx), need_qual_(need_qual), evidence_(evidence), candidates_(candidates), placements_(placements), segments_(segments), alignments_(alignments) {}
   // false: the batch failed at once (b.rc is set) and is not in flight
   bool submit(std::unique_ptr<ReadBatch> b)
   {
@@ -1040,13 +1065,18 @@ class ReadAnalyzer {
           b->seg_entries.assign(sg.entries, sg.entries + 2 * sg.n_assoc * sg.m);
         }
       }
+      if (alignments_ && b->rc == SHK_OK) {
+        shk_alignments al{};
+        b->rc = shk_alignments_last(ctx_, &al);
+        if (b->rc == SHK_OK) b->alignments.assign(al.entries, al.entries + 2 * al.n_assoc);
+      }
     }
     return b;
   }
 
  private:
   shk_ctx *ctx_;
-  bool need_qual_, evidence_, candidates_, placements_, segments_;
+  bool need_qual_, evidence_, candidates_, placements_, segments_, alignments_;
   std::deque<std::pair<uint64_t, std::unique_ptr<ReadBatch>>> flying_;
   std::unique_ptr<ReadBatch> failed_;
 };
@@ -1159,13 +1189,14 @@ struct FormattedSegment {
   std::string cnd;                  // (--candidates) <id> <len> <n_genes> { <gene> <cov> <nk>} of every read of the segment
   std::string plc;                  // (--placements) <id> <gene> <strand> <pos> <support> [mate 2's three] of every association of the segment
   std::string sgm;                  // (--segments) <id> <gene> and per mate <n_keys> and m x <strand> <pos> <support> <first> <last>, per association
+  std::string sam;                  // (--sam) one SAM line per association and mate with a block
   std::vector<JunctionHit> jnc;     // (--junctions) the junctions of the segment's mates, added to the run's table when the segment is written
   std::string head1, head2;         // the first associated read's FASTQ records, printed unless its name equals the carried one
   std::string head_id, last_id;
   bool has_assoc = false, carries = false;
   void reset()
   {
-    ssv.clear(); fq1.clear(); fq2.clear(); evd.clear(); cnd.clear(); plc.clear(); sgm.clear(); jnc.clear(); head1.clear(); head2.clear(); head_id.clear(); last_id.clear();
+    ssv.clear(); fq1.clear(); fq2.clear(); evd.clear(); cnd.clear(); plc.clear(); sgm.clear(); sam.clear(); jnc.clear(); head1.clear(); head2.clear(); head_id.clear(); last_id.clear();
     has_assoc = carries = false;
   }
 };
@@ -1215,7 +1246,7 @@ class TextPool {
             st->free.pop_back();
           }
           for (FormattedSegment &sg : q->segs)
-            for (std::string *x : {&sg.ssv, &sg.fq1, &sg.fq2, &sg.evd, &sg.cnd, &sg.plc, &sg.sgm}) drop_pages(*x);
+            for (std::string *x : {&sg.ssv, &sg.fq1, &sg.fq2, &sg.evd, &sg.cnd, &sg.plc, &sg.sgm, &sg.sam}) drop_pages(*x);
           // (the object itself and its small strings are left to the process's end)
         }
       });
@@ -1254,14 +1285,17 @@ class TextPool {
 class ReadOutput {
  public:
   ReadOutput(OffsetWriter *out1, OffsetWriter *out2, const std::vector<std::string> &legend, FILE *evidence = nullptr, FILE *candidates = nullptr,
-             FILE *placements = nullptr, bool paired = false, FILE *segments = nullptr, bool junctions = false, uint32_t k = 0, uint32_t junctions_min_support = 8)
+             FILE *placements = nullptr, bool paired = false, FILE *segments = nullptr, bool junctions = false, uint32_t k = 0, uint32_t junctions_min_support = 8,
+             FILE *sam = nullptr, uint32_t sam_min_intron = 20)
       : out1_(out1), out2_(out2), legend_(legend), evidence_(evidence), candidates_(candidates), placements_(placements), paired_(paired),
-        every_read_(evidence || candidates), segments_(segments), junctions_(junctions), k_(k), s_min_(junctions_min_support) {}
+        every_read_(evidence || candidates), segments_(segments), junctions_(junctions), k_(k), s_min_(junctions_min_support),
+        sam_(sam), sam_min_intron_(sam_min_intron) {}
   bool failed() const { return failed_.load(); }
   bool evidence_write_failed() const { return failed_write_; }
   bool candidates_write_failed() const { return failed_write_cand_; }
   bool placements_write_failed() const { return failed_write_plc_; }
   bool segments_write_failed() const { return failed_write_sgm_; }
+  bool sam_write_failed() const { return failed_write_sam_; }
 
   // The junctions of one mate of L bytes from its m reported segments (include/shark_hip.h, "segments"): the segments with at least
   // s_min votes on rank 0's strand, sorted by their record span [lo, hi); every consecutive pair whose second diagonal lies further
@@ -1317,7 +1351,7 @@ class ReadOutput {
         const size_t n_assoc = b.gene_off[last] - b.gene_off[first];
         if (n_assoc * 10 > last - first || every_read_) {     // (--evidence and --candidates name every read)
           f1.load_dense(b.part1, first, last);
-          if (out2_) f2.load_dense(b.part2, first, last);
+          if (out2_ || (sam_ && paired_)) f2.load_dense(b.part2, first, last);
         } else {
           f1.unload();
           f2.unload();
@@ -1332,7 +1366,7 @@ class ReadOutput {
         const char *id;
         size_t id_len;
         if (b.lean) {
-          if (!f1.get(b.part1, i, v1) || (assoc && out2_ && !f2.get(b.part2, i, v2))) { failed_ = true; continue; }
+          if (!f1.get(b.part1, i, v1) || (assoc && (out2_ || (sam_ && paired_)) && !f2.get(b.part2, i, v2))) { failed_ = true; continue; }
           id = v1.id;
           id_len = v1.id_len;
         } else {
@@ -1370,6 +1404,7 @@ class ReadOutput {
         }
         if (!assoc) continue;
         if (placements_ && b.placements.size() != b.gene_ids.size()) failed_ = true;   // (a batch without a record per association: an error exit)
+        if (sam_ && b.alignments.size() != 2 * b.gene_ids.size()) failed_ = true;      // (likewise)
         const bool seg_mode = segments_ || junctions_;
         if (seg_mode && (b.seg_m == 0 || b.seg_keys.size() != 2 * b.gene_ids.size() || b.seg_entries.size() != 2 * b.gene_ids.size() * b.seg_m)) failed_ = true;   // (likewise)
         for (uint32_t j = b.gene_off[i]; j < b.gene_off[i + 1]; ++j) {
@@ -1408,6 +1443,20 @@ class ReadOutput {
             if (junctions_) {
               mate_junctions(e, b.seg_m, (int64_t)b.seq1.len(i), k_, s_min_, b.gene_ids[j], sg.jnc);
               if (i < b.seq2.size()) mate_junctions(e + b.seg_m, b.seg_m, (int64_t)b.seq2.len(i), k_, s_min_, b.gene_ids[j], sg.jnc);
+            }
+          }
+          if (sam_ && 2 * (size_t)(j + 1) <= b.alignments.size()) {
+            // (--sam) mate 1's line, then mate 2's; a lean batch's qualities come from the file again, as the FASTQ output's do
+            const shk_mate_alignment *al = b.alignments.data() + 2 * (size_t)j;
+            for (uint32_t t = 0; t < (paired_ ? 2u : 1u); ++t) {
+              if (al[t].n_blocks == 0) continue;
+              const DevStrings &seq = t ? b.seq2 : b.seq1, &qual = t ? b.qual2 : b.qual1;
+              const std::map<size_t, std::string> &odd = t ? b.qual_as_read2 : b.qual_as_read1;
+              if (i >= seq.size()) { failed_ = true; continue; }
+              const char *q = nullptr;      // (nullptr: no quality string of the sequence's length -- FASTA input)
+              if (b.lean) q = t ? v2.qual : v1.qual;
+              else if (i < qual.size() && qual.len(i) == seq.len(i) && odd.find(i) == odd.end()) q = qual.at(i);
+              if (!sam_line(sg.sam, id, id_len, gene, j > b.gene_off[i], paired_, t, al[t], al[1 - t], seq.at(i), seq.len(i), q, sam_min_intron_)) failed_ = true;
             }
           }
           sg.ssv.append(id, id_len);
@@ -1457,6 +1506,7 @@ class ReadOutput {
       if (candidates_ && fwrite(sg.cnd.data(), 1, sg.cnd.size(), candidates_) != sg.cnd.size()) failed_write_cand_ = true;
       if (placements_ && fwrite(sg.plc.data(), 1, sg.plc.size(), placements_) != sg.plc.size()) failed_write_plc_ = true;
       if (segments_ && fwrite(sg.sgm.data(), 1, sg.sgm.size(), segments_) != sg.sgm.size()) failed_write_sgm_ = true;
+      if (sam_ && fwrite(sg.sam.data(), 1, sg.sam.size(), sam_) != sg.sam.size()) failed_write_sam_ = true;
       for (const JunctionHit &h : sg.jnc) {
         auto it = junction_table_.emplace(std::make_tuple(h.gene, h.donor, h.acceptor), std::make_pair(h.intron, (uint64_t)0)).first;
         it->second.first = std::min(it->second.first, h.intron);
@@ -1477,6 +1527,63 @@ class ReadOutput {
   }
 
  private:
+  // One line of --sam (include/shark_hip.h, "alignments"): `a` is this mate's record, `other` the same association's
+  // other mate's.  CIGAR and NM are shk_alignment_cigar's; SEQ and QUAL are the mate's bytes in the record's orientation.
+  // false: the record does not fit a mate of L bytes (the library's answer is inconsistent: an error exit, never a wrong line).
+  static bool sam_line(std::string &f, const char *id, size_t id_len, const std::string &gene, bool secondary, bool paired, uint32_t t,
+                       const shk_mate_alignment &a, const shk_mate_alignment &other, const char *seq, size_t L, const char *qual, uint32_t min_intron)
+  {
+    // (at most 4 M, 3 I, 3 N or D and 2 S, ten decimal digits each)
+    char cigar[160], num[64];
+    uint32_t nm = 0;
+    if (shk_alignment_cigar(&a, (uint32_t)L, min_intron, cigar, sizeof(cigar), &nm) != SHK_OK) return false;
+    unsigned flag = secondary ? 0x100u : 0u;
+    if (a.strand) flag |= 0x10u;
+    const bool mate_has = paired && other.n_blocks != 0;
+    if (paired) {
+      flag |= 0x1u | (t == 0 ? 0x40u : 0x80u);
+      if (!mate_has) flag |= 0x8u;
+      else if (other.strand) flag |= 0x20u;
+    }
+    f.append(id, id_len);
+    int w = snprintf(num, sizeof(num), "\t%u\t", flag);
+    f.append(num, (size_t)w);
+    f.append(gene);
+    w = snprintf(num, sizeof(num), "\t%u\t255\t", a.block[0].x + 1);
+    f.append(num, (size_t)w);
+    f.append(cigar);
+    if (mate_has) w = snprintf(num, sizeof(num), "\t=\t%u\t0\t", other.block[0].x + 1);
+    else w = snprintf(num, sizeof(num), "\t*\t0\t0\t");
+    f.append(num, (size_t)w);
+    if (!a.strand) {
+      f.append(seq, L);
+    } else {
+      // reversed; A<->T and C<->G with the case kept, every other byte N
+      for (size_t p = L; p-- > 0;) {
+        char c;
+        switch (seq[p]) {
+          case 'A': c = 'T'; break;
+          case 'C': c = 'G'; break;
+          case 'G': c = 'C'; break;
+          case 'T': c = 'A'; break;
+          case 'a': c = 't'; break;
+          case 'c': c = 'g'; break;
+          case 'g': c = 'c'; break;
+          case 't': c = 'a'; break;
+          default: c = 'N';
+        }
+        f.push_back(c);
+      }
+    }
+    f.push_back('\t');
+    if (!qual) f.push_back('*');
+    else if (!a.strand) f.append(qual, L);
+    else
+      for (size_t p = L; p-- > 0;) f.push_back(qual[p]);
+    w = snprintf(num, sizeof(num), "\tNM:i:%u\n", nm);
+    f.append(num, (size_t)w);
+    return true;
+  }
   static void record_view(std::string &f, const shk::RecordFetcher::View &v)
   {
     f.push_back('@');
@@ -1509,8 +1616,10 @@ class ReadOutput {
   FILE *segments_;          // (--segments) likewise, one line per association
   bool junctions_;          // (--junctions) the mates' junctions are collected; write_junctions prints the table
   uint32_t k_, s_min_;      // (--junctions) the k-mer length and the support either side needs
+  FILE *sam_;               // (--sam) likewise, one line per association and mate with a block
+  uint32_t sam_min_intron_; // (--sam) the gap from which shk_alignment_cigar writes N
   std::map<std::tuple<uint32_t, int64_t, int64_t>, std::pair<int64_t, uint64_t>> junction_table_;   // (gene, donor, acceptor) -> intron, mates
-  bool failed_write_ = false, failed_write_cand_ = false, failed_write_plc_ = false, failed_write_sgm_ = false;
+  bool failed_write_ = false, failed_write_cand_ = false, failed_write_plc_ = false, failed_write_sgm_ = false, failed_write_sam_ = false;
   mutable std::atomic<bool> failed_{false};   // a record could not be read back from its file (I/O error)
   std::string carry_;   // previd at the end of the previous batch (only used when a batch starts mid-chunk)
 };
@@ -1948,6 +2057,7 @@ std::string build_index(const Options &opt, GpuStart &gpu, std::vector<std::stri
     if (gpu.rc != SHK_OK)
       return "shark: cannot create a context on GPU " + std::to_string(opt.devices[(size_t)gpu.bad]) + ": " + shk_strerror(gpu.rc);
     shk::FastxRecord rec;
+    std::string sam_header = "@HD\tVN:1.6\tSO:unsorted\n";       // (--sam) one @SQ per gene in id order, under --depth's names
     while (fa.read(rec) >= 0) {
       legend_ID.push_back(rec.name.c_str());
       if (opt.placements_file && legend_ID.size() > 65536) return "shark: --placements is not available for a reference of more than 65536 records (gene ids wrap there).";
@@ -1956,23 +2066,27 @@ std::string build_index(const Options &opt, GpuStart &gpu, std::vector<std::stri
       if (opt.junctions_file && legend_ID.size() > 65536) return "shark: --junctions is not available for a reference of more than 65536 records (gene ids wrap there).";
       if (opt.pileup_file && legend_ID.size() > 65536) return "shark: --pileup is not available for a reference of more than 65536 records (gene ids wrap there).";
       if (opt.variants_file && legend_ID.size() > 65536) return "shark: --variants is not available for a reference of more than 65536 records (gene ids wrap there).";
+      if (opt.sam_file && legend_ID.size() > 65536) return "shark: --sam is not available for a reference of more than 65536 records (gene ids wrap there).";
       const size_t len = strnlen(rec.seq.data(), rec.seq.size());  // C-string semantics (main.cpp:164)
+      if (opt.sam_file) sam_header += "@SQ\tSN:" + legend_ID.back() + "\tLN:" + std::to_string(len) + "\n";
       for (auto *ctx : gpu.ctxs) {
         const int rc = shk_ref_add(ctx, rec.seq.data(), len);
         if (rc != SHK_OK) return std::string("shark: ") + shk_strerror(rc);
       }
     }
+    if (opt.sam_file && fwrite(sam_header.data(), 1, sam_header.size(), opt.sam_file) != sam_header.size()) return "shark: cannot write the SAM file " + opt.sam_path;
   }
   pelapsed("Transcript file processed");
   timeline("reference read");
-  if (opt.placements_file || opt.depth_file || opt.segments_file || opt.junctions_file || opt.pileup_file || opt.variants_file)
+  if (opt.placements_file || opt.depth_file || opt.segments_file || opt.junctions_file || opt.pileup_file || opt.variants_file || opt.sam_file)
     for (auto *ctx : gpu.ctxs)
       if (const int rc = shk_ref_keep_positions(ctx)) return std::string("shark: ") + shk_strerror(rc);
   // (the k-mer keyed table repays its enumeration behind several hundred million pairs classified at the GPU's speed: not in a run of this command)
   for (auto *ctx : gpu.ctxs)
     if (const int rc = shk_ref_kmer_table(ctx, opt.kmer_table ? 1 : 0)) return std::string("shark: ") + shk_strerror(rc);
   // (--variants: the records' bases stay on the device; only worker 0 is asked for the sites, but every replica is built alike)
-  if (opt.variants_file)
+  // (--sam: every worker's alignments kernel reads them)
+  if (opt.variants_file || opt.sam_file)
     for (auto *ctx : gpu.ctxs)
       if (const int rc = shk_ref_keep_bases(ctx)) return std::string("shark: ") + shk_strerror(rc);
   {
@@ -2024,12 +2138,12 @@ void serial_feed(const Options &opt, const FeedPlan &plan, ParallelFeed &feed, B
 }
 
 // analyzers: one thread per worker, SHK_PIPE_DEPTH batches in flight each; t_gpu[g]: seconds inside shk_classify_submit / _wait
-std::vector<std::thread> start_analyzers(const std::vector<shk_ctx *> &ctxs, bool need_qual, bool evidence, bool candidates, bool placements, bool segments, BatchOrder &order, BatchOrder::Queue &to_format, std::vector<double> &t_gpu)
+std::vector<std::thread> start_analyzers(const std::vector<shk_ctx *> &ctxs, bool need_qual, bool evidence, bool candidates, bool placements, bool segments, bool alignments, BatchOrder &order, BatchOrder::Queue &to_format, std::vector<double> &t_gpu)
 {
   std::vector<std::thread> analyzers;
   for (int g = 0; g < (int)ctxs.size(); ++g) {
-    analyzers.emplace_back([&, g, need_qual, evidence, candidates, placements, segments] {
-      ReadAnalyzer ra(ctxs[(size_t)g], need_qual, evidence, candidates, placements, segments);
+    analyzers.emplace_back([&, g, need_qual, evidence, candidates, placements, segments, alignments] {
+      ReadAnalyzer ra(ctxs[(size_t)g], need_qual, evidence, candidates, placements, segments, alignments);
       BatchOrder::Queue &todo = order.input(g);
       bool open = true;
       while (open || ra.in_flight()) {
@@ -2085,7 +2199,7 @@ int run_sample(const Options &opt, GpuStart &gpu, BatchPool &pool, std::vector<s
   if (opt.paired_flag && opt.out2_path != "") w2.open(opt.out2_path, write_helpers);
   OffsetWriter *out1 = w1.is_open() ? &w1 : nullptr, *out2 = w2.is_open() ? &w2 : nullptr;
   ReadOutput ro(out1, out2, legend_ID, opt.evidence_file, opt.candidates_file, opt.placements_file, opt.paired_flag, opt.segments_file,
-                opt.junctions_file != nullptr && !opt.junctions_device, opt.k, opt.junctions_min_support);
+                opt.junctions_file != nullptr && !opt.junctions_device, opt.k, opt.junctions_min_support, opt.sam_file, opt.sam_min_intron);
   setvbuf(stdout, nullptr, _IOFBF, 1 << 22);
 
   FeedPlan plan(opt, io_threads, need_qual);
@@ -2155,6 +2269,14 @@ int run_sample(const Options &opt, GpuStart &gpu, BatchPool &pool, std::vector<s
         std::cerr << "shark: pileup mode could not be switched on: " << shk_strerror(rc) << " " << shk_last_error(ctx) << std::endl;
         return EXIT_FAILURE;
       }
+  // (--sam: every worker's batches carry their mates' alignments)
+  if (opt.sam_file)
+    for (shk_ctx *ctx : gpu.ctxs)
+      if (const int rc = shk_alignments_enable(ctx, opt.sam_min_support)) {
+        feed.stop();
+        std::cerr << "shark: alignments mode could not be switched on: " << shk_strerror(rc) << " " << shk_last_error(ctx) << std::endl;
+        return EXIT_FAILURE;
+      }
   std::unique_ptr<BatchSplitter> fs;
   bool serial_failed = false;
   std::thread splitter([&] { serial_feed(opt, plan, feed, order, pool, fs, serial_failed); });
@@ -2182,7 +2304,7 @@ int run_sample(const Options &opt, GpuStart &gpu, BatchPool &pool, std::vector<s
     });
   }
   std::vector<std::thread> analyzers = start_analyzers(gpu.ctxs, need_qual, opt.evidence_file != nullptr, opt.candidates_file != nullptr, opt.placements_file != nullptr,
-                                                        opt.segments_file != nullptr || host_junctions, order, to_format, t_gpu);
+                                                        opt.segments_file != nullptr || host_junctions, opt.sam_file != nullptr, order, to_format, t_gpu);
   // ordered drain
   int failed = 0;
   double t_out = 0;
@@ -2229,6 +2351,7 @@ int run_sample(const Options &opt, GpuStart &gpu, BatchPool &pool, std::vector<s
   const bool candidates_written = !opt.candidates_file || (fclose(opt.candidates_file) == 0 && !ro.candidates_write_failed());
   const bool placements_written = !opt.placements_file || (fclose(opt.placements_file) == 0 && !ro.placements_write_failed());
   const bool segments_written = !opt.segments_file || (fclose(opt.segments_file) == 0 && !ro.segments_write_failed());
+  const bool sam_written = !opt.sam_file || (fclose(opt.sam_file) == 0 && !ro.sam_write_failed());
   bool junctions_written = true;
   if (host_junctions) {      // (--junctions-device: written by main() from the workers' tables, as --depth is)
     junctions_written = ro.write_junctions(opt.junctions_file);
@@ -2261,6 +2384,10 @@ int run_sample(const Options &opt, GpuStart &gpu, BatchPool &pool, std::vector<s
   }
   if (!junctions_written) {
     std::cerr << "shark: cannot write the junctions file " << opt.junctions_path << std::endl;
+    return EXIT_FAILURE;
+  }
+  if (!sam_written) {
+    std::cerr << "shark: cannot write the SAM file " << opt.sam_path << std::endl;
     return EXIT_FAILURE;
   }
   if (failed) {
@@ -2516,6 +2643,7 @@ int main(int argc, char *argv[])
   if (opt_parsed.junctions_path != "" && samples_can_be_opened(opt_parsed, false)) opt_parsed.junctions_file = fopen(opt_parsed.junctions_path.c_str(), "w");   // (--junctions: likewise)
   if (opt_parsed.pileup_path != "" && samples_can_be_opened(opt_parsed, false)) opt_parsed.pileup_file = fopen(opt_parsed.pileup_path.c_str(), "w");   // (--pileup: likewise)
   if (opt_parsed.variants_path != "" && samples_can_be_opened(opt_parsed, false)) opt_parsed.variants_file = fopen(opt_parsed.variants_path.c_str(), "w");   // (--variants: likewise)
+  if (opt_parsed.sam_path != "" && samples_can_be_opened(opt_parsed, false)) opt_parsed.sam_file = fopen(opt_parsed.sam_path.c_str(), "w");   // (--sam: likewise)
   const Options opt = opt_parsed;
   if (opt.verbose) timeline.on();
   timeline("arguments parsed");
@@ -2560,6 +2688,10 @@ int main(int argc, char *argv[])
   }
   if (opt.variants_path != "" && !opt.variants_file) {
     std::cerr << "shark: cannot open the variants file " << opt.variants_path << std::endl;
+    return EXIT_FAILURE;
+  }
+  if (opt.sam_path != "" && !opt.sam_file) {
+    std::cerr << "shark: cannot open the SAM file " << opt.sam_path << std::endl;
     return EXIT_FAILURE;
   }
 

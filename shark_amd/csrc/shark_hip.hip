@@ -118,6 +118,8 @@ static void slot_free(Slot &s)
   if (s.h_place) (void)hipHostFree(s.h_place);
   hipFree(s.d_seg_keys); hipFree(s.d_seg_entries);
   hipFree(s.d_sp_keys); hipFree(s.d_sp_entries);
+  hipFree(s.d_align);
+  if (s.h_align) (void)hipHostFree(s.h_align);
   if (s.h_seg_keys) (void)hipHostFree(s.h_seg_keys);
   if (s.h_seg_entries) (void)hipHostFree(s.h_seg_entries);
   if (s.h_cand_reads) (void)hipHostFree(s.h_cand_reads);
@@ -315,8 +317,9 @@ static int enqueue_tail(Ctx *ctx, Slot &s, bool skip_hist_if_long, bool count_ge
   }
   // (spliced depth, the junction table: behind segments_kernel's records at m = SHK_MAX_SEGMENTS -- segments mode's own where it runs at that
   //  m, else a launch of that kernel into arrays nobody else sees --, under depth_accumulate_kernel's rule for a batch that comes through
-  //  here again; pileup mode: the third reader of the same records, its own kernel behind theirs)
-  if (s.sp_depth || s.sp_junc || s.pileup) {
+  //  here again; pileup mode: the third reader of the same records, its own kernel behind theirs; alignments mode: the fourth, behind pileup's,
+  //  and the one with records of its own per association, handed out as segments mode's are)
+  if (s.sp_depth || s.sp_junc || s.pileup || s.align) {
     const shk_segment *entries = s.d_seg_entries;
     uint64_t cap_assoc = segments_cap(s);
     if (s.seg_m != SHK_MAX_SEGMENTS) {
@@ -328,6 +331,14 @@ static int enqueue_tail(Ctx *ctx, Slot &s, bool skip_hist_if_long, bool count_ge
     }
     if ((s.sp_depth || s.sp_junc) && (rc = launch_spliced_accumulate(ctx, s, entries, cap_assoc, skip_hist_if_long, st))) return rc;
     if (s.pileup && (rc = launch_pileup(ctx, s, entries, cap_assoc, skip_hist_if_long, st))) return rc;
+    if (s.align) {
+      if ((rc = ensure_capacity(ctx, &s.d_align, &s.cap_align, 2 * s.cap_gene_ids))) return rc;
+      if ((rc = launch_alignments(ctx, s, entries, cap_assoc, skip_hist_if_long, st))) return rc;
+      if (s.host_batch) {
+        if ((rc = ensure_pinned(ctx, &s.h_align, &s.cap_h_align, 2 * s.cap_gene_ids))) return rc;
+        if ((rc = launch_publish_alignments(s, std::min<uint64_t>(std::min<uint64_t>(s.cap_h_align, s.cap_align) / 2, cap_assoc), st))) return rc;
+      }
+    }
   }
   SHK_HIP(ctx, hipEventRecord(s.ev_done, st));
   return SHK_OK;
@@ -373,6 +384,7 @@ static int enqueue_classify(Ctx *ctx, Slot &s, const shk_batch *b, uint32_t max_
   s.sp_depth = count_genes && ctx->depth_spliced ? ctx->depth : 0u;
   s.sp_junc = count_genes ? ctx->junc : 0u;
   s.pileup = count_genes ? ctx->pileup : 0u;
+  s.align = ctx->align;
   if (s.depth || s.sp_depth) ctx->depth_dirty = true;
   if (s.sp_junc) ctx->junc_dirty = true;
   if ((rc = slot_reserve(ctx, s, n))) return rc;
@@ -563,6 +575,7 @@ static int classify_resident(Ctx *ctx, const shk_batch *b, uint32_t max_read_len
   ctx->last_cand_valid = false;
   ctx->last_place_valid = false;
   ctx->last_seg_valid = false;
+  ctx->last_align_valid = false;
   if (n >= 0xFFFFFFFFull) { ctx->last_error = "batch too large (n must be < 2^32-1)"; return SHK_ERR_ARG; }
   const bool paired = b->seq2 != nullptr;
   const uint32_t max_slots = max_read_len ? slots_for_len(max_read_len, ctx->prm.k, paired) : 0;
@@ -626,6 +639,9 @@ static int classify_resident(Ctx *ctx, const shk_batch *b, uint32_t max_read_len
   ctx->last_seg_keys = s.d_seg_keys;
   ctx->last_seg_entries = s.d_seg_entries;
   ctx->last_seg_n = n_assoc;
+  ctx->last_align_valid = s.align != 0 && wc == nullptr;
+  ctx->last_align = s.d_align;
+  ctx->last_align_n = n_assoc;
   return SHK_OK;
 }
 
@@ -1144,6 +1160,7 @@ int shk_classify_wait(shk_ctx *ctx, uint64_t ticket, shk_result *result)
   ctx->last_cand_valid = false;
   ctx->last_place_valid = false;
   ctx->last_seg_valid = false;
+  ctx->last_align_valid = false;
   SHK_HIP(ctx, hipEventSynchronize(s.ev_done));
   bool redone = false;
   int rc = finish_classify(ctx, s, s.long_speculative, true, &redone);
@@ -1184,6 +1201,10 @@ int shk_classify_wait(shk_ctx *ctx, uint64_t ticket, shk_result *result)
   ctx->last_seg_keys = s.host_batch ? s.h_seg_keys : s.d_seg_keys;
   ctx->last_seg_entries = s.host_batch ? s.h_seg_entries : s.d_seg_entries;
   ctx->last_seg_n = n_assoc;
+  if (s.align && s.host_batch && n_assoc > s.cap_h_align / 2) { ctx->last_error = "alignments publication failed"; return SHK_ERR_HIP; }
+  ctx->last_align_valid = s.align != 0;
+  ctx->last_align = s.host_batch ? s.h_align : s.d_align;
+  ctx->last_align_n = n_assoc;
   return SHK_OK;
 }
 
@@ -1658,6 +1679,80 @@ int shk_variants_summary(shk_ctx *ctx, const shk_variant_params *p, shk_gene_var
   if (const int rc = launch_variants_summary(ctx, *p)) return rc;
   SHK_HIP(ctx, hipMemcpyAsync(out, ctx->d_var_summary, (size_t)n_genes * sizeof(shk_gene_variants), hipMemcpyDeviceToHost, ctx->stream));
   SHK_HIP(ctx, hipStreamSynchronize(ctx->stream));
+  return SHK_OK;
+}
+
+// ---- alignments mode (align.hip): per-batch records, handed out as segments mode's are ----
+int shk_alignments_enable(shk_ctx *ctx, uint32_t min_support)
+{
+  if (!ctx) return SHK_ERR_ARG;
+  if (tickets_outstanding(ctx)) { ctx->last_error = "shk_alignments_enable: tickets are outstanding (wait for them first)"; return SHK_ERR_STATE; }
+  if (min_support) {
+    if (ctx->mode != 2) { ctx->last_error = "shk_alignments_enable: the index is not finalized"; return SHK_ERR_STATE; }
+    if (!ctx->idx.ptab_lg) { ctx->last_error = "shk_alignments_enable: the index was finalized without shk_ref_keep_positions"; return SHK_ERR_STATE; }
+    if (ctx->n_records > 65536 || ctx->idx.wrap || !ctx->idx.gene_start) { ctx->last_error = "shk_alignments_enable: more than 65 536 records (gene ids wrap)"; return SHK_ERR_STATE; }
+    if (!ctx->idx.recbase) { ctx->last_error = "shk_alignments_enable: the index was finalized without shk_ref_keep_bases"; return SHK_ERR_STATE; }
+  }
+  ctx->align = min_support;
+  return SHK_OK;
+}
+
+int shk_alignments_last(const shk_ctx *ctx, shk_alignments *out)
+{
+  if (!ctx || !out) return SHK_ERR_ARG;
+  if (!ctx->last_align_valid) return SHK_ERR_STATE;
+  out->n_assoc = ctx->last_align_n;
+  out->entries = ctx->last_align;
+  return SHK_OK;
+}
+
+// the text form of one record (the header's walk): host code only
+int shk_alignment_cigar(const shk_mate_alignment *a, uint32_t L, uint32_t min_intron, char *buf, size_t cap, uint32_t *nm)
+{
+  if (!a || !buf) return SHK_ERR_ARG;
+  if (a->n_blocks == 0) {
+    if (cap < 2) return SHK_ERR_ARG;
+    buf[0] = '*'; buf[1] = 0;
+    if (nm) *nm = 0;
+    return SHK_OK;
+  }
+  if (a->n_blocks > SHK_MAX_SEGMENTS) return SHK_ERR_ARG;
+  // the operations, merged as they come: at most S + 4 M + 3 (I, N or D) + S
+  uint64_t len[2 + 3 * SHK_MAX_SEGMENTS];
+  char op[2 + 3 * SHK_MAX_SEGMENTS];
+  int n_ops = 0;
+  auto push = [&](char o, uint64_t l) {
+    if (!l) return;
+    if (n_ops && op[n_ops - 1] == o) { len[n_ops - 1] += l; return; }
+    op[n_ops] = o; len[n_ops] = l; ++n_ops;
+  };
+  uint64_t edits = a->mismatches, q_end = 0, x_end = 0;
+  for (uint32_t r = 0; r < a->n_blocks; ++r) {
+    const uint64_t x = a->block[r].x, q = a->block[r].q, l = a->block[r].len;
+    if (!l || q + l > L) return SHK_ERR_ARG;
+    if (r == 0) push('S', q);
+    else {
+      if (q < q_end || x < x_end) return SHK_ERR_ARG;
+      const uint64_t R = q - q_end, G = x - x_end;
+      push('I', R);
+      edits += R;
+      if (G >= min_intron) push('N', G);
+      else { push('D', G); edits += G; }
+    }
+    push('M', l);
+    q_end = q + l; x_end = x + l;
+  }
+  push('S', L - q_end);
+  size_t at = 0;
+  for (int o = 0; o < n_ops; ++o) {
+    char t[24];
+    const int w = snprintf(t, sizeof(t), "%llu%c", (unsigned long long)len[o], op[o]);
+    if (at + (size_t)w + 1 > cap) return SHK_ERR_ARG;
+    memcpy(buf + at, t, (size_t)w);
+    at += (size_t)w;
+  }
+  buf[at] = 0;
+  if (nm) *nm = (uint32_t)edits;
   return SHK_OK;
 }
 

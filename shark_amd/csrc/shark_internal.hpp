@@ -361,6 +361,12 @@ struct Slot {
   // pileup mode (pileup.hip): submitted with this floor (0: not).  The third reader of those records at m = SHK_MAX_SEGMENTS, from the same
   // arrays: segments mode's own at that m, else d_sp_*, which are filled when ANY of spliced depth, the junction table and pileup is on
   uint32_t pileup = 0;
+  // alignments mode (align.hip): submitted with this floor (0: not).  The fourth reader of those records, and the one whose result is per
+  // association: two 64-byte records each (d_align, allocated with the first such batch for as many associations as d_gene_ids holds;
+  // cap_align, cap_h_align count mates' records)
+  uint32_t align = 0;
+  shk_mate_alignment *d_align = nullptr; size_t cap_align = 0;
+  shk_mate_alignment *h_align = nullptr; size_t cap_h_align = 0;   // (host batches; filled by publish_alignments_kernel)
 };
 
 struct Ctx;
@@ -396,6 +402,10 @@ int launch_depth_accumulate(Ctx *ctx, const Slot &s, bool skip_if_long, hipStrea
 int launch_spliced_accumulate(Ctx *ctx, const Slot &s, const shk_segment *entries, uint64_t cap_assoc, bool skip_if_long, hipStream_t stream);
 // pileup.hip: the batch in `s` from the same records into Ctx::d_pileup at floor s.pileup, behind segments_kernel; skip_if_long: as launch_gene_hist
 int launch_pileup(Ctx *ctx, const Slot &s, const shk_segment *entries, uint64_t cap_assoc, bool skip_if_long, hipStream_t stream);
+// align.hip: per association of the batch in `s` and per mate its blocks on the gene's record with their match and mismatch counts, from the
+// same records and DeviceIndex::recbase into s.d_align at floor s.align, behind segments_kernel; skip_if_long: as launch_gene_hist
+int launch_alignments(Ctx *ctx, const Slot &s, const shk_segment *entries, uint64_t cap_assoc, bool skip_if_long, hipStream_t stream);
+int launch_publish_alignments(const Slot &s, uint64_t h_cap, hipStream_t stream);   // h_cap: associations the pinned array (and the device's) holds
 // variants.hip: d_pileup[i] += d_add[i] over n_entries counters (d_add 16-byte aligned: SHK_ERR_ARG otherwise), *d_pileup_mates += mates, on ctx->stream
 int launch_pileup_add(Ctx *ctx, const uint32_t *d_add, uint64_t n_entries, uint64_t mates);
 // variants.hip: the sites of the pileup state against DeviceIndex::recbase: their number into *n_sites (host; the stream is drained) and, with
@@ -537,6 +547,11 @@ struct Ctx {
   uint64_t *d_var_temp = nullptr;              // exclusive_scan_u32's temp over d_var_waves (allocated with it)
   shk_variant *d_var_out = nullptr;   size_t cap_var_out = 0;   // records
   shk_gene_variants *d_var_summary = nullptr;  // nidx records
+  // alignments mode (shk_alignments_enable; align.hip), as segments mode: the floor for the batches submitted from now on (0: off)
+  uint32_t align = 0;
+  bool last_align_valid = false;
+  const shk_mate_alignment *last_align = nullptr;
+  uint64_t last_align_n = 0;
 
   // timing
   bool timing = false;
