@@ -581,8 +581,15 @@ __global__ __launch_bounds__((UniGeom<U, MODE, LSL>::THREADS), (UniGeom<U, MODE,
     if (cutE < (uint32_t)U || JA_ROUNDS < U) {
       // the plan assumed len = L1 + L2; a read with invalid characters (N, masked qualities) has a lower threshold
       if (any_inv) {
-        const uint32_t len = wave_sum_u32(lane_valid_bases());
-        thr_r = cov_threshold(P.c, len);
+        // (three pairs, uniform batch: no chunk of the pair with two of them -- the pair's share of inv_any counts them, and the wave's
+        //  table has the threshold of that count; else, and everywhere else, the reduction over the validity bytes)
+        const uint64_t pm = (1ull << tri_lp) - 1ull;
+        if (THRTAB && ((inv_two >> (tp * tri_lp)) & pm) == 0ull) {
+          thr_r = (uint32_t)__builtin_amdgcn_readlane((int)thr_tab, (int)__builtin_popcountll((inv_any >> (tp * tri_lp)) & pm));
+        } else {
+          const uint32_t len = wave_sum_u32(lane_valid_bases());
+          thr_r = cov_threshold(P.c, len);
+        }
       }
     }
 

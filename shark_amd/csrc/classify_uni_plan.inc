@@ -77,6 +77,13 @@
     if (ub < thr_full) { cutE = (uint32_t)CutPlan<U>::E0; cutUb = ub; }
   };
   if (UNI) plan_cut(L1, L2);
+  // (three pairs, uniform batch) the thresholds of the batch's pairs, lane i's = that of a pair with i invalid characters: len is
+  // L1 + L2 - i, and a pair's count is a popcount of a ballot share when none of its chunks holds two (the tiles' fragment) -- so the
+  // double arithmetic of cov_threshold runs once per wave, here, and a pair reads its threshold with one v_readlane.  The same
+  // function of the same len: entry by entry what per_pair's reduction gives.  (The offsets form has a pair's own lengths: tro_thr)
+  constexpr bool THRTAB = TRI && !TRO;
+  uint32_t thr_tab = 0u;
+  if constexpr (THRTAB) thr_tab = cov_threshold(P.c, L1 + L2 > (uint32_t)lane ? L1 + L2 - (uint32_t)lane : 0u);
   // ---- the sparse first round (one-gene index in LDS; DESIGN.md 3).  With ONE gene in the index nothing competes: a read is that
   // gene's iff the bases covered by its k-mers that are in the filter reach c * len, and a LOWER bound on that coverage which
   // passes settles it.  So the 128 probes in front of the cut's stop are made in another order: round A = the even slots of

@@ -45,8 +45,18 @@
     };
     // (TRI) does pair p of the triple hold an invalid character (N)?  -- its threshold is then lower than the plan's, and its slots need
     // their validity windows: per_pair's business
+    // (uniform batch, THRTAB) two ballots per triple instead of one per pair: the chunks with an invalid character, and the chunks with
+    // more than one.  Pair p's share of either is tri_lp bits from bit p tri_lp (a lane outside the triple has inv_real = 0).  The first
+    // share says whether the pair holds one at all; where the second share is empty its popcount IS the number of the pair's invalid
+    // characters (one per chunk, at most 21) -- all but a few pairs in a thousand at an N per 500 bases -- and thr_tab has the threshold
     bool inv3[3] = {false, false, false};
-    if (TRI) {
+    uint64_t inv_any = 0ull, inv_two = 0ull;
+    if constexpr (THRTAB) {
+      inv_any = __ballot(inv_real != 0u);
+      inv_two = __ballot((inv_real & (inv_real - 1u)) != 0u);
+#pragma unroll
+      for (uint32_t p3 = 0; p3 < 3u; ++p3) inv3[p3] = ((inv_any >> (p3 * tri_lp)) & ((1ull << tri_lp) - 1ull)) != 0ull;
+    } else if (TRI) {
 #pragma unroll
       for (uint32_t p3 = 0; p3 < 3u; ++p3) inv3[p3] = __ballot((inv_real != 0u) & (tri_pr == p3)) != 0ull;
     }
