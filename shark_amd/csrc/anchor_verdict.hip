@@ -158,22 +158,19 @@ __global__ __launch_bounds__(AV_WAVES * 64) void anchor_verdict_kernel(const Cla
   };
   // 32 bytes -> their 2-bit codes (first base LOW: classify_uni.hpp's `fw` stream) and one bit per byte: not one of ACGTacgt
   auto codes_of = [&](const AvRaw &r, uint64_t &code, uint32_t &inv) {
-    uint32_t msb[2] = {0u, 0u};
-    inv = 0u;
+    uint32_t b[8], msb[2], iv[2];
 #pragma unroll
-    for (int i = 0; i < 8; ++i) {
-      const uint32_t b = __builtin_amdgcn_alignbyte(r.d[i + 1], r.d[i], r.sh);
-      uint32_t c4, i4;
-      classify4(b, c4, i4);
-      msb[i >> 2] |= pack4(c4) << (24 - 8 * (i & 3));      // first base in bits 31:30
-      inv |= gather4(i4) << (4 * i);
-    }
+    for (int i = 0; i < 8; ++i) b[i] = __builtin_amdgcn_alignbyte(r.d[i + 1], r.d[i], r.sh);
+    stage16(b[0], b[1], b[2], b[3], msb[0], iv[0]);        // first base in bits 31:30, in bit 0
+    stage16(b[4], b[5], b[6], b[7], msb[1], iv[1]);
+    inv = (iv[1] << 16) | iv[0];
     code = ((uint64_t)av_rev2(msb[1]) << 32) | av_rev2(msb[0]);
   };
   auto qmask_of = [&](const AvRaw &r) -> uint32_t {
     uint32_t m = 0u;
 #pragma unroll
-    for (int i = 0; i < 8; ++i) m |= gather4(qmask4(__builtin_amdgcn_alignbyte(r.d[i + 1], r.d[i], r.sh), P.mq)) << (4 * i);   // FastqSplitter.hpp:104-109
+    for (int i = 0; i < 8; i += 2)   // FastqSplitter.hpp:104-109
+      m |= gather8(qmask4(__builtin_amdgcn_alignbyte(r.d[i + 1], r.d[i], r.sh), P.mq), qmask4(__builtin_amdgcn_alignbyte(r.d[i + 2], r.d[i + 1], r.sh), P.mq)) << (4 * i);
     return m;
   };
   // (trimmed reads) a pass's offsets: the lane's mate's start and end of read ppw gg + pr; its length, and the other mate's by a

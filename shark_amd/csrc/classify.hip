@@ -152,18 +152,15 @@ __device__ __forceinline__ void process_read(const ClassifyParams &P, const uint
     uint32_t msb16 = 0, valid8 = 0;
     if (b < L) {
       const uint32_t rem = L - b;
-      uint32_t c_lo, c_hi, i_lo, i_hi;
-      classify4((uint32_t)w, c_lo, i_lo);
-      classify4((uint32_t)(w >> 32), c_hi, i_hi);
-      msb16 = (pack4(c_lo) << 8) | pack4(c_hi);           // first base in bits 15:14
-      uint32_t inv8 = gather4(i_lo) | (gather4(i_hi) << 4);
+      uint32_t inv8;
+      // (the form with multiplies, stage_bases.hpp: these kernels are held at 64 / 80 VGPRs and spill a few as it is)
+      stage8<true>((uint32_t)w, (uint32_t)(w >> 32), msb16, inv8);   // first base in bits 15:14, in bit 0
       if (HASQ) inv8 |= gather4(qmask4((uint32_t)q, P.mq)) | (gather4(qmask4((uint32_t)(q >> 32), P.mq)) << 4);
       if (rem < 8) inv8 |= 0xFFu << rem;
       valid8 = ~inv8 & 0xFFu;
     }
     // the same 8 codes with the first base in the LOW bits: reverse the bits, swap each pair back
-    uint32_t lsb = __builtin_bitreverse32(msb16);         // lands in the high half
-    lsb = ((lsb >> 1) & 0x55555555u) | ((lsb & 0x55555555u) << 1);
+    const uint32_t lsb = stg_lsb_first(msb16);            // lands in the high half
     reinterpret_cast<uint16_t *>(st.fw)[gi] = (uint16_t)(lsb >> 16);
     reinterpret_cast<uint16_t *>(st.rv)[rv_last - gi] = (uint16_t)msb16;
     reinterpret_cast<uint8_t *>(st.vbits)[gi] = (uint8_t)valid8;

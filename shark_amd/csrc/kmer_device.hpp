@@ -7,6 +7,8 @@
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 
+#include "stage_bases.hpp"
+
 #if defined(SHK_FAKE_HASH) && !defined(SHK_TIMING_ONLY)
 #error "-DSHK_FAKE_HASH builds a library whose results are WRONG (timing-only ablation): say so with -DSHK_TIMING_ONLY as well"
 #endif
@@ -108,26 +110,9 @@ __host__ __device__ __forceinline__ void ktab_home(const uint64_t fwd, const uin
 }
 
 // ---------------------------------------------------------------------------
-// Base classification, 4 ASCII bytes at a time (SWAR).
-// Result must agree with to_int (kmer_utils.hpp:29-41): A/a C/c G/g T/t are
-// valid with codes 0..3 (= to_int-1, kmer_utils.hpp:68), every other byte --
-// including bytes >= 128, which are undefined behaviour in the reference -- is
-// invalid.
-//   code4 : 2-bit code in the low bits of each byte
-//   inv4  : bit 0 of each byte set when that byte is NOT one of ACGTacgt
+// Base classification, 8 or 16 ASCII bytes at a time (SWAR): stage_bases.hpp -- stage8 / stage16 / gather8, and the
+// word-at-a-time classify4 / pack4 / gather4 they replace (-DSHK_STAGE_MUL=1 brings those back).
 // ---------------------------------------------------------------------------
-__device__ __forceinline__ void classify4(uint32_t w, uint32_t &code4, uint32_t &inv4)
-{
-  const uint32_t t = w & 0xDFDFDFDFu;                       // fold lower case onto upper case
-  code4 = ((t >> 1) ^ (t >> 2)) & 0x03030303u;              // A->0 C->1 G->2 T->3
-  const uint32_t expect = __builtin_amdgcn_perm(0u, 0x54474341u /* "ACGT" */, code4);
-  uint32_t x = expect ^ t;                                  // zero byte <=> valid base
-  x |= x >> 4;
-  x |= x >> 2;
-  x |= x >> 1;
-  inv4 = x & 0x01010101u;
-}
-
 // the same for one byte: 0..3, or 4 = invalid (the index build and the placement table classify the reference byte by byte)
 __device__ __forceinline__ uint32_t base_code(uint32_t c)
 {
@@ -136,13 +121,6 @@ __device__ __forceinline__ uint32_t base_code(uint32_t c)
   const uint32_t expect = (0x54474341u >> (8 * code)) & 0xFFu;
   return expect == t ? code : 4u;
 }
-
-// 4 x 2-bit codes (one per byte, first character in the LOW byte) -> 8 bits,
-// first character most significant (kmer_utils.hpp:67-69 packs MSB first).
-__device__ __forceinline__ uint32_t pack4(uint32_t code4) { return (code4 * 0x40100401u) >> 24; }
-
-// bit 0 of each byte -> 4 contiguous bits, byte 0 -> bit 0
-__device__ __forceinline__ uint32_t gather4(uint32_t flags4) { return ((flags4 * 0x00204081u) >> 21) & 0xFu; }
 
 // quality mask (FastqSplitter.hpp:70,:104-109): a base is masked when its
 // quality character, compared as a SIGNED char, is below mq = Q + 33.

@@ -63,7 +63,7 @@ __global__ __launch_bounds__(256) void random_lookup_kernel(const uint8_t *__res
 }
 
 // shk_measure_valu_mix: the ISSUE ceiling of the exact-table classify kernel's own instruction mix.  One iteration is the
-// arithmetic that kernel does for a read on its shortest way through -- stage eight bases (classify4 / pack4 / gather4, the two code
+// arithmetic that kernel does for a read on its shortest way through -- stage eight bases (stage_bases.hpp's stage8, the two code
 // streams), cut a slot's two windows out of six dwords, canonical form, XXH64, the exact table's address arithmetic and compare,
 // the validity window and the coverage step -- on REGISTER operands: no LDS, no memory, nothing to wait for but the VALU itself;
 // every lane carries its own dependent chain, as in the kernel, and W waves per SIMD interleave.  bench.py divides the kernel's
@@ -89,13 +89,9 @@ __global__ __launch_bounds__(256) void valu_mix_kernel(const uint32_t iters, con
     // stage (classify_uni.hpp, "stage")
     const uint32_t sh = d0 & 3u;
     const uint32_t lo = __builtin_amdgcn_alignbyte(d1, d0, sh), hi = __builtin_amdgcn_alignbyte(d2, d1, sh);
-    uint32_t c_lo, c_hi, i_lo, i_hi;
-    classify4(lo, c_lo, i_lo);
-    classify4(hi, c_hi, i_hi);
-    const uint32_t msb16 = (pack4(c_lo) << 8) | pack4(c_hi);
-    const uint32_t inv8 = gather4(i_lo) | (gather4(i_hi) << 4);
-    uint32_t lsb = __builtin_bitreverse32(msb16);
-    lsb = ((lsb >> 1) & 0x55555555u) | ((lsb & 0x55555555u) << 1);
+    uint32_t msb16, inv8;
+    stage8(lo, hi, msb16, inv8);
+    const uint32_t lsb = stg_lsb_first(msb16);
     // a slot's windows out of six dwords (`windows`)
     const uint32_t f0 = lsb ^ d0, f1 = lsb + d1, f2 = msb16 ^ d2, e0 = msb16 + d0, e1 = lsb ^ d2, e2 = msb16 ^ d1;
     const uint32_t sf = (lane & 15u) << 1, sr = ((lane * 7u + it) & 15u) << 1;

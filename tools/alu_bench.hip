@@ -24,6 +24,8 @@ template <int OP> __global__ __launch_bounds__(256) void k(uint32_t* out, uint32
     if (OP == 12) { a = __builtin_bitreverse32(a) + 1; b = __builtin_bitreverse32(b) + 1; c = __builtin_bitreverse32(c) + 1; d = __builtin_bitreverse32(d) + 1; }
     if (OP == 13) { a += 1; b += 3; a = (a & 0x55555555u) | (b & ~0x55555555u); b = (b & 0x33333333u) | (c & ~0x33333333u); c = (c & 0x0f0f0f0fu) | (d & ~0x0f0f0f0fu); d = (d & 0x00ff00ffu) | (a & ~0x00ff00ffu); }   // v_bfi x4
     if (OP == 14) { x = (x << 31) | (x >> 33); y = (y << 27) | (y >> 37); x += 1; y += 1; }   // constant 64-bit rotates
+    if (OP == 15) { a = __builtin_amdgcn_udot4(a, b, 0u, false); b = __builtin_amdgcn_udot4(b, c, 0u, false); c = __builtin_amdgcn_udot4(c, d, 0u, false); d = __builtin_amdgcn_udot4(d, a, 0u, false); }   // v_dot4_u32_u8 x4
+    if (OP == 16) { a = __builtin_amdgcn_udot4(a | 0x01010101u, 0x01041040u, b, false); b += 1; }   // v_dot4_u32_u8 by a constant, a v_or and a v_add: three instructions, the figure is per instruction of the three (stage_bases.hpp's packing step)
   }
   out[blockIdx.x * 256 + threadIdx.x] = a ^ b ^ c ^ d ^ (uint32_t)x ^ (uint32_t)(x >> 32) ^ (uint32_t)y;
 }
@@ -43,5 +45,6 @@ int main() {
   run<4>("v_mul_u32_u24 x4 (+2 xor)", 4); run<5>("u64*u64 x2", 2); run<6>("xxh64_u64 x1", 1); run<7>("64-bit shift/rot group", 1);
   run<8>("v_alignbit_b32 x4", 4); run<9>("var 64-bit shift x2 (+4 xor)", 2); run<10>("v_perm_b32 x4", 4); run<11>("u64 cmp+select group", 1);
   run<12>("v_bfrev(+add) x4", 4); run<13>("v_bfi x4", 4); run<14>("const rotl64 x2 (+2 add64)", 2);
+  run<15>("v_dot4_u32_u8 x4", 4); run<16>("dot4 const + or + add (x3)", 3);
   return 0;
 }
