@@ -550,6 +550,22 @@ int shk_junctions_reset(shk_ctx *ctx);
  * allocates and clears the state (SHK_ERR_NOMEM if it cannot: the mode is left off); switching off keeps what has been accumulated,
  * switching on again goes on from it.  New: no counterpart. */
 int shk_pileup_enable(shk_ctx *ctx, uint32_t min_support);
+/* ALIGNED PILEUP: as shk_pileup_enable, but the batches submitted AFTERWARDS count what alignments mode shows instead of the owned
+ * pieces.  With s_min = min_support, every base of every FINAL BLOCK of the alignments section -- after trimming, gap closure and,
+ * at the context's current shk_alignments_extend parameters, end extension -- makes one observation at its record coordinate under
+ * the OBSERVATION rule above: read base q + t of block {x, q, len} at x + t; c == 0 makes none; the base is complemented on strand
+ * 1.  A mate is a pileup mate iff n_blocks >= 1.  Blocks are disjoint in the read, so a read base is observed at most once (owned
+ * pileup observes the microhomology of a junction twice and the bases gap closure places not at all), and sum_b counts over the
+ * state equals the number of base-bearing block bases.  The record base is not consulted: an observation needs no r < 4.
+ * The state, its layout, the read-outs, shk_pileup_add, shk_variants_* and the mate guard are pileup's own, and ONE STATE HOLDS ONE
+ * KIND: switching between owned and aligned (either way) returns SHK_ERR_STATE if a pileup batch of the other kind was submitted
+ * since the first enable or the last shk_pileup_reset (the host keeps a flag; the device is not asked).  shk_pileup_enable(ctx, 0)
+ * and shk_pileup_enable_aligned(ctx, 0) switch either kind off.  Switching on additionally returns SHK_ERR_STATE on an index
+ * finalized without shk_ref_keep_bases (the walk is alignments mode's and closes gaps against the record).  A batch is counted
+ * exactly once by pileup's rules word for word.  pileup_kernel does not run: align_kernel's accumulating instantiation does, with
+ * alignments mode off too (no records are stored or allocated then); with alignments mode on at the same floor one launch does
+ * both, at another floor each has its own.  New: no counterpart. */
+int shk_pileup_enable_aligned(shk_ctx *ctx, uint32_t min_support);
 /* The read-outs, with depth's rules: SHK_ERR_STATE if the mode was never enabled on this context or while tickets are outstanding,
  * SHK_ERR_INDEX_TOO_LARGE behind the guard above; otherwise they run on the context's stream behind everything enqueued so far and
  * leave the state untouched.  New: no counterpart.
@@ -645,6 +661,26 @@ int shk_variants_summary(shk_ctx *ctx, const shk_variant_params *p, shk_gene_var
  *    cost, ties to the LARGEST s; then  len_A += s;  x_B -= R - s;  q_B -= R - s;  len_B += R - s.  G >= R keeps the record
  *    intervals disjoint and inside [0, len_g).  A gap consumes only its own bases, so the gaps are independent of each other.  Every
  *    other gap stays open: R > 64, or G < R (an insertion in the read).
+ * 3a. END EXTENSION (shk_alignments_extend; off by default), after gap closure, on a mate with n_blocks >= 1, with mismatch penalty
+ *    P (1 .. 15) and end bonus B (0 .. 15).  K-mers are blind outside the outermost voting windows: a substitution at read index
+ *    i < k or i >= L - k silences every window on its outer side, and the span, the owned piece and the block all stop short of it.
+ *    This step compares the overhang with the record base by base, with step 4's kinds: a match scores +1, a mismatch -P, a base that
+ *    is neither 0.
+ *      RIGHT END.  The last block ends at (xe, qe) = (x + len, q + len); H = min(L - qe, len_g - xe).  Overhang base t = 0 .. H - 1 is
+ *      read base qe + t on record base xe + t.  score(e) = the sum over t < e, plus B iff qe + e == L and e >= 1 (the extension
+ *      reaches the mate's end, not merely the record's).  Take the e in 0 .. H of largest score, ties to the SMALLEST e; len += e.
+ *      LEFT END.  The mirror image on block 0 = {x0, q0, len}: H = min(q0, x0), base t is read base q0 - 1 - t on record base
+ *      x0 - 1 - t, the bonus applies iff e == q0 and e >= 1; then x0 -= e, q0 -= e, len += e.
+ *    With one block the left end is done first and then the right; the two are independent.  Interior gaps are untouched, step 4
+ *    counts over the extended blocks, and the record stays consistent (blocks inside [0, len_g) and [0, L), ascending, disjoint):
+ *    shk_alignment_cigar takes it as it is.  Consequences:
+ *      - an isolated substitution at distance d (counted from 0) from the block in an overhang of h bases that otherwise matches up
+ *        to the mate's end is extended through iff the whole overhang scores more than its first d bases: h - 1 - P + B > d (at
+ *        d = 0, next to the block: h - 1 - P + B > 0).  With the command's P = 4, B = 5 that always holds (h - 1 - 4 + 5 = h > d);
+ *      - an overhang into unrelated sequence (an intron behind a junction) keeps only its matching prefix: the expected score per
+ *        base is 0.25 - 0.75 P < 0, and no bonus waits at the record's end;
+ *      - trailing bases that are neither are not taken (ties go to the smallest e) unless the bonus carries the extension to the end;
+ *      - with P = 0 the step is off and the records are bit-identical to those without it.
  * 4. COUNTING, over the final blocks.  For the read byte's c = to_int[byte behind the -q mask] and the record's code r at a block base:
  *    c == 0 or r == 4: neither a match nor a mismatch; otherwise b = c - 1 on strand 0 and 3 - (c - 1) on strand 1, and b == r is a
  *    match, anything else a mismatch.  (For a split's cost a base that is neither counts as not a match.)
@@ -656,8 +692,9 @@ int shk_variants_summary(shk_ctx *ctx, const shk_variant_params *p, shk_gene_var
  * at min_intron <= 1190 the text form is 74M1190N26M.
  *
  * What the mode does NOT do:
- *   - the mate's ends outside its outermost blocks are not extended: they become soft clips, for spliced depth's reason (nothing
- *     says on which side of an intron an overhang shorter than k lies);
+ *   - by default the mate's ends outside its outermost blocks are not extended: they become soft clips (step 3a extends them base
+ *     by base where shk_alignments_extend asks for it; an overhang past a junction still stays a clip: the mode does not look for
+ *     the other side of the intron);
  *   - no pair-level claim is made: no proper-pair flag, no template length;
  *   - there is no mapping quality.
  *
@@ -679,6 +716,12 @@ typedef struct shk_alignments {
  * shk_ref_keep_positions, on an index of more than 65 536 records; either way while tickets are outstanding.  Switching on also
  * returns SHK_ERR_STATE on an index finalized without shk_ref_keep_bases.  New: no counterpart. */
 int shk_alignments_enable(shk_ctx *ctx, uint32_t min_support);
+/* Step 3a's parameters for the batches submitted AFTERWARDS: mismatch_penalty P = 0 switches the step off (the default), 1 .. 15
+ * on; end_bonus B = 0 .. 15; anything else is SHK_ERR_ARG.  SHK_ERR_STATE while tickets are outstanding.  Needs no index and may
+ * be called before shk_ref_finalize; it takes effect only where alignments mode or aligned pileup (shk_pileup_enable_aligned) runs.
+ * The command's --extend-ends is P = 4, B = 5: the familiar match 1 / mismatch 4 / clip 5.  With P = 0 the kernel launched is the
+ * one that ran before this call existed.  New: no counterpart. */
+int shk_alignments_extend(shk_ctx *ctx, uint32_t mismatch_penalty, uint32_t end_bonus);
 /* The alignments of the batch whose result was handed out LAST, with shk_segments_last's rules: that result's lifetime and memory
  * space (pinned host memory for host batches, DEVICE memory for resident ones).  SHK_ERR_STATE if that batch was submitted with
  * the mode off, if its wait returned an error, behind shk_count_work, or if no batch has been waited for yet.  New: no counterpart. */

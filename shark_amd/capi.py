@@ -107,7 +107,7 @@ EXPORTS = [
     "shk_pileup_enable", "shk_pileup_get", "shk_pileup_get_all", "shk_pileup_mates", "shk_pileup_reset",
     "shk_pileup_add", "shk_ref_keep_bases", "shk_variants_get", "shk_variants_summary",
     "shk_ref_kmer_table",
-    "shk_alignments_enable", "shk_alignments_last", "shk_alignment_cigar",
+    "shk_alignments_enable", "shk_alignments_last", "shk_alignment_cigar", "shk_alignments_extend", "shk_pileup_enable_aligned",
 ]
 SHK_PIPE_DEPTH = 3
 SHK_DIST_ID_BYTES = 128
@@ -200,6 +200,8 @@ def load():
         "shk_variants_get": (C.c_int, [p, C.POINTER(ShkVariantParams), p, C.c_uint64, C.POINTER(C.c_uint64)]),
         "shk_variants_summary": (C.c_int, [p, C.POINTER(ShkVariantParams), p, C.c_uint32]),
         "shk_alignments_enable": (C.c_int, [p, C.c_uint32]),
+        "shk_alignments_extend": (C.c_int, [p, C.c_uint32, C.c_uint32]),
+        "shk_pileup_enable_aligned": (C.c_int, [p, C.c_uint32]),
         "shk_alignments_last": (C.c_int, [p, C.POINTER(ShkAlignments)]),
         "shk_alignment_cigar": (C.c_int, [p, C.c_uint32, C.c_uint32, C.c_char_p, C.c_size_t, C.POINTER(C.c_uint32)]),
     }
@@ -579,6 +581,12 @@ class SharkHip:
         by the earliest span that holds it) to the context's pileup state; 0 switches the mode off and keeps the state"""
         self._check(self.L.shk_pileup_enable(self.h, int(min_support)), "shk_pileup_enable")
 
+    def pileup_enable_aligned(self, min_support=8):
+        """as pileup_enable, but batches submitted from now on add every base of the alignment's final blocks (alignments mode's walk at
+        s_min = min_support with the context's alignments_extend parameters) instead of the owned pieces; one state holds one kind;
+        needs an index built with keep_bases; 0 switches pileup off"""
+        self._check(self.L.shk_pileup_enable_aligned(self.h, int(min_support)), "shk_pileup_enable_aligned")
+
     def pileup(self, gene):
         """the counts of one gene: uint32 (len_g, 4), columns A, C, G, T on the record's strand"""
         gs = self.depth_layout()
@@ -623,6 +631,11 @@ class SharkHip:
         blocks from its kept spans at s_min = min_support, with match and mismatch counts); 0 switches the mode off; needs an index
         built with keep_bases; refused while tickets are outstanding"""
         self._check(self.L.shk_alignments_enable(self.h, int(min_support)), "shk_alignments_enable")
+
+    def alignments_extend(self, penalty=4, bonus=5):
+        """end extension for the batches submitted from now on: a mate's outermost blocks grow over the clipped ends base by base, match
+        +1, mismatch -penalty, +bonus for reaching the mate's end; penalty 0 switches it off (the default), 1 .. 15 on; bonus 0 .. 15"""
+        self._check(self.L.shk_alignments_extend(self.h, int(penalty), int(bonus)), "shk_alignments_extend")
 
     def alignments_last(self):
         """alignments of the batch whose result was handed out last: an (n_assoc, 2) array of ALIGNMENT_DTYPE records, parallel to

@@ -14,6 +14,11 @@
 // ballots give the not-a-match masks, lane s < R prices split s with two popcounts, split R (all on A) is priced by the wave, and one
 // wave minimum over cost << 7 | (64 - s) settles the split and the tie.  Counting: 64 block coordinates per pass, ballot and popcount
 // into scalar counters.  A mate's record is one aligned 64-byte line: lanes 0 .. 15 store one dword each.  No LDS.
+//
+// Two compile-time switches of the one kernel (template parameters): end extension (the header's step 3a) scores a mate's
+// two overhangs against the record 64 bases per pass -- two ballots, two popcounts per lane, one wave maximum -- when the first block
+// becomes the open block and before the last one is counted; accumulation (aligned pileup) adds every base of a final block to the
+// pileup state with one atomic where the counting loop has it loaded.  With both off the kernel is the code it always was.
 #include <hip/hip_runtime.h>
 
 #include <algorithm>
@@ -50,6 +55,14 @@ struct AlignParams {
   uint32_t n_waves;                // of the launch: a wave's step through the reads (a kernel argument costs no register between its uses)
   uint32_t cap;                    // associations `entries` and `out` hold (at most 2^32 - 1: a batch has no more)
   uint32_t *out;                   // [(j * 2 + mate) * AL_WORDS + w]
+};
+
+// what the extending and the accumulating instantiations take on top (align_kernel itself keeps its arguments as they were)
+struct AlignParamsX : AlignParams {
+  uint32_t ext_p, ext_b;           // end extension: mismatch penalty 1 .. 15 and end bonus 0 .. 15 (read by the extending instantiations only)
+  uint32_t n_store[2];             // the lanes that store mate m's record: 16, 32 for mate 1 of a single-end batch (as align_kernel works out), 0: no records
+  uint32_t *counts;                // aligned pileup: [(gene_start[g] + x) * 4 + b]; `out` may then be nullptr and n_store 0: no records are stored
+  unsigned long long *mates;
 };
 
 // one mate's bytes behind the -q mask, read in the record's orientation
@@ -107,7 +120,62 @@ __device__ __forceinline__ uint32_t close_gap(const Mate &M, const uint8_t *__re
   return __builtin_amdgcn_readfirstlane(AL_MAX_CLOSE - (best & 127u));
 }
 
-__global__ __launch_bounds__(PL_THREADS) void align_kernel(const AlignParams P)
+__device__ __forceinline__ uint32_t wave_max_u32(uint32_t v)
+{
+#pragma unroll
+  for (int o = 32; o >= 1; o >>= 1) {
+    const uint32_t t = (uint32_t)__shfl_xor((int)v, o, 64);
+    v = t > v ? t : v;
+  }
+  return v;
+}
+
+constexpr int32_t AL_EXT_BIAS = 15 * 64;   // a pass prices 64 bases at -15 at worst: relative scores lie in [-960, 64], [-960, 79] in the lane that adds the bonus
+
+// End extension (the header's step between 3 and 4) of one end: base t = 0 .. H - 1 of the overhang is read base q + dir * t on record base
+// x + dir * t (dir = +1 from the last block's end, -1 from the base in front of block 0); to_end: the overhang's H bases reach the mate's
+// end, so e == H earns the bonus.  Returns the e in 0 .. H of largest score, ties to the smallest.  64 bases per pass: two ballots, lane
+// t prices e = t0 + t + 1 relative to the pass with two popcounts, one wave maximum over (score + 960) << 7 | (64 - t) settles the pass
+// and its tie; the score up to the pass and the best (score, e) so far are 64-bit scalars (|score| <= 15 * 2^31).
+__device__ __forceinline__ uint32_t extend_end(const Mate &M, const uint8_t *__restrict__ rec, int32_t len_g, int32_t q, int32_t x, int32_t dir, int32_t H,
+                                               bool to_end, uint32_t pen, uint32_t bonus, uint32_t lane)
+{
+  int64_t base = 0, best = 0;
+  uint32_t best_e = 0;
+  for (int32_t t0 = 0; t0 < H; t0 += 64) {
+    const int32_t t = t0 + (int32_t)lane;
+    bool is_m = false, is_x = false;
+    if (t < H) {
+      const uint32_t b = read_base(M, q + dir * t), rb = record_base(rec, len_g, x + dir * t);
+      is_m = b < 4u && b == rb;
+      is_x = b < 4u && rb < 4u && b != rb;
+    }
+    const uint64_t mm = __ballot(is_m), mx = __ballot(is_x);
+    const uint64_t low = ~0ull >> (63u - lane);   // bits 0 .. lane
+    // (the popcounts as signed numbers: an unsigned difference would wrap and, added to the 64-bit score, stay wrapped)
+    int32_t rel = (int32_t)__popcll(mm & low) - (int32_t)pen * (int32_t)__popcll(mx & low);
+    if (to_end && t == H - 1) rel += (int32_t)bonus;
+    const uint32_t key = t < H ? ((uint32_t)(rel + AL_EXT_BIAS) << 7) | (64u - lane) : 0u;
+    const uint32_t top = __builtin_amdgcn_readfirstlane(wave_max_u32(key));   // (lane 0 is inside the overhang: top != 0)
+    const int64_t cand = base + ((int32_t)(top >> 7) - AL_EXT_BIAS);
+    if (cand > best) {
+      best = cand;
+      best_e = (uint32_t)t0 + (64u - (top & 127u)) + 1u;
+    }
+    base += (int32_t)__popcll(mm) - (int32_t)pen * (int32_t)__popcll(mx);
+    // nothing behind this pass can score more than every base left matching, and the bonus
+    if (base + (int64_t)(H - t0 - 64) + (int64_t)bonus <= best) break;
+  }
+  return best_e;
+}
+
+// The kernel.  EXT: the ends are extended (step 3a; P.ext_p >= 1, P.ext_b).  ACC: every base of a final block is added to the pileup state
+// where it is counted (P.counts, P.mates), and records are stored only where P.n_store says so.  The kernel takes its arguments by value
+// as a template parameter: behind a function that takes them by reference the same statements cost one scalar register more.
+// align_kernel<false, false, AlignParams> is the code and the arguments alignments mode always had; the other three take AlignParamsX,
+// whose fields a discarded branch never names.
+template <bool EXT, bool ACC, class Params>
+__global__ __launch_bounds__(PL_THREADS) void align_kernel(const Params P)
 {
   // the batch will be assembled again and comes through here again; or it will be refused in wait (pileup_kernel's rule)
   if (P.counters[CTR_OVERFLOW] || (P.skip_if_long && P.counters[CTR_LONG]) || P.counters[CTR_VOUCH_BAD]) return;
@@ -122,13 +190,18 @@ __global__ __launch_bounds__(PL_THREADS) void align_kernel(const AlignParams P)
 #pragma unroll
   for (uint32_t w = 0; w < 4; ++w) hdr[w] = 0u - (((lane ^ w) - 1u) >> 31);   // (lane == w: 0 - 1 has the top bit)
   const uint32_t hdr_any = hdr[0] | hdr[1] | hdr[2] | hdr[3];
+  // (ACC) pileup mates, mates with a block: counted in lane 0 of a vector register through hdr[0] -- a value the lanes share would take two
+  //  scalar registers across every loop and a compare of the lane id two more, which the scalar file has no room for
+  [[maybe_unused]] uint64_t counted = 0;
   for (uint64_t i = (uint64_t)blockIdx.x * PL_WAVES + wave; i < P.n; i += P.n_waves) {
     const uint32_t o0 = P.gene_off[i], o1 = P.gene_off[i + 1];
     if (o1 <= o0 || o1 > P.cap) continue;
     for (uint32_t m = 0; m < 2; ++m) {
       if (!P.seq[m]) continue;
       // (a single-end batch: mate 2's records are all zero, and they lie behind mate 1's -- lanes 16 .. 31 store them with mate 1's)
-      const uint32_t n_store = m == 0u && !P.seq[1] ? 2u * AL_WORDS : AL_WORDS;
+      uint32_t n_store;
+      if constexpr (EXT || ACC) n_store = P.n_store[m];
+      else n_store = m == 0u && !P.seq[1] ? 2u * AL_WORDS : AL_WORDS;
       Mate M{};
       const uint64_t a = P.off[m][i], len = P.off[m][i + 1] - a;
       M.L = len > 0x7FFFFFFFull ? 0x7FFFFFFFu : (uint32_t)len;   // (segments_kernel's L)
@@ -138,11 +211,17 @@ __global__ __launch_bounds__(PL_THREADS) void align_kernel(const AlignParams P)
       for (uint32_t j = o0; j < o1; ++j) {
         const uint32_t g = P.gene_ids[j];
         uint32_t word = 0;                        // this lane's dword of the record (lanes 0 .. 15)
-        uint32_t n_blocks = 0, matches = 0, mismatches = 0;
+        uint32_t n_blocks = 0;
+        [[maybe_unused]] uint32_t matches = 0, mismatches = 0;
+        [[maybe_unused]] uint32_t tally = 0;      // (EXT, ACC) matches in lane 2, mismatches in lane 3
         if (g < P.n_genes) {
           const uint64_t start = P.gene_start[g];
           const int32_t len_g = (int32_t)(P.gene_start[g + 1] - start);   // (a record has fewer than 2^31 bases: the placement table's bound)
           const uint8_t *const rec = P.recbase + start;
+          [[maybe_unused]] const int32_t L = (int32_t)M.L;
+          // (ACC) this lane's counters of record base `lane` of the gene: a vector value for the same reason
+          [[maybe_unused]] uint32_t *lane_counts = nullptr;
+          if constexpr (ACC) lane_counts = P.counts + (start + lane) * 4u;
           const shk_segment *e = P.entries + ((uint64_t)j * 2u + m) * SHK_MAX_SEGMENTS;
           M.strand = e[0].strand;   // (rank 0's: every kept span lies on it)
           KeptSpans S = kept_spans(e, M.L, P.k, P.s_min);
@@ -172,6 +251,13 @@ __global__ __launch_bounds__(PL_THREADS) void align_kernel(const AlignParams P)
               if (!bl) continue;
             }
             if (al) {
+              if constexpr (EXT) {
+                // the last pass: the open block is the last one, its right end is extended before it is counted
+                if (!bl) {
+                  const int32_t hq = L - (aq + al), hx = len_g - (ax + al), H = hq < hx ? hq : hx;
+                  if (H > 0) al += (int32_t)extend_end(M, rec, len_g, aq + al, ax + al, 1, H, hq <= hx, P.ext_p, P.ext_b, lane);
+                }
+              }
               if (bl) {
                 const int32_t R = bq - (aq + al), G = bx - (ax + al);
                 if (R >= 1 && R <= (int32_t)AL_MAX_CLOSE && G >= R) {
@@ -184,27 +270,54 @@ __global__ __launch_bounds__(PL_THREADS) void align_kernel(const AlignParams P)
               for (int32_t t0 = 0; t0 < al; t0 += 64) {
                 const int32_t t = t0 + (int32_t)lane;
                 bool is_m = false, is_x = false;
+                [[maybe_unused]] uint32_t seen = 4u;   // (ACC) the read base this lane observes; 4: none
                 if (t < al) {
                   const uint32_t b = read_base(M, aq + t), rb = record_base(rec, len_g, ax + t);
                   is_m = b < 4u && b == rb;
                   is_x = b < 4u && rb < 4u && b != rb;
+                  // (a block lies inside the record: the compare keeps a lane inside the state whatever the records hold)
+                  if constexpr (ACC) seen = (uint32_t)(ax + t) < (uint32_t)len_g ? b : 4u;
                 }
-                matches += (uint32_t)__popcll(__ballot(is_m));
-                mismatches += (uint32_t)__popcll(__ballot(is_x));
+                if constexpr (ACC) {
+                  // pileup's OBSERVATION at the base's record coordinate (behind the compare above, not inside it: one level of lane masks)
+                  if (seen < 4u) atomicAdd(lane_counts + ((uint64_t)(uint32_t)(ax + t0) * 4u + seen), 1u);
+                }
+                if constexpr (EXT || ACC) {
+                  // (the new instantiations count in the lanes that store the two words: two scalar registers fewer across the loops)
+                  tally += ((uint32_t)__popcll(__ballot(is_m)) & hdr[2]) | ((uint32_t)__popcll(__ballot(is_x)) & hdr[3]);
+                } else {
+                  matches += (uint32_t)__popcll(__ballot(is_m));
+                  mismatches += (uint32_t)__popcll(__ballot(is_x));
+                }
               }
               const uint32_t w = lane - (4u + 3u * n_blocks);
               word = w == 0u ? (uint32_t)ax : (w == 1u ? (uint32_t)aq : (w == 2u ? (uint32_t)al : word));
               ++n_blocks;
             }
+            if constexpr (EXT) {
+              // the first block becomes the open block: its left end is extended (closure moves only A's right and B's left)
+              if (!n_blocks && bl) {
+                const int32_t H = bq < bx ? bq : bx;
+                if (H > 0) {
+                  const int32_t e = (int32_t)extend_end(M, rec, len_g, bq - 1, bx - 1, -1, H, bq <= bx, P.ext_p, P.ext_b, lane);
+                  bx -= e; bq -= e; bl += e;
+                }
+              }
+            }
             ax = bx; aq = bq; al = bl;
           }
         }
+        if constexpr (ACC) counted += (n_blocks ? 1u : 0u) & hdr[0];
         if (n_blocks) {
-          word = (word & ~hdr_any) | (n_blocks & hdr[0]) | (M.strand & hdr[1]) | (matches & hdr[2]) | (mismatches & hdr[3]);
+          if constexpr (EXT || ACC) word = (word & ~hdr_any) | (n_blocks & hdr[0]) | (M.strand & hdr[1]) | tally;
+          else word = (word & ~hdr_any) | (n_blocks & hdr[0]) | (M.strand & hdr[1]) | (matches & hdr[2]) | (mismatches & hdr[3]);
         }
-        if (lane < n_store) P.out[((uint64_t)j * 2u + m) * AL_WORDS + lane] = word;
+        if (lane < n_store) P.out[((uint64_t)j * 2u + m) * AL_WORDS + lane] = word;   // (ACC without records: n_store is 0)
       }
     }
+  }
+  if constexpr (ACC) {
+    if (counted) atomicAdd(P.mates, (unsigned long long)counted);
   }
 }
 
@@ -221,20 +334,24 @@ __global__ __launch_bounds__(256) void publish_alignments_kernel(const uint32_t 
 
 }  // namespace
 
-int launch_alignments(Ctx *ctx, const Slot &s, const shk_segment *entries, uint64_t cap_assoc, bool skip_if_long, hipStream_t stream)
+int launch_alignments(Ctx *ctx, const Slot &s, const shk_segment *entries, uint64_t cap_assoc, bool skip_if_long, bool store, bool accumulate, hipStream_t stream)
 {
   const DeviceIndex &ix = ctx->idx;
-  if (!ix.gene_start || !ix.recbase || !entries || !s.align || !s.d_align) {
+  if (!ix.gene_start || !ix.recbase || !entries || (!store && !accumulate) || (store && (!s.align || !s.d_align))) {
     ctx->last_error = "alignments mode without its state";
     return SHK_ERR_STATE;
   }
+  if (accumulate && (!s.pileup_al || !ctx->d_pileup || !ctx->d_pileup_mates || (store && s.align != s.pileup_al))) {
+    ctx->last_error = "aligned pileup without its state";
+    return SHK_ERR_STATE;
+  }
   if (s.n == 0) return SHK_OK;
-  AlignParams P{};
+  AlignParamsX P{};
   P.gene_off = s.d_gene_off;
   P.gene_ids = s.d_gene_ids;
   P.counters = s.d_counters;
   P.n = s.n;
-  P.cap = (uint32_t)std::min<uint64_t>(std::min<uint64_t>(std::min<uint64_t>(s.cap_gene_ids, cap_assoc), s.cap_align / 2), 0xFFFFFFFFull);   // (launch_segments')
+  P.cap = (uint32_t)std::min<uint64_t>(std::min<uint64_t>(std::min<uint64_t>(s.cap_gene_ids, cap_assoc), store ? s.cap_align / 2 : ~0ull), 0xFFFFFFFFull);   // (launch_segments')
   P.seq[0] = s.p.seq1; P.off[0] = s.p.off1; P.qual[0] = s.p.hasq ? s.p.qual1 : nullptr;
   P.seq[1] = s.p.seq2; P.off[1] = s.p.off2; P.qual[1] = s.p.hasq ? s.p.qual2 : nullptr;
   P.mq = s.p.mq;
@@ -244,12 +361,23 @@ int launch_alignments(Ctx *ctx, const Slot &s, const shk_segment *entries, uint6
   P.recbase = ix.recbase;
   P.n_genes = (uint32_t)(ctx->gene_start.size() - 1);
   P.skip_if_long = skip_if_long ? 1u : 0u;
-  P.s_min = s.align;
-  P.out = reinterpret_cast<uint32_t *>(s.d_align);
+  P.s_min = store ? s.align : s.pileup_al;
+  P.out = store ? reinterpret_cast<uint32_t *>(s.d_align) : nullptr;
+  P.n_store[0] = !store ? 0u : (P.seq[1] ? AL_WORDS : 2u * AL_WORDS);
+  P.n_store[1] = !store ? 0u : AL_WORDS;
+  P.ext_p = s.ext_p;
+  P.ext_b = s.ext_b;
+  P.counts = accumulate ? ctx->d_pileup : nullptr;
+  P.mates = accumulate ? ctx->d_pileup_mates : nullptr;
   // one wave per read up to 2 048 workgroups, persistent beyond (launch_segments' bound)
   const unsigned blocks = (unsigned)std::min<uint64_t>((s.n + PL_WAVES - 1) / PL_WAVES, 2048);
   P.n_waves = blocks * PL_WAVES;
-  hipLaunchKernelGGL(align_kernel, dim3(blocks), dim3(PL_THREADS), 0, stream, P);
+  const bool ext = s.ext_p != 0;
+  // (everything new off: the kernel and the arguments this mode always had)
+  if (!ext && !accumulate) hipLaunchKernelGGL((align_kernel<false, false, AlignParams>), dim3(blocks), dim3(PL_THREADS), 0, stream, static_cast<const AlignParams &>(P));
+  else if (ext && !accumulate) hipLaunchKernelGGL((align_kernel<true, false, AlignParamsX>), dim3(blocks), dim3(PL_THREADS), 0, stream, P);
+  else if (!ext) hipLaunchKernelGGL((align_kernel<false, true, AlignParamsX>), dim3(blocks), dim3(PL_THREADS), 0, stream, P);
+  else hipLaunchKernelGGL((align_kernel<true, true, AlignParamsX>), dim3(blocks), dim3(PL_THREADS), 0, stream, P);
   const hipError_t e = hipGetLastError();
   return e == hipSuccess ? SHK_OK : set_hip_error(ctx, e, "align_kernel");
 }

@@ -123,6 +123,13 @@ const char *USAGE_MESSAGE =
     "                                        clips; the same refusals as --segments; combines with every other output)\n"
     "          --sam-min-support N           unique k-mers a diagonal of a mate needs to become a block of --sam (default:8)\n"
     "          --sam-min-intron N            record bases a gap between two blocks needs to be written as N, not D (default:20)\n"
+    "          --extend-ends                 --sam and --pileup-aligned: grow a mate's outermost blocks over its clipped ends base by base\n"
+    "                                        (match 1, mismatch 4, 5 for reaching the mate's end), so that a substitution within k of\n"
+    "                                        an end is shown instead of clipped\n"
+    "          --extend-penalty N            the mismatch penalty of --extend-ends (1 .. 15, default:4)\n"
+    "          --extend-bonus N              its bonus for reaching the mate's end (0 .. 15, default:5)\n"
+    "          --pileup-aligned              --pileup / --variants count the bases of the alignment --sam shows (trimmed, gaps closed,\n"
+    "                                        ends extended under --extend-ends) instead of the bases under the voting windows\n"
     "          --kmer-table                  one gene, k <= 17: also build the exact table keyed by the k-mer itself (no XXH64 per probe; the\n"
     "                                        same output).  Costs tens of milliseconds when the index is built and pays on the GPU\n"
     "                                        alone, so it is off here, where the host and the link bound a run\n"
@@ -175,6 +182,10 @@ struct Options {
   FILE *sam_file = nullptr;        // (--sam, likewise; the header is written once the reference is read, the lines per batch)
   unsigned sam_min_support = 8, sam_min_intron = 20;
   bool sam_sub_flag_given = false;
+  bool extend_ends = false;               // (--extend-ends; --extend-penalty, --extend-bonus)
+  unsigned extend_penalty = 4, extend_bonus = 5;
+  bool extend_sub_flag_given = false;
+  bool pileup_aligned = false;            // (--pileup-aligned)
   bool kmer_table = false;         // (--kmer-table: the one-gene index's table keyed by the k-mer, shk_ref_kmer_table; off here unless asked for)
   shk_variant_params variants_params{8, 3, 1, 5};   // (--variants-min-depth, -min-alt, -min-frac)
   bool variants_sub_flag_given = false;
@@ -342,6 +353,20 @@ const OptionRow OPTION_TABLE[] = {
        o.sam_min_intron = value_of<unsigned>(v);
        o.sam_sub_flag_given = true;
      }},
+    {1027, "extend-ends", false, [](Options &o, const char *) { o.extend_ends = true; }},
+    {1028, "extend-penalty", true,
+     [](Options &o, const char *v) {
+       o.extend_penalty = value_of<unsigned>(v);
+       o.extend_sub_flag_given = true;
+       if (o.extend_penalty < 1 || o.extend_penalty > 15) reject(USAGE_MESSAGE, "shark: --extend-penalty must be in the range [1, 15].");
+     }},
+    {1029, "extend-bonus", true,
+     [](Options &o, const char *v) {
+       o.extend_bonus = value_of<unsigned>(v);
+       o.extend_sub_flag_given = true;
+       if (o.extend_bonus > 15) reject(USAGE_MESSAGE, "shark: --extend-bonus must be in the range [0, 15].");
+     }},
+    {1030, "pileup-aligned", false, [](Options &o, const char *) { o.pileup_aligned = true; }},
 };
 
 // Reads per device batch when --batch does not say.  A batch costs the device path 0.5-2 ms of launches, copies and bookkeeping
@@ -412,6 +437,9 @@ Options parse_arguments(int argc, char **argv)
   if (!opt.variants_path.empty() && !opt.pileup_path.empty() && opt.variants_min_support != opt.pileup_min_support)
     reject(USAGE_MESSAGE, "shark: --variants-min-support and --pileup-min-support must be equal (there is one pileup).");
   if (opt.sam_sub_flag_given && opt.sam_path.empty()) reject(USAGE_MESSAGE, "shark: --sam-min-support and --sam-min-intron need --sam FILE.");
+  if (opt.pileup_aligned && opt.pileup_path.empty() && opt.variants_path.empty()) reject(USAGE_MESSAGE, "shark: --pileup-aligned needs --pileup FILE or --variants FILE.");
+  if (opt.extend_sub_flag_given && !opt.extend_ends) reject(USAGE_MESSAGE, "shark: --extend-penalty and --extend-bonus need --extend-ends.");
+  if (opt.extend_ends && opt.sam_path.empty() && !opt.pileup_aligned) reject(USAGE_MESSAGE, "shark: --extend-ends needs --sam FILE or --pileup-aligned.");
   if (opt.out1_path.empty()) opt.out1_path = "sharked_sample.1";
   if (opt.out2_path.empty() && !opt.sample2_path.empty()) opt.out2_path = "sharked_sample.2";
   // --devices alone says how many workers there are; with --gpus N it has to name N devices
@@ -2086,7 +2114,8 @@ std::string build_index(const Options &opt, GpuStart &gpu, std::vector<std::stri
     if (const int rc = shk_ref_kmer_table(ctx, opt.kmer_table ? 1 : 0)) return std::string("shark: ") + shk_strerror(rc);
   // (--variants: the records' bases stay on the device; only worker 0 is asked for the sites, but every replica is built alike)
   // (--sam: every worker's alignments kernel reads them)
-  if (opt.variants_file || opt.sam_file)
+  // (--pileup-aligned: the accumulating alignments kernel reads them as well)
+  if (opt.variants_file || opt.sam_file || opt.pileup_aligned)
     for (auto *ctx : gpu.ctxs)
       if (const int rc = shk_ref_keep_bases(ctx)) return std::string("shark: ") + shk_strerror(rc);
   {
@@ -2264,9 +2293,17 @@ int run_sample(const Options &opt, GpuStart &gpu, BatchPool &pool, std::vector<s
   // (--variants reads the same state, at the same floor: parse_arguments saw to that)
   if (opt.pileup_file || opt.variants_file)
     for (shk_ctx *ctx : gpu.ctxs)
-      if (const int rc = shk_pileup_enable(ctx, opt.pileup_file ? opt.pileup_min_support : opt.variants_min_support)) {
+      if (const int rc = (opt.pileup_aligned ? shk_pileup_enable_aligned : shk_pileup_enable)(ctx, opt.pileup_file ? opt.pileup_min_support : opt.variants_min_support)) {
         feed.stop();
         std::cerr << "shark: pileup mode could not be switched on: " << shk_strerror(rc) << " " << shk_last_error(ctx) << std::endl;
+        return EXIT_FAILURE;
+      }
+  // (--extend-ends: every worker's alignments kernel extends the ends alike, for --sam and for --pileup-aligned)
+  if (opt.extend_ends)
+    for (shk_ctx *ctx : gpu.ctxs)
+      if (const int rc = shk_alignments_extend(ctx, opt.extend_penalty, opt.extend_bonus)) {
+        feed.stop();
+        std::cerr << "shark: end extension could not be switched on: " << shk_strerror(rc) << " " << shk_last_error(ctx) << std::endl;
         return EXIT_FAILURE;
       }
   // (--sam: every worker's batches carry their mates' alignments)

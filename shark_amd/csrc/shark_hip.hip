@@ -318,8 +318,9 @@ static int enqueue_tail(Ctx *ctx, Slot &s, bool skip_hist_if_long, bool count_ge
   // (spliced depth, the junction table: behind segments_kernel's records at m = SHK_MAX_SEGMENTS -- segments mode's own where it runs at that
   //  m, else a launch of that kernel into arrays nobody else sees --, under depth_accumulate_kernel's rule for a batch that comes through
   //  here again; pileup mode: the third reader of the same records, its own kernel behind theirs; alignments mode: the fourth, behind pileup's,
-  //  and the one with records of its own per association, handed out as segments mode's are)
-  if (s.sp_depth || s.sp_junc || s.pileup || s.align) {
+  //  and the one with records of its own per association, handed out as segments mode's are; aligned pileup: align_kernel's accumulating
+  //  instantiation in pileup_kernel's stead -- the same launch as alignments mode's where the two floors are equal, else one of its own)
+  if (s.sp_depth || s.sp_junc || s.pileup || s.align || s.pileup_al) {
     const shk_segment *entries = s.d_seg_entries;
     uint64_t cap_assoc = segments_cap(s);
     if (s.seg_m != SHK_MAX_SEGMENTS) {
@@ -331,9 +332,11 @@ static int enqueue_tail(Ctx *ctx, Slot &s, bool skip_hist_if_long, bool count_ge
     }
     if ((s.sp_depth || s.sp_junc) && (rc = launch_spliced_accumulate(ctx, s, entries, cap_assoc, skip_hist_if_long, st))) return rc;
     if (s.pileup && (rc = launch_pileup(ctx, s, entries, cap_assoc, skip_hist_if_long, st))) return rc;
+    const bool acc_with_records = s.pileup_al && s.pileup_al == s.align;
+    if (s.pileup_al && !acc_with_records && (rc = launch_alignments(ctx, s, entries, cap_assoc, skip_hist_if_long, false, true, st))) return rc;
     if (s.align) {
       if ((rc = ensure_capacity(ctx, &s.d_align, &s.cap_align, 2 * s.cap_gene_ids))) return rc;
-      if ((rc = launch_alignments(ctx, s, entries, cap_assoc, skip_hist_if_long, st))) return rc;
+      if ((rc = launch_alignments(ctx, s, entries, cap_assoc, skip_hist_if_long, true, acc_with_records, st))) return rc;
       if (s.host_batch) {
         if ((rc = ensure_pinned(ctx, &s.h_align, &s.cap_h_align, 2 * s.cap_gene_ids))) return rc;
         if ((rc = launch_publish_alignments(s, std::min<uint64_t>(std::min<uint64_t>(s.cap_h_align, s.cap_align) / 2, cap_assoc), st))) return rc;
@@ -383,8 +386,12 @@ static int enqueue_classify(Ctx *ctx, Slot &s, const shk_batch *b, uint32_t max_
   s.depth = count_genes && !ctx->depth_spliced ? ctx->depth : 0u;   // (shk_count_work is a measurement: its batch is not counted)
   s.sp_depth = count_genes && ctx->depth_spliced ? ctx->depth : 0u;
   s.sp_junc = count_genes ? ctx->junc : 0u;
-  s.pileup = count_genes ? ctx->pileup : 0u;
+  s.pileup = count_genes && !ctx->pileup_aligned ? ctx->pileup : 0u;
+  s.pileup_al = count_genes && ctx->pileup_aligned ? ctx->pileup : 0u;
   s.align = ctx->align;
+  s.ext_p = ctx->ext_p;
+  s.ext_b = ctx->ext_b;
+  if (s.pileup || s.pileup_al) ctx->pileup_dirty = true;
   if (s.depth || s.sp_depth) ctx->depth_dirty = true;
   if (s.sp_junc) ctx->junc_dirty = true;
   if ((rc = slot_reserve(ctx, s, n))) return rc;
@@ -1546,14 +1553,20 @@ int shk_junctions_reset(shk_ctx *ctx)
 // the counters: four per record base, and at least one allocation's worth for an index without a base
 static size_t pileup_bytes(const shk_ctx *ctx) { return std::max<size_t>((size_t)ctx->gene_start.back() * 4 * sizeof(uint32_t), 16); }
 
-int shk_pileup_enable(shk_ctx *ctx, uint32_t min_support)
+// both kinds of pileup (owned pieces, the alignment's final blocks) over the one state
+static int pileup_enable_kind(shk_ctx *ctx, uint32_t min_support, bool aligned, const char *who)
 {
   if (!ctx) return SHK_ERR_ARG;
-  if (tickets_outstanding(ctx)) { ctx->last_error = "shk_pileup_enable: tickets are outstanding (wait for them first)"; return SHK_ERR_STATE; }
+  if (tickets_outstanding(ctx)) { ctx->last_error = std::string(who) + ": tickets are outstanding (wait for them first)"; return SHK_ERR_STATE; }
   if (min_support) {
-    if (ctx->mode != 2) { ctx->last_error = "shk_pileup_enable: the index is not finalized"; return SHK_ERR_STATE; }
-    if (!ctx->idx.ptab_lg) { ctx->last_error = "shk_pileup_enable: the index was finalized without shk_ref_keep_positions"; return SHK_ERR_STATE; }
-    if (ctx->n_records > 65536 || ctx->idx.wrap || !ctx->idx.gene_start) { ctx->last_error = "shk_pileup_enable: more than 65 536 records (gene ids wrap)"; return SHK_ERR_STATE; }
+    if (ctx->mode != 2) { ctx->last_error = std::string(who) + ": the index is not finalized"; return SHK_ERR_STATE; }
+    if (!ctx->idx.ptab_lg) { ctx->last_error = std::string(who) + ": the index was finalized without shk_ref_keep_positions"; return SHK_ERR_STATE; }
+    if (ctx->n_records > 65536 || ctx->idx.wrap || !ctx->idx.gene_start) { ctx->last_error = std::string(who) + ": more than 65 536 records (gene ids wrap)"; return SHK_ERR_STATE; }
+    if (aligned && !ctx->idx.recbase) { ctx->last_error = std::string(who) + ": the index was finalized without shk_ref_keep_bases"; return SHK_ERR_STATE; }
+    if (ctx->d_pileup_mates && ctx->pileup_dirty && aligned != ctx->pileup_aligned) {
+      ctx->last_error = std::string(who) + ": the state holds pileup of the other kind (owned / aligned): shk_pileup_reset first";
+      return SHK_ERR_STATE;
+    }
     if (!ctx->d_pileup_mates) {
       SHK_HIP(ctx, hipSetDevice(ctx->prm.device));
       const size_t bytes = pileup_bytes(ctx);
@@ -1566,10 +1579,14 @@ int shk_pileup_enable(shk_ctx *ctx, uint32_t min_support)
       SHK_HIP(ctx, hipMemsetAsync(counts, 0, bytes, ctx->stream));
       SHK_HIP(ctx, hipMemsetAsync(mates, 0, sizeof(unsigned long long), ctx->stream));
     }
+    ctx->pileup_aligned = aligned;
   }
   ctx->pileup = min_support;
   return SHK_OK;
 }
+
+int shk_pileup_enable(shk_ctx *ctx, uint32_t min_support) { return pileup_enable_kind(ctx, min_support, false, "shk_pileup_enable"); }
+int shk_pileup_enable_aligned(shk_ctx *ctx, uint32_t min_support) { return pileup_enable_kind(ctx, min_support, true, "shk_pileup_enable_aligned"); }
 
 // what every read-out starts with: the state rules, the stream drained behind everything enqueued so far, the mate counter and its guard
 static int pileup_read_mates(shk_ctx *ctx, const char *who, uint64_t *n_mates)
@@ -1627,6 +1644,7 @@ int shk_pileup_reset(shk_ctx *ctx)
   SHK_HIP(ctx, hipSetDevice(ctx->prm.device));
   SHK_HIP(ctx, hipMemsetAsync(ctx->d_pileup, 0, pileup_bytes(ctx), ctx->stream));
   SHK_HIP(ctx, hipMemsetAsync(ctx->d_pileup_mates, 0, sizeof(unsigned long long), ctx->stream));
+  ctx->pileup_dirty = false;
   SHK_HIP(ctx, hipStreamSynchronize(ctx->stream));
   return SHK_OK;
 }
@@ -1694,6 +1712,16 @@ int shk_alignments_enable(shk_ctx *ctx, uint32_t min_support)
     if (!ctx->idx.recbase) { ctx->last_error = "shk_alignments_enable: the index was finalized without shk_ref_keep_bases"; return SHK_ERR_STATE; }
   }
   ctx->align = min_support;
+  return SHK_OK;
+}
+
+int shk_alignments_extend(shk_ctx *ctx, uint32_t mismatch_penalty, uint32_t end_bonus)
+{
+  if (!ctx) return SHK_ERR_ARG;
+  if (mismatch_penalty > 15 || end_bonus > 15) { ctx->last_error = "shk_alignments_extend: mismatch_penalty and end_bonus are at most 15"; return SHK_ERR_ARG; }
+  if (tickets_outstanding(ctx)) { ctx->last_error = "shk_alignments_extend: tickets are outstanding (wait for them first)"; return SHK_ERR_STATE; }
+  ctx->ext_p = mismatch_penalty;
+  ctx->ext_b = end_bonus;
   return SHK_OK;
 }
 

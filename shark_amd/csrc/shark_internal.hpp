@@ -367,6 +367,10 @@ struct Slot {
   uint32_t align = 0;
   shk_mate_alignment *d_align = nullptr; size_t cap_align = 0;
   shk_mate_alignment *h_align = nullptr; size_t cap_h_align = 0;   // (host batches; filled by publish_alignments_kernel)
+  // end extension (shk_alignments_extend) as submitted: mismatch penalty (0: off) and end bonus; aligned pileup (shk_pileup_enable_aligned):
+  // submitted with this floor (0: not) -- align_kernel's accumulating instantiation adds the batch to Ctx::d_pileup, pileup_kernel does not run
+  uint32_t ext_p = 0, ext_b = 0;
+  uint32_t pileup_al = 0;
 };
 
 struct Ctx;
@@ -404,7 +408,9 @@ int launch_spliced_accumulate(Ctx *ctx, const Slot &s, const shk_segment *entrie
 int launch_pileup(Ctx *ctx, const Slot &s, const shk_segment *entries, uint64_t cap_assoc, bool skip_if_long, hipStream_t stream);
 // align.hip: per association of the batch in `s` and per mate its blocks on the gene's record with their match and mismatch counts, from the
 // same records and DeviceIndex::recbase into s.d_align at floor s.align, behind segments_kernel; skip_if_long: as launch_gene_hist
-int launch_alignments(Ctx *ctx, const Slot &s, const shk_segment *entries, uint64_t cap_assoc, bool skip_if_long, hipStream_t stream);
+// store: the records go to s.d_align at floor s.align; accumulate: the final blocks' bases go to Ctx::d_pileup at floor s.pileup_al (one launch
+// does both where the floors are equal).  With s.ext_p == 0 and no accumulation the kernel launched is the one this mode always launched
+int launch_alignments(Ctx *ctx, const Slot &s, const shk_segment *entries, uint64_t cap_assoc, bool skip_if_long, bool store, bool accumulate, hipStream_t stream);
 int launch_publish_alignments(const Slot &s, uint64_t h_cap, hipStream_t stream);   // h_cap: associations the pinned array (and the device's) holds
 // variants.hip: d_pileup[i] += d_add[i] over n_entries counters (d_add 16-byte aligned: SHK_ERR_ARG otherwise), *d_pileup_mates += mates, on ctx->stream
 int launch_pileup_add(Ctx *ctx, const uint32_t *d_add, uint64_t n_entries, uint64_t mates);
@@ -541,6 +547,8 @@ struct Ctx {
   uint32_t pileup = 0;                         // min_support for the batches submitted from now on (0: off)
   uint32_t *d_pileup = nullptr;                // gene_start[nidx] x 4 counters, [x * 4 + b]: the observations of base b at x (allocated by the first enable)
   unsigned long long *d_pileup_mates = nullptr;   // pileup mates since the last reset (not null: the mode was enabled once)
+  bool pileup_aligned = false;                 // the kind `pileup` stands for: owned pieces (pileup.hip) or the alignment's final blocks (align.hip)
+  bool pileup_dirty = false;                   // a pileup batch of either kind was submitted since the first enable / the last reset
   // variants mode (shk_ref_keep_bases, shk_variants_get / _summary; variants.hip): read-outs of the pileup state; scratch only grows
   bool keep_bases = false;                     // finalize builds DeviceIndex::recbase
   uint32_t *d_var_waves = nullptr;             // sites per wavefront of 256 positions, then their exclusive scan
@@ -549,6 +557,7 @@ struct Ctx {
   shk_gene_variants *d_var_summary = nullptr;  // nidx records
   // alignments mode (shk_alignments_enable; align.hip), as segments mode: the floor for the batches submitted from now on (0: off)
   uint32_t align = 0;
+  uint32_t ext_p = 0, ext_b = 0;               // shk_alignments_extend: mismatch penalty (0: off) and end bonus for the batches submitted from now on
   bool last_align_valid = false;
   const shk_mate_alignment *last_align = nullptr;
   uint64_t last_align_n = 0;
