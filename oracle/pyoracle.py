@@ -61,8 +61,42 @@ def lib():
         L.so_bf_rank.restype = u64; L.so_bf_rank.argtypes = [p, u64]
         L.so_bf_get_index.restype = None
         L.so_bf_get_index.argtypes = [p, u64, C.POINTER(C.c_int), C.POINTER(C.c_int)]
+        L.so_get_hash_many.restype = None; L.so_get_hash_many.argtypes = [p, C.c_size_t, p]
+        L.so_filter_sweep.restype = C.c_size_t
+        L.so_filter_sweep.argtypes = [C.c_uint, p, u64, u64, u64, p, C.c_size_t, C.c_int]
         _lib = L
     return _lib
+
+
+def get_hash_many(kmers):
+    """so_get_hash of every k-mer of an array (uint64)"""
+    km = np.ascontiguousarray(kmers, dtype=np.uint64)
+    out = np.empty(len(km), dtype=np.uint64)
+    if len(km):
+        lib().so_get_hash_many(km.ctypes.data_as(C.c_void_p), len(km), out.ctypes.data_as(C.c_void_p))
+    return out
+
+
+def filter_sweep(k, bf_words, bf_bits, x_lo, x_hi, cap=None, nthreads=1):
+    """so_filter_sweep: the canonical k-mers of [x_lo, x_hi) whose filter bit is set, ascending -> (count, the first `cap` of them);
+    cap=None: all of them (a second call when the first guess was too small)"""
+    words = np.ascontiguousarray(bf_words, dtype=np.uint64)
+    if len(words) < (bf_bits + 63) // 64:
+        raise ValueError("filter_sweep: %d words for %d bits" % (len(words), bf_bits))
+    L = lib()
+    if cap is None:     # the set bits' own k-mers at most, plus the false positives expected among the range's canonical k-mers
+        n_set = int(np.bitwise_count(words).sum())
+        room = n_set + int(1.25 * n_set * (x_hi - x_lo) / (2.0 * bf_bits)) + (1 << 16)
+    else:
+        room = int(cap)
+    while True:
+        out = np.empty(max(room, 1), dtype=np.uint64)
+        n = L.so_filter_sweep(k, words.ctypes.data_as(C.c_void_p), bf_bits, x_lo, x_hi, out.ctypes.data_as(C.c_void_p), room, int(nthreads))
+        if n == C.c_size_t(-1).value:
+            raise RuntimeError("so_filter_sweep failed")
+        if cap is not None or n <= room:
+            return int(n), out[:min(n, room)].copy()
+        room = int(n)
 
 
 _ref = None

@@ -955,3 +955,164 @@ int so_classify_batch(const so_shark *s, uint64_t n,
 }
 
 void so_free(void *p) { free(p); }
+
+/* ======================================================================== */
+/* Bulk helpers for the audits of the k-mer keyed tables.                   */
+/* ======================================================================== */
+void so_get_hash_many(const uint64_t *kmers, size_t n, uint64_t *out)
+{
+  for (size_t i = 0; i < n; ++i) out[i] = so_get_hash(kmers[i]);
+}
+
+/* so_revcompl without the loop: complement, reverse the 32 two-bit groups of the word (bytes, nibbles in a byte, groups in a
+ * nibble), keep the top k groups -- the low k groups of ~x in reverse order, which is what so_revcompl shifts together.
+ * The sweep compares the two as it goes. */
+static inline uint64_t revcompl_word(uint64_t x, unsigned k)
+{
+  x = __builtin_bswap64(~x);
+  x = ((x >> 4) & 0x0F0F0F0F0F0F0F0FULL) | ((x & 0x0F0F0F0F0F0F0F0FULL) << 4);
+  x = ((x >> 2) & 0x3333333333333333ULL) | ((x & 0x3333333333333333ULL) << 2);
+  return x >> (64 - 2 * k);
+}
+
+/* so_get_hash without the byte buffer: of so_xxh64 for len == 8 and seed 0 only the short-input start, one 8-byte lane and the
+ * avalanche execute, and the lane read back little-endian is the k-mer itself.  The sweep compares the two as it goes. */
+static inline uint64_t get_hash_word(uint64_t kmer)
+{
+  uint64_t h = P64_5 + 8;
+  h ^= xxh_round(0, kmer);
+  h = rotl64(h, 27) * P64_1 + P64_4;
+  h ^= h >> 33;
+  h *= P64_2;
+  h ^= h >> 29;
+  h *= P64_3;
+  h ^= h >> 32;
+  return h;
+}
+
+#define SWEEP_BLOCK_LG 20
+typedef struct {
+  unsigned k;
+  const uint64_t *words;
+  uint64_t bits, lo, hi;
+  int t, nthreads;
+  size_t *block_count; /* shared: keys found per block (each block has one owner) */
+  uint64_t *buf;       /* this worker's keys, its blocks in ascending order */
+  size_t n, room;
+  int err;
+} sweep_job;
+
+static int sweep_keep(sweep_job *j, uint64_t x)
+{
+  if (j->n == j->room) {
+    const size_t room = j->room ? 2 * j->room : 4096;
+    uint64_t *nb = (uint64_t *)realloc(j->buf, room * sizeof(uint64_t));
+    if (!nb) return 1;
+    j->buf = nb;
+    j->room = room;
+  }
+  j->buf[j->n++] = x;
+  return 0;
+}
+
+/* the filter words of the canonical k-mers are asked for SWEEP_PENDING k-mers ahead of being read (a filter beyond the caches:
+ * a miss per k-mer otherwise); the k-mers wait in order, so the output stays ascending */
+#define SWEEP_PENDING 64
+static int sweep_drain(sweep_job *j, const uint64_t *px, const uint64_t *pp, unsigned n)
+{
+  for (unsigned i = 0; i < n; ++i)
+    if (((j->words[pp[i] >> 6] >> (pp[i] & 63)) & 1) && sweep_keep(j, px[i])) return 1;
+  return 0;
+}
+
+static void *sweep_worker(void *arg)
+{
+  sweep_job *j = (sweep_job *)arg;
+  const unsigned k = j->k;
+  const int pow2 = (j->bits & (j->bits - 1)) == 0;
+  const uint64_t n_blocks = (j->hi - j->lo + ((1ULL << SWEEP_BLOCK_LG) - 1)) >> SWEEP_BLOCK_LG;
+  uint64_t px[SWEEP_PENDING], pp[SWEEP_PENDING];
+  for (uint64_t b = (uint64_t)j->t; b < n_blocks; b += (uint64_t)j->nthreads) {
+    const uint64_t x0 = j->lo + (b << SWEEP_BLOCK_LG);
+    const uint64_t x1 = (j->hi - x0 > (1ULL << SWEEP_BLOCK_LG)) ? x0 + (1ULL << SWEEP_BLOCK_LG) : j->hi;
+    const size_t before = j->n;
+    unsigned np = 0;
+    uint64_t x = x0;
+    while (x < x1) {
+      uint64_t rcs[4];
+      unsigned cnt = 1;
+      if (k >= 2 && (x & 3) == 0 && x1 - x >= 4) {
+        /* four k-mers that differ in their last base alone: the reverse complement of each is the complement of that base
+         * in front of the reverse complement of the k - 1 bases they share */
+        const uint64_t rcy = revcompl_word(x >> 2, k - 1);
+        for (unsigned l = 0; l < 4; ++l) rcs[l] = ((uint64_t)(3 - l) << (2 * (k - 1))) | rcy;
+        cnt = 4;
+      } else {
+        rcs[0] = revcompl_word(x, k);
+      }
+      for (unsigned l = 0; l < cnt; ++l) {
+        const uint64_t xl = x + l, rc = rcs[l];
+        const int check = (xl & 1020) == 0 || xl == x0 || xl + 1 == x1;
+        if (check && (rc != so_revcompl(xl, (uint8_t)k) || get_hash_word(xl) != so_get_hash(xl))) { j->err = 1; return NULL; }
+        if (xl > rc) continue;
+        const uint64_t h = get_hash_word(xl);
+        const uint64_t p = pow2 ? (h & (j->bits - 1)) : (h % j->bits); /* (the same number; a 64-bit division per k-mer otherwise) */
+        __builtin_prefetch(&j->words[p >> 6]);
+        px[np] = xl;
+        pp[np] = p;
+        if (++np == SWEEP_PENDING) {
+          if (sweep_drain(j, px, pp, np)) { j->err = 2; return NULL; }
+          np = 0;
+        }
+      }
+      x += cnt;
+    }
+    if (sweep_drain(j, px, pp, np)) { j->err = 2; return NULL; }
+    j->block_count[b] = j->n - before;
+  }
+  return NULL;
+}
+
+size_t so_filter_sweep(unsigned k, const uint64_t *bf_words, uint64_t bf_bits, uint64_t x_lo, uint64_t x_hi,
+                       uint64_t *out, size_t cap, int nthreads)
+{
+  if (k < 1 || k > 31 || !bf_words || bf_bits == 0 || x_hi > (1ULL << (2 * k)) || x_lo > x_hi || (cap && !out)) return (size_t)-1;
+  if (x_lo == x_hi) return 0;
+  if (nthreads < 1) nthreads = 1;
+  if (nthreads > 256) nthreads = 256;
+  const uint64_t n_blocks = (x_hi - x_lo + ((1ULL << SWEEP_BLOCK_LG) - 1)) >> SWEEP_BLOCK_LG;
+  if ((uint64_t)nthreads > n_blocks) nthreads = (int)n_blocks;
+  size_t *block_count = (size_t *)calloc((size_t)n_blocks, sizeof(size_t));
+  sweep_job *jobs = (sweep_job *)calloc((size_t)nthreads, sizeof(sweep_job));
+  pthread_t *th = (pthread_t *)malloc((size_t)nthreads * sizeof(pthread_t));
+  size_t total = (size_t)-1;
+  if (block_count && jobs && th) {
+    for (int t = 0; t < nthreads; ++t) {
+      sweep_job *j = &jobs[t];
+      j->k = k; j->words = bf_words; j->bits = bf_bits; j->lo = x_lo; j->hi = x_hi;
+      j->t = t; j->nthreads = nthreads; j->block_count = block_count;
+    }
+    int started = 0;
+    for (; started < nthreads; ++started)
+      if (pthread_create(&th[started], NULL, sweep_worker, &jobs[started]) != 0) break;
+    for (int t = 0; t < started; ++t) pthread_join(th[t], NULL);
+    int err = started != nthreads;
+    for (int t = 0; t < nthreads; ++t) err |= jobs[t].err;
+    if (!err) {
+      /* block b belongs to worker b % nthreads, whose buffer holds its blocks in ascending order */
+      total = 0;
+      for (int t = 0; t < nthreads; ++t) jobs[t].n = 0; /* (now: the read cursor) */
+      for (uint64_t b = 0; b < n_blocks; ++b) {
+        sweep_job *j = &jobs[b % (uint64_t)nthreads];
+        for (size_t i = 0; i < block_count[b]; ++i, ++total)
+          if (total < cap) out[total] = j->buf[j->n + i];
+        j->n += block_count[b];
+      }
+    }
+  }
+  if (jobs) for (int t = 0; t < nthreads; ++t) free(jobs[t].buf);
+  free(th);
+  free(jobs);
+  free(block_count);
+  return total;
+}

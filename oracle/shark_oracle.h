@@ -108,6 +108,17 @@ int       so_classify_batch(const so_shark *s, uint64_t n,
                             uint32_t *gene_off, uint16_t **gene_ids);
 void      so_free(void *p);
 
+/* ---- bulk helpers for the audits of the k-mer keyed tables (tests/ktab_audit.py) ---- */
+/* out[i] = so_get_hash(kmers[i]) */
+void      so_get_hash_many(const uint64_t *kmers, size_t n, uint64_t *out);
+/* What BF::get_index asks of every k-mer (bloomfilter.h:87-89), asked of a whole range: every x in [x_lo, x_hi) that is its own
+ * canonical form (x <= so_revcompl(x, k)) and whose bit so_get_hash(x) % bf_bits is set in bf_words (bit p = bit p & 63 of word
+ * p >> 6), written in ascending order to out, at most cap of them.  Returns how many there are (may exceed cap), (size_t)-1 when
+ * an argument is unusable or the word-at-a-time reverse complement and hash the sweep uses ever differ from so_revcompl and
+ * so_get_hash (they are compared on four of every 1024 x and at both ends of every block).  nthreads workers share the range in interleaved blocks. */
+size_t    so_filter_sweep(unsigned k, const uint64_t *bf_words, uint64_t bf_bits, uint64_t x_lo, uint64_t x_hi,
+                          uint64_t *out, size_t cap, int nthreads);
+
 #ifdef __cplusplus
 }
 #endif

@@ -322,8 +322,10 @@ class SharkHip:
                     "lbig32": np.uint32, "tab": np.uint64, "atab": np.uint64, "ltab": np.uint32, "ref2": np.uint32,
                     "refpay": np.uint32, "refext": np.uint32, "refmul": np.uint32, "recbase": np.uint8,
                     "kxtab": np.uint8, "kxkeys": np.uint64, "kxmeta": np.uint64,
-                    "ptab": np.uint32, "pdir": np.uint32, "pmeta": np.uint64}      # (ptab: 4 words per entry; pmeta: DEBUG_PMETA)
+                    "ptab": np.uint32, "pdir": np.uint32, "pmeta": np.uint64,      # (ptab: 4 words per entry; pmeta: DEBUG_PMETA)
+                    "ktab": np.uint64, "ktmeta": np.uint64}                        # (ktab: the slots as allocated; ktmeta: DEBUG_KTMETA)
     DEBUG_PMETA = ("ptab_lg", "ptab_n")
+    DEBUG_KTMETA = ("ktab_lg", "ktab_w", "ktab_keys")
     DEBUG_META = ("tab_lg", "sum_shift", "lsum_shift", "lbig_shift", "ltab_mul", "ref_total", "n_set", "tot_idx", "pow2", "wrap",
                   "ent_len", "ids_len", "bf_bits", "bf_words64", "sum_bits", "ktab_lg")
     DEBUG_KXMETA = ("kx_in_use", "kx_m1", "kx_m2", "kx_keys", "kx_enum_us", "kx_build_us")
@@ -351,6 +353,10 @@ class SharkHip:
     def debug_kx_meta(self):
         """the k-mer keyed table of a one-gene index (kmer_table.hpp): is it in use, its multipliers, its key count, what building it took"""
         return dict(zip(self.DEBUG_KXMETA, (int(x) for x in self._debug_read("kxmeta", np.uint64))))
+
+    def debug_ktab_meta(self):
+        """the minimiser-bucketed table (tests/ktab_audit.py): log2 of its buckets (0 = not built), the minimiser's length, its key count"""
+        return dict(zip(self.DEBUG_KTMETA, (int(x) for x in self._debug_read("ktmeta", np.uint64))))
 
     # ---- classification --------------------------------------------------------
     def _host_batch(self, seq1, off1, seq2, off2, qual1, qual2):

@@ -954,6 +954,15 @@ int shk_debug_index_array(const shk_ctx *cctx, const char *name, void *dst, uint
     memcpy(dst, pmeta, sizeof(pmeta));
     return SHK_OK;
   }
+  if (what == "ktmeta") {   // (the minimiser-bucketed table's scalars, on every index; a name of its own: `meta` keeps its 16 words)
+    const bool kt = ix.ktab && ix.ktab_lg;
+    const uint64_t ktmeta[SHK_DEBUG_KTMETA_WORDS] = {kt ? ix.ktab_lg : 0u, kt ? ix.ktab_w : 0u, kt ? ix.ktab_keys : 0ull};
+    *bytes_needed = sizeof(ktmeta);
+    if (!dst) return SHK_OK;
+    if (dst_bytes < sizeof(ktmeta)) return SHK_ERR_ARG;
+    memcpy(dst, ktmeta, sizeof(ktmeta));
+    return SHK_OK;
+  }
   const void *src = nullptr;
   uint64_t bytes = 0;
   if (what == "rank_w") { src = ix.rank_w; bytes = (ix.bf_words64 + 2) * sizeof(uint32_t); }
@@ -967,6 +976,7 @@ int shk_debug_index_array(const shk_ctx *cctx, const char *name, void *dst, uint
   else if (what == "ltab") { src = ix.ltab; bytes = LTAB_BYTES; }
   else if (what == "kxtab") { src = ix.kxtab; bytes = LTAB_BYTES; }
   else if (what == "kxkeys") { src = ix.kxtab ? ix.kxkeys : nullptr; bytes = ix.kx_nkeys * sizeof(uint64_t); }
+  else if (what == "ktab") { src = ix.ktab_lg >= 3 ? ix.ktab : nullptr; bytes = src ? ((2ull << ix.ktab_lg) + 16) * sizeof(uint64_t) : 0; }   // (as allocated: the eight spare buckets included)
   else if (what == "ref2") { src = total ? ix.ref2 : nullptr; bytes = ((total + 15) / 16 + 4) * sizeof(uint32_t); }
   else if (what == "refpay") { src = total ? ix.refpay : nullptr; bytes = (total + 8) * sizeof(uint32_t); }
   else if (what == "refext") { src = total ? ix.refext : nullptr; bytes = (total + 8) * sizeof(uint32_t); }

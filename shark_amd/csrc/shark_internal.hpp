@@ -148,10 +148,15 @@ struct DeviceIndex {
 // The placement table (tests/placement_audit.py audits it): ptab = ptab_n + 1 entries of 16 bytes as allocated (the last one is
 // spare and never written), pdir = 2^ptab_lg + 2 words, "pmeta" = SHK_DEBUG_PMETA_WORDS uint64_t scalars in this order: ptab_lg,
 // ptab_n.  All three have size 0 on an index finalized without shk_ref_keep_positions.  (gene_start: shk_depth_layout.)
+// The minimiser-bucketed table (tests/ktab_audit.py audits it): ktab = (16 << line_lg) + 16 uint64_t slots as allocated, line_lg =
+// ktab_lg - 3, the eight spare buckets behind the last line included; size 0 when the table is not built.  "ktmeta" =
+// SHK_DEBUG_KTMETA_WORDS uint64_t scalars on every index, in this order: ktab_lg, ktab_w, ktab_keys (all 0 without the table; a name
+// of its own, as kxmeta and pmeta: `meta` keeps its 16 words).
 // Exported from the library but deliberately not declared in include/shark_hip.h; no classify path uses it.
 constexpr uint32_t SHK_DEBUG_META_WORDS = 16;
 constexpr uint32_t SHK_DEBUG_KXMETA_WORDS = 6;
 constexpr uint32_t SHK_DEBUG_PMETA_WORDS = 2;
+constexpr uint32_t SHK_DEBUG_KTMETA_WORDS = 3;
 constexpr uint32_t REFEXT_NONE = 0xFFFFFFFFu, REFEXT_CLIP = 254u;   // (an extent never reads 255: no entry looks like REFEXT_NONE)
 constexpr uint32_t REFPAY_NONE = 0xFFFFFFFFu;   // (multi with payload 2^30-1: not a rank, n_set <= 2^30-1 entries have ranks below that)
 

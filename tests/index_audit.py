@@ -202,6 +202,13 @@ def audit_lbig32(m, A, meta):
     return _audit_summary("lbig32", "lbig_shift", 1 << 20, m, A, meta)
 
 
+def expected_low(m, rk):
+    """the low word of a table slot (tab and ktab alike) whose key has the filter position of rank rk: the gene of a single-gene
+    list, else multi | rank"""
+    rk = np.asarray(rk, dtype=np.int64)
+    return np.where(m.list_len[rk] == 1, m.gene0[rk], (1 << 31) | rk)
+
+
 def _tab_decode(tab, lg):
     """valid slots of the table body: slot index, bucket, displacement, home, decoded position"""
     nb = 1 << lg
@@ -251,7 +258,7 @@ def audit_tab(m, A, meta):
     _report(out, "tab", (lo[1::2] & TAB_OVERFLOW) != 0, "overflow mark in slot 1", np.arange(nb) * 2 + 1)
     # the low word: the gene of a single-gene list, else multi | rank
     rk = r[known]
-    exp = np.where(m.list_len[rk] == 1, m.gene0[rk], (1 << 31) | rk)
+    exp = expected_low(m, rk)
     low = lo[idx[known]] & ~TAB_OVERFLOW
     _report(out, "tab", low != exp, lambda i: "low word %#x, expected %#x (rank %d)" % (low[i], exp[i], rk[i]), idx[known])
     for i in (2 * nb, 2 * nb + 1):

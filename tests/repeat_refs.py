@@ -197,11 +197,13 @@ def smallest_hash_wmer(w):
     raise AssertionError("no w-mer found")
 
 
-def saturated_neighbourhood(rng, k, w):
+def saturated_neighbourhood(rng, k, w, wmer=None):
     """genes that together contain every k-mer around the w-mer with the smallest hash: for each of its k - w + 1 places in a k-mer
     and each of the 4^(k - w) fillings of the other places, the k-mer between two random flanks of 12 bases; one gene per place.
-    All (k - w + 1) * 4^(k - w) k-mers (48 for k = 17, w = 15) share that minimiser, hence one 16-slot line of the table."""
-    m, _ = smallest_hash_wmer(w)
+    All (k - w + 1) * 4^(k - w) k-mers (48 for k = 17, w = 15) share that minimiser, hence one 16-slot line of the table.
+    wmer: another w-mer to build the neighbourhood of (its k-mers share it as their minimiser only where no other w-mer of theirs
+    hashes lower)."""
+    m = smallest_hash_wmer(w)[0] if wmer is None else np.asarray(wmer, np.uint8)
     genes, marks = [], []
     for place in range(k - w + 1):
         parts, at = [], 0

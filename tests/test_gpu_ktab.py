@@ -3,7 +3,8 @@ index for k = 15 ... 17, keyed by the canonical k-mer itself -- every canonical 
 and the filter's false positives alike, enumerated over all 4^k / 2 of them when the index is built -- and laid out so that the
 consecutive k-mers of a read, which share their minimiser, are looked up in one 128-byte line.  It must answer exactly what
 `BF::get_index` answers (bloomfilter.h:78-102): parity with the oracle on whole reads, on every reference k-mer as a read of its own,
-and -- the false-positive enumeration has no other witness -- on uniform-random k-mers against the plain filter words.
+and on uniform-random k-mers against the plain filter words.  (The table itself -- which keys it holds, where, with which marks --
+is audited entry by entry in tests/test_gpu_ktab_audit.py: every false positive of the filter at k = 15 and 16, slices at k = 17.)
 
 Run on the GPU box with `pytest -m gpu`."""
 import numpy as np

@@ -324,3 +324,71 @@ def test_multithreaded_build_equals_the_serial_one(oracle, k, bf_bits, n_genes, 
     assert np.array_equal(ra[0], rb[0]) and np.array_equal(ra[1], rb[1])
     a.close()
     b.close()
+
+
+@pytest.mark.parametrize("k,bf_bits", [(8, 1 << 12), (9, 1 << 14), (9, 3 * 5000)])
+def test_filter_sweep_and_bulk_hash(oracle, k, bf_bits):
+    """so_filter_sweep / so_get_hash_many, the bulk helpers of tests/ktab_audit.py: the sweep over ALL k-mers is the per-k-mer loop
+    over so_revcompl and so_get_hash on an oracle-built filter (a power-of-two size and one that is not); 1 and 5 threads, ranges
+    that begin and end mid-way (within a block, across blocks), a `cap` too small and an empty range behave as documented"""
+    L = oracle.lib()
+    rng = np.random.default_rng(k)
+    genes = [bytes(g) for g in synth.make_genes(rng, 3, 60, 120)]
+    o = oracle.Shark(k=k, c=0.5, bf_bits=bf_bits)
+    o.build(genes)
+    words = o.bf_words().copy()
+    n_all = 1 << (2 * k)
+    want = []
+    for x in range(n_all):
+        if x <= L.so_revcompl(x, k):
+            p = L.so_get_hash(x) % bf_bits
+            if (int(words[p >> 6]) >> (p & 63)) & 1:
+                want.append(x)
+    want = np.array(want, dtype=np.uint64)
+    assert len(want) >= o.num_kmer() > 50
+    for nthreads in (1, 5):
+        n, got = oracle.filter_sweep(k, words, bf_bits, 0, n_all, nthreads=nthreads)
+        assert n == len(want) and np.array_equal(got, want), nthreads
+    # (SWEEP_BLOCK_LG = 20 exceeds 4^9: ranges across block boundaries are covered at k = 11 below)
+    for lo, hi in ((n_all // 3 + 1, 2 * n_all // 3 + 5), (17, 18), (n_all - 1000, n_all), (5, 5)):
+        sel = want[(want >= lo) & (want < hi)]
+        for nthreads in (1, 5):
+            n, got = oracle.filter_sweep(k, words, bf_bits, lo, hi, nthreads=nthreads)
+            assert n == len(sel) and np.array_equal(got, sel), (lo, hi, nthreads)
+    n, got = oracle.filter_sweep(k, words, bf_bits, 0, n_all, cap=7, nthreads=3)
+    assert n == len(want) and np.array_equal(got, want[:7])
+    n, got = oracle.filter_sweep(k, words, bf_bits, 0, n_all, cap=0)
+    assert n == len(want) and len(got) == 0
+    with pytest.raises(RuntimeError):
+        oracle.filter_sweep(k, words, bf_bits, 9, 5)
+    with pytest.raises(RuntimeError):
+        oracle.filter_sweep(k, words, bf_bits, 0, n_all + 1)
+    h = oracle.get_hash_many(want)
+    assert [int(v) for v in h] == [L.so_get_hash(int(x)) for x in want]
+    assert len(oracle.get_hash_many(np.zeros(0, np.uint64))) == 0
+    o.close()
+
+
+def test_filter_sweep_across_blocks(oracle):
+    """k = 11 (four blocks of 2^20 values): workers that take interleaved blocks give the ascending list one worker gives, for
+    whole and ragged ranges; a vectorised restatement (numpy reverse complement, so_get_hash_many) agrees"""
+    k, bf_bits = 11, 1 << 16
+    rng = np.random.default_rng(3)
+    o = oracle.Shark(k=k, c=0.5, bf_bits=bf_bits)
+    o.build([bytes(g) for g in synth.make_genes(rng, 4, 100, 200)])
+    words = o.bf_words().copy()
+    n_all = 1 << (2 * k)
+    x = np.arange(n_all, dtype=np.uint64)
+    rc, t = np.zeros(n_all, np.uint64), ~x
+    for _ in range(k):
+        rc = (rc << np.uint64(2)) | (t & np.uint64(3))
+        t = t >> np.uint64(2)
+    xs = x[x <= rc]
+    p = oracle.get_hash_many(xs) % np.uint64(bf_bits)
+    want = xs[((words[(p >> np.uint64(6)).astype(np.int64)] >> (p & np.uint64(63))) & np.uint64(1)) != 0]
+    for lo, hi in ((0, n_all), ((1 << 20) - 3, (3 << 20) + 11), (12345, n_all - 54321)):
+        sel = want[(want >= lo) & (want < hi)]
+        for nthreads in (1, 3, 5):
+            n, got = oracle.filter_sweep(k, words, bf_bits, lo, hi, nthreads=nthreads)
+            assert n == len(sel) and np.array_equal(got, sel), (lo, hi, nthreads)
+    o.close()
