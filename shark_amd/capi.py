@@ -358,6 +358,39 @@ class SharkHip:
         """the minimiser-bucketed table (tests/ktab_audit.py): log2 of its buckets (0 = not built), the minimiser's length, its key count"""
         return dict(zip(self.DEBUG_KTMETA, (int(x) for x in self._debug_read("ktmeta", np.uint64))))
 
+    # ---- test-only runs of the device scan and radix sort (shk_debug_scan_u32 / shk_debug_sort_u64: as shk_debug_index_array) ----
+    DEBUG_SCAN_GUARDS = ("in_front", "in_back", "out_front", "out_back", "temp_front", "temp_back")
+    DEBUG_SORT_GUARDS = ("a_front", "a_back", "b_front", "b_back", "hist_front", "hist_back", "scan_tmp_front", "scan_tmp_back")
+
+    def debug_scan_u32(self, values, in_off=0, out_off=0, in_place=False):
+        """exclusive_scan_u32 over `values` (uint32) with in / out placed in_off / out_off words behind a 16-byte aligned address
+        (in_place: out is in).  Returns (out, total, in_after, guards): out and in_after as uint32 arrays, the 64-bit total as an
+        int, guards = changed guard words per band in the order of DEBUG_SCAN_GUARDS (uint32; all zero on a clean run)"""
+        fn = self.L.shk_debug_scan_u32
+        fn.restype = C.c_int
+        fn.argtypes = [C.c_void_p, C.c_void_p, C.c_uint64, C.c_uint32, C.c_uint32, C.c_int, C.c_void_p, C.c_void_p,
+                       C.POINTER(C.c_uint64), C.c_void_p]
+        a = np.ascontiguousarray(values, dtype=np.uint32)
+        out, after = np.zeros(len(a), dtype=np.uint32), np.zeros(len(a), dtype=np.uint32)
+        guards = np.zeros(len(self.DEBUG_SCAN_GUARDS), dtype=np.uint32)
+        total = C.c_uint64()
+        self._check(fn(self.h, _ptr(a), len(a), in_off, out_off, 1 if in_place else 0, _ptr(out), _ptr(after), C.byref(total), _ptr(guards)),
+                    "shk_debug_scan_u32")
+        return out, int(total.value), after, guards
+
+    def debug_sort_u64(self, keys, end_bit=64):
+        """radix_sort_u64 over `keys` (uint64).  Returns (sorted, which, guards): the keys of the buffer the sort returned, which one
+        that was (0 = a, the input's; 1 = b), guards = changed guard words per band in the order of DEBUG_SORT_GUARDS"""
+        fn = self.L.shk_debug_sort_u64
+        fn.restype = C.c_int
+        fn.argtypes = [C.c_void_p, C.c_void_p, C.c_uint64, C.c_uint32, C.c_void_p, C.POINTER(C.c_int), C.c_void_p]
+        a = np.ascontiguousarray(keys, dtype=np.uint64)
+        out = np.zeros(len(a), dtype=np.uint64)
+        guards = np.zeros(len(self.DEBUG_SORT_GUARDS), dtype=np.uint32)
+        which = C.c_int(-1)
+        self._check(fn(self.h, _ptr(a), len(a), end_bit, _ptr(out), C.byref(which), _ptr(guards)), "shk_debug_sort_u64")
+        return out, int(which.value), guards
+
     # ---- classification --------------------------------------------------------
     def _host_batch(self, seq1, off1, seq2, off2, qual1, qual2):
         seq1, seq2, qual1, qual2 = _u8(seq1), _u8(seq2), _u8(qual1), _u8(qual2)

@@ -12,6 +12,9 @@
 
 namespace shk {
 
+static_assert(RS_THREADS == 256, "one thread per digit: the kernels below index h[], run[] and hist[] by threadIdx.x");
+static_assert(RS_THREADS % 64 == 0 && RS_TILE == RS_THREADS * RS_ITEMS, "whole waves; a tile is RS_ITEMS rows of RS_THREADS keys");
+
 __global__ __launch_bounds__(RS_THREADS) void rs_histogram_kernel(const uint64_t *__restrict__ keys, uint64_t n, unsigned shift,
                                                                   uint32_t *__restrict__ hist, uint32_t n_blocks)
 {

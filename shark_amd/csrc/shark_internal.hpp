@@ -153,6 +153,26 @@ struct DeviceIndex {
 // SHK_DEBUG_KTMETA_WORDS uint64_t scalars on every index, in this order: ktab_lg, ktab_w, ktab_keys (all 0 without the table; a name
 // of its own, as kxmeta and pmeta: `meta` keeps its 16 words).
 // Exported from the library but deliberately not declared in include/shark_hip.h; no classify path uses it.
+//
+// Test-only runs of the two device primitives on caller-supplied data (debug_primitives.hip; tests/test_gpu_primitives.py compares
+// them with the exact host models of tests/primitives_model.py).  Both work in any mode of the context, on its device and stream,
+// allocate what they need and free it again:
+//   extern "C" int shk_debug_scan_u32(shk_ctx *, const uint32_t *in, uint64_t n, uint32_t in_off, uint32_t out_off, int in_place,
+//                                     uint32_t *out, uint32_t *in_after, uint64_t *total, uint32_t *guard_changed /* [6] */)
+// runs exclusive_scan_u32 over the n host words `in` with a temp of exactly scan_temp_words(n) words.  in_off / out_off (0 .. 3)
+// place the device copies of in / out that many words behind a 16-byte aligned address -- (0, 0) takes the vector kernels, anything
+// else the item-by-item ones --; in_place != 0 means out == in (the offsets must be equal).  Hands back out[0 .. n), the 64-bit
+// total read through the returned pointer, and in[0 .. n) as it stands afterwards.
+//   extern "C" int shk_debug_sort_u64(shk_ctx *, const uint64_t *keys, uint64_t n, uint32_t end_bit, uint64_t *out, int *which,
+//                                     uint32_t *guard_changed /* [8] */)
+// runs radix_sort_u64 with `hist` of exactly radix_sort_hist_words(n) words and `scan_tmp` of exactly scan_temp_words(that) words.
+// Hands back the n keys of the buffer the function returned and which one that was (0 = a, 1 = b).
+// Guard bands: every device buffer handed down lies inside an allocation of its own between two bands of at least 64 words of a
+// fixed pattern (out's payload, b, temp, hist and scan_tmp start as a second pattern).  guard_changed counts, per buffer, the guard
+// words in front of it and behind it that lost the pattern: scan {in front, in back, out front, out back, temp front, temp back}
+// (in place the out pair repeats the in pair), sort {a, b, hist, scan_tmp} x {front, back}.  All zero unless a kernel wrote outside
+// its arrays.  n == 0 works and changes nothing but the scan's total.
+// As shk_debug_index_array: exported, not declared in include/shark_hip.h, no classify or build path uses them.
 constexpr uint32_t SHK_DEBUG_META_WORDS = 16;
 constexpr uint32_t SHK_DEBUG_KXMETA_WORDS = 6;
 constexpr uint32_t SHK_DEBUG_PMETA_WORDS = 2;
