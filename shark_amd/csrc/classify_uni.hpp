@@ -165,6 +165,11 @@ __device__ unsigned long long shk_stamp_waves[2 * 4096];   // per wave of the la
 #ifndef SHK_KX_ONE_STAGE
 #define SHK_KX_ONE_STAGE 0
 #endif
+// The tiles' round's three results (three pairs per pass): lanes 0, 1, 2 take a pair's verdict each, under one ballot, and one store
+// writes the three counts, one the three inline entries (-DSHK_TRI_PLAIN=1: a branch and two stores per pair, as before; for A/B timing)
+#ifndef SHK_TRI_PLAIN
+#define SHK_TRI_PLAIN 0
+#endif
 // (-DSHK_NO_PARTIAL=1: the round between the cut's two stops is always probed whole, for A/B timing)
 #ifndef SHK_NO_PARTIAL
 #define SHK_NO_PARTIAL 0

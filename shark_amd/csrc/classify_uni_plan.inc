@@ -30,6 +30,10 @@
   uint32_t tri_lp = 0, tri_pr = 0, tri_cl = 0, tri_bofs = 0, tri_tail = 0, tri_Lm = 0;
   bool tri_act = false;
   const uint8_t *tri_base = nullptr;
+  // (the tiles' round's results, lanes 0, 1, 2 = pairs 0, 1, 2 of the triple) the lane's pair -- ~0: none, behind every batch's end --
+  // and where the pair's sixteen tiles stand in the round's ballot
+  const uint32_t tfr_pair = (uint32_t)lane < 3u ? (uint32_t)lane : ~0u;
+  const uint32_t tfr_sh = (uint32_t)lane < 3u ? 16u * (uint32_t)lane : 0u;
   if (TRI) {
     const uint32_t c1 = (L1 + 15u) >> 4, c2 = (L2 + 15u) >> 4;
     tri_lp = c1 + c2;
@@ -84,6 +88,9 @@
   constexpr bool THRTAB = TRI && !TRO;
   uint32_t thr_tab = 0u;
   if constexpr (THRTAB) thr_tab = cov_threshold(P.c, L1 + L2 > (uint32_t)lane ? L1 + L2 - (uint32_t)lane : 0u);
+  // (the tiles' round, uniform batch) cnt k >= thr_full as a number of tiles: cnt >= ceil(thr_full / k), once per wave
+  uint32_t tf_need = 0u;
+  if constexpr (THRTAB) tf_need = k ? (thr_full + k - 1u) / k : 0u;
   // ---- the sparse first round (one-gene index in LDS; DESIGN.md 3).  With ONE gene in the index nothing competes: a read is that
   // gene's iff the bases covered by its k-mers that are in the filter reach c * len, and a LOWER bound on that coverage which
   // passes settles it.  So the 128 probes in front of the cut's stop are made in another order: round A = the even slots of

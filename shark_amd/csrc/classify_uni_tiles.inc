@@ -77,6 +77,45 @@
           hit = hit & ((win & km) == km);
         }
         const uint64_t Hb = __ballot(hit);
+        // (the hashed offsets form stands at 128 VGPRs with XXH64's state and spills with one lane constant more: it keeps the form below)
+        constexpr bool TF_BY_LANES = !SHK_TRI_PLAIN && !(TRO && !KX);
+        // lanes 0, 1, 2 each own pair p = lane: its sixteen tiles' popcount and its threshold per lane, ONE ballot for the three verdicts
+        // -- tf_done is that ballot, a scalar by construction --, and under it one store of the three counts (consecutive dwords) and
+        // one of the three inline entries (24 consecutive bytes), from a scalar base and the lane's constant offset
+        // (TRO: tro_thr holds pair p's own threshold in lane p -- of its two lengths; a pair with N has a lower one still: passing this
+        //  one is sufficient.  Uniform batch: tf_need tiles, the plan's threshold as a number of tiles)
+        if constexpr (TF_BY_LANES) {
+          // (the asm statements are empty: they keep a scalar a scalar -- left to itself the compiler adds the lane's number to 3 it, and
+          //  to both addresses, with a v_mad_u64_u32 each)
+          uint32_t it3 = 3u * it;
+          asm("" : "+s"(it3));
+          // (the offsets form stands at 128 VGPRs: it keeps ONE lane constant and shifts it here, three full-rate instructions a triple;
+          //  the shift by 16 (~0): bits 48 ... of the ballot, and the lane has no pair)
+          uint32_t tfr_p = tfr_pair, tfr_s = tfr_sh;
+          if constexpr (TRO) {
+            asm volatile("" : "+v"(tfr_p));
+            tfr_s = tfr_p << 4;
+          }
+          const uint32_t cnt = (uint32_t)__builtin_popcount((uint32_t)(Hb >> (tfr_s & 63u)) & 0xFFFFu);
+          bool pass = tfr_p < n_reads - it3;               // (it3 < n_reads; a lane behind the third has no pair: tfr_pair = ~0)
+          if constexpr (TRO && !(SHK_TRO_ABL & 2)) pass = pass && tro_thr != 0u && __umul24(cnt, k) >= tro_thr;
+          else if constexpr (TRO) pass = pass && thr_full != 0u && __umul24(cnt, k) >= thr_full;
+          else pass = pass && cnt >= tf_need;
+          tf_done = (uint32_t)__builtin_amdgcn_ballot_w64(pass);
+          if (pass && !SHK_ABL(P, 64u)) {
+            // (global, not flat: the scalar base stays in its two SGPRs, the lane's offset is the instruction's vector operand)
+            typedef __attribute__((address_space(1))) uint32_t GlobalU32;
+            typedef __attribute__((address_space(1))) uint64_t GlobalU64;
+            typedef __attribute__((address_space(1))) char GlobalChar;
+            constexpr uint32_t INL_BYTES = (uint32_t)(SHK_INLINE_IDS * sizeof(uint16_t));
+            GlobalChar *cb = (GlobalChar *)sp_count + 4ull * it3;
+            GlobalChar *ib = (GlobalChar *)sp_inl + (uint64_t)INL_BYTES * it3;
+            uint32_t co = tfr_p << 2, io = tfr_p * INL_BYTES;
+            asm("" : "+s"(cb), "+s"(ib), "+v"(co), "+v"(io));   // (the offsets too: widened to 64 bits in front of the loop they are no operand of the store any more)
+            *(GlobalU32 *)(cb + co) = 1u;
+            *(GlobalU64 *)(ib + io) = (uint64_t)(P.lx_gene & 0xFFFFu);   // {the gene, 0, 0, 0}
+          }
+        } else {
 #pragma unroll
         for (uint32_t p3 = 0; p3 < 3u; ++p3) {
           const uint32_t cnt = (uint32_t)__builtin_popcount((uint32_t)(Hb >> (16u * p3)) & 0xFFFFu);
@@ -95,6 +134,7 @@
             }
             tf_done |= 1u << p3;
           }
+        }
         }
       }
     }
