@@ -170,6 +170,11 @@ __device__ unsigned long long shk_stamp_waves[2 * 4096];   // per wave of the la
 #ifndef SHK_TRI_PLAIN
 #define SHK_TRI_PLAIN 0
 #endif
+// The sparse rounds of a one-gene index: a pair without a candidate in round A runs round B and the bound cut as straight code of its
+// own, apart from everything a candidate needs (-DSHK_SPARSE_PLAIN=1: one sequence for every pair, as before; for A/B timing)
+#ifndef SHK_SPARSE_PLAIN
+#define SHK_SPARSE_PLAIN 0
+#endif
 // (-DSHK_NO_PARTIAL=1: the round between the cut's two stops is always probed whole, for A/B timing)
 #ifndef SHK_NO_PARTIAL
 #define SHK_NO_PARTIAL 0
@@ -599,6 +604,40 @@ __global__ __launch_bounds__((UniGeom<U, MODE, LSL>::THREADS), (UniGeom<U, MODE,
     }
 
     SHK_STAMP(11);
+    // ---- THE MISS PATH (SP_STRAIGHT: the sparse order of a one-gene index; spT != 0 is the whole condition -- plan_sparse sets it only
+    // with cutE == 2 and sp_on).  Round A's candidate stage on every lane and one ballot; no candidate: round B's and one ballot; none
+    // again and what the other slots cover under the threshold: the pair is through -- every pair from elsewhere, straight down these
+    // lines, with no confirm stage, no slot_valid, no coverage, no look at cutE and no wave-uniform bool of the general code behind it,
+    // which a pair with a candidate enters as ever (classify_staged<2> -> sparse_first) and finds the rounds' answers in mp_*.
+    // (Here and not inside classify_staged: a return from in there leaves through every stop of the general sequence, a scalar flag
+    //  tested at each; from here it is one.)
+    // (A's are set whenever sparse_first runs, B's whenever it reads them: not initialised, or every pair with a candidate in A pays for
+    //  the zeros of B's on its way)
+    [[maybe_unused]] bool mp_hA, mp_hB;
+    [[maybe_unused]] uint64_t mp_HA, mp_HB;
+    [[maybe_unused]] uint32_t mp_tgA, mp_s2A, mp_tgB, mp_s2B;
+    if constexpr (SP_STRAIGHT) {
+      // (the empty asm: the test is a scalar compare of spT here -- left to itself the compiler keeps `spT != 0` from in front of the loop
+      //  as a 64-bit lane mask, spilled, and builds its complement with two vector instructions per pair)
+      uint32_t sp_go = spT;
+      asm volatile("" : "+s"(sp_go));
+      if (sp_go) {
+        const uint32_t nA = 64u - spT, ln = (uint32_t)lane;
+        uint32_t pay;
+        SHK_STAMP(12);
+        SHK_STAMP(2);
+        mp_hA = lx_probe(fw, rv, ln >= nA ? spLast - (ln - nA) * k : 2u * ln, pay, std::true_type{}, mp_tgA, mp_s2A);   // (sparse_first's sA)
+        mp_HA = __ballot(mp_hA);
+        SHK_STAMP(3);
+        if (!mp_HA) {
+          SHK_STAMP(4);
+          mp_hB = lx_probe(fw, rv, ln < nA - 1u ? 2u * ln + 1u : ln + nA, pay, std::true_type{}, mp_tgB, mp_s2B);       // (its sB)
+          mp_HB = __ballot(mp_hB);
+          SHK_STAMP(5);
+          if (!mp_HB && spUb < thr_r) return;   // the bound cut: nothing of the prefix is in the filter
+        }
+      }
+    }
     // ---- everything behind the staging, for a compile-time E: rounds [0, E) first; E == U: all at once, no cut; E < 0: the anchored
     // extension (table modes), which returns false when the read has to take one of the other sequences after all.
     // (State and steps are declared INSIDE the lambda: shared between its instantiations from outside, hipcc 7.2 stops with

@@ -112,6 +112,9 @@
   // sp_one: ONE gene in the index (the argument above).  Several genes (the LXM instantiation): the same two rounds in the same order
   // settle a read too, by the early decision's argument instead -- see sparse_first
   constexpr bool sp_one = !LXM;
+  // SP_STRAIGHT: the pair without a candidate in round A or B -- every pair from elsewhere -- as straight code of its own (per_pair,
+  // classify_uni.hpp: the miss path); sparse_first takes over what its two rounds found
+  constexpr bool SP_STRAIGHT = SPARSE && sp_one && !SHK_SPARSE_PLAIN;
   const bool sp_on = SPARSE && (LXM ? P.lx_multi != 0u : P.lx_gene != 0xFFFFFFFFu);
   // floor(x / k) and floor(x / (k - 1)) for x < 2048 as a multiplication (k <= 32)
   const uint32_t sp_rk = sp_on ? (65536u + k - 1u) / k : 0u, sp_rk1 = (sp_on && k > 1u) ? (65536u + k - 2u) / (k - 1u) : 0u;

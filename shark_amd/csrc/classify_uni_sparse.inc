@@ -44,32 +44,48 @@
       };
       const bool tile = ln >= nA;
       const uint32_t sA = tile ? spLast - (ln - nA) * k : 2u * ln;
-      uint32_t pA = 0u, pB = 0u, tgA = 0u, tgB = 0u, s2A = 0u, s2B = 0u;
-      SHK_STAMP(2);
-      bool hA = lx_hit_at(sA, true, pA, tgA, s2A);
-      uint64_t HA = __ballot(hA);
-      SHK_STAMP(3);
-      if (HA) {
-        hA = hA && lx_confirm(tgA, s2A) && slot_valid(sA);   // (the entry's other bits; the slot has to exist and be a valid k-mer)
-        HA = __ballot(hA);
-      }
-      if (HA && sp_one) {
-        // bases covered by what matched: an even slot adds min(k, distance to the next even match), a tile k
-        const uint64_t H1 = HA & ((1ull << nA) - 1ull);
-        const uint64_t nx = (H1 >> ln) >> 1;
-        const uint32_t step = nx ? 2u * ((uint32_t)__builtin_ctzll(nx) + 1u) : k;
-        const uint32_t cov = wave_sum_u32((hA && !tile) ? (step < k ? step : k) : 0u) + k * (uint32_t)__builtin_popcountll(HA >> nA);
-        if (cov >= thr_r) {
-          write_the_gene(P.lx_gene);
-          SHK_STAMP(4);
-          return 1;
-        }
-      }
-      SHK_STAMP(4);
       const uint32_t sB = ln < nA - 1u ? 2u * ln + 1u : ln + nA;
-      bool hB = lx_hit_at(sB, true, pB, tgB, s2B);
-      uint64_t HB = __ballot(hB);
-      SHK_STAMP(5);
+      uint32_t pA = 0u, pB = 0u, tgA = 0u, tgB = 0u, s2A = 0u, s2B = 0u;
+      bool hA, hB = false;
+      uint64_t HA, HB = 0ull;
+      if constexpr (SP_STRAIGHT) {
+        // round A's candidate stage was per_pair's (the miss path, classify_uni.hpp) -- and round B's too where A had no candidate:
+        // what they left is taken over, no round is probed twice
+        // (the empty asm: A's ballot is looked at again here, two scalar instructions -- told where it came from, the compiler carries
+        //  "B was probed" as a lane mask of its own from there to here, spilled on the way)
+        hA = mp_hA; HA = mp_HA; tgA = mp_tgA; s2A = mp_s2A;
+        asm volatile("" : "+s"(HA));
+      } else {
+        SHK_STAMP(2);
+        hA = lx_hit_at(sA, true, pA, tgA, s2A);
+        HA = __ballot(hA);
+        SHK_STAMP(3);
+      }
+      if (SP_STRAIGHT && !HA) {
+        hB = mp_hB; HB = mp_HB; tgB = mp_tgB; s2B = mp_s2B;
+      } else {
+        if (HA) {
+          hA = hA && lx_confirm(tgA, s2A) && slot_valid(sA);   // (the entry's other bits; the slot has to exist and be a valid k-mer)
+          HA = __ballot(hA);
+        }
+        if (HA && sp_one) {
+          // bases covered by what matched: an even slot adds min(k, distance to the next even match), a tile k
+          const uint64_t H1 = HA & ((1ull << nA) - 1ull);
+          const uint64_t nx = (H1 >> ln) >> 1;
+          const uint32_t step = nx ? 2u * ((uint32_t)__builtin_ctzll(nx) + 1u) : k;
+          const uint32_t cov = wave_sum_u32((hA && !tile) ? (step < k ? step : k) : 0u) + k * (uint32_t)__builtin_popcountll(HA >> nA);
+          if (cov >= thr_r) {
+            write_the_gene(P.lx_gene);
+            SHK_STAMP(4);
+            return 1;
+          }
+        }
+        SHK_STAMP(4);
+        hB = lx_hit_at(sB, true, pB, tgB, s2B);
+        HB = __ballot(hB);
+        SHK_STAMP(5);
+      }
+      // (a pair with a candidate in A or B joins here, hA / tgA / s2A and B's as the rounds left them: no round is probed twice)
       if (HB) {
         hB = hB && lx_confirm(tgB, s2B) && slot_valid(sB);
         HB = __ballot(hB);
