@@ -695,8 +695,8 @@ int shk_variants_summary(shk_ctx *ctx, const shk_variant_params *p, shk_gene_var
  *   - by default the mate's ends outside its outermost blocks are not extended: they become soft clips (step 3a extends them base
  *     by base where shk_alignments_extend asks for it; an overhang past a junction still stays a clip: the mode does not look for
  *     the other side of the intron);
- *   - no pair-level claim is made: no proper-pair flag, no template length;
- *   - there is no mapping quality.
+ *   - the records themselves make no pair-level claim and carry no mapping quality: orientation, template length, the proper-pair
+ *     flag and MAPQ are pairs mode's (the next section), which reads these records and changes none of them.
  *
  * Independent of every other mode: gene_off, gene_ids, n_assoc, shk_last_kernel, shk_gene_counts and every other mode's records and
  * state are the same with the mode on and off.  It reads segments_kernel's records at m = SHK_MAX_SEGMENTS as spliced depth, the
@@ -735,6 +735,89 @@ int shk_alignments_last(const shk_ctx *ctx, shk_alignments *out);
  * inconsistent: more than 4 blocks, a block of length 0, blocks that do not ascend without overlap in x and in q, a block that ends
  * behind L.  New: no counterpart. */
 int shk_alignment_cigar(const shk_mate_alignment *a, uint32_t L, uint32_t min_intron, char *buf, size_t cap, uint32_t *nm);
+
+/* ---- pairs: what the two mates of an association say together -- orientation, template, proper pair, MAPQ, fragment sizes ---- */
+/* Alignments mode stops at the mate.  Pairs mode reads the two 64-byte records of an association side by side, the mates' lengths and
+ * the read's number of associations, and hands out one 32-byte record per ASSOCIATION plus one aggregate over the sample: the
+ * fragment-size histogram.  It rests on the alignments section's definitions, unchanged: block {x, q, len}, read coordinate (q counts
+ * in the RECORD'S orientation on either strand), strand, and G = x_B - (x_A + len_A) between consecutive blocks A, B.  It changes no
+ * alignment record.  Parameters: min_intron >= 1, max_frag, n_bins (2 .. 4096).  Integers only, no tolerance anywhere; a consistent
+ * alignment record (blocks ascending and disjoint inside [0, len_g) and [0, L)) makes no difference below negative.
+ *
+ * PER MATE.  For an association (read i, gene g) take each mate m (0: mate 1, 1: mate 2) whose record has n_blocks >= 1; `last` is
+ * block[n_blocks - 1]; L_m is the mate's length in bytes as align_kernel takes it, min(length, 2^31 - 1):
+ *     s_m  = block[0].x                      the first record base under the mate
+ *     e_m  = last.x + last.len               one behind the last
+ *     cl_m = block[0].q                      read bases clipped on the record's LEFT
+ *     cr_m = L_m - (last.q + last.len)       read bases clipped on the record's RIGHT
+ *     intron intervals  [x_A + len_A, x_B)  for consecutive blocks A, B of the mate with G >= min_intron: exactly the gaps
+ *                       shk_alignment_cigar writes as N at that min_intron (at most three per mate, six per association).
+ * The mate on strand 0 reads along the record, so its 5' end is on the left and cl is what it lacks there; the mate on strand 1
+ * reads against it, so its 5' end is on the right and cr is what it lacks there.
+ *
+ * PER ASSOCIATION: shk_pair.
+ *   cls      0  no mate has a block.  Every other field but mapq is 0.
+ *            1  only mate 1 has a block.           2  only mate 2 has a block.
+ *            both have blocks, on different strands; F is the mate on strand 0, R the mate on strand 1:
+ *            3  (inward)   s_F <= s_R and e_F <= e_R        4  (outward)  otherwise
+ *            5  (tandem)   both have blocks on the same strand.
+ *            (Mates that dovetail -- s_F <= s_R but e_F > e_R -- and an F that contains R are therefore outward, not inward.)
+ *   left     the mate (0 or 1) with the smaller s; ties go to the smaller e, then to mate 0.  cls 1: 0; cls 2: 1.
+ *   tstart   the smallest s, tend the largest e, over the mates with blocks.
+ *   introns  the length of the UNION of both mates' intron intervals: two mates that cross the same intron count it once, two
+ *            introns that overlap in part count every record base once.
+ *   frag     cls 3 only, else 0:   (tend - tstart) - introns + cl_F + cr_R
+ *            the template from one mate's 5' end to the other's: the span on the record, with the introns either mate SHOWS taken
+ *            out and the clipped outer ends put back.  An intron that lies wholly inside the unsequenced insert between the mates
+ *            is invisible to both and stays in: there frag is an UPPER BOUND of the fragment's length, not the length.
+ *   proper   1 iff cls == 3 and frag <= max_frag, else 0.
+ *   mapq     from the read's number of associations n = gene_off[i + 1] - gene_off[i] alone, the STAR scale with 60 for a unique
+ *            read:  n = 1: 60;  n = 2: 3;  n = 3 or 4: 1;  n >= 5: 0.  Set on every association of the read, cls 0 included.
+ * A single-end batch has no mate 2 record with a block: cls 0 or 1 only.
+ * Example: L = 60 both; mate 1 on strand 0 with blocks {100, 2, 58}; mate 2 on strand 1 with blocks {300, 0, 20}, {1400, 20, 37}
+ * (3 bases clipped on the right), min_intron = 20: s = 100, 300; e = 158, 1437; cls 3, left 0, tstart 100, tend 1437, introns 1080
+ * ([320, 1400)), frag = 1337 - 1080 + 2 + 3 = 262.
+ *
+ * FRAGMENTS STATE, on the device, accumulated over all COUNTED batches under depth's, pileup's and the junction table's rule word for
+ * word: a batch is counted exactly once (a batch with more associations than the result buffer holds, or with reads beyond a length
+ * bound taken on trust, is counted when the tail runs again; a batch vouched for wrongly and a shk_count_work batch are never
+ * counted -- the latter still gets its records).
+ *   classes[6]    uint64: every association adds 1 to classes[cls];
+ *   hist[n_bins]  uint64: an association with cls == 3 of a read with EXACTLY ONE association adds 1 to hist[min(frag, n_bins - 1)].
+ *                 The last bin is the overflow bin: every frag >= n_bins - 1.
+ *
+ * Kernel (pairs.hip): pair_kernel directly behind the align_kernel launch that stores the records, one lane per read; a workgroup keeps
+ * the histogram in LDS and flushes its non-zero bins once.  Independent of every other mode: gene_off, gene_ids, n_assoc,
+ * shk_last_kernel, shk_gene_counts, the alignment records and every other mode's records and state are the same with the mode on and
+ * off.  With the mode off no launch and no allocation is added.  New: the reference has no counterpart. */
+typedef struct shk_pair {
+  uint32_t cls, left, proper, mapq;
+  int32_t  tstart, tend;
+  uint32_t introns, frag;
+} shk_pair;                                    /* 32 bytes */
+typedef struct shk_pairs {
+  uint64_t        n_assoc;                     /* = that result's n_assoc */
+  const shk_pair *entries;                     /* n_assoc records, parallel to gene_ids */
+} shk_pairs;
+/* Switches pairs mode on (n_bins in 2 .. 4096, min_intron >= 1; anything else is SHK_ERR_ARG) or off (n_bins == 0; the other two are
+ * ignored) for the batches submitted AFTERWARDS, through any of the four families.  State rules are shk_alignments_enable's; switching
+ * on also returns SHK_ERR_STATE while alignments mode is off.  A batch gets pair records (and is counted) only if it was submitted
+ * with alignments mode on as well: switching alignments mode off later leaves pairs mode set and idle.  The first enable allocates
+ * and clears the fragments state; a later enable with another n_bins returns SHK_ERR_ARG unless no batch was submitted with the mode
+ * on since the first enable or the last shk_fragments_reset (the state is then allocated anew) -- shk_junctions_enable's rule for its
+ * capacity.  Switching off keeps the state.  New: no counterpart. */
+int shk_pairs_enable(shk_ctx *ctx, uint32_t min_intron, uint32_t max_frag, uint32_t n_bins);
+/* The pair records of the batch whose result was handed out LAST, with shk_alignments_last's rules: that result's lifetime and memory
+ * space (pinned host memory for host batches, DEVICE memory for resident ones).  SHK_ERR_STATE if that batch was submitted without
+ * pairs mode (or without alignments mode), if its wait returned an error, behind shk_count_work, or if no batch has been waited for
+ * yet.  New: no counterpart. */
+int shk_pairs_last(const shk_ctx *ctx, shk_pairs *out);
+/* The fragments state's read-out and reset, with depth's rules: SHK_ERR_STATE if pairs mode was never enabled on this context or
+ * while tickets are outstanding; stream-ordered behind everything enqueued so far; the read-out leaves the state untouched.
+ *   shk_fragments_get    hist[0 .. n_bins) and classes[0 .. 6) into host memory; SHK_ERR_ARG if n_bins is not the state's
+ *   shk_fragments_reset  clears both (the mode and n_bins stay as they are) */
+int shk_fragments_get(shk_ctx *ctx, uint64_t *hist, uint32_t n_bins, uint64_t classes[6]);
+int shk_fragments_reset(shk_ctx *ctx);
 
 /* Per-gene number of assigned reads accumulated over all classify calls (all
  * waited tickets) since the last reset (counts[g] for g in [0, 65536)); the quantity all-reduced

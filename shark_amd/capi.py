@@ -75,6 +75,19 @@ assert ALIGNMENT_DTYPE.itemsize == 64
 SAM_DEFAULT_MIN_INTRON = 20
 
 
+class ShkPairs(C.Structure):
+    _fields_ = [("n_assoc", C.c_uint64), ("entries", C.c_void_p)]
+
+
+# shk_pair as a numpy record (32 bytes)
+PAIR_DTYPE = np.dtype([("cls", np.uint32), ("left", np.uint32), ("proper", np.uint32), ("mapq", np.uint32),
+                       ("tstart", np.int32), ("tend", np.int32), ("introns", np.uint32), ("frag", np.uint32)])
+assert PAIR_DTYPE.itemsize == 32
+PAIR_CLASS_NAMES = ("none", "mate1", "mate2", "inward", "outward", "tandem")
+FRAGMENTS_DEFAULT_MAX = 1000
+FRAGMENTS_DEFAULT_BINS = 1024
+
+
 class ShkVariantParams(C.Structure):
     _fields_ = [("min_depth", C.c_uint32), ("min_alt", C.c_uint32), ("frac_num", C.c_uint32), ("frac_den", C.c_uint32)]
 
@@ -108,6 +121,7 @@ EXPORTS = [
     "shk_pileup_add", "shk_ref_keep_bases", "shk_variants_get", "shk_variants_summary",
     "shk_ref_kmer_table",
     "shk_alignments_enable", "shk_alignments_last", "shk_alignment_cigar", "shk_alignments_extend", "shk_pileup_enable_aligned",
+    "shk_pairs_enable", "shk_pairs_last", "shk_fragments_get", "shk_fragments_reset",
 ]
 SHK_PIPE_DEPTH = 3
 SHK_DIST_ID_BYTES = 128
@@ -204,6 +218,10 @@ def load():
         "shk_pileup_enable_aligned": (C.c_int, [p, C.c_uint32]),
         "shk_alignments_last": (C.c_int, [p, C.POINTER(ShkAlignments)]),
         "shk_alignment_cigar": (C.c_int, [p, C.c_uint32, C.c_uint32, C.c_char_p, C.c_size_t, C.POINTER(C.c_uint32)]),
+        "shk_pairs_enable": (C.c_int, [p, C.c_uint32, C.c_uint32, C.c_uint32]),
+        "shk_pairs_last": (C.c_int, [p, C.POINTER(ShkPairs)]),
+        "shk_fragments_get": (C.c_int, [p, p, C.c_uint32, p]),
+        "shk_fragments_reset": (C.c_int, [p]),
     }
     variant = bool(os.environ.get("SHK_LIB_PATH"))
     for name, (res, args) in later.items():
@@ -691,6 +709,36 @@ class SharkHip:
         raw = np.ctypeslib.as_array(C.cast(al.entries, C.POINTER(C.c_uint32)), shape=(n, 2, 16)).copy()
         return alignments_from_raw(raw)
 
+    # ---- pairs: per association what its two mates' alignments say together, and the sample's fragment-size histogram --------
+    def pairs_enable(self, min_intron=SAM_DEFAULT_MIN_INTRON, max_frag=FRAGMENTS_DEFAULT_MAX, n_bins=FRAGMENTS_DEFAULT_BINS):
+        """batches submitted from now on (with alignments mode on) carry one PAIR_DTYPE record per association and are added to the
+        fragments state (classes[6], hist[n_bins]); n_bins 0 switches the mode off and keeps the state; needs alignments mode on"""
+        self._check(self.L.shk_pairs_enable(self.h, int(min_intron), int(max_frag), int(n_bins)), "shk_pairs_enable")
+
+    def pairs_last(self):
+        """pair records of the batch whose result was handed out last: (n_assoc,) records of PAIR_DTYPE, parallel to gene_ids, copied
+        from the context's pinned memory for a host batch; for a resident one (n_assoc, DEVICE pointer) -- pairs_from_device reads them
+        back.  Raises (SHK_ERR_STATE) when that batch was submitted without the mode"""
+        pr = ShkPairs()
+        self._check(self.L.shk_pairs_last(self.h, C.byref(pr)), "shk_pairs_last")
+        n = int(pr.n_assoc)
+        if not self._last_on_host:
+            return n, pr.entries
+        if n == 0:
+            return np.zeros(0, dtype=PAIR_DTYPE)
+        raw = np.ctypeslib.as_array(C.cast(pr.entries, C.POINTER(C.c_uint32)), shape=(n, 8)).copy()
+        return raw.view(PAIR_DTYPE).reshape(-1)
+
+    def fragments(self, n_bins=FRAGMENTS_DEFAULT_BINS):
+        """the fragments state: (hist uint64 (n_bins,), classes uint64 (6,)); n_bins must be the state's"""
+        hist = np.zeros(int(n_bins), dtype=np.uint64)
+        classes = np.zeros(6, dtype=np.uint64)
+        self._check(self.L.shk_fragments_get(self.h, _ptr(hist), int(n_bins), _ptr(classes)), "shk_fragments_get")
+        return hist, classes
+
+    def fragments_reset(self):
+        self._check(self.L.shk_fragments_reset(self.h), "shk_fragments_reset")
+
     # ---- variants: the record positions where the pileup shows another base than the record (needs an index built with keep_bases) --------
     def variants(self, min_depth=8, min_alt=3, frac=(1, 5)):
         """the sites of the pileup state at these thresholds (include/shark_hip.h, "variants"): a structured array (VARIANT_DTYPE: gene,
@@ -859,6 +907,14 @@ def alignments_from_device(n_assoc, ptr):
     if n_assoc:
         hip_memcpy_dtoh(raw, ptr, raw.nbytes)
     return alignments_from_raw(raw)
+
+
+def pairs_from_device(n_assoc, ptr):
+    """read the records of a resident batch back: (n_assoc,) records of PAIR_DTYPE as pairs_last gives them"""
+    raw = np.zeros((n_assoc, 8), dtype=np.uint32)
+    if n_assoc:
+        hip_memcpy_dtoh(raw, ptr, raw.nbytes)
+    return raw.view(PAIR_DTYPE).reshape(-1)
 
 
 def cigar(rec, L, min_intron=SAM_DEFAULT_MIN_INTRON):

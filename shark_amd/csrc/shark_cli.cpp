@@ -123,6 +123,17 @@ const char *USAGE_MESSAGE =
     "                                        clips; the same refusals as --segments; combines with every other output)\n"
     "          --sam-min-support N           unique k-mers a diagonal of a mate needs to become a block of --sam (default:8)\n"
     "          --sam-min-intron N            record bases a gap between two blocks needs to be written as N, not D (default:20)\n"
+    "          --sam-pairs                   --sam: fill in the pair-level fields -- MAPQ from the read's number of genes (1: 60, 2: 3, 3-4: 1,\n"
+    "                                        more: 0), 0x2 on both lines of an inward pair whose fragment is at most --fragments-max, TLEN\n"
+    "                                        = the pair's span on the record, positive on the left mate's line (needs --sam FILE)\n"
+    "          --fragments FILE              write the sample's pair classes and fragment-size histogram, accumulated on the GPUs: six\n"
+    "                                        lines `class <name> <count>` (none mate1 mate2 inward outward tandem; every association),\n"
+    "                                        one line `frag <len> <count>` per non-empty bin and `frag >=<bins-1> <count>` for the rest\n"
+    "                                        (inward pairs of reads with one gene; introns either mate shows are taken out; alignments as\n"
+    "                                        --sam's, at --sam-min-support; the same refusals as --sam)\n"
+    "          --fragments-max N             the longest fragment of a proper pair (default:1000)\n"
+    "          --fragments-bins N            bins of the histogram, the last one open-ended (2 .. 4096, default:1024)\n"
+    "          --fragments-min-intron N      record bases a gap needs to count as an intron of the pair (default: --sam-min-intron's)\n"
     "          --extend-ends                 --sam and --pileup-aligned: grow a mate's outermost blocks over its clipped ends base by base\n"
     "                                        (match 1, mismatch 4, 5 for reaching the mate's end), so that a substitution within k of\n"
     "                                        an end is shown instead of clipped\n"
@@ -182,6 +193,11 @@ struct Options {
   FILE *sam_file = nullptr;        // (--sam, likewise; the header is written once the reference is read, the lines per batch)
   unsigned sam_min_support = 8, sam_min_intron = 20;
   bool sam_sub_flag_given = false;
+  bool sam_pairs = false;                 // (--sam-pairs)
+  std::string fragments_path;
+  FILE *fragments_file = nullptr;  // (--fragments, likewise; written once, after the last batch)
+  unsigned fragments_max = 1000, fragments_bins = 1024, fragments_min_intron = 0;   // (0: --sam-min-intron's value)
+  bool fragments_sub_flag_given = false;
   bool extend_ends = false;               // (--extend-ends; --extend-penalty, --extend-bonus)
   unsigned extend_penalty = 4, extend_bonus = 5;
   bool extend_sub_flag_given = false;
@@ -367,6 +383,25 @@ const OptionRow OPTION_TABLE[] = {
        if (o.extend_bonus > 15) reject(USAGE_MESSAGE, "shark: --extend-bonus must be in the range [0, 15].");
      }},
     {1030, "pileup-aligned", false, [](Options &o, const char *) { o.pileup_aligned = true; }},
+    {1031, "sam-pairs", false, [](Options &o, const char *) { o.sam_pairs = true; }},
+    {1032, "fragments", true, [](Options &o, const char *v) { o.fragments_path = value_of<std::string>(v); }},
+    {1033, "fragments-max", true,
+     [](Options &o, const char *v) {
+       o.fragments_max = value_of<unsigned>(v);
+       o.fragments_sub_flag_given = true;
+     }},
+    {1034, "fragments-bins", true,
+     [](Options &o, const char *v) {
+       o.fragments_bins = value_of<unsigned>(v);
+       o.fragments_sub_flag_given = true;
+       if (o.fragments_bins < 2 || o.fragments_bins > 4096) reject(USAGE_MESSAGE, "shark: --fragments-bins must be 2 to 4096.");
+     }},
+    {1035, "fragments-min-intron", true,
+     [](Options &o, const char *v) {
+       o.fragments_min_intron = value_of<unsigned>(v);
+       o.fragments_sub_flag_given = true;
+       if (o.fragments_min_intron < 1) reject(USAGE_MESSAGE, "shark: --fragments-min-intron must be at least 1.");
+     }},
 };
 
 // Reads per device batch when --batch does not say.  A batch costs the device path 0.5-2 ms of launches, copies and bookkeeping
@@ -437,6 +472,12 @@ Options parse_arguments(int argc, char **argv)
   if (!opt.variants_path.empty() && !opt.pileup_path.empty() && opt.variants_min_support != opt.pileup_min_support)
     reject(USAGE_MESSAGE, "shark: --variants-min-support and --pileup-min-support must be equal (there is one pileup).");
   if (opt.sam_sub_flag_given && opt.sam_path.empty()) reject(USAGE_MESSAGE, "shark: --sam-min-support and --sam-min-intron need --sam FILE.");
+  if (opt.sam_pairs && opt.sam_path.empty()) reject(USAGE_MESSAGE, "shark: --sam-pairs needs --sam FILE.");
+  if (opt.fragments_sub_flag_given && opt.fragments_path.empty() && !opt.sam_pairs)
+    reject(USAGE_MESSAGE, "shark: --fragments-max, --fragments-bins and --fragments-min-intron need --fragments FILE (or --sam FILE --sam-pairs).");
+  if (opt.fragments_min_intron == 0) opt.fragments_min_intron = opt.sam_min_intron;
+  if ((opt.sam_pairs || !opt.fragments_path.empty()) && opt.fragments_min_intron < 1)
+    reject(USAGE_MESSAGE, "shark: --sam-pairs and --fragments need an intron length of at least 1 (--sam-min-intron, --fragments-min-intron).");
   if (opt.pileup_aligned && opt.pileup_path.empty() && opt.variants_path.empty()) reject(USAGE_MESSAGE, "shark: --pileup-aligned needs --pileup FILE or --variants FILE.");
   if (opt.extend_sub_flag_given && !opt.extend_ends) reject(USAGE_MESSAGE, "shark: --extend-penalty and --extend-bonus need --extend-ends.");
   if (opt.extend_ends && opt.sam_path.empty() && !opt.pileup_aligned) reject(USAGE_MESSAGE, "shark: --extend-ends needs --sam FILE or --pileup-aligned.");
@@ -574,6 +615,7 @@ struct ReadBatch {
   std::vector<shk_segment> seg_entries;          // ... and 2 x seg_m entries
   uint32_t seg_m = 0;
   std::vector<shk_mate_alignment> alignments;    // (--sam) two records per association
+  std::vector<shk_pair> pairs;                   // (--sam-pairs) one record per association
   int rc = 0;
   void reset()
   {
@@ -584,6 +626,7 @@ struct ReadBatch {
     gene_off.clear(); gene_ids.clear(); evidence.clear(); cand_reads.clear(); cand_entries.clear(); cand_m = 0; placements.clear();
     seg_keys.clear(); seg_entries.clear(); seg_m = 0;
     alignments.clear();
+    pairs.clear();
     rc = 0;
   }
 };
@@ -1028,8 +1071,10 @@ class GzCutter {
 // flight: the copies of the next batches overlap the kernels of the current one (shk_classify_submit / _wait).
 class ReadAnalyzer {
  public:
-  ReadAnalyzer(shk_ctx *ctx, bool need_qual, bool evidence, bool candidates = false, bool placements = false, bool segments = false, bool alignments = false)
-      : ctx_(ctx), need_qual_(need_qual), evidence_(evidence), candidates_(candidates), placements_(placements), segments_(segments), alignments_(alignments) {}
+  ReadAnalyzer(shk_ctx *ctx, bool need_qual, bool evidence, bool candidates = false, bool placements = false, bool segments = false, bool alignments = false,
+               bool pairs = false)
+      : ctx_(ctx), need_qual_(need_qual), evidence_(evidence), candidates_(candidates), placements_(placements), segments_(segments), alignments_(alignments),
+        pairs_(pairs) {}
   // false: the batch failed at once (b.rc is set) and is not in flight
   bool submit(std::unique_ptr<ReadBatch> b)
   {
@@ -1098,13 +1143,18 @@ class ReadAnalyzer {
         b->rc = shk_alignments_last(ctx_, &al);
         if (b->rc == SHK_OK) b->alignments.assign(al.entries, al.entries + 2 * al.n_assoc);
       }
+      if (pairs_ && b->rc == SHK_OK) {
+        shk_pairs pr{};
+        b->rc = shk_pairs_last(ctx_, &pr);
+        if (b->rc == SHK_OK) b->pairs.assign(pr.entries, pr.entries + pr.n_assoc);
+      }
     }
     return b;
   }
 
  private:
   shk_ctx *ctx_;
-  bool need_qual_, evidence_, candidates_, placements_, segments_, alignments_;
+  bool need_qual_, evidence_, candidates_, placements_, segments_, alignments_, pairs_;
   std::deque<std::pair<uint64_t, std::unique_ptr<ReadBatch>>> flying_;
   std::unique_ptr<ReadBatch> failed_;
 };
@@ -1314,10 +1364,10 @@ class ReadOutput {
  public:
   ReadOutput(OffsetWriter *out1, OffsetWriter *out2, const std::vector<std::string> &legend, FILE *evidence = nullptr, FILE *candidates = nullptr,
              FILE *placements = nullptr, bool paired = false, FILE *segments = nullptr, bool junctions = false, uint32_t k = 0, uint32_t junctions_min_support = 8,
-             FILE *sam = nullptr, uint32_t sam_min_intron = 20)
+             FILE *sam = nullptr, uint32_t sam_min_intron = 20, bool sam_pairs = false)
       : out1_(out1), out2_(out2), legend_(legend), evidence_(evidence), candidates_(candidates), placements_(placements), paired_(paired),
         every_read_(evidence || candidates), segments_(segments), junctions_(junctions), k_(k), s_min_(junctions_min_support),
-        sam_(sam), sam_min_intron_(sam_min_intron) {}
+        sam_(sam), sam_min_intron_(sam_min_intron), sam_pairs_(sam_pairs) {}
   bool failed() const { return failed_.load(); }
   bool evidence_write_failed() const { return failed_write_; }
   bool candidates_write_failed() const { return failed_write_cand_; }
@@ -1433,6 +1483,7 @@ class ReadOutput {
         if (!assoc) continue;
         if (placements_ && b.placements.size() != b.gene_ids.size()) failed_ = true;   // (a batch without a record per association: an error exit)
         if (sam_ && b.alignments.size() != 2 * b.gene_ids.size()) failed_ = true;      // (likewise)
+        if (sam_ && sam_pairs_ && b.pairs.size() != b.gene_ids.size()) failed_ = true;  // (likewise)
         const bool seg_mode = segments_ || junctions_;
         if (seg_mode && (b.seg_m == 0 || b.seg_keys.size() != 2 * b.gene_ids.size() || b.seg_entries.size() != 2 * b.gene_ids.size() * b.seg_m)) failed_ = true;   // (likewise)
         for (uint32_t j = b.gene_off[i]; j < b.gene_off[i + 1]; ++j) {
@@ -1476,6 +1527,7 @@ class ReadOutput {
           if (sam_ && 2 * (size_t)(j + 1) <= b.alignments.size()) {
             // (--sam) mate 1's line, then mate 2's; a lean batch's qualities come from the file again, as the FASTQ output's do
             const shk_mate_alignment *al = b.alignments.data() + 2 * (size_t)j;
+            const shk_pair *pr = sam_pairs_ && (size_t)j < b.pairs.size() ? b.pairs.data() + (size_t)j : nullptr;   // (--sam-pairs)
             for (uint32_t t = 0; t < (paired_ ? 2u : 1u); ++t) {
               if (al[t].n_blocks == 0) continue;
               const DevStrings &seq = t ? b.seq2 : b.seq1, &qual = t ? b.qual2 : b.qual1;
@@ -1484,7 +1536,7 @@ class ReadOutput {
               const char *q = nullptr;      // (nullptr: no quality string of the sequence's length -- FASTA input)
               if (b.lean) q = t ? v2.qual : v1.qual;
               else if (i < qual.size() && qual.len(i) == seq.len(i) && odd.find(i) == odd.end()) q = qual.at(i);
-              if (!sam_line(sg.sam, id, id_len, gene, j > b.gene_off[i], paired_, t, al[t], al[1 - t], seq.at(i), seq.len(i), q, sam_min_intron_)) failed_ = true;
+              if (!sam_line(sg.sam, id, id_len, gene, j > b.gene_off[i], paired_, t, al[t], al[1 - t], seq.at(i), seq.len(i), q, sam_min_intron_, pr)) failed_ = true;
             }
           }
           sg.ssv.append(id, id_len);
@@ -1558,8 +1610,11 @@ class ReadOutput {
   // One line of --sam (include/shark_hip.h, "alignments"): `a` is this mate's record, `other` the same association's
   // other mate's.  CIGAR and NM are shk_alignment_cigar's; SEQ and QUAL are the mate's bytes in the record's orientation.
   // false: the record does not fit a mate of L bytes (the library's answer is inconsistent: an error exit, never a wrong line).
+  // pair (--sam-pairs; nullptr without): the association's pair record (include/shark_hip.h, "pairs") -- MAPQ is its mapq, 0x2
+  // is set iff proper, TLEN is tend - tstart on the left mate's line and its negative on the other's for classes 3, 4 and 5.
   static bool sam_line(std::string &f, const char *id, size_t id_len, const std::string &gene, bool secondary, bool paired, uint32_t t,
-                       const shk_mate_alignment &a, const shk_mate_alignment &other, const char *seq, size_t L, const char *qual, uint32_t min_intron)
+                       const shk_mate_alignment &a, const shk_mate_alignment &other, const char *seq, size_t L, const char *qual, uint32_t min_intron,
+                       const shk_pair *pair = nullptr)
   {
     // (at most 4 M, 3 I, 3 N or D and 2 S, ten decimal digits each)
     char cigar[160], num[64];
@@ -1573,14 +1628,21 @@ class ReadOutput {
       if (!mate_has) flag |= 0x8u;
       else if (other.strand) flag |= 0x20u;
     }
+    unsigned mapq = 255;
+    long long tlen = 0;
+    if (pair) {
+      if (pair->proper) flag |= 0x2u;
+      mapq = pair->mapq;
+      if (pair->cls >= 3 && pair->cls <= 5) tlen = pair->left == t ? (long long)pair->tend - pair->tstart : (long long)pair->tstart - pair->tend;
+    }
     f.append(id, id_len);
     int w = snprintf(num, sizeof(num), "\t%u\t", flag);
     f.append(num, (size_t)w);
     f.append(gene);
-    w = snprintf(num, sizeof(num), "\t%u\t255\t", a.block[0].x + 1);
+    w = snprintf(num, sizeof(num), "\t%u\t%u\t", a.block[0].x + 1, mapq);
     f.append(num, (size_t)w);
     f.append(cigar);
-    if (mate_has) w = snprintf(num, sizeof(num), "\t=\t%u\t0\t", other.block[0].x + 1);
+    if (mate_has) w = snprintf(num, sizeof(num), "\t=\t%u\t%lld\t", other.block[0].x + 1, tlen);
     else w = snprintf(num, sizeof(num), "\t*\t0\t0\t");
     f.append(num, (size_t)w);
     if (!a.strand) {
@@ -1646,6 +1708,7 @@ class ReadOutput {
   uint32_t k_, s_min_;      // (--junctions) the k-mer length and the support either side needs
   FILE *sam_;               // (--sam) likewise, one line per association and mate with a block
   uint32_t sam_min_intron_; // (--sam) the gap from which shk_alignment_cigar writes N
+  bool sam_pairs_;          // (--sam-pairs) the lines carry the pair records' MAPQ, 0x2 and TLEN
   std::map<std::tuple<uint32_t, int64_t, int64_t>, std::pair<int64_t, uint64_t>> junction_table_;   // (gene, donor, acceptor) -> intron, mates
   bool failed_write_ = false, failed_write_cand_ = false, failed_write_plc_ = false, failed_write_sgm_ = false, failed_write_sam_ = false;
   mutable std::atomic<bool> failed_{false};   // a record could not be read back from its file (I/O error)
@@ -2095,6 +2158,7 @@ std::string build_index(const Options &opt, GpuStart &gpu, std::vector<std::stri
       if (opt.pileup_file && legend_ID.size() > 65536) return "shark: --pileup is not available for a reference of more than 65536 records (gene ids wrap there).";
       if (opt.variants_file && legend_ID.size() > 65536) return "shark: --variants is not available for a reference of more than 65536 records (gene ids wrap there).";
       if (opt.sam_file && legend_ID.size() > 65536) return "shark: --sam is not available for a reference of more than 65536 records (gene ids wrap there).";
+      if (opt.fragments_file && legend_ID.size() > 65536) return "shark: --fragments is not available for a reference of more than 65536 records (gene ids wrap there).";
       const size_t len = strnlen(rec.seq.data(), rec.seq.size());  // C-string semantics (main.cpp:164)
       if (opt.sam_file) sam_header += "@SQ\tSN:" + legend_ID.back() + "\tLN:" + std::to_string(len) + "\n";
       for (auto *ctx : gpu.ctxs) {
@@ -2106,7 +2170,8 @@ std::string build_index(const Options &opt, GpuStart &gpu, std::vector<std::stri
   }
   pelapsed("Transcript file processed");
   timeline("reference read");
-  if (opt.placements_file || opt.depth_file || opt.segments_file || opt.junctions_file || opt.pileup_file || opt.variants_file || opt.sam_file)
+  if (opt.placements_file || opt.depth_file || opt.segments_file || opt.junctions_file || opt.pileup_file || opt.variants_file || opt.sam_file ||
+      opt.fragments_file)
     for (auto *ctx : gpu.ctxs)
       if (const int rc = shk_ref_keep_positions(ctx)) return std::string("shark: ") + shk_strerror(rc);
   // (the k-mer keyed table repays its enumeration behind several hundred million pairs classified at the GPU's speed: not in a run of this command)
@@ -2115,7 +2180,8 @@ std::string build_index(const Options &opt, GpuStart &gpu, std::vector<std::stri
   // (--variants: the records' bases stay on the device; only worker 0 is asked for the sites, but every replica is built alike)
   // (--sam: every worker's alignments kernel reads them)
   // (--pileup-aligned: the accumulating alignments kernel reads them as well)
-  if (opt.variants_file || opt.sam_file || opt.pileup_aligned)
+  // (--fragments: alignments mode runs for it as it does for --sam)
+  if (opt.variants_file || opt.sam_file || opt.pileup_aligned || opt.fragments_file)
     for (auto *ctx : gpu.ctxs)
       if (const int rc = shk_ref_keep_bases(ctx)) return std::string("shark: ") + shk_strerror(rc);
   {
@@ -2167,12 +2233,12 @@ void serial_feed(const Options &opt, const FeedPlan &plan, ParallelFeed &feed, B
 }
 
 // analyzers: one thread per worker, SHK_PIPE_DEPTH batches in flight each; t_gpu[g]: seconds inside shk_classify_submit / _wait
-std::vector<std::thread> start_analyzers(const std::vector<shk_ctx *> &ctxs, bool need_qual, bool evidence, bool candidates, bool placements, bool segments, bool alignments, BatchOrder &order, BatchOrder::Queue &to_format, std::vector<double> &t_gpu)
+std::vector<std::thread> start_analyzers(const std::vector<shk_ctx *> &ctxs, bool need_qual, bool evidence, bool candidates, bool placements, bool segments, bool alignments, bool pairs, BatchOrder &order, BatchOrder::Queue &to_format, std::vector<double> &t_gpu)
 {
   std::vector<std::thread> analyzers;
   for (int g = 0; g < (int)ctxs.size(); ++g) {
-    analyzers.emplace_back([&, g, need_qual, evidence, candidates, placements, segments, alignments] {
-      ReadAnalyzer ra(ctxs[(size_t)g], need_qual, evidence, candidates, placements, segments, alignments);
+    analyzers.emplace_back([&, g, need_qual, evidence, candidates, placements, segments, alignments, pairs] {
+      ReadAnalyzer ra(ctxs[(size_t)g], need_qual, evidence, candidates, placements, segments, alignments, pairs);
       BatchOrder::Queue &todo = order.input(g);
       bool open = true;
       while (open || ra.in_flight()) {
@@ -2228,7 +2294,8 @@ int run_sample(const Options &opt, GpuStart &gpu, BatchPool &pool, std::vector<s
   if (opt.paired_flag && opt.out2_path != "") w2.open(opt.out2_path, write_helpers);
   OffsetWriter *out1 = w1.is_open() ? &w1 : nullptr, *out2 = w2.is_open() ? &w2 : nullptr;
   ReadOutput ro(out1, out2, legend_ID, opt.evidence_file, opt.candidates_file, opt.placements_file, opt.paired_flag, opt.segments_file,
-                opt.junctions_file != nullptr && !opt.junctions_device, opt.k, opt.junctions_min_support, opt.sam_file, opt.sam_min_intron);
+                opt.junctions_file != nullptr && !opt.junctions_device, opt.k, opt.junctions_min_support, opt.sam_file, opt.sam_min_intron,
+                opt.sam_pairs);
   setvbuf(stdout, nullptr, _IOFBF, 1 << 22);
 
   FeedPlan plan(opt, io_threads, need_qual);
@@ -2306,12 +2373,21 @@ int run_sample(const Options &opt, GpuStart &gpu, BatchPool &pool, std::vector<s
         std::cerr << "shark: end extension could not be switched on: " << shk_strerror(rc) << " " << shk_last_error(ctx) << std::endl;
         return EXIT_FAILURE;
       }
-  // (--sam: every worker's batches carry their mates' alignments)
-  if (opt.sam_file)
+  // (--sam: every worker's batches carry their mates' alignments; --fragments: the same records are what pairs mode reads)
+  if (opt.sam_file || opt.fragments_file)
     for (shk_ctx *ctx : gpu.ctxs)
       if (const int rc = shk_alignments_enable(ctx, opt.sam_min_support)) {
         feed.stop();
         std::cerr << "shark: alignments mode could not be switched on: " << shk_strerror(rc) << " " << shk_last_error(ctx) << std::endl;
+        return EXIT_FAILURE;
+      }
+  // (--sam-pairs, --fragments: every worker's batches carry their pair records and add to that worker's fragments state;
+  //  write_fragments sums the workers' states at the end)
+  if (opt.sam_pairs || opt.fragments_file)
+    for (shk_ctx *ctx : gpu.ctxs)
+      if (const int rc = shk_pairs_enable(ctx, opt.fragments_min_intron, opt.fragments_max, opt.fragments_bins)) {
+        feed.stop();
+        std::cerr << "shark: pairs mode could not be switched on: " << shk_strerror(rc) << " " << shk_last_error(ctx) << std::endl;
         return EXIT_FAILURE;
       }
   std::unique_ptr<BatchSplitter> fs;
@@ -2341,7 +2417,8 @@ int run_sample(const Options &opt, GpuStart &gpu, BatchPool &pool, std::vector<s
     });
   }
   std::vector<std::thread> analyzers = start_analyzers(gpu.ctxs, need_qual, opt.evidence_file != nullptr, opt.candidates_file != nullptr, opt.placements_file != nullptr,
-                                                        opt.segments_file != nullptr || host_junctions, opt.sam_file != nullptr, order, to_format, t_gpu);
+                                                        opt.segments_file != nullptr || host_junctions, opt.sam_file != nullptr, opt.sam_file != nullptr && opt.sam_pairs, order,
+                                                        to_format, t_gpu);
   // ordered drain
   int failed = 0;
   double t_out = 0;
@@ -2617,6 +2694,36 @@ bool write_pileup(const Options &opt, std::vector<shk_ctx *> &ctxs, const std::v
   return ok;
 }
 
+// --fragments: the workers' fragments states (one per context, each over the batches that worker classified) summed on the host -- both
+// arrays are additive over contexts --, then six lines `class <name> <count>`, one line `frag <len> <count>` per non-empty bin below the
+// last and `frag >=<n_bins - 1> <count>` for the last, the overflow bin
+bool write_fragments(const Options &opt, std::vector<shk_ctx *> &ctxs)
+{
+  static const char *const names[6] = {"none", "mate1", "mate2", "inward", "outward", "tandem"};
+  const uint32_t n_bins = opt.fragments_bins;
+  std::vector<uint64_t> hist(n_bins, 0), part(n_bins, 0);
+  uint64_t classes[6] = {0, 0, 0, 0, 0, 0}, cpart[6];
+  for (size_t g = 0; g < ctxs.size(); ++g) {
+    const int rc = shk_fragments_get(ctxs[g], part.data(), n_bins, cpart);
+    if (rc != SHK_OK) {
+      std::cerr << "shark: the fragments state of worker " << g << " could not be read: " << shk_strerror(rc) << " " << shk_last_error(ctxs[g]) << std::endl;
+      fclose(opt.fragments_file);
+      return false;
+    }
+    for (uint32_t b = 0; b < n_bins; ++b) hist[b] += part[b];
+    for (int c = 0; c < 6; ++c) classes[c] += cpart[c];
+  }
+  std::string text;
+  for (int c = 0; c < 6; ++c) text += std::string("class ") + names[c] + " " + std::to_string(classes[c]) + "\n";
+  for (uint32_t b = 0; b + 1 < n_bins; ++b)
+    if (hist[b]) text += "frag " + std::to_string(b) + " " + std::to_string(hist[b]) + "\n";
+  text += "frag >=" + std::to_string(n_bins - 1) + " " + std::to_string(hist[n_bins - 1]) + "\n";
+  bool ok = fwrite(text.data(), 1, text.size(), opt.fragments_file) == text.size();
+  ok = (fclose(opt.fragments_file) == 0) && ok;
+  if (!ok) std::cerr << "shark: cannot write the fragments file " << opt.fragments_path << std::endl;
+  return ok;
+}
+
 // --variants: a variant call is not linear in the counters, so the workers' states are summed first -- every other worker's array and
 // mate counter added into worker 0's on its device (shk_pileup_get_all, shk_pileup_add) -- and worker 0 is asked once.  One line per
 // site: <gene> <x> <ref> <alt> <A> <C> <G> <T>, genes in id order, x ascending (the order the library hands them out in).  Runs behind
@@ -2681,6 +2788,7 @@ int main(int argc, char *argv[])
   if (opt_parsed.pileup_path != "" && samples_can_be_opened(opt_parsed, false)) opt_parsed.pileup_file = fopen(opt_parsed.pileup_path.c_str(), "w");   // (--pileup: likewise)
   if (opt_parsed.variants_path != "" && samples_can_be_opened(opt_parsed, false)) opt_parsed.variants_file = fopen(opt_parsed.variants_path.c_str(), "w");   // (--variants: likewise)
   if (opt_parsed.sam_path != "" && samples_can_be_opened(opt_parsed, false)) opt_parsed.sam_file = fopen(opt_parsed.sam_path.c_str(), "w");   // (--sam: likewise)
+  if (opt_parsed.fragments_path != "" && samples_can_be_opened(opt_parsed, false)) opt_parsed.fragments_file = fopen(opt_parsed.fragments_path.c_str(), "w");   // (--fragments: likewise)
   const Options opt = opt_parsed;
   if (opt.verbose) timeline.on();
   timeline("arguments parsed");
@@ -2731,6 +2839,10 @@ int main(int argc, char *argv[])
     std::cerr << "shark: cannot open the SAM file " << opt.sam_path << std::endl;
     return EXIT_FAILURE;
   }
+  if (opt.fragments_path != "" && !opt.fragments_file) {
+    std::cerr << "shark: cannot open the fragments file " << opt.fragments_path << std::endl;
+    return EXIT_FAILURE;
+  }
 
   BatchPool &pool = *new BatchPool;     // (never destroyed: the process leaves through _exit)
   GpuStart gpu(opt, pool);              // the contexts come up on a thread of their own from here on
@@ -2742,6 +2854,7 @@ int main(int argc, char *argv[])
   if (opt.junctions_file && opt.junctions_device && !write_junctions_device(opt, gpu.ctxs, legend_ID)) return EXIT_FAILURE;
   if (opt.pileup_file && !write_pileup(opt, gpu.ctxs, legend_ID)) return EXIT_FAILURE;
   if (opt.variants_file && !write_variants(opt, gpu.ctxs, legend_ID)) return EXIT_FAILURE;
+  if (opt.fragments_file && !write_fragments(opt, gpu.ctxs)) return EXIT_FAILURE;
 
   if ((opt.gene_counts_path != "" || (opt.verbose && opt.gpus > 1)) && !gene_counts(opt, gpu.ctxs, legend_ID)) return EXIT_FAILURE;
   if (opt.verbose) {

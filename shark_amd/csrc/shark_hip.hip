@@ -120,6 +120,8 @@ static void slot_free(Slot &s)
   hipFree(s.d_sp_keys); hipFree(s.d_sp_entries);
   hipFree(s.d_align);
   if (s.h_align) (void)hipHostFree(s.h_align);
+  hipFree(s.d_pairs);
+  if (s.h_pairs) (void)hipHostFree(s.h_pairs);
   if (s.h_seg_keys) (void)hipHostFree(s.h_seg_keys);
   if (s.h_seg_entries) (void)hipHostFree(s.h_seg_entries);
   if (s.h_cand_reads) (void)hipHostFree(s.h_cand_reads);
@@ -337,6 +339,15 @@ static int enqueue_tail(Ctx *ctx, Slot &s, bool skip_hist_if_long, bool count_ge
     if (s.align) {
       if ((rc = ensure_capacity(ctx, &s.d_align, &s.cap_align, 2 * s.cap_gene_ids))) return rc;
       if ((rc = launch_alignments(ctx, s, entries, cap_assoc, skip_hist_if_long, true, acc_with_records, st))) return rc;
+      // (pairs mode: the two mates' records of an association read together, directly behind the kernel that stored them)
+      if (s.pairs) {
+        if ((rc = ensure_capacity(ctx, &s.d_pairs, &s.cap_pairs, s.cap_gene_ids))) return rc;
+        if ((rc = launch_pairs(ctx, s, cap_assoc, skip_hist_if_long, st))) return rc;
+        if (s.host_batch) {
+          if ((rc = ensure_pinned(ctx, &s.h_pairs, &s.cap_h_pairs, s.cap_gene_ids))) return rc;
+          if ((rc = launch_publish_pairs(s, std::min<uint64_t>(std::min<uint64_t>(s.cap_h_pairs, s.cap_pairs), cap_assoc), st))) return rc;
+        }
+      }
       if (s.host_batch) {
         if ((rc = ensure_pinned(ctx, &s.h_align, &s.cap_h_align, 2 * s.cap_gene_ids))) return rc;
         if ((rc = launch_publish_alignments(s, std::min<uint64_t>(std::min<uint64_t>(s.cap_h_align, s.cap_align) / 2, cap_assoc), st))) return rc;
@@ -391,6 +402,11 @@ static int enqueue_classify(Ctx *ctx, Slot &s, const shk_batch *b, uint32_t max_
   s.align = ctx->align;
   s.ext_p = ctx->ext_p;
   s.ext_b = ctx->ext_b;
+  s.pairs = s.align ? ctx->pairs_bins : 0u;      // (pair records only behind alignment records)
+  s.pairs_min_intron = ctx->pairs_min_intron;
+  s.pairs_max_frag = ctx->pairs_max_frag;
+  s.pairs_count = s.pairs && count_genes;
+  if (s.pairs_count) ctx->frag_dirty = true;
   if (s.pileup || s.pileup_al) ctx->pileup_dirty = true;
   if (s.depth || s.sp_depth) ctx->depth_dirty = true;
   if (s.sp_junc) ctx->junc_dirty = true;
@@ -583,6 +599,7 @@ static int classify_resident(Ctx *ctx, const shk_batch *b, uint32_t max_read_len
   ctx->last_place_valid = false;
   ctx->last_seg_valid = false;
   ctx->last_align_valid = false;
+  ctx->last_pairs_valid = false;
   if (n >= 0xFFFFFFFFull) { ctx->last_error = "batch too large (n must be < 2^32-1)"; return SHK_ERR_ARG; }
   const bool paired = b->seq2 != nullptr;
   const uint32_t max_slots = max_read_len ? slots_for_len(max_read_len, ctx->prm.k, paired) : 0;
@@ -649,6 +666,9 @@ static int classify_resident(Ctx *ctx, const shk_batch *b, uint32_t max_read_len
   ctx->last_align_valid = s.align != 0 && wc == nullptr;
   ctx->last_align = s.d_align;
   ctx->last_align_n = n_assoc;
+  ctx->last_pairs_valid = s.pairs != 0 && wc == nullptr;
+  ctx->last_pairs = s.d_pairs;
+  ctx->last_pairs_n = n_assoc;
   return SHK_OK;
 }
 
@@ -773,6 +793,7 @@ int shk_create(const shk_params *prm, shk_ctx **out)
     ctx->env_anchor_always = getenv("SHK_ANCHOR_ALWAYS") != nullptr;
     ctx->env_no_pre_verdict = getenv("SHK_NO_PRE_VERDICT") != nullptr;
     ctx->env_no_tri = getenv("SHK_NO_TRI") != nullptr;
+    ctx->env_pairs_global = getenv("SHK_PAIRS_GLOBAL_ATOMICS") != nullptr;
     ctx->env_no_tro = getenv("SHK_NO_TRO") != nullptr;
     ctx->env_force_tro = getenv("SHK_FORCE_TRO") != nullptr;
     ctx->env_tile_first = getenv("SHK_TILE_FIRST") ? (getenv("SHK_TILE_FIRST")[0] == '0' ? -1 : 1) : 0;
@@ -833,6 +854,7 @@ void shk_destroy(shk_ctx *ctx)
   hipFree(ctx->d_depth_diff); hipFree(ctx->d_depth_mates); hipFree(ctx->d_depth_scan); hipFree(ctx->d_depth_scan_temp); hipFree(ctx->d_depth_summary);
   hipFree(ctx->d_junc_tab); hipFree(ctx->d_junc_dropped);
   hipFree(ctx->d_pileup); hipFree(ctx->d_pileup_mates);
+  hipFree(ctx->d_frag);
   hipFree(ctx->d_var_waves); hipFree(ctx->d_var_temp); hipFree(ctx->d_var_out); hipFree(ctx->d_var_summary);
   dist_release(ctx);
   for (auto e : ctx->ev_start) (void)hipEventDestroy(e);
@@ -1178,6 +1200,7 @@ int shk_classify_wait(shk_ctx *ctx, uint64_t ticket, shk_result *result)
   ctx->last_place_valid = false;
   ctx->last_seg_valid = false;
   ctx->last_align_valid = false;
+  ctx->last_pairs_valid = false;
   SHK_HIP(ctx, hipEventSynchronize(s.ev_done));
   bool redone = false;
   int rc = finish_classify(ctx, s, s.long_speculative, true, &redone);
@@ -1222,6 +1245,10 @@ int shk_classify_wait(shk_ctx *ctx, uint64_t ticket, shk_result *result)
   ctx->last_align_valid = s.align != 0;
   ctx->last_align = s.host_batch ? s.h_align : s.d_align;
   ctx->last_align_n = n_assoc;
+  if (s.pairs && s.host_batch && n_assoc > s.cap_h_pairs) { ctx->last_error = "pairs publication failed"; return SHK_ERR_HIP; }
+  ctx->last_pairs_valid = s.pairs != 0;
+  ctx->last_pairs = s.host_batch ? s.h_pairs : s.d_pairs;
+  ctx->last_pairs_n = n_assoc;
   return SHK_OK;
 }
 
@@ -1741,6 +1768,77 @@ int shk_alignments_last(const shk_ctx *ctx, shk_alignments *out)
   if (!ctx->last_align_valid) return SHK_ERR_STATE;
   out->n_assoc = ctx->last_align_n;
   out->entries = ctx->last_align;
+  return SHK_OK;
+}
+
+// ---- pairs mode (pairs.hip): per-batch records as alignments mode's; the fragments state lives in the context, the batches' tails add to it ----
+int shk_pairs_enable(shk_ctx *ctx, uint32_t min_intron, uint32_t max_frag, uint32_t n_bins)
+{
+  if (!ctx) return SHK_ERR_ARG;
+  if (tickets_outstanding(ctx)) { ctx->last_error = "shk_pairs_enable: tickets are outstanding (wait for them first)"; return SHK_ERR_STATE; }
+  if (n_bins) {
+    if (n_bins < 2 || n_bins > 4096 || min_intron < 1) { ctx->last_error = "shk_pairs_enable: n_bins is 0 or 2 .. 4096 and min_intron at least 1"; return SHK_ERR_ARG; }
+    if (ctx->mode != 2) { ctx->last_error = "shk_pairs_enable: the index is not finalized"; return SHK_ERR_STATE; }
+    if (!ctx->idx.ptab_lg) { ctx->last_error = "shk_pairs_enable: the index was finalized without shk_ref_keep_positions"; return SHK_ERR_STATE; }
+    if (ctx->n_records > 65536 || ctx->idx.wrap || !ctx->idx.gene_start) { ctx->last_error = "shk_pairs_enable: more than 65 536 records (gene ids wrap)"; return SHK_ERR_STATE; }
+    if (!ctx->idx.recbase) { ctx->last_error = "shk_pairs_enable: the index was finalized without shk_ref_keep_bases"; return SHK_ERR_STATE; }
+    if (!ctx->align) { ctx->last_error = "shk_pairs_enable: alignments mode is off (shk_alignments_enable first)"; return SHK_ERR_STATE; }
+    if (ctx->d_frag && n_bins != ctx->frag_bins) {
+      if (ctx->frag_dirty) { ctx->last_error = "shk_pairs_enable: another n_bins than the state's (shk_fragments_reset first)"; return SHK_ERR_ARG; }
+      SHK_HIP(ctx, hipSetDevice(ctx->prm.device));
+      SHK_HIP(ctx, hipStreamSynchronize(ctx->stream));
+      (void)hipFree(ctx->d_frag);
+      ctx->d_frag = nullptr;
+      ctx->frag_bins = 0;
+    }
+    if (!ctx->d_frag) {
+      SHK_HIP(ctx, hipSetDevice(ctx->prm.device));
+      const size_t bytes = ((size_t)n_bins + 6) * sizeof(unsigned long long);
+      SHK_HIP(ctx, hipMalloc((void **)&ctx->d_frag, bytes));
+      ctx->frag_bins = n_bins;
+      ctx->frag_dirty = false;
+      SHK_HIP(ctx, hipMemsetAsync(ctx->d_frag, 0, bytes, ctx->stream));
+    }
+    ctx->pairs_min_intron = min_intron;
+    ctx->pairs_max_frag = max_frag;
+  }
+  ctx->pairs_bins = n_bins;
+  return SHK_OK;
+}
+
+int shk_pairs_last(const shk_ctx *ctx, shk_pairs *out)
+{
+  if (!ctx || !out) return SHK_ERR_ARG;
+  if (!ctx->last_pairs_valid) return SHK_ERR_STATE;
+  out->n_assoc = ctx->last_pairs_n;
+  out->entries = ctx->last_pairs;
+  return SHK_OK;
+}
+
+int shk_fragments_get(shk_ctx *ctx, uint64_t *hist, uint32_t n_bins, uint64_t classes[6])
+{
+  if (!ctx || !hist || !classes) return SHK_ERR_ARG;
+  if (!ctx->d_frag) { ctx->last_error = "shk_fragments_get: pairs mode was never enabled on this context"; return SHK_ERR_STATE; }
+  if (tickets_outstanding(ctx)) { ctx->last_error = "shk_fragments_get: tickets are outstanding (wait for them first)"; return SHK_ERR_STATE; }
+  if (n_bins != ctx->frag_bins) { ctx->last_error = "shk_fragments_get: n_bins is not the state's"; return SHK_ERR_ARG; }
+  SHK_HIP(ctx, hipSetDevice(ctx->prm.device));
+  std::vector<unsigned long long> h((size_t)n_bins + 6);
+  SHK_HIP(ctx, hipMemcpyAsync(h.data(), ctx->d_frag, h.size() * sizeof(unsigned long long), hipMemcpyDeviceToHost, ctx->stream));
+  SHK_HIP(ctx, hipStreamSynchronize(ctx->stream));
+  for (uint32_t b = 0; b < n_bins; ++b) hist[b] = h[b];
+  for (uint32_t c = 0; c < 6; ++c) classes[c] = h[(size_t)n_bins + c];
+  return SHK_OK;
+}
+
+int shk_fragments_reset(shk_ctx *ctx)
+{
+  if (!ctx) return SHK_ERR_ARG;
+  if (!ctx->d_frag) { ctx->last_error = "shk_fragments_reset: pairs mode was never enabled on this context"; return SHK_ERR_STATE; }
+  if (tickets_outstanding(ctx)) { ctx->last_error = "shk_fragments_reset: tickets are outstanding (wait for them first)"; return SHK_ERR_STATE; }
+  SHK_HIP(ctx, hipSetDevice(ctx->prm.device));
+  SHK_HIP(ctx, hipMemsetAsync(ctx->d_frag, 0, ((size_t)ctx->frag_bins + 6) * sizeof(unsigned long long), ctx->stream));
+  ctx->frag_dirty = false;
+  SHK_HIP(ctx, hipStreamSynchronize(ctx->stream));
   return SHK_OK;
 }
 

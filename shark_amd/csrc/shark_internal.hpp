@@ -396,6 +396,13 @@ struct Slot {
   // submitted with this floor (0: not) -- align_kernel's accumulating instantiation adds the batch to Ctx::d_pileup, pileup_kernel does not run
   uint32_t ext_p = 0, ext_b = 0;
   uint32_t pileup_al = 0;
+  // pairs mode (pairs.hip): submitted with this n_bins (0: not; only with `align`): pair_kernel ran behind the storing align_kernel, one
+  // 32-byte record per association (d_pairs, allocated with the first such batch for as many associations as d_gene_ids holds);
+  // pairs_count: the batch is added to Ctx::d_frag (not a shk_count_work batch)
+  uint32_t pairs = 0, pairs_min_intron = 0, pairs_max_frag = 0;
+  bool pairs_count = false;
+  shk_pair *d_pairs = nullptr; size_t cap_pairs = 0;
+  shk_pair *h_pairs = nullptr; size_t cap_h_pairs = 0;   // (host batches; filled by publish_pairs_kernel)
 };
 
 struct Ctx;
@@ -437,6 +444,10 @@ int launch_pileup(Ctx *ctx, const Slot &s, const shk_segment *entries, uint64_t 
 // does both where the floors are equal).  With s.ext_p == 0 and no accumulation the kernel launched is the one this mode always launched
 int launch_alignments(Ctx *ctx, const Slot &s, const shk_segment *entries, uint64_t cap_assoc, bool skip_if_long, bool store, bool accumulate, hipStream_t stream);
 int launch_publish_alignments(const Slot &s, uint64_t h_cap, hipStream_t stream);   // h_cap: associations the pinned array (and the device's) holds
+// pairs.hip: per association of the batch in `s` its pair record from the two mates' records in s.d_align (cap_assoc: launch_alignments') into
+// s.d_pairs and, where s.pairs_count, the batch into Ctx::d_frag; directly behind the storing launch_alignments; skip_if_long: as launch_gene_hist
+int launch_pairs(Ctx *ctx, const Slot &s, uint64_t cap_assoc, bool skip_if_long, hipStream_t stream);
+int launch_publish_pairs(const Slot &s, uint64_t h_cap, hipStream_t stream);   // h_cap: associations the pinned array (and the device's) holds
 // variants.hip: d_pileup[i] += d_add[i] over n_entries counters (d_add 16-byte aligned: SHK_ERR_ARG otherwise), *d_pileup_mates += mates, on ctx->stream
 int launch_pileup_add(Ctx *ctx, const uint32_t *d_add, uint64_t n_entries, uint64_t mates);
 // variants.hip: the sites of the pileup state against DeviceIndex::recbase: their number into *n_sites (host; the stream is drained) and, with
@@ -586,6 +597,17 @@ struct Ctx {
   bool last_align_valid = false;
   const shk_mate_alignment *last_align = nullptr;
   uint64_t last_align_n = 0;
+  // pairs mode (shk_pairs_enable; pairs.hip): per-batch records as alignments mode's, and the fragments state, which like the depth state
+  // outlives the mode's being switched off
+  uint32_t pairs_bins = 0;                     // n_bins for the batches submitted from now on (0: off)
+  uint32_t pairs_min_intron = 0, pairs_max_frag = 0;
+  uint32_t frag_bins = 0;                      // the state's n_bins (0: never enabled)
+  unsigned long long *d_frag = nullptr;        // hist[frag_bins], classes[6] (allocated by the first enable)
+  bool frag_dirty = false;                     // a pairs batch was submitted since the first enable / the last reset
+  bool env_pairs_global = false;               // SHK_PAIRS_GLOBAL_ATOMICS=1: the histogram by one global atomic per pair (A/B timing only)
+  bool last_pairs_valid = false;
+  const shk_pair *last_pairs = nullptr;
+  uint64_t last_pairs_n = 0;
 
   // timing
   bool timing = false;
