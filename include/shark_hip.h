@@ -819,6 +819,86 @@ int shk_pairs_last(const shk_ctx *ctx, shk_pairs *out);
 int shk_fragments_get(shk_ctx *ctx, uint64_t *hist, uint32_t n_bins, uint64_t classes[6]);
 int shk_fragments_reset(shk_ctx *ctx);
 
+/* ---- rescue: an unplaced mate placed beside its placed partner, by dense comparison with the record ---- */
+/* A mate gets a block only where a diagonal has s_min unique k-mers.  A mate with a few errors, one in a repeat of its gene, or a
+ * short one stays without a block while its partner has one: pairs class 1 or 2.  The partner's record says where and on which strand
+ * such a mate must lie for the pair to be proper; rescue mode compares the mate base by base with every such place and, where one
+ * place is good enough and clearly the best, gives the mate an alignment record of one ungapped block.  It rests on the alignments
+ * and the pairs section, unchanged: block, read coordinate, step 4's kinds, L_m, s_m, e_m, cl_m, cr_m, intron interval.  Parameters:
+ * min_intron >= 1, max_frag in 1 .. 4096, max_cost in 0 .. 255, min_gap in 0 .. 255.  Integers only, no tolerance anywhere. */
+#define SHK_RESCUE_MIN_LEN 32
+#define SHK_RESCUE_MAX_LEN 512
+/* ATTEMPTED.  Per association of a paired batch, after the alignments section's steps 1 .. 5 (3a included where it is on), rescue is
+ * attempted iff exactly one mate has n_blocks >= 1 -- the ANCHOR A -- and the other, the TARGET T, has n_blocks == 0 and a length
+ * L_T in [SHK_RESCUE_MIN_LEN, SHK_RESCUE_MAX_LEN].  s_A, e_A, cl_A, cr_A are the pairs section's; I_A = the total length of A's own
+ * intron intervals at min_intron.  T's strand is 1 - strand_A.
+ *
+ * CANDIDATE.  A candidate x puts the whole target ungapped on the record: read coordinate q (in the record's orientation on T's
+ * strand, as the alignments section defines it) on record base x + q for q = 0 .. L_T - 1.
+ *
+ * WINDOW, in signed 64-bit arithmetic (len_g: the record's length):
+ *     A on strand 0:   lo = max(s_A, e_A - L_T, 0)                        hi = min(s_A - cl_A + I_A + max_frag - L_T, len_g - L_T)
+ *     A on strand 1:   lo = max(e_A + cr_A - I_A - max_frag, 0)           hi = min(s_A, e_A - L_T, len_g - L_T)
+ *     n_cand = max(0, hi - lo + 1)
+ * These are exactly the x inside the record for which the pair would be pairs class 3 with frag <= max_frag.  The target's record
+ * would be {x, 0, L_T}: s_T = x, e_T = x + L_T, no clip, no intron.  A on strand 0 is F: class 3 asks s_A <= x and e_A <= x + L_T;
+ * then tstart = s_A, tend = x + L_T, introns = I_A and frag = x + L_T - s_A - I_A + cl_A, which is <= max_frag iff
+ * x <= s_A - cl_A + I_A + max_frag - L_T.  A on strand 1 is R: class 3 asks x <= s_A and x + L_T <= e_A; then tstart = x,
+ * tend = e_A and frag = e_A - x - I_A + cr_A, which is <= max_frag iff x >= e_A + cr_A - I_A - max_frag.
+ * n_cand never exceeds max_frag: on strand 0, hi - lo + 1 <= (s_A - cl_A + I_A + max_frag - L_T) - (e_A - L_T) + 1
+ * = max_frag - (e_A - s_A - I_A) - cl_A + 1, and e_A - s_A - I_A holds the anchor's block bases, at least one; on strand 1 the same
+ * with hi <= s_A and cr_A.
+ *
+ * COST.  cost(x) = the number of the L_T target bases that are NOT A MATCH under step 4's kinds: a base that is neither a match nor
+ * a mismatch (N, masked by -q, record code 4) counts as not a match, as it does in a split's cost.  cap = max_cost + min_gap; every
+ * cost is taken as min(cost, cap + 1) -- the saturation lets the comparison of a candidate stop early.
+ *     best   the x of smallest cost; ties go to the candidate of smallest frag: the smallest x for an anchor on strand 0, the
+ *            largest x for an anchor on strand 1.
+ *     cost2  the smallest cost over all OTHER candidates (a second candidate of the best's cost counts); cap + 1 with n_cand == 1.
+ *
+ * OUTCOME: shk_rescue, 16 bytes per association, parallel to gene_ids.
+ *   state   0  not attempted; cost, cost2 and n_cand are 0
+ *           1  attempted, n_cand == 0; cost = cost2 = cap + 1
+ *           2  cost(best) > max_cost
+ *           3  ambiguous: cost2 - cost(best) < min_gap (both saturated).  With min_gap == 0 this cannot occur.
+ *           4  mate 1 rescued          5  mate 2 rescued
+ *   cost    cost(best), cost2, both saturated; n_cand as above.
+ * On rescue the target's shk_mate_alignment becomes n_blocks = 1, strand = 1 - strand_A, block[0] = {best, 0, L_T}, matches and
+ * mismatches counted by step 4 over that block, everything else zero.  Every other alignment record of the batch stays bit-identical.
+ * Example: L = 60 both, max_frag = 300, len_g = 2000; mate 1 on strand 0 with the one block {100, 2, 58}; mate 2 has no block.
+ * s_A = 100, e_A = 158, cl_A = 2, I_A = 0: lo = max(100, 98, 0) = 100, hi = min(100 - 2 + 0 + 300 - 60, 1940) = 338, n_cand = 239.
+ * If mate 2, reversed and complemented, differs from record bases 300 .. 359 in 3 places and from every other candidate's in at
+ * least 30, then at max_cost = 8, min_gap = 4: cap = 12, cost = 3, cost2 = 13, state 5, and mate 2's record is strand 1, {300, 0, 60},
+ * matches 57, mismatches 3 (fewer where one of the three is an N); pairs mode then gives class 3, frag = 360 - 100 + 2 = 262, proper.
+ *
+ * What the mode does NOT do:
+ *   - a target that is itself spliced is not rescued: a candidate is one ungapped block;
+ *   - a target that hangs over a record end is not rescued: the window keeps x in [0, len_g - L_T];
+ *   - a target behind an intron that lies in the unsequenced insert is not rescued: the window is max_frag record bases wide;
+ *   - a rescued mate does not enter depth, spliced depth, the junction table, pileup or aligned pileup: those accumulate before or
+ *     inside align_kernel.  A rescued mate exists only in the alignment records, and through them in pairs mode and the SAM.
+ *
+ * Kernels (rescue.hip): directly behind the align_kernel launch that stores the records and in front of pair_kernel and the
+ * publication of the records, so both see the rescued mate without knowing of the mode.  rescue_scan_kernel, one lane per read,
+ * writes the state 0 records and queues the attempted associations; rescue_kernel, one wave per queued association, stages target
+ * and window in LDS and prices 64 candidates per pass, four bases per instruction.  Independent of every other mode but for the
+ * rescued mates' alignment records and what pairs mode derives from them.  With the mode off no launch and no allocation is added.
+ * New: the reference has no counterpart. */
+typedef struct shk_rescue {
+  uint32_t state, cost, cost2, n_cand;
+} shk_rescue;                                  /* 16 bytes */
+typedef struct shk_rescues {
+  uint64_t          n_assoc;                   /* = that result's n_assoc */
+  const shk_rescue *entries;                   /* n_assoc records, parallel to gene_ids */
+} shk_rescues;
+/* Switches rescue mode on (max_frag in 1 .. 4096, min_intron >= 1, max_cost and min_gap in 0 .. 255; anything else is SHK_ERR_ARG)
+ * or off (max_frag == 0; the others are ignored) for the batches submitted AFTERWARDS, through any of the four families.  State rules
+ * are shk_pairs_enable's: SHK_ERR_STATE while tickets are outstanding and, switching on, while alignments mode is off.  A batch is
+ * rescued only if it was submitted with alignments mode on as well.  The mode keeps no state of its own.  New: no counterpart. */
+int shk_rescue_enable(shk_ctx *ctx, uint32_t min_intron, uint32_t max_frag, uint32_t max_cost, uint32_t min_gap);
+/* The rescue records of the batch whose result was handed out LAST, with shk_pairs_last's rules.  New: no counterpart. */
+int shk_rescue_last(const shk_ctx *ctx, shk_rescues *out);
+
 /* Per-gene number of assigned reads accumulated over all classify calls (all
  * waited tickets) since the last reset (counts[g] for g in [0, 65536)); the quantity all-reduced
  * across GPUs.  n must be <= 65536. */

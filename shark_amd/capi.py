@@ -88,6 +88,20 @@ FRAGMENTS_DEFAULT_MAX = 1000
 FRAGMENTS_DEFAULT_BINS = 1024
 
 
+class ShkRescues(C.Structure):
+    _fields_ = [("n_assoc", C.c_uint64), ("entries", C.c_void_p)]
+
+
+# shk_rescue as a numpy record (16 bytes)
+RESCUE_DTYPE = np.dtype([("state", np.uint32), ("cost", np.uint32), ("cost2", np.uint32), ("n_cand", np.uint32)])
+assert RESCUE_DTYPE.itemsize == 16
+RESCUE_STATE_NAMES = ("not attempted", "no candidate", "too costly", "ambiguous", "mate1 rescued", "mate2 rescued")
+RESCUE_MIN_LEN = 32
+RESCUE_MAX_LEN = 512
+RESCUE_DEFAULT_MAX_COST = 8
+RESCUE_DEFAULT_MIN_GAP = 4
+
+
 class ShkVariantParams(C.Structure):
     _fields_ = [("min_depth", C.c_uint32), ("min_alt", C.c_uint32), ("frac_num", C.c_uint32), ("frac_den", C.c_uint32)]
 
@@ -122,6 +136,7 @@ EXPORTS = [
     "shk_ref_kmer_table",
     "shk_alignments_enable", "shk_alignments_last", "shk_alignment_cigar", "shk_alignments_extend", "shk_pileup_enable_aligned",
     "shk_pairs_enable", "shk_pairs_last", "shk_fragments_get", "shk_fragments_reset",
+    "shk_rescue_enable", "shk_rescue_last",
 ]
 SHK_PIPE_DEPTH = 3
 SHK_DIST_ID_BYTES = 128
@@ -222,6 +237,8 @@ def load():
         "shk_pairs_last": (C.c_int, [p, C.POINTER(ShkPairs)]),
         "shk_fragments_get": (C.c_int, [p, p, C.c_uint32, p]),
         "shk_fragments_reset": (C.c_int, [p]),
+        "shk_rescue_enable": (C.c_int, [p, C.c_uint32, C.c_uint32, C.c_uint32, C.c_uint32]),
+        "shk_rescue_last": (C.c_int, [p, C.POINTER(ShkRescues)]),
     }
     variant = bool(os.environ.get("SHK_LIB_PATH"))
     for name, (res, args) in later.items():
@@ -739,6 +756,27 @@ class SharkHip:
     def fragments_reset(self):
         self._check(self.L.shk_fragments_reset(self.h), "shk_fragments_reset")
 
+    # ---- rescue: a mate without a block placed beside its placed partner ------------------------------------------------------
+    def rescue_enable(self, min_intron=SAM_DEFAULT_MIN_INTRON, max_frag=FRAGMENTS_DEFAULT_MAX, max_cost=RESCUE_DEFAULT_MAX_COST,
+                      min_gap=RESCUE_DEFAULT_MIN_GAP):
+        """batches submitted from now on (with alignments mode on) carry one RESCUE_DTYPE record per association, and a rescued mate's
+        alignment record holds its one block; max_frag 0 switches the mode off; needs alignments mode on"""
+        self._check(self.L.shk_rescue_enable(self.h, int(min_intron), int(max_frag), int(max_cost), int(min_gap)), "shk_rescue_enable")
+
+    def rescue_last(self):
+        """rescue records of the batch whose result was handed out last: (n_assoc,) records of RESCUE_DTYPE, parallel to gene_ids, copied
+        from the context's pinned memory for a host batch; for a resident one (n_assoc, DEVICE pointer) -- rescues_from_device reads them
+        back.  Raises (SHK_ERR_STATE) when that batch was submitted without the mode"""
+        rs = ShkRescues()
+        self._check(self.L.shk_rescue_last(self.h, C.byref(rs)), "shk_rescue_last")
+        n = int(rs.n_assoc)
+        if not self._last_on_host:
+            return n, rs.entries
+        if n == 0:
+            return np.zeros(0, dtype=RESCUE_DTYPE)
+        raw = np.ctypeslib.as_array(C.cast(rs.entries, C.POINTER(C.c_uint32)), shape=(n, 4)).copy()
+        return raw.view(RESCUE_DTYPE).reshape(-1)
+
     # ---- variants: the record positions where the pileup shows another base than the record (needs an index built with keep_bases) --------
     def variants(self, min_depth=8, min_alt=3, frac=(1, 5)):
         """the sites of the pileup state at these thresholds (include/shark_hip.h, "variants"): a structured array (VARIANT_DTYPE: gene,
@@ -915,6 +953,14 @@ def pairs_from_device(n_assoc, ptr):
     if n_assoc:
         hip_memcpy_dtoh(raw, ptr, raw.nbytes)
     return raw.view(PAIR_DTYPE).reshape(-1)
+
+
+def rescues_from_device(n_assoc, ptr):
+    """read the records of a resident batch back: (n_assoc,) records of RESCUE_DTYPE as rescue_last gives them"""
+    raw = np.zeros((n_assoc, 4), dtype=np.uint32)
+    if n_assoc:
+        hip_memcpy_dtoh(raw, ptr, raw.nbytes)
+    return raw.view(RESCUE_DTYPE).reshape(-1)
 
 
 def cigar(rec, L, min_intron=SAM_DEFAULT_MIN_INTRON):

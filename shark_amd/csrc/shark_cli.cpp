@@ -126,6 +126,12 @@ const char *USAGE_MESSAGE =
     "          --sam-pairs                   --sam: fill in the pair-level fields -- MAPQ from the read's number of genes (1: 60, 2: 3, 3-4: 1,\n"
     "                                        more: 0), 0x2 on both lines of an inward pair whose fragment is at most --fragments-max, TLEN\n"
     "                                        = the pair's span on the record, positive on the left mate's line (needs --sam FILE)\n"
+    "          --sam-rescue                  --sam: a mate without a block whose partner has one is compared base by base with every place\n"
+    "                                        beside the partner at which the pair would be inward with a fragment of at most\n"
+    "                                        --fragments-max (1 .. 4096 here); the one clearly best place becomes its alignment, one\n"
+    "                                        ungapped block, and its line carries YR:i:<bases that are not a match> (needs --sam FILE)\n"
+    "          --rescue-max-cost N           bases of a rescued mate that may differ from the record (0 .. 255, default:8)\n"
+    "          --rescue-min-gap N            bases by which every other place must be worse (0 .. 255, default:4)\n"
     "          --fragments FILE              write the sample's pair classes and fragment-size histogram, accumulated on the GPUs: six\n"
     "                                        lines `class <name> <count>` (none mate1 mate2 inward outward tandem; every association),\n"
     "                                        one line `frag <len> <count>` per non-empty bin and `frag >=<bins-1> <count>` for the rest\n"
@@ -194,6 +200,9 @@ struct Options {
   unsigned sam_min_support = 8, sam_min_intron = 20;
   bool sam_sub_flag_given = false;
   bool sam_pairs = false;                 // (--sam-pairs)
+  bool sam_rescue = false;                // (--sam-rescue; --rescue-max-cost, --rescue-min-gap)
+  unsigned rescue_max_cost = 8, rescue_min_gap = 4;
+  bool rescue_sub_flag_given = false;
   std::string fragments_path;
   FILE *fragments_file = nullptr;  // (--fragments, likewise; written once, after the last batch)
   unsigned fragments_max = 1000, fragments_bins = 1024, fragments_min_intron = 0;   // (0: --sam-min-intron's value)
@@ -402,6 +411,19 @@ const OptionRow OPTION_TABLE[] = {
        o.fragments_sub_flag_given = true;
        if (o.fragments_min_intron < 1) reject(USAGE_MESSAGE, "shark: --fragments-min-intron must be at least 1.");
      }},
+    {1036, "sam-rescue", false, [](Options &o, const char *) { o.sam_rescue = true; }},
+    {1037, "rescue-max-cost", true,
+     [](Options &o, const char *v) {
+       o.rescue_max_cost = value_of<unsigned>(v);
+       o.rescue_sub_flag_given = true;
+       if (o.rescue_max_cost > 255) reject(USAGE_MESSAGE, "shark: --rescue-max-cost must be 0 to 255.");
+     }},
+    {1038, "rescue-min-gap", true,
+     [](Options &o, const char *v) {
+       o.rescue_min_gap = value_of<unsigned>(v);
+       o.rescue_sub_flag_given = true;
+       if (o.rescue_min_gap > 255) reject(USAGE_MESSAGE, "shark: --rescue-min-gap must be 0 to 255.");
+     }},
 };
 
 // Reads per device batch when --batch does not say.  A batch costs the device path 0.5-2 ms of launches, copies and bookkeeping
@@ -473,11 +495,16 @@ Options parse_arguments(int argc, char **argv)
     reject(USAGE_MESSAGE, "shark: --variants-min-support and --pileup-min-support must be equal (there is one pileup).");
   if (opt.sam_sub_flag_given && opt.sam_path.empty()) reject(USAGE_MESSAGE, "shark: --sam-min-support and --sam-min-intron need --sam FILE.");
   if (opt.sam_pairs && opt.sam_path.empty()) reject(USAGE_MESSAGE, "shark: --sam-pairs needs --sam FILE.");
-  if (opt.fragments_sub_flag_given && opt.fragments_path.empty() && !opt.sam_pairs)
+  if (opt.sam_rescue && opt.sam_path.empty()) reject(USAGE_MESSAGE, "shark: --sam-rescue needs --sam FILE.");
+  if (opt.rescue_sub_flag_given && !opt.sam_rescue) reject(USAGE_MESSAGE, "shark: --rescue-max-cost and --rescue-min-gap need --sam-rescue.");
+  if (opt.fragments_sub_flag_given && opt.fragments_path.empty() && !opt.sam_pairs && !opt.sam_rescue)
     reject(USAGE_MESSAGE, "shark: --fragments-max, --fragments-bins and --fragments-min-intron need --fragments FILE (or --sam FILE --sam-pairs).");
   if (opt.fragments_min_intron == 0) opt.fragments_min_intron = opt.sam_min_intron;
   if ((opt.sam_pairs || !opt.fragments_path.empty()) && opt.fragments_min_intron < 1)
     reject(USAGE_MESSAGE, "shark: --sam-pairs and --fragments need an intron length of at least 1 (--sam-min-intron, --fragments-min-intron).");
+  if (opt.sam_rescue && (opt.fragments_max < 1 || opt.fragments_max > 4096)) reject(USAGE_MESSAGE, "shark: --sam-rescue needs --fragments-max of 1 to 4096.");
+  if (opt.sam_rescue && opt.fragments_min_intron < 1)
+    reject(USAGE_MESSAGE, "shark: --sam-rescue needs an intron length of at least 1 (--sam-min-intron, --fragments-min-intron).");
   if (opt.pileup_aligned && opt.pileup_path.empty() && opt.variants_path.empty()) reject(USAGE_MESSAGE, "shark: --pileup-aligned needs --pileup FILE or --variants FILE.");
   if (opt.extend_sub_flag_given && !opt.extend_ends) reject(USAGE_MESSAGE, "shark: --extend-penalty and --extend-bonus need --extend-ends.");
   if (opt.extend_ends && opt.sam_path.empty() && !opt.pileup_aligned) reject(USAGE_MESSAGE, "shark: --extend-ends needs --sam FILE or --pileup-aligned.");
@@ -616,6 +643,7 @@ struct ReadBatch {
   uint32_t seg_m = 0;
   std::vector<shk_mate_alignment> alignments;    // (--sam) two records per association
   std::vector<shk_pair> pairs;                   // (--sam-pairs) one record per association
+  std::vector<shk_rescue> rescues;               // (--sam-rescue) likewise
   int rc = 0;
   void reset()
   {
@@ -627,6 +655,7 @@ struct ReadBatch {
     seg_keys.clear(); seg_entries.clear(); seg_m = 0;
     alignments.clear();
     pairs.clear();
+    rescues.clear();
     rc = 0;
   }
 };
@@ -1072,9 +1101,9 @@ class GzCutter {
 class ReadAnalyzer {
  public:
   ReadAnalyzer(shk_ctx *ctx, bool need_qual, bool evidence, bool candidates = false, bool placements = false, bool segments = false, bool alignments = false,
-               bool pairs = false)
+               bool pairs = false, bool rescue = false)
       : ctx_(ctx), need_qual_(need_qual), evidence_(evidence), candidates_(candidates), placements_(placements), segments_(segments), alignments_(alignments),
-        pairs_(pairs) {}
+        pairs_(pairs), rescue_(rescue) {}
   // false: the batch failed at once (b.rc is set) and is not in flight
   bool submit(std::unique_ptr<ReadBatch> b)
   {
@@ -1148,13 +1177,18 @@ class ReadAnalyzer {
         b->rc = shk_pairs_last(ctx_, &pr);
         if (b->rc == SHK_OK) b->pairs.assign(pr.entries, pr.entries + pr.n_assoc);
       }
+      if (rescue_ && b->rc == SHK_OK) {
+        shk_rescues rs{};
+        b->rc = shk_rescue_last(ctx_, &rs);
+        if (b->rc == SHK_OK) b->rescues.assign(rs.entries, rs.entries + rs.n_assoc);
+      }
     }
     return b;
   }
 
  private:
   shk_ctx *ctx_;
-  bool need_qual_, evidence_, candidates_, placements_, segments_, alignments_, pairs_;
+  bool need_qual_, evidence_, candidates_, placements_, segments_, alignments_, pairs_, rescue_;
   std::deque<std::pair<uint64_t, std::unique_ptr<ReadBatch>>> flying_;
   std::unique_ptr<ReadBatch> failed_;
 };
@@ -1364,10 +1398,10 @@ class ReadOutput {
  public:
   ReadOutput(OffsetWriter *out1, OffsetWriter *out2, const std::vector<std::string> &legend, FILE *evidence = nullptr, FILE *candidates = nullptr,
              FILE *placements = nullptr, bool paired = false, FILE *segments = nullptr, bool junctions = false, uint32_t k = 0, uint32_t junctions_min_support = 8,
-             FILE *sam = nullptr, uint32_t sam_min_intron = 20, bool sam_pairs = false)
+             FILE *sam = nullptr, uint32_t sam_min_intron = 20, bool sam_pairs = false, bool sam_rescue = false)
       : out1_(out1), out2_(out2), legend_(legend), evidence_(evidence), candidates_(candidates), placements_(placements), paired_(paired),
         every_read_(evidence || candidates), segments_(segments), junctions_(junctions), k_(k), s_min_(junctions_min_support),
-        sam_(sam), sam_min_intron_(sam_min_intron), sam_pairs_(sam_pairs) {}
+        sam_(sam), sam_min_intron_(sam_min_intron), sam_pairs_(sam_pairs), sam_rescue_(sam_rescue) {}
   bool failed() const { return failed_.load(); }
   bool evidence_write_failed() const { return failed_write_; }
   bool candidates_write_failed() const { return failed_write_cand_; }
@@ -1484,6 +1518,7 @@ class ReadOutput {
         if (placements_ && b.placements.size() != b.gene_ids.size()) failed_ = true;   // (a batch without a record per association: an error exit)
         if (sam_ && b.alignments.size() != 2 * b.gene_ids.size()) failed_ = true;      // (likewise)
         if (sam_ && sam_pairs_ && b.pairs.size() != b.gene_ids.size()) failed_ = true;  // (likewise)
+        if (sam_ && sam_rescue_ && b.rescues.size() != b.gene_ids.size()) failed_ = true;   // (likewise)
         const bool seg_mode = segments_ || junctions_;
         if (seg_mode && (b.seg_m == 0 || b.seg_keys.size() != 2 * b.gene_ids.size() || b.seg_entries.size() != 2 * b.gene_ids.size() * b.seg_m)) failed_ = true;   // (likewise)
         for (uint32_t j = b.gene_off[i]; j < b.gene_off[i + 1]; ++j) {
@@ -1528,6 +1563,7 @@ class ReadOutput {
             // (--sam) mate 1's line, then mate 2's; a lean batch's qualities come from the file again, as the FASTQ output's do
             const shk_mate_alignment *al = b.alignments.data() + 2 * (size_t)j;
             const shk_pair *pr = sam_pairs_ && (size_t)j < b.pairs.size() ? b.pairs.data() + (size_t)j : nullptr;   // (--sam-pairs)
+            const shk_rescue *rs = sam_rescue_ && (size_t)j < b.rescues.size() ? b.rescues.data() + (size_t)j : nullptr;   // (--sam-rescue)
             for (uint32_t t = 0; t < (paired_ ? 2u : 1u); ++t) {
               if (al[t].n_blocks == 0) continue;
               const DevStrings &seq = t ? b.seq2 : b.seq1, &qual = t ? b.qual2 : b.qual1;
@@ -1536,7 +1572,9 @@ class ReadOutput {
               const char *q = nullptr;      // (nullptr: no quality string of the sequence's length -- FASTA input)
               if (b.lean) q = t ? v2.qual : v1.qual;
               else if (i < qual.size() && qual.len(i) == seq.len(i) && odd.find(i) == odd.end()) q = qual.at(i);
-              if (!sam_line(sg.sam, id, id_len, gene, j > b.gene_off[i], paired_, t, al[t], al[1 - t], seq.at(i), seq.len(i), q, sam_min_intron_, pr)) failed_ = true;
+              if (!sam_line(sg.sam, id, id_len, gene, j > b.gene_off[i], paired_, t, al[t], al[1 - t], seq.at(i), seq.len(i), q, sam_min_intron_, pr,
+                            rs && rs->state == 4u + t ? rs : nullptr))
+                failed_ = true;
             }
           }
           sg.ssv.append(id, id_len);
@@ -1612,9 +1650,10 @@ class ReadOutput {
   // false: the record does not fit a mate of L bytes (the library's answer is inconsistent: an error exit, never a wrong line).
   // pair (--sam-pairs; nullptr without): the association's pair record (include/shark_hip.h, "pairs") -- MAPQ is its mapq, 0x2
   // is set iff proper, TLEN is tend - tstart on the left mate's line and its negative on the other's for classes 3, 4 and 5.
+  // rescued (--sam-rescue; nullptr for a mate that was not rescued): the association's rescue record -- YR:i:<cost> behind NM:i:.
   static bool sam_line(std::string &f, const char *id, size_t id_len, const std::string &gene, bool secondary, bool paired, uint32_t t,
                        const shk_mate_alignment &a, const shk_mate_alignment &other, const char *seq, size_t L, const char *qual, uint32_t min_intron,
-                       const shk_pair *pair = nullptr)
+                       const shk_pair *pair = nullptr, const shk_rescue *rescued = nullptr)
   {
     // (at most 4 M, 3 I, 3 N or D and 2 S, ten decimal digits each)
     char cigar[160], num[64];
@@ -1670,7 +1709,8 @@ class ReadOutput {
     else if (!a.strand) f.append(qual, L);
     else
       for (size_t p = L; p-- > 0;) f.push_back(qual[p]);
-    w = snprintf(num, sizeof(num), "\tNM:i:%u\n", nm);
+    if (rescued) w = snprintf(num, sizeof(num), "\tNM:i:%u\tYR:i:%u\n", nm, rescued->cost);
+    else w = snprintf(num, sizeof(num), "\tNM:i:%u\n", nm);
     f.append(num, (size_t)w);
     return true;
   }
@@ -1709,6 +1749,7 @@ class ReadOutput {
   FILE *sam_;               // (--sam) likewise, one line per association and mate with a block
   uint32_t sam_min_intron_; // (--sam) the gap from which shk_alignment_cigar writes N
   bool sam_pairs_;          // (--sam-pairs) the lines carry the pair records' MAPQ, 0x2 and TLEN
+  bool sam_rescue_;         // (--sam-rescue) a rescued mate's line carries YR:i:
   std::map<std::tuple<uint32_t, int64_t, int64_t>, std::pair<int64_t, uint64_t>> junction_table_;   // (gene, donor, acceptor) -> intron, mates
   bool failed_write_ = false, failed_write_cand_ = false, failed_write_plc_ = false, failed_write_sgm_ = false, failed_write_sam_ = false;
   mutable std::atomic<bool> failed_{false};   // a record could not be read back from its file (I/O error)
@@ -2233,12 +2274,12 @@ void serial_feed(const Options &opt, const FeedPlan &plan, ParallelFeed &feed, B
 }
 
 // analyzers: one thread per worker, SHK_PIPE_DEPTH batches in flight each; t_gpu[g]: seconds inside shk_classify_submit / _wait
-std::vector<std::thread> start_analyzers(const std::vector<shk_ctx *> &ctxs, bool need_qual, bool evidence, bool candidates, bool placements, bool segments, bool alignments, bool pairs, BatchOrder &order, BatchOrder::Queue &to_format, std::vector<double> &t_gpu)
+std::vector<std::thread> start_analyzers(const std::vector<shk_ctx *> &ctxs, bool need_qual, bool evidence, bool candidates, bool placements, bool segments, bool alignments, bool pairs, bool rescue, BatchOrder &order, BatchOrder::Queue &to_format, std::vector<double> &t_gpu)
 {
   std::vector<std::thread> analyzers;
   for (int g = 0; g < (int)ctxs.size(); ++g) {
-    analyzers.emplace_back([&, g, need_qual, evidence, candidates, placements, segments, alignments, pairs] {
-      ReadAnalyzer ra(ctxs[(size_t)g], need_qual, evidence, candidates, placements, segments, alignments, pairs);
+    analyzers.emplace_back([&, g, need_qual, evidence, candidates, placements, segments, alignments, pairs, rescue] {
+      ReadAnalyzer ra(ctxs[(size_t)g], need_qual, evidence, candidates, placements, segments, alignments, pairs, rescue);
       BatchOrder::Queue &todo = order.input(g);
       bool open = true;
       while (open || ra.in_flight()) {
@@ -2295,7 +2336,7 @@ int run_sample(const Options &opt, GpuStart &gpu, BatchPool &pool, std::vector<s
   OffsetWriter *out1 = w1.is_open() ? &w1 : nullptr, *out2 = w2.is_open() ? &w2 : nullptr;
   ReadOutput ro(out1, out2, legend_ID, opt.evidence_file, opt.candidates_file, opt.placements_file, opt.paired_flag, opt.segments_file,
                 opt.junctions_file != nullptr && !opt.junctions_device, opt.k, opt.junctions_min_support, opt.sam_file, opt.sam_min_intron,
-                opt.sam_pairs);
+                opt.sam_pairs, opt.sam_rescue);
   setvbuf(stdout, nullptr, _IOFBF, 1 << 22);
 
   FeedPlan plan(opt, io_threads, need_qual);
@@ -2390,6 +2431,14 @@ int run_sample(const Options &opt, GpuStart &gpu, BatchPool &pool, std::vector<s
         std::cerr << "shark: pairs mode could not be switched on: " << shk_strerror(rc) << " " << shk_last_error(ctx) << std::endl;
         return EXIT_FAILURE;
       }
+  // (--sam-rescue: in front of pairs mode on the device, so --sam-pairs sees the rescued mate)
+  if (opt.sam_file && opt.sam_rescue)
+    for (shk_ctx *ctx : gpu.ctxs)
+      if (const int rc = shk_rescue_enable(ctx, opt.fragments_min_intron, opt.fragments_max, opt.rescue_max_cost, opt.rescue_min_gap)) {
+        feed.stop();
+        std::cerr << "shark: rescue mode could not be switched on: " << shk_strerror(rc) << " " << shk_last_error(ctx) << std::endl;
+        return EXIT_FAILURE;
+      }
   std::unique_ptr<BatchSplitter> fs;
   bool serial_failed = false;
   std::thread splitter([&] { serial_feed(opt, plan, feed, order, pool, fs, serial_failed); });
@@ -2417,7 +2466,8 @@ int run_sample(const Options &opt, GpuStart &gpu, BatchPool &pool, std::vector<s
     });
   }
   std::vector<std::thread> analyzers = start_analyzers(gpu.ctxs, need_qual, opt.evidence_file != nullptr, opt.candidates_file != nullptr, opt.placements_file != nullptr,
-                                                        opt.segments_file != nullptr || host_junctions, opt.sam_file != nullptr, opt.sam_file != nullptr && opt.sam_pairs, order,
+                                                        opt.segments_file != nullptr || host_junctions, opt.sam_file != nullptr, opt.sam_file != nullptr && opt.sam_pairs,
+                                                        opt.sam_file != nullptr && opt.sam_rescue, order,
                                                         to_format, t_gpu);
   // ordered drain
   int failed = 0;

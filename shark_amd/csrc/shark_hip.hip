@@ -122,6 +122,8 @@ static void slot_free(Slot &s)
   if (s.h_align) (void)hipHostFree(s.h_align);
   hipFree(s.d_pairs);
   if (s.h_pairs) (void)hipHostFree(s.h_pairs);
+  hipFree(s.d_rescue); hipFree(s.d_rescue_queue);
+  if (s.h_rescue) (void)hipHostFree(s.h_rescue);
   if (s.h_seg_keys) (void)hipHostFree(s.h_seg_keys);
   if (s.h_seg_entries) (void)hipHostFree(s.h_seg_entries);
   if (s.h_cand_reads) (void)hipHostFree(s.h_cand_reads);
@@ -339,6 +341,16 @@ static int enqueue_tail(Ctx *ctx, Slot &s, bool skip_hist_if_long, bool count_ge
     if (s.align) {
       if ((rc = ensure_capacity(ctx, &s.d_align, &s.cap_align, 2 * s.cap_gene_ids))) return rc;
       if ((rc = launch_alignments(ctx, s, entries, cap_assoc, skip_hist_if_long, true, acc_with_records, st))) return rc;
+      // (rescue mode: a mate without a block placed beside its partner, in front of everything that reads the records)
+      if (s.rescue) {
+        if ((rc = ensure_capacity(ctx, &s.d_rescue, &s.cap_rescue, s.cap_gene_ids))) return rc;
+        if ((rc = ensure_capacity(ctx, &s.d_rescue_queue, &s.cap_rescue_queue, s.cap_gene_ids + 2))) return rc;
+        if ((rc = launch_rescue(ctx, s, cap_assoc, skip_hist_if_long, st))) return rc;
+        if (s.host_batch) {
+          if ((rc = ensure_pinned(ctx, &s.h_rescue, &s.cap_h_rescue, s.cap_gene_ids))) return rc;
+          if ((rc = launch_publish_rescue(s, std::min<uint64_t>(std::min<uint64_t>(s.cap_h_rescue, s.cap_rescue), cap_assoc), st))) return rc;
+        }
+      }
       // (pairs mode: the two mates' records of an association read together, directly behind the kernel that stored them)
       if (s.pairs) {
         if ((rc = ensure_capacity(ctx, &s.d_pairs, &s.cap_pairs, s.cap_gene_ids))) return rc;
@@ -406,6 +418,10 @@ static int enqueue_classify(Ctx *ctx, Slot &s, const shk_batch *b, uint32_t max_
   s.pairs_min_intron = ctx->pairs_min_intron;
   s.pairs_max_frag = ctx->pairs_max_frag;
   s.pairs_count = s.pairs && count_genes;
+  s.rescue = s.align ? ctx->rescue_max_frag : 0u;   // (rescue only behind alignment records)
+  s.rescue_min_intron = ctx->rescue_min_intron;
+  s.rescue_max_cost = ctx->rescue_max_cost;
+  s.rescue_min_gap = ctx->rescue_min_gap;
   if (s.pairs_count) ctx->frag_dirty = true;
   if (s.pileup || s.pileup_al) ctx->pileup_dirty = true;
   if (s.depth || s.sp_depth) ctx->depth_dirty = true;
@@ -600,6 +616,7 @@ static int classify_resident(Ctx *ctx, const shk_batch *b, uint32_t max_read_len
   ctx->last_seg_valid = false;
   ctx->last_align_valid = false;
   ctx->last_pairs_valid = false;
+  ctx->last_rescue_valid = false;
   if (n >= 0xFFFFFFFFull) { ctx->last_error = "batch too large (n must be < 2^32-1)"; return SHK_ERR_ARG; }
   const bool paired = b->seq2 != nullptr;
   const uint32_t max_slots = max_read_len ? slots_for_len(max_read_len, ctx->prm.k, paired) : 0;
@@ -669,6 +686,9 @@ static int classify_resident(Ctx *ctx, const shk_batch *b, uint32_t max_read_len
   ctx->last_pairs_valid = s.pairs != 0 && wc == nullptr;
   ctx->last_pairs = s.d_pairs;
   ctx->last_pairs_n = n_assoc;
+  ctx->last_rescue_valid = s.rescue != 0 && wc == nullptr;
+  ctx->last_rescue = s.d_rescue;
+  ctx->last_rescue_n = n_assoc;
   return SHK_OK;
 }
 
@@ -1201,6 +1221,7 @@ int shk_classify_wait(shk_ctx *ctx, uint64_t ticket, shk_result *result)
   ctx->last_seg_valid = false;
   ctx->last_align_valid = false;
   ctx->last_pairs_valid = false;
+  ctx->last_rescue_valid = false;
   SHK_HIP(ctx, hipEventSynchronize(s.ev_done));
   bool redone = false;
   int rc = finish_classify(ctx, s, s.long_speculative, true, &redone);
@@ -1249,6 +1270,10 @@ int shk_classify_wait(shk_ctx *ctx, uint64_t ticket, shk_result *result)
   ctx->last_pairs_valid = s.pairs != 0;
   ctx->last_pairs = s.host_batch ? s.h_pairs : s.d_pairs;
   ctx->last_pairs_n = n_assoc;
+  if (s.rescue && s.host_batch && n_assoc > s.cap_h_rescue) { ctx->last_error = "rescue publication failed"; return SHK_ERR_HIP; }
+  ctx->last_rescue_valid = s.rescue != 0;
+  ctx->last_rescue = s.host_batch ? s.h_rescue : s.d_rescue;
+  ctx->last_rescue_n = n_assoc;
   return SHK_OK;
 }
 
@@ -1812,6 +1837,38 @@ int shk_pairs_last(const shk_ctx *ctx, shk_pairs *out)
   if (!ctx->last_pairs_valid) return SHK_ERR_STATE;
   out->n_assoc = ctx->last_pairs_n;
   out->entries = ctx->last_pairs;
+  return SHK_OK;
+}
+
+// ---- rescue mode (rescue.hip): per-batch records as pairs mode's; nothing lives in the context but the parameters ----
+int shk_rescue_enable(shk_ctx *ctx, uint32_t min_intron, uint32_t max_frag, uint32_t max_cost, uint32_t min_gap)
+{
+  if (!ctx) return SHK_ERR_ARG;
+  if (tickets_outstanding(ctx)) { ctx->last_error = "shk_rescue_enable: tickets are outstanding (wait for them first)"; return SHK_ERR_STATE; }
+  if (max_frag) {
+    if (max_frag > 4096 || min_intron < 1 || max_cost > 255 || min_gap > 255) {
+      ctx->last_error = "shk_rescue_enable: max_frag is 0 or 1 .. 4096, min_intron at least 1, max_cost and min_gap at most 255";
+      return SHK_ERR_ARG;
+    }
+    if (ctx->mode != 2) { ctx->last_error = "shk_rescue_enable: the index is not finalized"; return SHK_ERR_STATE; }
+    if (!ctx->idx.ptab_lg) { ctx->last_error = "shk_rescue_enable: the index was finalized without shk_ref_keep_positions"; return SHK_ERR_STATE; }
+    if (ctx->n_records > 65536 || ctx->idx.wrap || !ctx->idx.gene_start) { ctx->last_error = "shk_rescue_enable: more than 65 536 records (gene ids wrap)"; return SHK_ERR_STATE; }
+    if (!ctx->idx.recbase) { ctx->last_error = "shk_rescue_enable: the index was finalized without shk_ref_keep_bases"; return SHK_ERR_STATE; }
+    if (!ctx->align) { ctx->last_error = "shk_rescue_enable: alignments mode is off (shk_alignments_enable first)"; return SHK_ERR_STATE; }
+    ctx->rescue_min_intron = min_intron;
+    ctx->rescue_max_cost = max_cost;
+    ctx->rescue_min_gap = min_gap;
+  }
+  ctx->rescue_max_frag = max_frag;
+  return SHK_OK;
+}
+
+int shk_rescue_last(const shk_ctx *ctx, shk_rescues *out)
+{
+  if (!ctx || !out) return SHK_ERR_ARG;
+  if (!ctx->last_rescue_valid) return SHK_ERR_STATE;
+  out->n_assoc = ctx->last_rescue_n;
+  out->entries = ctx->last_rescue;
   return SHK_OK;
 }
 

@@ -403,6 +403,13 @@ struct Slot {
   bool pairs_count = false;
   shk_pair *d_pairs = nullptr; size_t cap_pairs = 0;
   shk_pair *h_pairs = nullptr; size_t cap_h_pairs = 0;   // (host batches; filled by publish_pairs_kernel)
+  // rescue mode (rescue.hip): submitted with this max_frag (0: not; only with `align`): rescue_scan_kernel and rescue_kernel ran behind the
+  // storing align_kernel and in front of pair_kernel, one 16-byte record per association (d_rescue) and a queue of the attempted
+  // associations (d_rescue_queue: 16 bytes that hold the count, then (read, association) pairs), both allocated with the first such batch
+  uint32_t rescue = 0, rescue_min_intron = 0, rescue_max_cost = 0, rescue_min_gap = 0;
+  shk_rescue *d_rescue = nullptr; size_t cap_rescue = 0;
+  uint2 *d_rescue_queue = nullptr; size_t cap_rescue_queue = 0;
+  shk_rescue *h_rescue = nullptr; size_t cap_h_rescue = 0;   // (host batches; filled by publish_rescue_kernel)
 };
 
 struct Ctx;
@@ -448,6 +455,10 @@ int launch_publish_alignments(const Slot &s, uint64_t h_cap, hipStream_t stream)
 // s.d_pairs and, where s.pairs_count, the batch into Ctx::d_frag; directly behind the storing launch_alignments; skip_if_long: as launch_gene_hist
 int launch_pairs(Ctx *ctx, const Slot &s, uint64_t cap_assoc, bool skip_if_long, hipStream_t stream);
 int launch_publish_pairs(const Slot &s, uint64_t h_cap, hipStream_t stream);   // h_cap: associations the pinned array (and the device's) holds
+// rescue.hip: per association of the batch in `s` its rescue record into s.d_rescue and, where a mate is rescued, that mate's record in
+// s.d_align; directly behind the storing launch_alignments and in front of launch_pairs (cap_assoc, skip_if_long: launch_pairs')
+int launch_rescue(Ctx *ctx, const Slot &s, uint64_t cap_assoc, bool skip_if_long, hipStream_t stream);
+int launch_publish_rescue(const Slot &s, uint64_t h_cap, hipStream_t stream);   // h_cap: associations the pinned array (and the device's) holds
 // variants.hip: d_pileup[i] += d_add[i] over n_entries counters (d_add 16-byte aligned: SHK_ERR_ARG otherwise), *d_pileup_mates += mates, on ctx->stream
 int launch_pileup_add(Ctx *ctx, const uint32_t *d_add, uint64_t n_entries, uint64_t mates);
 // variants.hip: the sites of the pileup state against DeviceIndex::recbase: their number into *n_sites (host; the stream is drained) and, with
@@ -608,6 +619,12 @@ struct Ctx {
   bool last_pairs_valid = false;
   const shk_pair *last_pairs = nullptr;
   uint64_t last_pairs_n = 0;
+  // rescue mode (shk_rescue_enable; rescue.hip): per-batch records as pairs mode's; no state of its own
+  uint32_t rescue_max_frag = 0;                // for the batches submitted from now on (0: off)
+  uint32_t rescue_min_intron = 0, rescue_max_cost = 0, rescue_min_gap = 0;
+  bool last_rescue_valid = false;
+  const shk_rescue *last_rescue = nullptr;
+  uint64_t last_rescue_n = 0;
 
   // timing
   bool timing = false;
