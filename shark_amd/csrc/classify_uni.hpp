@@ -175,6 +175,11 @@ __device__ unsigned long long shk_stamp_waves[2 * 4096];   // per wave of the la
 #ifndef SHK_SPARSE_PLAIN
 #define SHK_SPARSE_PLAIN 0
 #endif
+// The miss path on the k-mer keyed table: the candidate stages of a pair's rounds A and B as one block in front of both ballots
+// (SP_JOINT, classify_uni_plan.inc; -DSHK_SPARSE_SERIAL=1: round B behind round A's ballot everywhere, as before; for A/B timing)
+#ifndef SHK_SPARSE_SERIAL
+#define SHK_SPARSE_SERIAL 0
+#endif
 // (-DSHK_NO_PARTIAL=1: the round between the cut's two stops is always probed whole, for A/B timing)
 #ifndef SHK_NO_PARTIAL
 #define SHK_NO_PARTIAL 0
@@ -611,6 +616,7 @@ __global__ __launch_bounds__((UniGeom<U, MODE, LSL>::THREADS), (UniGeom<U, MODE,
     // which a pair with a candidate enters as ever (classify_staged<2> -> sparse_first) and finds the rounds' answers in mp_*.
     // (Here and not inside classify_staged: a return from in there leaves through every stop of the general sequence, a scalar flag
     //  tested at each; from here it is one.)
+    // (SP_JOINT, the k-mer keyed table: the two candidate stages are ONE block in front of both ballots -- see below and classify_uni_plan.inc)
     // (A's are set whenever sparse_first runs, B's whenever it reads them: not initialised, or every pair with a candidate in A pays for
     //  the zeros of B's on its way)
     [[maybe_unused]] bool mp_hA, mp_hB;
@@ -626,6 +632,17 @@ __global__ __launch_bounds__((UniGeom<U, MODE, LSL>::THREADS), (UniGeom<U, MODE,
         uint32_t pay;
         SHK_STAMP(12);
         SHK_STAMP(2);
+        if constexpr (SP_JOINT) {
+          // both rounds' candidate stages in one block, then the two ballots: three LDS round trips for a pair without a candidate,
+          // not six.  B's answer is handed over whatever A's was (sparse_first never probes B itself here); a candidate of A's that
+          // settles the pair by coverage ignores it.  (Stamps: phase 3 is the joint block, phase 5 the second ballot alone.)
+          lx_candidates2(fw, rv, ln >= nA ? spLast - (ln - nA) * k : 2u * ln, ln < nA - 1u ? 2u * ln + 1u : ln + nA, mp_hA, mp_tgA, mp_s2A, mp_hB, mp_tgB, mp_s2B);
+          mp_HA = __ballot(mp_hA);
+          SHK_STAMP(3);
+          mp_HB = __ballot(mp_hB);
+          SHK_STAMP(5);
+          if (!(mp_HA | mp_HB) && spUb < thr_r) return;   // the bound cut: nothing of the prefix is in the filter
+        } else {
         mp_hA = lx_probe(fw, rv, ln >= nA ? spLast - (ln - nA) * k : 2u * ln, pay, std::true_type{}, mp_tgA, mp_s2A);   // (sparse_first's sA)
         mp_HA = __ballot(mp_hA);
         SHK_STAMP(3);
@@ -635,6 +652,7 @@ __global__ __launch_bounds__((UniGeom<U, MODE, LSL>::THREADS), (UniGeom<U, MODE,
           mp_HB = __ballot(mp_hB);
           SHK_STAMP(5);
           if (!mp_HB && spUb < thr_r) return;   // the bound cut: nothing of the prefix is in the filter
+        }
         }
       }
     }

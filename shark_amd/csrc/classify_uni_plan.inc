@@ -115,6 +115,11 @@
   // SP_STRAIGHT: the pair without a candidate in round A or B -- every pair from elsewhere -- as straight code of its own (per_pair,
   // classify_uni.hpp: the miss path); sparse_first takes over what its two rounds found
   constexpr bool SP_STRAIGHT = SPARSE && sp_one && !SHK_SPARSE_PLAIN;
+  // SP_JOINT (a form of SP_STRAIGHT; the k-mer keyed table): the candidate stages of the rounds A and B of a pair as ONE block -- both
+  // rounds' windows, both D reads, both T16 reads, then the two ballots.  B's slots are a function of the lane and the plan, not of A's
+  // answer, so a pair without a candidate waits for three LDS round trips instead of six; a pair that A alone would have settled has
+  // paid B's stage for nothing.  (The hashed forms have no registers for two XXH64 states at once: they keep the serial order.)
+  constexpr bool SP_JOINT = SP_STRAIGHT && KX && !SHK_KX_ONE_STAGE && !SHK_SPARSE_SERIAL;
   const bool sp_on = SPARSE && (LXM ? P.lx_multi != 0u : P.lx_gene != 0xFFFFFFFFu);
   // floor(x / k) and floor(x / (k - 1)) for x < 2048 as a multiplication (k <= 32)
   const uint32_t sp_rk = sp_on ? (65536u + k - 1u) / k : 0u, sp_rk1 = (sp_on && k > 1u) ? (65536u + k - 2u) / (k - 1u) : 0u;

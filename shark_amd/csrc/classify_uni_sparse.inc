@@ -49,8 +49,8 @@
       bool hA, hB = false;
       uint64_t HA, HB = 0ull;
       if constexpr (SP_STRAIGHT) {
-        // round A's candidate stage was per_pair's (the miss path, classify_uni.hpp) -- and round B's too where A had no candidate:
-        // what they left is taken over, no round is probed twice
+        // round A's candidate stage was per_pair's (the miss path, classify_uni.hpp) -- and round B's too where A had no candidate
+        // (SP_JOINT: always, beside A's): what they left is taken over, no round is probed twice
         // (the empty asm: A's ballot is looked at again here, two scalar instructions -- told where it came from, the compiler carries
         //  "B was probed" as a lane mask of its own from there to here, spilled on the way)
         hA = mp_hA; HA = mp_HA; tgA = mp_tgA; s2A = mp_s2A;
@@ -61,7 +61,7 @@
         HA = __ballot(hA);
         SHK_STAMP(3);
       }
-      if (SP_STRAIGHT && !HA) {
+      if (SP_STRAIGHT && !SP_JOINT && !HA) {
         hB = mp_hB; HB = mp_HB; tgB = mp_tgB; s2B = mp_s2B;
       } else {
         if (HA) {
@@ -81,9 +81,14 @@
           }
         }
         SHK_STAMP(4);
-        hB = lx_hit_at(sB, true, pB, tgB, s2B);
-        HB = __ballot(hB);
-        SHK_STAMP(5);
+        if constexpr (SP_JOINT) {
+          // (B's candidate stage ran beside A's in per_pair, whatever A's answer: taken over here, behind A's coverage)
+          hB = mp_hB; HB = mp_HB; tgB = mp_tgB; s2B = mp_s2B;
+        } else {
+          hB = lx_hit_at(sB, true, pB, tgB, s2B);
+          HB = __ballot(hB);
+          SHK_STAMP(5);
+        }
       }
       // (a pair with a candidate in A or B joins here, hA / tgA / s2A and B's as the rounds left them: no round is probed twice)
       if (HB) {

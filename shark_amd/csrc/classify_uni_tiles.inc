@@ -38,6 +38,37 @@
       payload = ee & LTAB_ESC;
       return (ee >> 13) == ((tg << 1) | 1u);
     };
+    // (SP_JOINT) the candidate stages of TWO slots of a staged pair -- a lane's slot of round A and its slot of round B -- stage by
+    // stage: the twelve window dwords, the two mixes, the two D reads, the two T16 reads.  Each answer is kxtab_candidate's for its
+    // slot (the same reads, the same compare); written out here so that no read of B's stands behind a wait for A's
+    auto lx_candidates2 = [&](const uint32_t *fwp, const uint32_t *rvp, const uint32_t sa, const uint32_t sb, bool &ha, uint32_t &tga, uint32_t &s2a,
+                              bool &hb, uint32_t &tgb, uint32_t &s2b) {
+      if constexpr (KX) {
+        const uint32_t qa = rcap - k - sa, qb = rcap - k - sb;
+        const uint32_t *fa = fwp + (sa >> 4), *ra = rvp + (qa >> 4), *fb = fwp + (sb >> 4), *rb = rvp + (qb >> 4);
+        const uint32_t a0 = fa[0], a1 = fa[1], a2 = fa[2], c0 = ra[0], c1 = ra[1], c2 = ra[2];
+        const uint32_t b0 = fb[0], b1 = fb[1], b2 = fb[2], e0 = rb[0], e1 = rb[1], e2 = rb[2];
+        auto canon = [&](const uint32_t d0, const uint32_t d1, const uint32_t d2, const uint32_t r0, const uint32_t r1, const uint32_t r2, const uint32_t ss, const uint32_t q) -> uint64_t {
+          const uint32_t af = (ss & 15u) << 1, ar = (q & 15u) << 1;
+          const uint64_t x = ((uint64_t)__builtin_amdgcn_alignbit(d2, d1, af) << 32) | __builtin_amdgcn_alignbit(d1, d0, af);
+          const uint64_t y = ((uint64_t)__builtin_amdgcn_alignbit(r2, r1, ar) << 32) | __builtin_amdgcn_alignbit(r1, r0, ar);
+          const uint64_t fwd = y & kmer_mask, rc = ~x & kmer_mask;
+          return fwd < rc ? fwd : rc;
+        };
+        const uint8_t *img = reinterpret_cast<const uint8_t *>(lsum);
+        uint32_t basea, baseb;
+        kxtab_mix(canon(a0, a1, a2, c0, c1, c2, sa, qa), P.lsum_shift, P.kx_m2, tga, basea);
+        kxtab_mix(canon(b0, b1, b2, e0, e1, e2, sb, qb), P.lsum_shift, P.kx_m2, tgb, baseb);
+        const uint32_t da = *reinterpret_cast<const uint16_t *>(img + KXTAB_D_OFF + ((tga << 1) & ((2u << KXTAB_GROUP_LG) - 2u)));
+        const uint32_t db = *reinterpret_cast<const uint16_t *>(img + KXTAB_D_OFF + ((tgb << 1) & ((2u << KXTAB_GROUP_LG) - 2u)));
+        s2a = ((basea + da) << 1) & ((2u << KXTAB_RING_LG) - 2u);
+        s2b = ((baseb + db) << 1) & ((2u << KXTAB_RING_LG) - 2u);
+        const uint16_t ta = *reinterpret_cast<const uint16_t *>(img + s2a);
+        const uint16_t tb = *reinterpret_cast<const uint16_t *>(img + s2b);
+        ha = ta == (uint16_t)tga;
+        hb = tb == (uint16_t)tgb;
+      }
+    };
     // the confirm stage of a sparse-round candidate (true where lx_probe's answer was final already)
     auto lx_confirm = [&](const uint32_t tag, const uint32_t s2) -> bool {
       if constexpr (KX && !SHK_KX_ONE_STAGE) return kxtab_confirm(reinterpret_cast<const uint8_t *>(lsum), tag, s2);
