@@ -986,6 +986,28 @@ int shk_measure_valu_mix(shk_ctx *ctx, int waves_per_simd, uint32_t iters, doubl
  * (`roofline.clock`).  On no product path; new (the reference has no counterpart). */
 int shk_measure_valu_mix_clock(shk_ctx *ctx, int waves_per_simd, uint32_t iters, double *ms, uint64_t *wave_iterations, double *shader_ghz);
 
+/* Test-only: the three launches that assemble the result of a batch against an index of ONE record (every association is gene 0's:
+ * the scan of the per-read counts writes the offsets, fills gene_ids with id 0, writes the batch's counters and counts gene 0) over
+ * the caller's `count[0 .. n)`, n >= 1, on the context's device and stream; works in any mode of the context, with or without an index,
+ * allocates what it needs and frees it again.  count_off / off_off (0 .. 3) place the device copies of count / gene_off that many
+ * words behind a 16-byte aligned address ((0, 0): 16-byte accesses, anything else word by word).  gene_ids_cap: the capacity of the
+ * device's gene_ids; ctr_long: what the counter of queued long reads holds beforehand; skip_if_long, count_genes: as a classify
+ * call sets them -- gene 0 is counted when count_genes, the total fits the capacity, and not (skip_if_long and ctr_long != 0).
+ * Hands back gene_off[0 .. n); gene_ids[0 .. gene_ids_cap), which starts as SHK_DEBUG_FILL16 in every word; the counter block of
+ * SHK_DEBUG_COUNTER_WORDS words ([SHK_DEBUG_CTR_LONG] as given, [SHK_DEBUG_CTR_OVERFLOW] = total > gene_ids_cap,
+ * [SHK_DEBUG_CTR_ASSOC_LO / _HI] = the total, every other word 0); what was added to gene 0's counter; and, per device buffer, the
+ * guard words in front of it and behind it that changed -- count, gene_off, the scan's temp, gene_ids, the counters, gene 0's
+ * counter, (front, back) each; a changed word of count itself is counted with its back band.  All zero on a clean run. */
+#define SHK_DEBUG_FILL16 0x0FF2u
+#define SHK_DEBUG_COUNTER_WORDS 16
+#define SHK_DEBUG_CTR_LONG 0
+#define SHK_DEBUG_CTR_OVERFLOW 2
+#define SHK_DEBUG_CTR_ASSOC_LO 6
+#define SHK_DEBUG_CTR_ASSOC_HI 7
+int shk_debug_assemble_one(shk_ctx *ctx, const uint32_t *count, uint64_t n, uint32_t count_off, uint32_t off_off, uint64_t gene_ids_cap,
+                           uint32_t ctr_long, int skip_if_long, int count_genes, uint32_t *gene_off, uint16_t *gene_ids,
+                           uint32_t *counters /* [SHK_DEBUG_COUNTER_WORDS] */, uint64_t *gene0_added, uint32_t *guard_changed /* [12] */);
+
 /* pinned host memory helpers for callers that stream batches */
 void *shk_alloc_pinned(size_t bytes);
 void  shk_free_pinned(void *p);

@@ -137,6 +137,7 @@ EXPORTS = [
     "shk_alignments_enable", "shk_alignments_last", "shk_alignment_cigar", "shk_alignments_extend", "shk_pileup_enable_aligned",
     "shk_pairs_enable", "shk_pairs_last", "shk_fragments_get", "shk_fragments_reset",
     "shk_rescue_enable", "shk_rescue_last",
+    "shk_debug_assemble_one",
 ]
 SHK_PIPE_DEPTH = 3
 SHK_DIST_ID_BYTES = 128
@@ -239,6 +240,8 @@ def load():
         "shk_fragments_reset": (C.c_int, [p]),
         "shk_rescue_enable": (C.c_int, [p, C.c_uint32, C.c_uint32, C.c_uint32, C.c_uint32]),
         "shk_rescue_last": (C.c_int, [p, C.POINTER(ShkRescues)]),
+        "shk_debug_assemble_one": (C.c_int, [p, p, C.c_uint64, C.c_uint32, C.c_uint32, C.c_uint64, C.c_uint32, C.c_int, C.c_int, p, p, p,
+                                             C.POINTER(C.c_uint64), p]),
     }
     variant = bool(os.environ.get("SHK_LIB_PATH"))
     for name, (res, args) in later.items():
@@ -425,6 +428,28 @@ class SharkHip:
         which = C.c_int(-1)
         self._check(fn(self.h, _ptr(a), len(a), end_bit, _ptr(out), C.byref(which), _ptr(guards)), "shk_debug_sort_u64")
         return out, int(which.value), guards
+
+    # ---- test-only run of the one-record assembly (shk_debug_assemble_one, include/shark_hip.h) ----
+    DEBUG_ASSEMBLE_GUARDS = ("count_front", "count_back", "off_front", "off_back", "temp_front", "temp_back", "ids_front", "ids_back",
+                             "counters_front", "counters_back", "gene0_front", "gene0_back")
+    DEBUG_FILL16 = 0x0FF2
+    DEBUG_COUNTER_WORDS = 16
+    DEBUG_CTR_LONG, DEBUG_CTR_OVERFLOW, DEBUG_CTR_ASSOC_LO, DEBUG_CTR_ASSOC_HI = 0, 2, 6, 7
+
+    def debug_assemble_one(self, count, gene_ids_cap, count_off=0, off_off=0, ctr_long=0, skip_if_long=False, count_genes=True):
+        """the three launches that assemble a one-record index's result over `count` (uint32, at least one word).  Returns (gene_off,
+        gene_ids, counters, gene0_added, guards): gene_off uint32[len(count)]; gene_ids uint16[gene_ids_cap], DEBUG_FILL16 where nothing was
+        written; the counter block; what was added to gene 0's counter; changed guard words per band in the order of DEBUG_ASSEMBLE_GUARDS"""
+        a = np.ascontiguousarray(count, dtype=np.uint32)
+        gene_off = np.zeros(len(a), dtype=np.uint32)
+        gene_ids = np.zeros(max(int(gene_ids_cap), 1), dtype=np.uint16)
+        counters = np.zeros(self.DEBUG_COUNTER_WORDS, dtype=np.uint32)
+        guards = np.zeros(len(self.DEBUG_ASSEMBLE_GUARDS), dtype=np.uint32)
+        added = C.c_uint64()
+        self._check(self.L.shk_debug_assemble_one(self.h, _ptr(a), len(a), count_off, off_off, int(gene_ids_cap), ctr_long, int(bool(skip_if_long)),
+                                                  int(bool(count_genes)), _ptr(gene_off), _ptr(gene_ids), _ptr(counters), C.byref(added), _ptr(guards)),
+                    "shk_debug_assemble_one")
+        return gene_off, gene_ids[:int(gene_ids_cap)], counters, int(added.value), guards
 
     # ---- classification --------------------------------------------------------
     def _host_batch(self, seq1, off1, seq2, off2, qual1, qual2):

@@ -1,5 +1,6 @@
 // device_scan.hip -- kernels behind device_scan.hpp (exclusive prefix sum, gfx950).
 #include "device_scan.hpp"
+#include "shark_internal.hpp"   // CTR_*: the counter block that the one-record form fills in
 
 namespace shk {
 
@@ -144,6 +145,126 @@ const uint64_t *exclusive_scan_u32(const uint32_t *in, uint32_t *out, uint64_t n
   hipLaunchKernelGGL(scan_tile_offsets_kernel, dim3(1), dim3(SCAN_OFFS_THREADS), 0, stream, temp, ntiles, total);
   if (vec) hipLaunchKernelGGL(scan_apply_kernel<true>, dim3((unsigned)ntiles), dim3(SCAN_THREADS), 0, stream, in, out, n, temp);
   else hipLaunchKernelGGL(scan_apply_kernel<false>, dim3((unsigned)ntiles), dim3(SCAN_THREADS), 0, stream, in, out, n, temp);
+  return total;
+}
+
+// ---------------------------------------------------------------------------
+// The one-record form (device_scan.hpp, OneRecordResult).  The two kernels below are scan_tile_offsets_kernel and scan_apply_kernel
+// with something behind them.  They repeat those kernels' text instead of sharing it through a function: the index build, the sort and
+// the depth / variants read-outs run the kernels above, and moving their bodies changed the order of their instructions.
+// ---------------------------------------------------------------------------
+// the thread that writes the total does finalize_total_kernel's job, and gene_hist_kernel's as well -- every association is gene 0's
+__global__ __launch_bounds__(SCAN_OFFS_THREADS) void scan_tile_offsets_one_kernel(uint64_t *__restrict__ tile_sums, uint64_t ntiles, uint64_t *__restrict__ total_out,
+                                                                                  uint32_t *__restrict__ counters, uint64_t gene_ids_cap, uint32_t count_genes,
+                                                                                  uint32_t skip_if_long, unsigned long long *__restrict__ gene_counts)
+{
+  __shared__ uint64_t lds[SCAN_OFFS_THREADS / 64];
+  const uint64_t per = (ntiles + SCAN_OFFS_THREADS - 1) / SCAN_OFFS_THREADS;
+  const uint64_t lo = (uint64_t)threadIdx.x * per, hi = lo + per < ntiles ? lo + per : ntiles;
+  uint64_t s = 0;
+  for (uint64_t i = lo; i < hi; ++i) s += tile_sums[i];
+  const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+  uint64_t inc = s;
+#pragma unroll
+  for (int o = 1; o < 64; o <<= 1) {
+    const uint64_t t = __shfl_up(inc, o, 64);
+    if (lane >= o) inc += t;
+  }
+  if (lane == 63) lds[wave] = inc;
+  __syncthreads();
+  uint64_t add = 0, tot = 0;
+#pragma unroll
+  for (int w = 0; w < SCAN_OFFS_THREADS / 64; ++w) {
+    const uint64_t t = lds[w];
+    if (w < wave) add += t;
+    tot += t;
+  }
+  uint64_t run = add + inc - s;
+  for (uint64_t i = lo; i < hi; ++i) {
+    const uint64_t t = tile_sums[i];
+    tile_sums[i] = run;
+    run += t;
+  }
+  if (threadIdx.x != 0) return;
+  *total_out = tot;
+  const bool overflow = tot > gene_ids_cap;
+  counters[CTR_ASSOC_LO] = (uint32_t)tot;
+  counters[CTR_ASSOC_HI] = (uint32_t)(tot >> 32);
+  counters[CTR_OVERFLOW] = overflow ? 1u : 0u;
+  // (gene_hist_kernel's rule: a batch that the host finishes by its slow path comes through here again and is counted then)
+  if (count_genes && !overflow && !(skip_if_long && counters[CTR_LONG]) && tot) atomicAdd(&gene_counts[0], (unsigned long long)tot);
+}
+
+// the tile's associations are all gene 0's, and the workgroup writes them: ids [tile_offs[b], tile_offs[b] + the tile's sum), cut at
+// gene_ids_cap; none when the batch overflows (the epilogue above has set the flag).  Coalesced: 16 bytes per lane between a head
+// that reaches the first 16-byte boundary and a tail, both of fewer than 8 ids
+template <bool VEC>
+__global__ __launch_bounds__(SCAN_THREADS) void scan_apply_fill_kernel(const uint32_t *__restrict__ in, uint32_t *__restrict__ out, uint64_t n,
+                                                                      const uint64_t *__restrict__ tile_offs, uint16_t *__restrict__ gene_ids, uint64_t gene_ids_cap,
+                                                                      const uint32_t *__restrict__ counters)
+{
+  __shared__ uint32_t lds[SCAN_THREADS / 64];
+  const uint64_t base = (uint64_t)blockIdx.x * SCAN_TILE + (uint64_t)threadIdx.x * SCAN_ITEMS;
+  uint32_t v[SCAN_ITEMS];
+  load_items<VEC>(in, base, n, v);
+  uint32_t s = 0;
+#pragma unroll
+  for (int i = 0; i < SCAN_ITEMS; ++i) s += v[i];
+  const uint32_t inc = wave_inclusive_scan_u32(s);
+  const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+  if (lane == 63) lds[wave] = inc;
+  __syncthreads();
+  uint32_t add = 0, tile = 0;   // tile: the tile's sum (a tile of 0 / 1 counts: at most SCAN_TILE)
+#pragma unroll
+  for (int w = 0; w < SCAN_THREADS / 64; ++w) {
+    add += w < wave ? lds[w] : 0u;
+    tile += lds[w];
+  }
+  const uint64_t off = tile_offs[blockIdx.x];
+  uint32_t run = (uint32_t)off + add + inc - s;
+#pragma unroll
+  for (int i = 0; i < SCAN_ITEMS; ++i) {
+    const uint32_t t = v[i];
+    v[i] = run;
+    run += t;
+  }
+  if (VEC && base + SCAN_ITEMS <= n) {
+    uint4 *p = reinterpret_cast<uint4 *>(out + base);
+#pragma unroll
+    for (int q = 0; q < 4; ++q) p[q] = make_uint4(v[4 * q], v[4 * q + 1], v[4 * q + 2], v[4 * q + 3]);
+  } else {
+#pragma unroll
+    for (int i = 0; i < SCAN_ITEMS; ++i)
+      if (base + i < n) out[base + i] = v[i];
+  }
+  if (counters[CTR_OVERFLOW]) return;
+  const uint64_t lo = off < gene_ids_cap ? off : gene_ids_cap;
+  const uint64_t hi = tile < gene_ids_cap - lo ? lo + tile : gene_ids_cap;
+  uint64_t head = ((16u - (uint32_t)(reinterpret_cast<uintptr_t>(gene_ids + lo) & 15u)) & 15u) / 2;
+  if (head > hi - lo) head = hi - lo;
+  if (threadIdx.x < head) gene_ids[lo + threadIdx.x] = 0;
+  const uint64_t body = lo + head, n8 = (hi - body) / 8;
+  uint4 *p8 = reinterpret_cast<uint4 *>(gene_ids + body);
+  for (uint64_t i = threadIdx.x; i < n8; i += SCAN_THREADS) p8[i] = make_uint4(0u, 0u, 0u, 0u);
+  const uint64_t tail = body + 8 * n8;
+  if (threadIdx.x < hi - tail) gene_ids[tail + threadIdx.x] = 0;
+}
+
+// the same three launches as exclusive_scan_u32, with the epilogue and the fill; n >= 1
+const uint64_t *exclusive_scan_assemble_one(const uint32_t *count, uint32_t *gene_off, uint64_t n, uint64_t *temp, const OneRecordResult &r,
+                                            hipStream_t stream)
+{
+  const uint64_t ntiles = (n + SCAN_TILE - 1) / SCAN_TILE;
+  uint64_t *total = temp + ntiles;
+  const bool vec = ((reinterpret_cast<uintptr_t>(count) | reinterpret_cast<uintptr_t>(gene_off)) & 15u) == 0;
+  if (vec) hipLaunchKernelGGL(scan_tile_sums_kernel<true>, dim3((unsigned)ntiles), dim3(SCAN_THREADS), 0, stream, count, n, temp);
+  else hipLaunchKernelGGL(scan_tile_sums_kernel<false>, dim3((unsigned)ntiles), dim3(SCAN_THREADS), 0, stream, count, n, temp);
+  hipLaunchKernelGGL(scan_tile_offsets_one_kernel, dim3(1), dim3(SCAN_OFFS_THREADS), 0, stream, temp, ntiles, total, r.counters, r.gene_ids_cap,
+                     r.count_genes ? 1u : 0u, r.skip_if_long ? 1u : 0u, r.gene_counts);
+  if (vec) hipLaunchKernelGGL(scan_apply_fill_kernel<true>, dim3((unsigned)ntiles), dim3(SCAN_THREADS), 0, stream, count, gene_off, n, temp, r.gene_ids,
+                              r.gene_ids_cap, r.counters);
+  else hipLaunchKernelGGL(scan_apply_fill_kernel<false>, dim3((unsigned)ntiles), dim3(SCAN_THREADS), 0, stream, count, gene_off, n, temp, r.gene_ids,
+                          r.gene_ids_cap, r.counters);
   return total;
 }
 

@@ -22,4 +22,23 @@ inline uint64_t scan_temp_words(uint64_t n) { return (n + SCAN_TILE - 1) / SCAN_
 // exclusive scan in -> out (may alias); returns the device pointer holding the 64-bit total
 const uint64_t *exclusive_scan_u32(const uint32_t *in, uint32_t *out, uint64_t n, uint64_t *temp, hipStream_t stream);
 
+// The result of a batch against an index of ONE record without wrap, assembled by the scan itself (shark_hip.hip, enqueue_tail): a
+// read's list there is {} or {0}, so gene_ids[0 .. total) is `total` copies of id 0 and gene 0 was assigned `total` reads.  The same
+// three launches as exclusive_scan_u32 over count[0 .. n) -> gene_off[0 .. n) (n >= 1, no aliasing, temp as above), with
+//   * an epilogue in the tile-offsets kernel: the thread that writes the total also writes counters[CTR_ASSOC_LO / _HI], sets
+//     counters[CTR_OVERFLOW] = total > gene_ids_cap (finalize_total_kernel's job) and adds the total to gene_counts[0] exactly when
+//     gene_hist_kernel would have counted the batch: count_genes, no overflow, and not (skip_if_long and counters[CTR_LONG] != 0);
+//   * a fill in the apply kernel: workgroup b writes id 0 to gene_ids[tile_offs[b] .. tile_offs[b] + its tile's sum), coalesced (16-byte
+//     stores between a head and a tail of fewer than 8 ids); nothing at or beyond gene_ids_cap, nothing at all on overflow.
+// Returns the device pointer holding the 64-bit total.
+struct OneRecordResult {
+  uint16_t *gene_ids;
+  uint64_t gene_ids_cap;
+  uint32_t *counters;                   // the batch's counter block (shark_internal.hpp, CTR_*)
+  unsigned long long *gene_counts;      // the context's per-gene counters (only [0] is touched); may be null when !count_genes
+  bool count_genes, skip_if_long;
+};
+const uint64_t *exclusive_scan_assemble_one(const uint32_t *count, uint32_t *gene_off, uint64_t n, uint64_t *temp, const OneRecordResult &r,
+                                            hipStream_t stream);
+
 }  // namespace shk

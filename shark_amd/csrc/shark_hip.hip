@@ -256,11 +256,19 @@ static int enqueue_tail(Ctx *ctx, Slot &s, bool skip_hist_if_long, bool count_ge
   hipStream_t st = ctx->stream;
   const uint64_t n = s.n;
   int rc;
-  const uint64_t *d_total = exclusive_scan_u32(s.d_count, s.d_gene_off, n + 1, s.d_scan_temp, st);
-  SHK_HIP(ctx, hipGetLastError());
-  if ((rc = launch_finalize_total(d_total, s.d_counters, s.cap_gene_ids, st))) return rc;
-  if ((rc = launch_gather_inline(s.d_count, s.d_inl, s.d_gene_off, s.d_gene_ids, n, s.d_counters, st))) return rc;
-  {
+  // An index of one record without wrap: a read's list is {} or {0}, whichever kernel classified it, so gene_ids is `total` copies of id 0,
+  // gene 0 was assigned `total` reads and the tie queue is empty by construction -- the scan assembles all of it in its own three
+  // launches (device_scan.hpp, OneRecordResult): no finalize, gather, EMIT or histogram launch.  SHK_PLAIN_TAIL=1: the sequence below
+  const bool one_record = ctx->n_records == 1 && !ctx->idx.wrap && !ctx->env_plain_tail;
+  if (one_record) {
+    const OneRecordResult r{s.d_gene_ids, s.cap_gene_ids, s.d_counters, ctx->d_gene_counts, count_genes, skip_hist_if_long};
+    (void)exclusive_scan_assemble_one(s.d_count, s.d_gene_off, n + 1, s.d_scan_temp, r, st);
+    SHK_HIP(ctx, hipGetLastError());
+  } else {
+    const uint64_t *d_total = exclusive_scan_u32(s.d_count, s.d_gene_off, n + 1, s.d_scan_temp, st);
+    SHK_HIP(ctx, hipGetLastError());
+    if ((rc = launch_finalize_total(d_total, s.d_counters, s.cap_gene_ids, st))) return rc;
+    if ((rc = launch_gather_inline(s.d_count, s.d_inl, s.d_gene_off, s.d_gene_ids, n, s.d_counters, st))) return rc;
     ClassifyParams p = s.p;
     unsigned n_waves = 0;
     if ((rc = size_scratch(ctx, p, s.gen_slots, std::min<uint64_t>(n, 1024), &n_waves))) return rc;
@@ -270,8 +278,8 @@ static int enqueue_tail(Ctx *ctx, Slot &s, bool skip_hist_if_long, bool count_ge
     p.gene_off = s.d_gene_off;
     p.gene_ids = s.d_gene_ids;
     if ((rc = launch_classify_general(ctx, p, true, n_waves, st))) return rc;
+    if (count_genes && (rc = launch_gene_hist(s.d_gene_ids, s.d_counters, skip_hist_if_long, ctx->d_gene_counts, n, ctx->n_records, st))) return rc;
   }
-  if (count_genes && (rc = launch_gene_hist(s.d_gene_ids, s.d_counters, skip_hist_if_long, ctx->d_gene_counts, n, ctx->n_records, st))) return rc;
   // counters (and, for host batches, the associations) are stored into pinned host memory by a kernel: no copy-engine
   // command ever sits in this stream waiting for kernels (see publish_results_kernel)
   if (s.host_batch) {
@@ -813,6 +821,7 @@ int shk_create(const shk_params *prm, shk_ctx **out)
     ctx->env_anchor_always = getenv("SHK_ANCHOR_ALWAYS") != nullptr;
     ctx->env_no_pre_verdict = getenv("SHK_NO_PRE_VERDICT") != nullptr;
     ctx->env_no_tri = getenv("SHK_NO_TRI") != nullptr;
+    { const char *pt = getenv("SHK_PLAIN_TAIL"); ctx->env_plain_tail = pt && pt[0] == '1'; }
     ctx->env_pairs_global = getenv("SHK_PAIRS_GLOBAL_ATOMICS") != nullptr;
     ctx->env_no_tro = getenv("SHK_NO_TRO") != nullptr;
     ctx->env_force_tro = getenv("SHK_FORCE_TRO") != nullptr;

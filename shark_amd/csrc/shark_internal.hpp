@@ -173,6 +173,8 @@ struct DeviceIndex {
 // (in place the out pair repeats the in pair), sort {a, b, hist, scan_tmp} x {front, back}.  All zero unless a kernel wrote outside
 // its arrays.  n == 0 works and changes nothing but the scan's total.
 // As shk_debug_index_array: exported, not declared in include/shark_hip.h, no classify or build path uses them.
+// shk_debug_assemble_one (the same file, the same guard bands) runs exclusive_scan_assemble_one, the tail of a one-record index, over a
+// caller's counts; it is declared and described in include/shark_hip.h (tests/test_gpu_one_gene_tail.py).
 constexpr uint32_t SHK_DEBUG_META_WORDS = 16;
 constexpr uint32_t SHK_DEBUG_KXMETA_WORDS = 6;
 constexpr uint32_t SHK_DEBUG_PMETA_WORDS = 2;
@@ -300,7 +302,7 @@ struct ClassifyParams {
 enum {
   CTR_LONG = 0,      // entries in long_queue
   CTR_TIE = 1,       // entries in tie_queue
-  CTR_OVERFLOW = 2,  // 1 = the batch has more associations than gene_ids holds (finalize_total_kernel)
+  CTR_OVERFLOW = 2,  // 1 = the batch has more associations than gene_ids holds (finalize_total_kernel; scan_tile_offsets_one_kernel)
   CTR_UNUSED3 = 3,
   CTR_MAX_SLOTS = 4, // max k-mer slots over queued long reads
   CTR_UNUSED5 = 5,
@@ -537,6 +539,7 @@ struct Ctx {
   bool env_no_tro = false;          // SHK_NO_TRO=1: trimmed batches never through the three-pairs kernel by offsets (the class-by-class path instead; tests, A/B timing)
   bool env_force_tro = false;      // SHK_FORCE_TRO=1: batches of one length through the offsets kernel as well (diagnostic: what the offsets cost)
   bool env_no_tri = false;          // SHK_NO_TRI=1: no three-pairs-per-pass instantiation (A/B timing, tests)
+  bool env_plain_tail = false;      // SHK_PLAIN_TAIL=1: a one-record index's results through gather, EMIT pass and histogram as every other index's (A/B timing, tests)
   bool env_no_pre_verdict = false;  // SHK_NO_PRE_VERDICT=1: no anchor_verdict_kernel in front of the table kernels (A/B timing, tests)
   bool env_anchor_always = false;   // SHK_ANCHOR_ALWAYS=1: the anchored extension for every batch of an index that has the reference arrays (tests, A/B timing)
   bool env_ktab_always = false;     // SHK_KTAB=1: the minimiser table for every batch of an index that has it (tests)
