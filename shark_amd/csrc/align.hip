@@ -321,23 +321,12 @@ __global__ __launch_bounds__(PL_THREADS) void align_kernel(const Params P)
   }
 }
 
-// publish_segments_kernel's copy for this mode's records: the associations the batch has, as far as both arrays hold them
-__global__ __launch_bounds__(256) void publish_alignments_kernel(const uint32_t *__restrict__ counters, const uint4 *__restrict__ src, uint4 *__restrict__ h_dst,
-                                                                 uint64_t h_cap)
-{
-  if (counters[CTR_OVERFLOW]) return;
-  const uint64_t total = ((uint64_t)counters[CTR_ASSOC_HI] << 32) | counters[CTR_ASSOC_LO];
-  const uint64_t n4 = (total < h_cap ? total : h_cap) * (2u * AL_WORDS / 4u);
-  const uint64_t tid = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x, nth = (uint64_t)gridDim.x * blockDim.x;
-  for (uint64_t i = tid; i < n4; i += nth) h_dst[i] = src[i];
-}
-
 }  // namespace
 
 int launch_alignments(Ctx *ctx, const Slot &s, const shk_segment *entries, uint64_t cap_assoc, bool skip_if_long, bool store, bool accumulate, hipStream_t stream)
 {
   const DeviceIndex &ix = ctx->idx;
-  if (!ix.gene_start || !ix.recbase || !entries || (!store && !accumulate) || (store && (!s.align || !s.d_align))) {
+  if (!ix.gene_start || !ix.recbase || !entries || (!store && !accumulate) || (store && (!s.align || !s.rec_align.d.p))) {
     ctx->last_error = "alignments mode without its state";
     return SHK_ERR_STATE;
   }
@@ -347,11 +336,11 @@ int launch_alignments(Ctx *ctx, const Slot &s, const shk_segment *entries, uint6
   }
   if (s.n == 0) return SHK_OK;
   AlignParamsX P{};
-  P.gene_off = s.d_gene_off;
-  P.gene_ids = s.d_gene_ids;
+  P.gene_off = s.d_gene_off.p;
+  P.gene_ids = s.d_gene_ids.p;
   P.counters = s.d_counters;
   P.n = s.n;
-  P.cap = (uint32_t)std::min<uint64_t>(std::min<uint64_t>(std::min<uint64_t>(s.cap_gene_ids, cap_assoc), store ? s.cap_align / 2 : ~0ull), 0xFFFFFFFFull);   // (launch_segments')
+  P.cap = (uint32_t)std::min<uint64_t>(std::min<uint64_t>(std::min<uint64_t>(s.d_gene_ids.cap, cap_assoc), store ? s.rec_align.d.cap / 2 : ~0ull), 0xFFFFFFFFull);   // (launch_segments')
   P.seq[0] = s.p.seq1; P.off[0] = s.p.off1; P.qual[0] = s.p.hasq ? s.p.qual1 : nullptr;
   P.seq[1] = s.p.seq2; P.off[1] = s.p.off2; P.qual[1] = s.p.hasq ? s.p.qual2 : nullptr;
   P.mq = s.p.mq;
@@ -362,7 +351,7 @@ int launch_alignments(Ctx *ctx, const Slot &s, const shk_segment *entries, uint6
   P.n_genes = (uint32_t)(ctx->gene_start.size() - 1);
   P.skip_if_long = skip_if_long ? 1u : 0u;
   P.s_min = store ? s.align : s.pileup_al;
-  P.out = store ? reinterpret_cast<uint32_t *>(s.d_align) : nullptr;
+  P.out = store ? reinterpret_cast<uint32_t *>(s.rec_align.d.p) : nullptr;
   P.n_store[0] = !store ? 0u : (P.seq[1] ? AL_WORDS : 2u * AL_WORDS);
   P.n_store[1] = !store ? 0u : AL_WORDS;
   P.ext_p = s.ext_p;
@@ -380,14 +369,6 @@ int launch_alignments(Ctx *ctx, const Slot &s, const shk_segment *entries, uint6
   else hipLaunchKernelGGL((align_kernel<true, true, AlignParamsX>), dim3(blocks), dim3(PL_THREADS), 0, stream, P);
   const hipError_t e = hipGetLastError();
   return e == hipSuccess ? SHK_OK : set_hip_error(ctx, e, "align_kernel");
-}
-
-int launch_publish_alignments(const Slot &s, uint64_t h_cap, hipStream_t stream)
-{
-  const uint64_t want = (h_cap * (2u * AL_WORDS / 4u) + 255) / 256;
-  hipLaunchKernelGGL(publish_alignments_kernel, dim3((unsigned)(want < 1 ? 1 : (want < 512 ? want : 512))), dim3(256), 0, stream, s.d_counters,
-                     reinterpret_cast<const uint4 *>(s.d_align), reinterpret_cast<uint4 *>(s.h_align), h_cap);
-  return hipGetLastError() == hipSuccess ? SHK_OK : SHK_ERR_HIP;
 }
 
 }  // namespace shk

@@ -1175,15 +1175,26 @@ __global__ __launch_bounds__(256) void publish_results_kernel(const uint32_t *__
   if (tid < CTR_WORDS) h_counters[tid] = tid == CTR_VERDICT ? (uni_flag ? 1u + uni_flag[0] : 0u) : counters[tid];
 }
 
-// ... and a host batch's evidence records (evidence mode), three words per read, the same way
-__global__ __launch_bounds__(256) void publish_evidence_kernel(const uint32_t *__restrict__ evid, uint32_t *__restrict__ h_evid, uint64_t n_words)
+// ... and a host batch's records of every other kind (evidence, candidates, placements, segments, alignments, pairs, rescue), the same way: one
+// launch per array, `units` records of words_per_unit words.  Per read (counters == nullptr): units = limit, the batch's reads.  Per
+// association: as many as the batch has, up to `limit` (what the device array and its pinned mirror both hold), none for a batch that
+// overflowed -- it comes through the tail again.  The word tail: a placement is 6 words, a mate's segment entries 10 m, evidence 3
+__global__ __launch_bounds__(256) void publish_records_kernel(const uint32_t *__restrict__ counters, const uint32_t *__restrict__ src, uint32_t *__restrict__ h_dst,
+                                                             uint64_t limit, uint32_t words_per_unit)
 {
+  uint64_t units = limit;
+  if (counters) {
+    if (counters[CTR_OVERFLOW]) return;
+    const uint64_t total = ((uint64_t)counters[CTR_ASSOC_HI] << 32) | counters[CTR_ASSOC_LO];
+    units = total < limit ? total : limit;
+  }
+  const uint64_t n_words = units * words_per_unit;
   const uint64_t tid = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x, nth = (uint64_t)gridDim.x * blockDim.x;
   const uint64_t n4 = n_words / 4;
-  const uint4 *src = reinterpret_cast<const uint4 *>(evid);
-  uint4 *dst = reinterpret_cast<uint4 *>(h_evid);
-  for (uint64_t i = tid; i < n4; i += nth) dst[i] = src[i];
-  for (uint64_t i = n4 * 4 + tid; i < n_words; i += nth) h_evid[i] = evid[i];
+  const uint4 *s4 = reinterpret_cast<const uint4 *>(src);
+  uint4 *d4 = reinterpret_cast<uint4 *>(h_dst);
+  for (uint64_t i = tid; i < n4; i += nth) d4[i] = s4[i];
+  for (uint64_t i = n4 * 4 + tid; i < n_words; i += nth) h_dst[i] = src[i];
 }
 
 // off[i] = i * stride: batches whose reads all have one length need no offsets over PCIe
@@ -1546,20 +1557,12 @@ int launch_publish_results(const uint32_t *counters, uint32_t *h_counters, const
   return hipGetLastError() == hipSuccess ? SHK_OK : SHK_ERR_HIP;
 }
 
-int launch_publish_evidence(const shk_read_evidence *evid, shk_read_evidence *h_evid, uint64_t n, hipStream_t stream)
+int launch_publish_records(const uint32_t *counters, const void *src, void *h_dst, uint64_t limit, uint32_t words_per_unit, hipStream_t stream)
 {
-  if (n == 0) return SHK_OK;
-  const uint64_t want = (3 * n / 4 + 255) / 256;
-  hipLaunchKernelGGL(publish_evidence_kernel, dim3((unsigned)(want < 1 ? 1 : (want < 512 ? want : 512))), dim3(256), 0, stream,
-                     reinterpret_cast<const uint32_t *>(evid), reinterpret_cast<uint32_t *>(h_evid), 3 * n);
-  return hipGetLastError() == hipSuccess ? SHK_OK : SHK_ERR_HIP;
-}
-
-int launch_publish_words(const uint32_t *src, uint32_t *h_dst, uint64_t n_words, hipStream_t stream)
-{
-  if (n_words == 0) return SHK_OK;
-  const uint64_t want = (n_words / 4 + 255) / 256;
-  hipLaunchKernelGGL(publish_evidence_kernel, dim3((unsigned)(want < 1 ? 1 : (want < 512 ? want : 512))), dim3(256), 0, stream, src, h_dst, n_words);
+  if (limit * words_per_unit == 0) return SHK_OK;
+  const uint64_t want = (limit * words_per_unit / 4 + 255) / 256;
+  hipLaunchKernelGGL(publish_records_kernel, dim3((unsigned)(want < 1 ? 1 : (want < 512 ? want : 512))), dim3(256), 0, stream, counters,
+                     static_cast<const uint32_t *>(src), static_cast<uint32_t *>(h_dst), limit, words_per_unit);
   return hipGetLastError() == hipSuccess ? SHK_OK : SHK_ERR_HIP;
 }
 

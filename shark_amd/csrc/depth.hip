@@ -136,17 +136,17 @@ __global__ __launch_bounds__(DP_THREADS) void depth_summary_kernel(const uint32_
 int launch_depth_accumulate(Ctx *ctx, const Slot &s, bool skip_if_long, hipStream_t stream)
 {
   const DeviceIndex &ix = ctx->idx;
-  if (!ix.gene_start || !ctx->d_depth_diff || !ctx->d_depth_mates || !s.d_place) { ctx->last_error = "depth mode without its state"; return SHK_ERR_STATE; }
+  if (!ix.gene_start || !ctx->d_depth_diff || !ctx->d_depth_mates || !s.rec_place.d.p) { ctx->last_error = "depth mode without its state"; return SHK_ERR_STATE; }
   if (s.n == 0) return SHK_OK;
   DepthParams P{};
-  P.gene_off = s.d_gene_off;
-  P.gene_ids = s.d_gene_ids;
+  P.gene_off = s.d_gene_off.p;
+  P.gene_ids = s.d_gene_ids.p;
   P.counters = s.d_counters;
   P.n = s.n;
-  P.cap = std::min<uint64_t>(std::min<uint64_t>(s.cap_gene_ids, s.cap_place), 0xFFFFFFFFull);   // (launch_placement's)
+  P.cap = std::min<uint64_t>(std::min<uint64_t>(s.d_gene_ids.cap, s.rec_place.d.cap), 0xFFFFFFFFull);   // (launch_placement's)
   P.off[0] = s.p.seq1 ? s.p.off1 : nullptr;
   P.off[1] = s.p.seq2 ? s.p.off2 : nullptr;
-  P.place = s.d_place;
+  P.place = s.rec_place.d.p;
   P.gene_start = ix.gene_start;
   P.n_genes = (uint32_t)(ctx->gene_start.size() - 1);
   P.min_support = s.depth;

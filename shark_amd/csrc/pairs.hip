@@ -179,37 +179,26 @@ __global__ __launch_bounds__(PR_THREADS) void pair_kernel(const PairParams P)
   }
 }
 
-// publish_alignments_kernel's copy for this mode's records: the associations the batch has, as far as both arrays hold them
-__global__ __launch_bounds__(256) void publish_pairs_kernel(const uint32_t *__restrict__ counters, const uint4 *__restrict__ src, uint4 *__restrict__ h_dst,
-                                                            uint64_t h_cap)
-{
-  if (counters[CTR_OVERFLOW]) return;
-  const uint64_t total = ((uint64_t)counters[CTR_ASSOC_HI] << 32) | counters[CTR_ASSOC_LO];
-  const uint64_t n4 = (total < h_cap ? total : h_cap) * (sizeof(shk_pair) / 16u);
-  const uint64_t tid = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x, nth = (uint64_t)gridDim.x * blockDim.x;
-  for (uint64_t i = tid; i < n4; i += nth) h_dst[i] = src[i];
-}
-
 }  // namespace
 
 int launch_pairs(Ctx *ctx, const Slot &s, uint64_t cap_assoc, bool skip_if_long, hipStream_t stream)
 {
-  if (!s.pairs || !s.align || !s.d_align || !s.d_pairs || s.pairs > PR_MAX_BINS || (s.pairs_count && (!ctx->d_frag || ctx->frag_bins != s.pairs))) {
+  if (!s.pairs || !s.align || !s.rec_align.d.p || !s.rec_pairs.d.p || s.pairs > PR_MAX_BINS || (s.pairs_count && (!ctx->d_frag || ctx->frag_bins != s.pairs))) {
     ctx->last_error = "pairs mode without its state";
     return SHK_ERR_STATE;
   }
   if (s.n == 0) return SHK_OK;
   PairParams P{};
-  P.gene_off = s.d_gene_off;
+  P.gene_off = s.d_gene_off.p;
   P.counters = s.d_counters;
   P.n = s.n;
   P.off[0] = s.p.seq1 ? s.p.off1 : nullptr;
   P.off[1] = s.p.seq2 ? s.p.off2 : nullptr;
-  P.align = reinterpret_cast<const uint4 *>(s.d_align);
-  P.out = reinterpret_cast<uint4 *>(s.d_pairs);
+  P.align = reinterpret_cast<const uint4 *>(s.rec_align.d.p);
+  P.out = reinterpret_cast<uint4 *>(s.rec_pairs.d.p);
   P.state = s.pairs_count ? ctx->d_frag : nullptr;
   // (launch_alignments' bound on the associations its records hold, and this mode's own array)
-  P.cap = (uint32_t)std::min<uint64_t>(std::min<uint64_t>(std::min<uint64_t>(s.cap_gene_ids, cap_assoc), std::min<uint64_t>(s.cap_align / 2, s.cap_pairs)), 0xFFFFFFFFull);
+  P.cap = (uint32_t)std::min<uint64_t>(std::min<uint64_t>(std::min<uint64_t>(s.d_gene_ids.cap, cap_assoc), std::min<uint64_t>(s.rec_align.d.cap / 2, s.rec_pairs.d.cap)), 0xFFFFFFFFull);
   P.skip_if_long = skip_if_long ? 1u : 0u;
   P.min_intron = s.pairs_min_intron;
   P.max_frag = s.pairs_max_frag;
@@ -220,14 +209,6 @@ int launch_pairs(Ctx *ctx, const Slot &s, uint64_t cap_assoc, bool skip_if_long,
   else hipLaunchKernelGGL(pair_kernel<false>, dim3(blocks), dim3(PR_THREADS), 0, stream, P);
   const hipError_t e = hipGetLastError();
   return e == hipSuccess ? SHK_OK : set_hip_error(ctx, e, "pair_kernel");
-}
-
-int launch_publish_pairs(const Slot &s, uint64_t h_cap, hipStream_t stream)
-{
-  const uint64_t want = (h_cap * (sizeof(shk_pair) / 16u) + 255) / 256;
-  hipLaunchKernelGGL(publish_pairs_kernel, dim3((unsigned)(want < 1 ? 1 : (want < 512 ? want : 512))), dim3(256), 0, stream, s.d_counters,
-                     reinterpret_cast<const uint4 *>(s.d_pairs), reinterpret_cast<uint4 *>(s.h_pairs), h_cap);
-  return hipGetLastError() == hipSuccess ? SHK_OK : SHK_ERR_HIP;
 }
 
 }  // namespace shk

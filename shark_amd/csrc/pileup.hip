@@ -108,11 +108,11 @@ int launch_pileup(Ctx *ctx, const Slot &s, const shk_segment *entries, uint64_t 
   }
   if (s.n == 0) return SHK_OK;
   PileupParams P{};
-  P.gene_off = s.d_gene_off;
-  P.gene_ids = s.d_gene_ids;
+  P.gene_off = s.d_gene_off.p;
+  P.gene_ids = s.d_gene_ids.p;
   P.counters = s.d_counters;
   P.n = s.n;
-  P.cap = std::min<uint64_t>(std::min<uint64_t>(s.cap_gene_ids, cap_assoc), 0xFFFFFFFFull);   // (launch_segments')
+  P.cap = std::min<uint64_t>(std::min<uint64_t>(s.d_gene_ids.cap, cap_assoc), 0xFFFFFFFFull);   // (launch_segments')
   P.seq[0] = s.p.seq1; P.off[0] = s.p.off1; P.qual[0] = s.p.hasq ? s.p.qual1 : nullptr;
   P.seq[1] = s.p.seq2; P.off[1] = s.p.off2; P.qual[1] = s.p.hasq ? s.p.qual2 : nullptr;
   P.mq = s.p.mq;

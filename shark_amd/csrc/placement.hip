@@ -112,34 +112,19 @@ __global__ __launch_bounds__(PL_THREADS) void placement_kernel(const PlaceParams
   }
 }
 
-// a host batch's records -> pinned host memory by kernel stores (classify.hip, publish_results_kernel); their number is on the device
-__global__ __launch_bounds__(256) void publish_placements_kernel(const uint32_t *__restrict__ counters, const uint32_t *__restrict__ src, uint32_t *__restrict__ h_dst,
-                                                                 uint64_t h_cap)
-{
-  if (counters[CTR_OVERFLOW]) return;
-  const uint64_t total = ((uint64_t)counters[CTR_ASSOC_HI] << 32) | counters[CTR_ASSOC_LO];
-  const uint64_t n_words = (total < h_cap ? total : h_cap) * (sizeof(shk_placement) / sizeof(uint32_t));
-  const uint64_t tid = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x, nth = (uint64_t)gridDim.x * blockDim.x;
-  const uint64_t n4 = n_words / 4;
-  const uint4 *s4 = reinterpret_cast<const uint4 *>(src);
-  uint4 *d4 = reinterpret_cast<uint4 *>(h_dst);
-  for (uint64_t i = tid; i < n4; i += nth) d4[i] = s4[i];
-  for (uint64_t i = n4 * 4 + tid; i < n_words; i += nth) h_dst[i] = src[i];
-}
-
 }  // namespace
 
 int launch_placement(Ctx *ctx, const Slot &s, hipStream_t stream)
 {
   const DeviceIndex &ix = ctx->idx;
-  if (!ix.ptab_lg || !ix.ptab || !ix.pdir || !s.d_place) { ctx->last_error = "placement mode without its table"; return SHK_ERR_STATE; }
+  if (!ix.ptab_lg || !ix.ptab || !ix.pdir || !s.rec_place.d.p) { ctx->last_error = "placement mode without its table"; return SHK_ERR_STATE; }
   if (s.n == 0) return SHK_OK;
   PlaceParams P{};
-  P.gene_off = s.d_gene_off;
-  P.gene_ids = s.d_gene_ids;
+  P.gene_off = s.d_gene_off.p;
+  P.gene_ids = s.d_gene_ids.p;
   P.counters = s.d_counters;
   P.n = s.n;
-  P.cap = std::min<uint64_t>(std::min<uint64_t>(s.cap_gene_ids, s.cap_place), 0xFFFFFFFFull);
+  P.cap = std::min<uint64_t>(std::min<uint64_t>(s.d_gene_ids.cap, s.rec_place.d.cap), 0xFFFFFFFFull);
   P.seq[0] = s.p.seq1; P.off[0] = s.p.off1; P.qual[0] = s.p.hasq ? s.p.qual1 : nullptr;
   P.seq[1] = s.p.seq2; P.off[1] = s.p.off2; P.qual[1] = s.p.hasq ? s.p.qual2 : nullptr;
   P.mq = s.p.mq;
@@ -147,20 +132,12 @@ int launch_placement(Ctx *ctx, const Slot &s, hipStream_t stream)
   P.ptab = ix.ptab;
   P.pdir = ix.pdir;
   P.ptab_lg = ix.ptab_lg;
-  P.out = s.d_place;
+  P.out = s.rec_place.d.p;
   // one wave per read up to eight workgroups per CU's worth of them, persistent beyond
   const uint64_t want = (s.n + PL_WAVES - 1) / PL_WAVES;
   hipLaunchKernelGGL(placement_kernel, dim3((unsigned)std::min<uint64_t>(want, 2048)), dim3(PL_THREADS), 0, stream, P);
   const hipError_t e = hipGetLastError();
   return e == hipSuccess ? SHK_OK : set_hip_error(ctx, e, "placement_kernel");
-}
-
-int launch_publish_placements(const uint32_t *counters, const shk_placement *src, shk_placement *h_dst, uint64_t h_cap, hipStream_t stream)
-{
-  const uint64_t want = (h_cap * 6 / 4 + 255) / 256;
-  hipLaunchKernelGGL(publish_placements_kernel, dim3((unsigned)(want < 1 ? 1 : (want < 512 ? want : 512))), dim3(256), 0, stream, counters,
-                     reinterpret_cast<const uint32_t *>(src), reinterpret_cast<uint32_t *>(h_dst), h_cap);
-  return hipGetLastError() == hipSuccess ? SHK_OK : SHK_ERR_HIP;
 }
 
 }  // namespace shk

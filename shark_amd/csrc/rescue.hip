@@ -325,30 +325,19 @@ __global__ __launch_bounds__(RS_THREADS) void rescue_kernel(const RescueParams P
   }
 }
 
-// publish_pairs_kernel's copy for this mode's records
-__global__ __launch_bounds__(256) void publish_rescue_kernel(const uint32_t *__restrict__ counters, const uint4 *__restrict__ src, uint4 *__restrict__ h_dst,
-                                                             uint64_t h_cap)
-{
-  if (counters[CTR_OVERFLOW]) return;
-  const uint64_t total = ((uint64_t)counters[CTR_ASSOC_HI] << 32) | counters[CTR_ASSOC_LO];
-  const uint64_t n4 = total < h_cap ? total : h_cap;
-  const uint64_t tid = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x, nth = (uint64_t)gridDim.x * blockDim.x;
-  for (uint64_t i = tid; i < n4; i += nth) h_dst[i] = src[i];
-}
-
 }  // namespace
 
 int launch_rescue(Ctx *ctx, const Slot &s, uint64_t cap_assoc, bool skip_if_long, hipStream_t stream)
 {
   const DeviceIndex &ix = ctx->idx;
-  if (!s.rescue || !s.align || !s.d_align || !s.d_rescue || !s.d_rescue_queue || s.rescue > RS_MAX_FRAG || !ix.gene_start || !ix.recbase) {
+  if (!s.rescue || !s.align || !s.rec_align.d.p || !s.rec_rescue.d.p || !s.d_rescue_queue.p || s.rescue > RS_MAX_FRAG || !ix.gene_start || !ix.recbase) {
     ctx->last_error = "rescue mode without its state";
     return SHK_ERR_STATE;
   }
   if (s.n == 0) return SHK_OK;
   RescueParams P{};
-  P.gene_off = s.d_gene_off;
-  P.gene_ids = s.d_gene_ids;
+  P.gene_off = s.d_gene_off.p;
+  P.gene_ids = s.d_gene_ids.p;
   P.counters = s.d_counters;
   P.n = s.n;
   P.seq[0] = s.p.seq1; P.off[0] = s.p.off1; P.qual[0] = s.p.hasq ? s.p.qual1 : nullptr;
@@ -360,13 +349,13 @@ int launch_rescue(Ctx *ctx, const Slot &s, uint64_t cap_assoc, bool skip_if_long
   P.n_genes = (uint32_t)(ctx->gene_start.size() - 1);
   P.skip_if_long = skip_if_long ? 1u : 0u;
   // (launch_alignments' bound on the associations its records hold, and this mode's own array)
-  P.cap = (uint32_t)std::min<uint64_t>(std::min<uint64_t>(std::min<uint64_t>(s.cap_gene_ids, cap_assoc), std::min<uint64_t>(s.cap_align / 2, s.cap_rescue)), 0xFFFFFFFFull);
-  P.align = reinterpret_cast<uint4 *>(s.d_align);
-  P.out = reinterpret_cast<uint4 *>(s.d_rescue);
+  P.cap = (uint32_t)std::min<uint64_t>(std::min<uint64_t>(std::min<uint64_t>(s.d_gene_ids.cap, cap_assoc), std::min<uint64_t>(s.rec_align.d.cap / 2, s.rec_rescue.d.cap)), 0xFFFFFFFFull);
+  P.align = reinterpret_cast<uint4 *>(s.rec_align.d.p);
+  P.out = reinterpret_cast<uint4 *>(s.rec_rescue.d.p);
   // the queue's first 16 bytes hold the count
-  P.queue_count = reinterpret_cast<uint32_t *>(s.d_rescue_queue);
-  P.queue = s.d_rescue_queue + 2;
-  P.cap_queue = (uint32_t)std::min<uint64_t>(s.cap_rescue_queue - 2, 0xFFFFFFFFull);
+  P.queue_count = reinterpret_cast<uint32_t *>(s.d_rescue_queue.p);
+  P.queue = s.d_rescue_queue.p + 2;
+  P.cap_queue = (uint32_t)std::min<uint64_t>(s.d_rescue_queue.cap - 2, 0xFFFFFFFFull);
   P.min_intron = s.rescue_min_intron;
   P.max_frag = s.rescue;
   P.max_cost = s.rescue_max_cost;
@@ -383,14 +372,6 @@ int launch_rescue(Ctx *ctx, const Slot &s, uint64_t cap_assoc, bool skip_if_long
   hipLaunchKernelGGL(rescue_kernel, dim3(blocks), dim3(RS_THREADS), 0, stream, P);
   e = hipGetLastError();
   return e == hipSuccess ? SHK_OK : set_hip_error(ctx, e, "rescue_kernel");
-}
-
-int launch_publish_rescue(const Slot &s, uint64_t h_cap, hipStream_t stream)
-{
-  const uint64_t want = (h_cap + 255) / 256;
-  hipLaunchKernelGGL(publish_rescue_kernel, dim3((unsigned)(want < 1 ? 1 : (want < 512 ? want : 512))), dim3(256), 0, stream, s.d_counters,
-                     reinterpret_cast<const uint4 *>(s.d_rescue), reinterpret_cast<uint4 *>(s.h_rescue), h_cap);
-  return hipGetLastError() == hipSuccess ? SHK_OK : SHK_ERR_HIP;
 }
 
 }  // namespace shk

@@ -155,30 +155,7 @@ __global__ __launch_bounds__(PL_THREADS) void segments_kernel(const SegParams P)
   }
 }
 
-// a host batch's records -> pinned host memory by kernel stores (placement.hip, publish_placements_kernel); `words` 32-bit words per
-// association, their number is on the device
-__global__ __launch_bounds__(256) void publish_segments_kernel(const uint32_t *__restrict__ counters, const uint32_t *__restrict__ src, uint32_t *__restrict__ h_dst,
-                                                               uint64_t h_cap, uint32_t words)
-{
-  if (counters[CTR_OVERFLOW]) return;
-  const uint64_t total = ((uint64_t)counters[CTR_ASSOC_HI] << 32) | counters[CTR_ASSOC_LO];
-  const uint64_t n_words = (total < h_cap ? total : h_cap) * words;
-  const uint64_t tid = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x, nth = (uint64_t)gridDim.x * blockDim.x;
-  const uint64_t n4 = n_words / 4;
-  const uint4 *s4 = reinterpret_cast<const uint4 *>(src);
-  uint4 *d4 = reinterpret_cast<uint4 *>(h_dst);
-  for (uint64_t i = tid; i < n4; i += nth) d4[i] = s4[i];
-  for (uint64_t i = n4 * 4 + tid; i < n_words; i += nth) h_dst[i] = src[i];
-}
-
 }  // namespace
-
-// associations the segment arrays of `s` hold, for the m it was submitted with
-uint64_t segments_cap(const Slot &s)
-{
-  if (!s.seg_m) return 0;
-  return std::min<uint64_t>(s.cap_seg_keys / 2, s.cap_seg_entries / (2ull * s.seg_m));
-}
 
 int launch_segments_into(Ctx *ctx, const Slot &s, uint32_t m, uint32_t *d_keys, shk_segment *d_entries, uint64_t cap_assoc, hipStream_t stream)
 {
@@ -189,11 +166,11 @@ int launch_segments_into(Ctx *ctx, const Slot &s, uint32_t m, uint32_t *d_keys, 
   }
   if (s.n == 0) return SHK_OK;
   SegParams P{};
-  P.gene_off = s.d_gene_off;
-  P.gene_ids = s.d_gene_ids;
+  P.gene_off = s.d_gene_off.p;
+  P.gene_ids = s.d_gene_ids.p;
   P.counters = s.d_counters;
   P.n = s.n;
-  P.cap = std::min<uint64_t>(std::min<uint64_t>(s.cap_gene_ids, cap_assoc), 0xFFFFFFFFull);
+  P.cap = std::min<uint64_t>(std::min<uint64_t>(s.d_gene_ids.cap, cap_assoc), 0xFFFFFFFFull);
   P.seq[0] = s.p.seq1; P.off[0] = s.p.off1; P.qual[0] = s.p.hasq ? s.p.qual1 : nullptr;
   P.seq[1] = s.p.seq2; P.off[1] = s.p.off2; P.qual[1] = s.p.hasq ? s.p.qual2 : nullptr;
   P.mq = s.p.mq;
@@ -213,21 +190,7 @@ int launch_segments_into(Ctx *ctx, const Slot &s, uint32_t m, uint32_t *d_keys, 
 
 int launch_segments(Ctx *ctx, const Slot &s, hipStream_t stream)
 {
-  return launch_segments_into(ctx, s, s.seg_m, s.d_seg_keys, s.d_seg_entries, segments_cap(s), stream);
-}
-
-int launch_publish_segments(const Slot &s, uint64_t h_cap, hipStream_t stream)
-{
-  const uint32_t words[2] = {2u, 2u * s.seg_m * SEG_WORDS};
-  const uint32_t *src[2] = {s.d_seg_keys, reinterpret_cast<const uint32_t *>(s.d_seg_entries)};
-  uint32_t *dst[2] = {s.h_seg_keys, reinterpret_cast<uint32_t *>(s.h_seg_entries)};
-  for (int a = 0; a < 2; ++a) {
-    const uint64_t want = (h_cap * words[a] / 4 + 255) / 256;
-    hipLaunchKernelGGL(publish_segments_kernel, dim3((unsigned)(want < 1 ? 1 : (want < 512 ? want : 512))), dim3(256), 0, stream, s.d_counters, src[a], dst[a], h_cap,
-                       words[a]);
-    if (hipGetLastError() != hipSuccess) return SHK_ERR_HIP;
-  }
-  return SHK_OK;
+  return launch_segments_into(ctx, s, s.seg_m, s.rec_seg_keys.d.p, s.rec_seg_entries.d.p, segments_cap(s.rec_seg_keys.d, s.rec_seg_entries.d, s.seg_m), stream);
 }
 
 }  // namespace shk

@@ -83,18 +83,6 @@ static uint32_t slots_of_read(uint64_t L1, uint64_t L2, uint32_t k)
   return ns > 0xFFFFFFFFull ? 0xFFFFFFFFu : (uint32_t)ns;
 }
 
-template <typename T>
-static int ensure_pinned(Ctx *ctx, T **ptr, size_t *cap, size_t need)
-{
-  if (need <= *cap && *ptr) return SHK_OK;
-  if (*ptr) { (void)hipHostFree(*ptr); *ptr = nullptr; *cap = 0; }
-  const size_t want = need + need / 4 + 64;
-  hipError_t e = hipHostMalloc((void **)ptr, want * sizeof(T), hipHostMallocDefault);
-  if (e != hipSuccess) return set_hip_error(ctx, e, "hipHostMalloc");
-  *cap = want;
-  return SHK_OK;
-}
-
 static int slot_init(Ctx *ctx, Slot &s)
 {
   // (the batch's counters and, behind them, the words of the uniformity check: one allocation, cleared by one memset per batch)
@@ -110,32 +98,12 @@ static int slot_init(Ctx *ctx, Slot &s)
 
 static void slot_free(Slot &s)
 {
-  hipFree(s.d_seq1); hipFree(s.d_seq2); hipFree(s.d_qual1); hipFree(s.d_qual2); hipFree(s.d_off1); hipFree(s.d_off2);
-  hipFree(s.d_count); hipFree(s.d_inl); hipFree(s.d_gene_off); hipFree(s.d_gene_ids);
-  hipFree(s.d_long_queue); hipFree(s.d_tie_queue); hipFree(s.d_counters); hipFree(s.d_scan_temp); hipFree(s.d_out); hipFree(s.d_plan); hipFree(s.d_cls_entries); hipFree(s.d_cls_list); hipFree(s.d_cls_share); hipFree(s.d_cls_hist); hipFree(s.d_evid);
-  hipFree(s.d_cand_reads); hipFree(s.d_cand_entries);
-  hipFree(s.d_place);
-  if (s.h_place) (void)hipHostFree(s.h_place);
-  hipFree(s.d_seg_keys); hipFree(s.d_seg_entries);
-  hipFree(s.d_sp_keys); hipFree(s.d_sp_entries);
-  hipFree(s.d_align);
-  if (s.h_align) (void)hipHostFree(s.h_align);
-  hipFree(s.d_pairs);
-  if (s.h_pairs) (void)hipHostFree(s.h_pairs);
-  hipFree(s.d_rescue); hipFree(s.d_rescue_queue);
-  if (s.h_rescue) (void)hipHostFree(s.h_rescue);
-  if (s.h_seg_keys) (void)hipHostFree(s.h_seg_keys);
-  if (s.h_seg_entries) (void)hipHostFree(s.h_seg_entries);
-  if (s.h_cand_reads) (void)hipHostFree(s.h_cand_reads);
-  if (s.h_cand_entries) (void)hipHostFree(s.h_cand_entries);
-  if (s.h_evid) (void)hipHostFree(s.h_evid);
+  hipFree(s.d_counters); hipFree(s.d_out); hipFree(s.d_cls_share);
   if (s.h_counters) (void)hipHostFree(s.h_counters);
-  if (s.h_gene_off) (void)hipHostFree(s.h_gene_off);
-  if (s.h_gene_ids) (void)hipHostFree(s.h_gene_ids);
   if (s.ev_h2d) (void)hipEventDestroy(s.ev_h2d);
   if (s.ev_done) (void)hipEventDestroy(s.ev_done);
   if (s.ev_d2h) (void)hipEventDestroy(s.ev_d2h);
-  s = Slot{};
+  s = Slot{};   // (every growable buffer frees itself)
 }
 
 // result buffers of a batch of n reads; *d_out is rewritten only when one of them moved (a blocking
@@ -143,25 +111,25 @@ static void slot_free(Slot &s)
 static int slot_reserve(Ctx *ctx, Slot &s, uint64_t n)
 {
   int rc;
-  if ((rc = ensure_capacity(ctx, &s.d_count, &s.cap_count, n + 1))) return rc;
-  if ((rc = ensure_capacity(ctx, &s.d_inl, &s.cap_inl, n * SHK_INLINE_IDS + 8))) return rc;
-  if ((rc = ensure_capacity(ctx, &s.d_gene_off, &s.cap_gene_off, n + 1))) return rc;
-  if ((rc = ensure_capacity(ctx, &s.d_long_queue, &s.cap_long_queue, n + 1))) return rc;
-  if ((rc = ensure_capacity(ctx, &s.d_tie_queue, &s.cap_tie_queue, 3 * n + 3))) return rc;
-  if ((rc = ensure_capacity(ctx, &s.d_scan_temp, &s.cap_scan_temp, scan_temp_words(n + 1)))) return rc;
+  if ((rc = s.d_count.reserve(ctx, n + 1))) return rc;
+  if ((rc = s.d_inl.reserve(ctx, n * SHK_INLINE_IDS + 8))) return rc;
+  if ((rc = s.d_gene_off.reserve(ctx, n + 1))) return rc;
+  if ((rc = s.d_long_queue.reserve(ctx, n + 1))) return rc;
+  if ((rc = s.d_tie_queue.reserve(ctx, 3 * n + 3))) return rc;
+  if ((rc = s.d_scan_temp.reserve(ctx, scan_temp_words(n + 1)))) return rc;
   // associations: two per read to start with; a batch that needs more is finished by the overflow path
-  if ((rc = ensure_capacity(ctx, &s.d_gene_ids, &s.cap_gene_ids, 2 * n + 4096))) return rc;
+  if ((rc = s.d_gene_ids.reserve(ctx, 2 * n + 4096))) return rc;
   // (evidence mode only: 12 bytes per read that no other batch pays for)
-  if (s.evidence && (rc = ensure_capacity(ctx, &s.d_evid, &s.cap_evid, n + 1))) return rc;
-  // (candidates mode only: 8 + 12 m bytes per read; the spare words keep publish_evidence_kernel's 16-byte copies inside)
-  if (s.cand_m && (rc = ensure_capacity(ctx, &s.d_cand_reads, &s.cap_cand_reads, n + 2))) return rc;
-  if (s.cand_m && (rc = ensure_capacity(ctx, &s.d_cand_entries, &s.cap_cand_entries, n * s.cand_m + 2))) return rc;
+  if (s.evidence && (rc = s.rec_evid.d.reserve(ctx, n + 1))) return rc;
+  // (candidates mode only: 8 + 12 m bytes per read; the spare records keep publish_records_kernel's 16-byte copies inside)
+  if (s.cand_m && (rc = s.rec_cand_reads.d.reserve(ctx, n + 2))) return rc;
+  if (s.cand_m && (rc = s.rec_cand_entries.d.reserve(ctx, n * s.cand_m + 2))) return rc;
   ClassifyOut ho{};
-  ho.evid = s.evidence ? s.d_evid : nullptr;
-  ho.cand_reads = s.cand_m ? s.d_cand_reads : nullptr;
-  ho.cand_entries = s.cand_m ? s.d_cand_entries : nullptr;
+  ho.evid = s.evidence ? s.rec_evid.d.p : nullptr;
+  ho.cand_reads = s.cand_m ? s.rec_cand_reads.d.p : nullptr;
+  ho.cand_entries = s.cand_m ? s.rec_cand_entries.d.p : nullptr;
   ho.cand_m = s.cand_m;
-  ho.count = s.d_count; ho.inl = s.d_inl; ho.counters = s.d_counters; ho.long_queue = s.d_long_queue; ho.tie_queue = s.d_tie_queue;
+  ho.count = s.d_count.p; ho.inl = s.d_inl.p; ho.counters = s.d_counters; ho.long_queue = s.d_long_queue.p; ho.tie_queue = s.d_tie_queue.p;
   if (memcmp(&ho, &s.out_shadow, sizeof(ho)) != 0) {
     SHK_HIP(ctx, hipMemcpy(s.d_out, &ho, sizeof(ho), hipMemcpyHostToDevice));
     s.out_shadow = ho;
@@ -236,21 +204,107 @@ static int run_long_reads(Ctx *ctx, Slot &s, uint32_t n_long)
   unsigned n_waves = 0;
   int rc;
   if ((rc = size_scratch(ctx, p, s.gen_slots, n_long, &n_waves))) return rc;
-  p.work = s.d_long_queue;
+  p.work = s.d_long_queue.p;
   p.n_work = n_long;
   p.work_count = nullptr;
   return launch_classify_general(ctx, p, false, n_waves, ctx->stream, s.evidence, s.cand_m != 0);
 }
 
-// associations the pinned segment arrays of `s` hold at s.seg_m (segments_cap: the device's)
-static uint64_t segments_host_cap(const Slot &s)
+// a host batch's records of one kind into their pinned mirror, which is reserved for `need` records first.  Per association, `per_assoc`
+// records each: as many associations as the device array and the mirror both hold, and at most `bound` (what the kernel that wrote them held)
+template <typename T>
+static int publish_assoc(Ctx *ctx, const Slot &s, Mirrored<T> &rec, size_t need, uint32_t per_assoc, uint64_t bound)
 {
-  return s.seg_m ? std::min<uint64_t>(s.cap_h_seg_keys / 2, s.cap_h_seg_entries / (2ull * s.seg_m)) : 0;
+  if (const int rc = rec.h.reserve(ctx, need)) return rc;
+  const uint64_t limit = std::min<uint64_t>(std::min<uint64_t>(rec.h.cap, rec.d.cap) / per_assoc, bound);
+  return launch_publish_records(s.d_counters, rec.d.p, rec.h.p, limit, per_assoc * (uint32_t)(sizeof(T) / 4), ctx->stream);
+}
+// ... and per read, `per_read` records each (the spare records in `need` keep the 16-byte copies inside)
+template <typename T>
+static int publish_reads(Ctx *ctx, const Slot &s, Mirrored<T> &rec, size_t need, uint32_t per_read)
+{
+  if (const int rc = rec.h.reserve(ctx, need)) return rc;
+  return launch_publish_records(nullptr, rec.d.p, rec.h.p, s.n, per_read * (uint32_t)(sizeof(T) / 4), ctx->stream);
+}
+
+// The record modes of the batch in `s`, behind its assembled result (gene_off / gene_ids as they now stand: a redone batch comes through
+// here again).  Each mode: reserve its device array for as many associations as d_gene_ids holds, launch, and for a host batch publish into
+// the pinned mirror (per read: evidence and candidates, whose records the classify kernels wrote).  The modes that add to a state of the
+// context do so under gene_hist_kernel's rule for a batch that comes through here again (skip_if_long)
+static int enqueue_record_modes(Ctx *ctx, Slot &s, bool skip_if_long)
+{
+  hipStream_t st = ctx->stream;
+  const uint64_t n = s.n;
+  const size_t ids = s.d_gene_ids.cap;
+  const bool host = s.host_batch;
+  int rc;
+  if (s.evidence && host && (rc = publish_reads(ctx, s, s.rec_evid, n + 1, 1))) return rc;
+  if (s.cand_m && host) {
+    if ((rc = s.rec_cand_entries.h.reserve(ctx, n * s.cand_m + 2))) return rc;   // (both mirrors in front of both launches)
+    if ((rc = publish_reads(ctx, s, s.rec_cand_reads, n + 2, 1))) return rc;
+    if ((rc = publish_reads(ctx, s, s.rec_cand_entries, n * s.cand_m + 2, s.cand_m))) return rc;
+  }
+  // (depth mode needs placement's records as well: the kernel runs for either mode, only placement mode hands its records out)
+  if (s.placement || s.depth) {
+    if ((rc = s.rec_place.d.reserve(ctx, ids))) return rc;
+    if ((rc = launch_placement(ctx, s, st))) return rc;
+    if (s.depth && (rc = launch_depth_accumulate(ctx, s, skip_if_long, st))) return rc;
+    if (s.placement && host && (rc = publish_assoc(ctx, s, s.rec_place, ids, 1, ~0ull))) return rc;
+  }
+  if (s.seg_m) {
+    if ((rc = s.rec_seg_keys.d.reserve(ctx, 2 * ids))) return rc;
+    if ((rc = s.rec_seg_entries.d.reserve(ctx, 2 * ids * s.seg_m))) return rc;
+    if ((rc = launch_segments(ctx, s, st))) return rc;
+    if (host) {
+      if ((rc = s.rec_seg_keys.h.reserve(ctx, 2 * ids))) return rc;
+      if ((rc = s.rec_seg_entries.h.reserve(ctx, 2 * ids * s.seg_m))) return rc;
+      // (the two arrays hold associations together: one bound for both)
+      const uint64_t both = std::min(segments_cap(s.rec_seg_keys.h, s.rec_seg_entries.h, s.seg_m), segments_cap(s.rec_seg_keys.d, s.rec_seg_entries.d, s.seg_m));
+      if ((rc = launch_publish_records(s.d_counters, s.rec_seg_keys.d.p, s.rec_seg_keys.h.p, both, 2, st))) return rc;
+      if ((rc = launch_publish_records(s.d_counters, s.rec_seg_entries.d.p, s.rec_seg_entries.h.p, both, 2 * s.seg_m * (uint32_t)(sizeof(shk_segment) / 4), st))) return rc;
+    }
+  }
+  // the readers of segments_kernel's records at m = SHK_MAX_SEGMENTS -- segments mode's own where it runs at that m, else a launch of that
+  // kernel into arrays nobody else sees --: spliced depth and the junction table; pileup; aligned pileup (align_kernel's accumulating
+  // instantiation in pileup_kernel's stead: the same launch as alignments mode's where the two floors are equal, else one of its own);
+  // alignments mode, the one with records of its own per association
+  if (!(s.sp_depth || s.sp_junc || s.pileup || s.align || s.pileup_al)) return SHK_OK;
+  const shk_segment *entries = s.rec_seg_entries.d.p;
+  uint64_t cap_assoc = segments_cap(s.rec_seg_keys.d, s.rec_seg_entries.d, s.seg_m);
+  if (s.seg_m != SHK_MAX_SEGMENTS) {
+    if ((rc = s.d_sp_keys.reserve(ctx, 2 * ids))) return rc;
+    if ((rc = s.d_sp_entries.reserve(ctx, 2 * ids * SHK_MAX_SEGMENTS))) return rc;
+    entries = s.d_sp_entries.p;
+    cap_assoc = segments_cap(s.d_sp_keys, s.d_sp_entries, SHK_MAX_SEGMENTS);
+    if ((rc = launch_segments_into(ctx, s, SHK_MAX_SEGMENTS, s.d_sp_keys.p, s.d_sp_entries.p, cap_assoc, st))) return rc;
+  }
+  if ((s.sp_depth || s.sp_junc) && (rc = launch_spliced_accumulate(ctx, s, entries, cap_assoc, skip_if_long, st))) return rc;
+  if (s.pileup && (rc = launch_pileup(ctx, s, entries, cap_assoc, skip_if_long, st))) return rc;
+  const bool acc_with_records = s.pileup_al && s.pileup_al == s.align;
+  if (s.pileup_al && !acc_with_records && (rc = launch_alignments(ctx, s, entries, cap_assoc, skip_if_long, false, true, st))) return rc;
+  if (!s.align) return SHK_OK;
+  if ((rc = s.rec_align.d.reserve(ctx, 2 * ids))) return rc;
+  if ((rc = launch_alignments(ctx, s, entries, cap_assoc, skip_if_long, true, acc_with_records, st))) return rc;
+  // (rescue mode: a mate without a block placed beside its partner, in front of everything that reads the alignment records)
+  if (s.rescue) {
+    if ((rc = s.rec_rescue.d.reserve(ctx, ids))) return rc;
+    if ((rc = s.d_rescue_queue.reserve(ctx, ids + 2))) return rc;
+    if ((rc = launch_rescue(ctx, s, cap_assoc, skip_if_long, st))) return rc;
+    if (host && (rc = publish_assoc(ctx, s, s.rec_rescue, ids, 1, cap_assoc))) return rc;
+  }
+  // (pairs mode: the two mates' records of an association read together, directly behind the kernels that stored them)
+  if (s.pairs) {
+    if ((rc = s.rec_pairs.d.reserve(ctx, ids))) return rc;
+    if ((rc = launch_pairs(ctx, s, cap_assoc, skip_if_long, st))) return rc;
+    if (host && (rc = publish_assoc(ctx, s, s.rec_pairs, ids, 1, cap_assoc))) return rc;
+  }
+  if (host && (rc = publish_assoc(ctx, s, s.rec_align, 2 * ids, 2, cap_assoc))) return rc;
+  return SHK_OK;
 }
 
 // Everything behind the classify kernels, WITHOUT a host round trip: per-read counts -> offsets (scan), inline ids ->
 // CSR (gather), reads with more than SHK_INLINE_IDS genes (EMIT pass of the general kernel over the tie queue, whose
-// length stays on the device), per-gene histogram, counters -> pinned host memory, event.
+// length stays on the device), per-gene histogram, counters -> pinned host memory, the record modes, event.
 static int enqueue_tail(Ctx *ctx, Slot &s, bool skip_hist_if_long, bool count_genes)
 {
   hipStream_t st = ctx->stream;
@@ -261,119 +315,35 @@ static int enqueue_tail(Ctx *ctx, Slot &s, bool skip_hist_if_long, bool count_ge
   // launches (device_scan.hpp, OneRecordResult): no finalize, gather, EMIT or histogram launch.  SHK_PLAIN_TAIL=1: the sequence below
   const bool one_record = ctx->n_records == 1 && !ctx->idx.wrap && !ctx->env_plain_tail;
   if (one_record) {
-    const OneRecordResult r{s.d_gene_ids, s.cap_gene_ids, s.d_counters, ctx->d_gene_counts, count_genes, skip_hist_if_long};
-    (void)exclusive_scan_assemble_one(s.d_count, s.d_gene_off, n + 1, s.d_scan_temp, r, st);
+    const OneRecordResult r{s.d_gene_ids.p, s.d_gene_ids.cap, s.d_counters, ctx->d_gene_counts, count_genes, skip_hist_if_long};
+    (void)exclusive_scan_assemble_one(s.d_count.p, s.d_gene_off.p, n + 1, s.d_scan_temp.p, r, st);
     SHK_HIP(ctx, hipGetLastError());
   } else {
-    const uint64_t *d_total = exclusive_scan_u32(s.d_count, s.d_gene_off, n + 1, s.d_scan_temp, st);
+    const uint64_t *d_total = exclusive_scan_u32(s.d_count.p, s.d_gene_off.p, n + 1, s.d_scan_temp.p, st);
     SHK_HIP(ctx, hipGetLastError());
-    if ((rc = launch_finalize_total(d_total, s.d_counters, s.cap_gene_ids, st))) return rc;
-    if ((rc = launch_gather_inline(s.d_count, s.d_inl, s.d_gene_off, s.d_gene_ids, n, s.d_counters, st))) return rc;
+    if ((rc = launch_finalize_total(d_total, s.d_counters, s.d_gene_ids.cap, st))) return rc;
+    if ((rc = launch_gather_inline(s.d_count.p, s.d_inl.p, s.d_gene_off.p, s.d_gene_ids.p, n, s.d_counters, st))) return rc;
     ClassifyParams p = s.p;
     unsigned n_waves = 0;
     if ((rc = size_scratch(ctx, p, s.gen_slots, std::min<uint64_t>(n, 1024), &n_waves))) return rc;
-    p.work = s.d_tie_queue;
+    p.work = s.d_tie_queue.p;
     p.n_work = 0;
     p.work_count = s.d_counters + CTR_TIE;
-    p.gene_off = s.d_gene_off;
-    p.gene_ids = s.d_gene_ids;
+    p.gene_off = s.d_gene_off.p;
+    p.gene_ids = s.d_gene_ids.p;
     if ((rc = launch_classify_general(ctx, p, true, n_waves, st))) return rc;
-    if (count_genes && (rc = launch_gene_hist(s.d_gene_ids, s.d_counters, skip_hist_if_long, ctx->d_gene_counts, n, ctx->n_records, st))) return rc;
+    if (count_genes && (rc = launch_gene_hist(s.d_gene_ids.p, s.d_counters, skip_hist_if_long, ctx->d_gene_counts, n, ctx->n_records, st))) return rc;
   }
   // counters (and, for host batches, the associations) are stored into pinned host memory by a kernel: no copy-engine
   // command ever sits in this stream waiting for kernels (see publish_results_kernel)
   if (s.host_batch) {
-    if ((rc = ensure_pinned(ctx, &s.h_gene_off, &s.cap_h_gene_off, n + 1))) return rc;
-    if ((rc = ensure_pinned(ctx, &s.h_gene_ids, &s.cap_h_gene_ids, s.cap_gene_ids))) return rc;
+    if ((rc = s.h_gene_off.reserve(ctx, n + 1))) return rc;
+    if ((rc = s.h_gene_ids.reserve(ctx, s.d_gene_ids.cap))) return rc;
   }
-  if ((rc = launch_publish_results(s.d_counters, s.h_counters, s.d_gene_off, s.host_batch ? s.h_gene_off : nullptr, n + 1, s.d_gene_ids,
-                                   s.h_gene_ids, s.cap_h_gene_ids, s.p.uni_flag, st)))
+  if ((rc = launch_publish_results(s.d_counters, s.h_counters, s.d_gene_off.p, s.host_batch ? s.h_gene_off.p : nullptr, n + 1, s.d_gene_ids.p,
+                                   s.h_gene_ids.p, s.h_gene_ids.cap, s.p.uni_flag, st)))
     return rc;
-  // (evidence mode: the records follow the associations, by kernel stores as well; a redone batch comes through here again, behind the
-  //  general kernel that has written its long reads' records)
-  if (s.evidence && s.host_batch) {
-    if ((rc = ensure_pinned(ctx, &s.h_evid, &s.cap_h_evid, n + 1))) return rc;
-    if ((rc = launch_publish_evidence(s.d_evid, s.h_evid, n, st))) return rc;
-  }
-  // (candidates mode: the headers and the entries, the same way)
-  if (s.cand_m && s.host_batch) {
-    if ((rc = ensure_pinned(ctx, &s.h_cand_reads, &s.cap_h_cand_reads, n + 2))) return rc;
-    if ((rc = ensure_pinned(ctx, &s.h_cand_entries, &s.cap_h_cand_entries, n * s.cand_m + 2))) return rc;
-    if ((rc = launch_publish_words(reinterpret_cast<const uint32_t *>(s.d_cand_reads), reinterpret_cast<uint32_t *>(s.h_cand_reads), 2 * n, st))) return rc;
-    if ((rc = launch_publish_words(reinterpret_cast<const uint32_t *>(s.d_cand_entries), reinterpret_cast<uint32_t *>(s.h_cand_entries), 3 * n * s.cand_m, st)))
-      return rc;
-  }
-  // (placement mode: from the associations as they now stand in gene_off / gene_ids -- a redone batch comes through here again --, one
-  //  record per association; as many fit as gene_ids holds)
-  // (depth mode needs the records as well: the kernel runs for either mode, only placement mode hands its records out; the batch is added
-  //  to the depth state behind it, under gene_hist_kernel's rule for a batch that comes through here again)
-  if (s.placement || s.depth) {
-    if ((rc = ensure_capacity(ctx, &s.d_place, &s.cap_place, s.cap_gene_ids))) return rc;
-    if ((rc = launch_placement(ctx, s, st))) return rc;
-    if (s.depth && (rc = launch_depth_accumulate(ctx, s, skip_hist_if_long, st))) return rc;
-    if (s.placement && s.host_batch) {
-      if ((rc = ensure_pinned(ctx, &s.h_place, &s.cap_h_place, s.cap_gene_ids))) return rc;
-      if ((rc = launch_publish_placements(s.d_counters, s.d_place, s.h_place, std::min<uint64_t>(s.cap_h_place, s.cap_place), st))) return rc;
-    }
-  }
-  // (segments mode: the same place in the tail for the same reason, its own kernel and its own arrays)
-  if (s.seg_m) {
-    if ((rc = ensure_capacity(ctx, &s.d_seg_keys, &s.cap_seg_keys, 2 * s.cap_gene_ids))) return rc;
-    if ((rc = ensure_capacity(ctx, &s.d_seg_entries, &s.cap_seg_entries, 2 * s.cap_gene_ids * s.seg_m))) return rc;
-    if ((rc = launch_segments(ctx, s, st))) return rc;
-    if (s.host_batch) {
-      if ((rc = ensure_pinned(ctx, &s.h_seg_keys, &s.cap_h_seg_keys, 2 * s.cap_gene_ids))) return rc;
-      if ((rc = ensure_pinned(ctx, &s.h_seg_entries, &s.cap_h_seg_entries, 2 * s.cap_gene_ids * s.seg_m))) return rc;
-      if ((rc = launch_publish_segments(s, std::min<uint64_t>(segments_host_cap(s), segments_cap(s)), st))) return rc;
-    }
-  }
-  // (spliced depth, the junction table: behind segments_kernel's records at m = SHK_MAX_SEGMENTS -- segments mode's own where it runs at that
-  //  m, else a launch of that kernel into arrays nobody else sees --, under depth_accumulate_kernel's rule for a batch that comes through
-  //  here again; pileup mode: the third reader of the same records, its own kernel behind theirs; alignments mode: the fourth, behind pileup's,
-  //  and the one with records of its own per association, handed out as segments mode's are; aligned pileup: align_kernel's accumulating
-  //  instantiation in pileup_kernel's stead -- the same launch as alignments mode's where the two floors are equal, else one of its own)
-  if (s.sp_depth || s.sp_junc || s.pileup || s.align || s.pileup_al) {
-    const shk_segment *entries = s.d_seg_entries;
-    uint64_t cap_assoc = segments_cap(s);
-    if (s.seg_m != SHK_MAX_SEGMENTS) {
-      if ((rc = ensure_capacity(ctx, &s.d_sp_keys, &s.cap_sp_keys, 2 * s.cap_gene_ids))) return rc;
-      if ((rc = ensure_capacity(ctx, &s.d_sp_entries, &s.cap_sp_entries, 2 * s.cap_gene_ids * SHK_MAX_SEGMENTS))) return rc;
-      entries = s.d_sp_entries;
-      cap_assoc = std::min<uint64_t>(s.cap_sp_keys / 2, s.cap_sp_entries / (2ull * SHK_MAX_SEGMENTS));
-      if ((rc = launch_segments_into(ctx, s, SHK_MAX_SEGMENTS, s.d_sp_keys, s.d_sp_entries, cap_assoc, st))) return rc;
-    }
-    if ((s.sp_depth || s.sp_junc) && (rc = launch_spliced_accumulate(ctx, s, entries, cap_assoc, skip_hist_if_long, st))) return rc;
-    if (s.pileup && (rc = launch_pileup(ctx, s, entries, cap_assoc, skip_hist_if_long, st))) return rc;
-    const bool acc_with_records = s.pileup_al && s.pileup_al == s.align;
-    if (s.pileup_al && !acc_with_records && (rc = launch_alignments(ctx, s, entries, cap_assoc, skip_hist_if_long, false, true, st))) return rc;
-    if (s.align) {
-      if ((rc = ensure_capacity(ctx, &s.d_align, &s.cap_align, 2 * s.cap_gene_ids))) return rc;
-      if ((rc = launch_alignments(ctx, s, entries, cap_assoc, skip_hist_if_long, true, acc_with_records, st))) return rc;
-      // (rescue mode: a mate without a block placed beside its partner, in front of everything that reads the records)
-      if (s.rescue) {
-        if ((rc = ensure_capacity(ctx, &s.d_rescue, &s.cap_rescue, s.cap_gene_ids))) return rc;
-        if ((rc = ensure_capacity(ctx, &s.d_rescue_queue, &s.cap_rescue_queue, s.cap_gene_ids + 2))) return rc;
-        if ((rc = launch_rescue(ctx, s, cap_assoc, skip_hist_if_long, st))) return rc;
-        if (s.host_batch) {
-          if ((rc = ensure_pinned(ctx, &s.h_rescue, &s.cap_h_rescue, s.cap_gene_ids))) return rc;
-          if ((rc = launch_publish_rescue(s, std::min<uint64_t>(std::min<uint64_t>(s.cap_h_rescue, s.cap_rescue), cap_assoc), st))) return rc;
-        }
-      }
-      // (pairs mode: the two mates' records of an association read together, directly behind the kernel that stored them)
-      if (s.pairs) {
-        if ((rc = ensure_capacity(ctx, &s.d_pairs, &s.cap_pairs, s.cap_gene_ids))) return rc;
-        if ((rc = launch_pairs(ctx, s, cap_assoc, skip_hist_if_long, st))) return rc;
-        if (s.host_batch) {
-          if ((rc = ensure_pinned(ctx, &s.h_pairs, &s.cap_h_pairs, s.cap_gene_ids))) return rc;
-          if ((rc = launch_publish_pairs(s, std::min<uint64_t>(std::min<uint64_t>(s.cap_h_pairs, s.cap_pairs), cap_assoc), st))) return rc;
-        }
-      }
-      if (s.host_batch) {
-        if ((rc = ensure_pinned(ctx, &s.h_align, &s.cap_h_align, 2 * s.cap_gene_ids))) return rc;
-        if ((rc = launch_publish_alignments(s, std::min<uint64_t>(std::min<uint64_t>(s.cap_h_align, s.cap_align) / 2, cap_assoc), st))) return rc;
-      }
-    }
-  }
+  if ((rc = enqueue_record_modes(ctx, s, skip_hist_if_long))) return rc;
   SHK_HIP(ctx, hipEventRecord(s.ev_done, st));
   return SHK_OK;
 }
@@ -474,9 +444,9 @@ static int enqueue_classify(Ctx *ctx, Slot &s, const shk_batch *b, uint32_t max_
   const bool with_plans = table_kernel && uni_mode != UNI_YES;
   if (by_classes) {
     // (32 bytes per pair of extra HBM: a device too full for them classifies the batch with the ragged instantiation instead)
-    if (ensure_capacity(ctx, &s.d_cls_entries, &s.cap_cls_entries, (size_t)(2 * n)) != SHK_OK ||
-        ensure_capacity(ctx, &s.d_cls_list, &s.cap_cls_list, (size_t)classes) != SHK_OK ||
-        ensure_capacity(ctx, &s.d_cls_hist, &s.cap_cls_hist, (size_t)(2 * classes)) != SHK_OK ||
+    if (s.d_cls_entries.reserve(ctx, (size_t)(2 * n)) != SHK_OK ||
+        s.d_cls_list.reserve(ctx, (size_t)classes) != SHK_OK ||
+        s.d_cls_hist.reserve(ctx, (size_t)(2 * classes)) != SHK_OK ||
         (!s.d_cls_share && hipMalloc((void **)&s.d_cls_share, CLS_SHARES * sizeof(uint32_t)) != hipSuccess)) {
       (void)hipGetLastError();
       ctx->last_error.clear();
@@ -484,24 +454,24 @@ static int enqueue_classify(Ctx *ctx, Slot &s, const shk_batch *b, uint32_t max_
     }
   }
   if (by_classes) {
-    s.p.cls_entries = s.d_cls_entries;
-    s.p.cls_list = s.d_cls_list;
+    s.p.cls_entries = s.d_cls_entries.p;
+    s.p.cls_list = s.d_cls_list.p;
     s.p.cls_share_first = s.d_cls_share;
-    s.p.cls_hist = s.d_cls_hist;
+    s.p.cls_hist = s.d_cls_hist.p;
     s.p.cls_cap = (uint32_t)classes;
     s.p.cls_min_fill = ctx->env_cls_min_fill;
   }
   if (with_plans) {
-    if ((rc = ensure_capacity(ctx, &s.d_plan, &s.cap_plan, (size_t)classes))) return rc;
-    s.p.plan_tab = s.d_plan;
+    if ((rc = s.d_plan.reserve(ctx, (size_t)classes))) return rc;
+    s.p.plan_tab = s.d_plan.p;
     s.p.plan_cap = (uint32_t)classes;
   }
   if (!table_kernel) {
     uni_mode = UNI_NO;
-    SHK_HIP(ctx, hipMemsetAsync(s.d_count + n, 0, sizeof(uint32_t), st));
+    SHK_HIP(ctx, hipMemsetAsync(s.d_count.p + n, 0, sizeof(uint32_t), st));
   } else {
     // classify_uni_kernel writes count[] only for reads with associations
-    SHK_HIP(ctx, hipMemsetAsync(s.d_count, 0, (n + 1) * sizeof(uint32_t), st));
+    SHK_HIP(ctx, hipMemsetAsync(s.d_count.p, 0, (n + 1) * sizeof(uint32_t), st));
   }
   // timed: the classify launches (shk_timing::total_ms) and, for a batch the device has to look at first, the passes over its
   // offsets in front of them (prepass_ms)
@@ -524,7 +494,7 @@ static int enqueue_classify(Ctx *ctx, Slot &s, const shk_batch *b, uint32_t max_
   if (table_kernel) {
     if (by_classes) {
       uni_mode = UNI_ASK_DEVICE;
-      SHK_HIP(ctx, hipMemsetAsync(s.d_cls_hist, 0, classes * sizeof(uint32_t), st));
+      SHK_HIP(ctx, hipMemsetAsync(s.d_cls_hist.p, 0, classes * sizeof(uint32_t), st));
     }
     if (uni_mode == UNI_ASK_DEVICE) {
       s.p.tro = tro_ask ? (ctx->env_force_tro ? 2u : 1u) : 0u;
@@ -538,7 +508,7 @@ static int enqueue_classify(Ctx *ctx, Slot &s, const shk_batch *b, uint32_t max_
       // (a resident batch whose caller vouched for the lengths: nobody has looked at its offsets)
       if (uni_mode == UNI_YES && !s.host_batch && n != 0 && (rc = launch_vouch_check(s.p, uni_L1, uni_L2, s.d_counters, st))) return rc;
     }
-    if (with_plans) SHK_HIP(ctx, hipMemsetAsync(s.d_plan, 0, classes * sizeof(uint4), st));
+    if (with_plans) SHK_HIP(ctx, hipMemsetAsync(s.d_plan.p, 0, classes * sizeof(uint4), st));
   }
   if (ctx->timing) SHK_HIP(ctx, hipEventRecord(e0, st));
 
@@ -604,11 +574,46 @@ static int finish_classify(Ctx *ctx, Slot &s, bool long_was_speculative, bool co
     const uint64_t n_assoc = ((uint64_t)s.h_counters[CTR_ASSOC_HI] << 32) | s.h_counters[CTR_ASSOC_LO];
     if (n_assoc >= 0xFFFFFFFFull) { ctx->last_error = "more than 2^32-1 associations in one batch"; return SHK_ERR_ARG; }
     SHK_HIP(ctx, hipStreamSynchronize(st));     // gene_ids is about to be replaced
-    if ((rc = ensure_capacity(ctx, &s.d_gene_ids, &s.cap_gene_ids, n_assoc + 8))) return rc;
+    if ((rc = s.d_gene_ids.reserve(ctx, n_assoc + 8))) return rc;
     if ((rc = enqueue_tail(ctx, s, false, count_genes))) return rc;
     SHK_HIP(ctx, hipStreamSynchronize(st));
     *redone = true;
   }
+  return SHK_OK;
+}
+
+// The records of the batch in `s`, whose result is being handed out, become the context's last records (shk_*_last).  host: the pinned
+// mirrors (a host batch), else the device arrays; measurement: no kind is valid.  A host batch with more associations than a kind's mirror
+// holds was not published whole: the kinds in front of that one are valid, it and all behind it are not
+static int hand_out_records(Ctx *ctx, const Slot &s, bool host, bool measurement, uint64_t n_assoc)
+{
+  LastRecords &l = ctx->last_rec;
+  const bool on = !measurement;
+  l.n = s.n;
+  l.n_assoc = n_assoc;
+  l.evid_valid = s.evidence && on;
+  l.evid = s.rec_evid.handed(host);
+  l.cand_valid = s.cand_m != 0 && on;
+  l.cand_m = s.cand_m;
+  l.cand_reads = s.rec_cand_reads.handed(host);
+  l.cand_entries = s.rec_cand_entries.handed(host);
+  if (s.placement && host && n_assoc > s.rec_place.h.cap) { ctx->last_error = "placement publication failed"; return SHK_ERR_HIP; }
+  l.place_valid = s.placement && on;
+  l.place = s.rec_place.handed(host);
+  if (s.seg_m && host && n_assoc > segments_cap(s.rec_seg_keys.h, s.rec_seg_entries.h, s.seg_m)) { ctx->last_error = "segments publication failed"; return SHK_ERR_HIP; }
+  l.seg_valid = s.seg_m != 0 && on;
+  l.seg_m = s.seg_m;
+  l.seg_keys = s.rec_seg_keys.handed(host);
+  l.seg_entries = s.rec_seg_entries.handed(host);
+  if (s.align && host && n_assoc > s.rec_align.h.cap / 2) { ctx->last_error = "alignments publication failed"; return SHK_ERR_HIP; }
+  l.align_valid = s.align != 0 && on;
+  l.align = s.rec_align.handed(host);
+  if (s.pairs && host && n_assoc > s.rec_pairs.h.cap) { ctx->last_error = "pairs publication failed"; return SHK_ERR_HIP; }
+  l.pairs_valid = s.pairs != 0 && on;
+  l.pairs = s.rec_pairs.handed(host);
+  if (s.rescue && host && n_assoc > s.rec_rescue.h.cap) { ctx->last_error = "rescue publication failed"; return SHK_ERR_HIP; }
+  l.rescue_valid = s.rescue != 0 && on;
+  l.rescue = s.rec_rescue.handed(host);
   return SHK_OK;
 }
 
@@ -618,13 +623,7 @@ static int classify_resident(Ctx *ctx, const shk_batch *b, uint32_t max_read_len
   hipStream_t st = ctx->stream;
   Slot &s = ctx->slots[PIPE_DEPTH];
   const uint64_t n = b->n;
-  ctx->last_evid_valid = false;   // (until this batch's result is handed out)
-  ctx->last_cand_valid = false;
-  ctx->last_place_valid = false;
-  ctx->last_seg_valid = false;
-  ctx->last_align_valid = false;
-  ctx->last_pairs_valid = false;
-  ctx->last_rescue_valid = false;
+  ctx->last_rec = LastRecords{};   // (until this batch's result is handed out)
   if (n >= 0xFFFFFFFFull) { ctx->last_error = "batch too large (n must be < 2^32-1)"; return SHK_ERR_ARG; }
   const bool paired = b->seq2 != nullptr;
   const uint32_t max_slots = max_read_len ? slots_for_len(max_read_len, ctx->prm.k, paired) : 0;
@@ -669,35 +668,11 @@ static int classify_resident(Ctx *ctx, const shk_batch *b, uint32_t max_read_len
 #endif
   ctx->last.last_n_assoc = n_assoc;
   res->n = n;
-  res->gene_off = s.d_gene_off;
-  res->gene_ids = s.d_gene_ids;
+  res->gene_off = s.d_gene_off.p;
+  res->gene_ids = s.d_gene_ids.p;
   res->n_assoc = n_assoc;
-  // (shk_count_work is a measurement, not one of the calls that hand out evidence: none is left behind it)
-  ctx->last_evid_valid = s.evidence && wc == nullptr;
-  ctx->last_evid = s.d_evid;
-  ctx->last_evid_n = n;
-  ctx->last_cand_valid = s.cand_m != 0 && wc == nullptr;
-  ctx->last_cand_m = s.cand_m;
-  ctx->last_cand_reads = s.d_cand_reads;
-  ctx->last_cand_entries = s.d_cand_entries;
-  ctx->last_place_valid = s.placement && wc == nullptr;
-  ctx->last_place = s.d_place;
-  ctx->last_place_n = n_assoc;
-  ctx->last_seg_valid = s.seg_m != 0 && wc == nullptr;
-  ctx->last_seg_m = s.seg_m;
-  ctx->last_seg_keys = s.d_seg_keys;
-  ctx->last_seg_entries = s.d_seg_entries;
-  ctx->last_seg_n = n_assoc;
-  ctx->last_align_valid = s.align != 0 && wc == nullptr;
-  ctx->last_align = s.d_align;
-  ctx->last_align_n = n_assoc;
-  ctx->last_pairs_valid = s.pairs != 0 && wc == nullptr;
-  ctx->last_pairs = s.d_pairs;
-  ctx->last_pairs_n = n_assoc;
-  ctx->last_rescue_valid = s.rescue != 0 && wc == nullptr;
-  ctx->last_rescue = s.d_rescue;
-  ctx->last_rescue_n = n_assoc;
-  return SHK_OK;
+  // (shk_count_work is a measurement, not one of the calls that hand out records: none is left behind it)
+  return hand_out_records(ctx, s, false, wc != nullptr, n_assoc);
 }
 
 }  // namespace shk
@@ -1136,37 +1111,37 @@ int shk_classify_submit(shk_ctx *ctx, const shk_batch *b, uint64_t *ticket)
   hipStream_t up = ctx->h2d_stream, st = ctx->stream;
   shk_batch d{};
   d.n = n;
-  if ((rc = ensure_capacity(ctx, &s.d_seq1, &s.cap_seq1, bytes1 + 16))) return rc;
-  if ((rc = ensure_capacity(ctx, &s.d_off1, &s.cap_off1, n + 1))) return rc;
+  if ((rc = s.d_seq1.reserve(ctx, bytes1 + 16))) return rc;
+  if ((rc = s.d_off1.reserve(ctx, n + 1))) return rc;
   if (paired) {
-    if ((rc = ensure_capacity(ctx, &s.d_seq2, &s.cap_seq2, bytes2 + 16))) return rc;
-    if ((rc = ensure_capacity(ctx, &s.d_off2, &s.cap_off2, n + 1))) return rc;
+    if ((rc = s.d_seq2.reserve(ctx, bytes2 + 16))) return rc;
+    if ((rc = s.d_off2.reserve(ctx, n + 1))) return rc;
   }
   const bool hasq = ctx->q8 != 0;
   if (hasq) {
-    if ((rc = ensure_capacity(ctx, &s.d_qual1, &s.cap_qual1, bytes1 + 16))) return rc;
-    if (paired && (rc = ensure_capacity(ctx, &s.d_qual2, &s.cap_qual2, bytes2 + 16))) return rc;
+    if ((rc = s.d_qual1.reserve(ctx, bytes1 + 16))) return rc;
+    if (paired && (rc = s.d_qual2.reserve(ctx, bytes2 + 16))) return rc;
   }
   if (n) {
-    SHK_HIP(ctx, hipMemcpyAsync(s.d_seq1, b->seq1, bytes1, hipMemcpyHostToDevice, up));
-    if (paired) SHK_HIP(ctx, hipMemcpyAsync(s.d_seq2, b->seq2, bytes2, hipMemcpyHostToDevice, up));
+    SHK_HIP(ctx, hipMemcpyAsync(s.d_seq1.p, b->seq1, bytes1, hipMemcpyHostToDevice, up));
+    if (paired) SHK_HIP(ctx, hipMemcpyAsync(s.d_seq2.p, b->seq2, bytes2, hipMemcpyHostToDevice, up));
     if (hasq) {
-      SHK_HIP(ctx, hipMemcpyAsync(s.d_qual1, b->qual1, bytes1, hipMemcpyHostToDevice, up));
-      if (paired) SHK_HIP(ctx, hipMemcpyAsync(s.d_qual2, b->qual2, bytes2, hipMemcpyHostToDevice, up));
+      SHK_HIP(ctx, hipMemcpyAsync(s.d_qual1.p, b->qual1, bytes1, hipMemcpyHostToDevice, up));
+      if (paired) SHK_HIP(ctx, hipMemcpyAsync(s.d_qual2.p, b->qual2, bytes2, hipMemcpyHostToDevice, up));
     }
     if (uniform) {
-      if ((rc = launch_fill_offsets(s.d_off1, n + 1, f1, st))) return rc;
-      if (paired && (rc = launch_fill_offsets(s.d_off2, n + 1, f2, st))) return rc;
+      if ((rc = launch_fill_offsets(s.d_off1.p, n + 1, f1, st))) return rc;
+      if (paired && (rc = launch_fill_offsets(s.d_off2.p, n + 1, f2, st))) return rc;
     } else {
-      SHK_HIP(ctx, hipMemcpyAsync(s.d_off1, b->off1, (n + 1) * sizeof(uint64_t), hipMemcpyHostToDevice, up));
-      if (paired) SHK_HIP(ctx, hipMemcpyAsync(s.d_off2, b->off2, (n + 1) * sizeof(uint64_t), hipMemcpyHostToDevice, up));
+      SHK_HIP(ctx, hipMemcpyAsync(s.d_off1.p, b->off1, (n + 1) * sizeof(uint64_t), hipMemcpyHostToDevice, up));
+      if (paired) SHK_HIP(ctx, hipMemcpyAsync(s.d_off2.p, b->off2, (n + 1) * sizeof(uint64_t), hipMemcpyHostToDevice, up));
     }
   }
   SHK_HIP(ctx, hipEventRecord(s.ev_h2d, up));
   SHK_HIP(ctx, hipStreamWaitEvent(st, s.ev_h2d, 0));
-  d.seq1 = (const char *)s.d_seq1; d.off1 = s.d_off1;
-  if (paired) { d.seq2 = (const char *)s.d_seq2; d.off2 = s.d_off2; }
-  if (hasq) { d.qual1 = (const char *)s.d_qual1; if (paired) d.qual2 = (const char *)s.d_qual2; }
+  d.seq1 = (const char *)s.d_seq1.p; d.off1 = s.d_off1.p;
+  if (paired) { d.seq2 = (const char *)s.d_seq2.p; d.off2 = s.d_off2.p; }
+  if (hasq) { d.qual1 = (const char *)s.d_qual1.p; if (paired) d.qual2 = (const char *)s.d_qual2.p; }
   s.host_batch = true;
   s.long_speculative = false;
   const bool uni_fits = uniform && n_long == 0 && groups_fit;
@@ -1224,13 +1199,7 @@ int shk_classify_wait(shk_ctx *ctx, uint64_t ticket, shk_result *result)
   TraceRange tr("shk_classify_wait");
   Slot &s = ctx->slots[(ticket - 1) % PIPE_DEPTH];
   if (s.ticket != ticket || s.waited) { ctx->last_error = "unknown or already waited ticket"; return SHK_ERR_STATE; }
-  ctx->last_evid_valid = false;   // (a batch that is refused below hands out no evidence either, and leaves none of an earlier batch behind)
-  ctx->last_cand_valid = false;
-  ctx->last_place_valid = false;
-  ctx->last_seg_valid = false;
-  ctx->last_align_valid = false;
-  ctx->last_pairs_valid = false;
-  ctx->last_rescue_valid = false;
+  ctx->last_rec = LastRecords{};   // (a batch that is refused below hands out no records either, and leaves none of an earlier batch behind)
   SHK_HIP(ctx, hipEventSynchronize(s.ev_done));
   bool redone = false;
   int rc = finish_classify(ctx, s, s.long_speculative, true, &redone);
@@ -1243,7 +1212,7 @@ int shk_classify_wait(shk_ctx *ctx, uint64_t ticket, shk_result *result)
   // (finish_classify re-ran the tail when it had to, and the tail publishes the results again)
   const uint64_t n = s.n;
   const uint64_t n_assoc = ((uint64_t)s.h_counters[CTR_ASSOC_HI] << 32) | s.h_counters[CTR_ASSOC_LO];
-  if (s.h_counters[CTR_OVERFLOW] || (s.host_batch && n_assoc > s.cap_h_gene_ids)) { ctx->last_error = "result publication failed"; s.waited = true; return SHK_ERR_HIP; }
+  if (s.h_counters[CTR_OVERFLOW] || (s.host_batch && n_assoc > s.h_gene_ids.cap)) { ctx->last_error = "result publication failed"; s.waited = true; return SHK_ERR_HIP; }
   s.waited = true;
   ctx->last.last_n_reads = n;
   ctx->last.last_n_long = s.h_counters[CTR_LONG];
@@ -1251,49 +1220,39 @@ int shk_classify_wait(shk_ctx *ctx, uint64_t ticket, shk_result *result)
   note_verdict(ctx, s.h_counters[CTR_VERDICT]);
   ctx->last.last_n_assoc = n_assoc;
   result->n = n;
-  result->gene_off = s.host_batch ? s.h_gene_off : s.d_gene_off;     // (a device-resident ticket: device pointers)
-  result->gene_ids = s.host_batch ? s.h_gene_ids : s.d_gene_ids;
+  result->gene_off = s.host_batch ? s.h_gene_off.p : s.d_gene_off.p;     // (a device-resident ticket: device pointers)
+  result->gene_ids = s.host_batch ? s.h_gene_ids.p : s.d_gene_ids.p;
   result->n_assoc = n_assoc;
-  ctx->last_evid_valid = s.evidence;
-  ctx->last_evid = s.host_batch ? s.h_evid : s.d_evid;
-  ctx->last_evid_n = n;
-  ctx->last_cand_valid = s.cand_m != 0;
-  ctx->last_cand_m = s.cand_m;
-  ctx->last_cand_reads = s.host_batch ? s.h_cand_reads : s.d_cand_reads;
-  ctx->last_cand_entries = s.host_batch ? s.h_cand_entries : s.d_cand_entries;
-  if (s.placement && s.host_batch && n_assoc > s.cap_h_place) { ctx->last_error = "placement publication failed"; return SHK_ERR_HIP; }
-  ctx->last_place_valid = s.placement;
-  ctx->last_place = s.host_batch ? s.h_place : s.d_place;
-  ctx->last_place_n = n_assoc;
-  if (s.seg_m && s.host_batch && n_assoc > segments_host_cap(s)) { ctx->last_error = "segments publication failed"; return SHK_ERR_HIP; }
-  ctx->last_seg_valid = s.seg_m != 0;
-  ctx->last_seg_m = s.seg_m;
-  ctx->last_seg_keys = s.host_batch ? s.h_seg_keys : s.d_seg_keys;
-  ctx->last_seg_entries = s.host_batch ? s.h_seg_entries : s.d_seg_entries;
-  ctx->last_seg_n = n_assoc;
-  if (s.align && s.host_batch && n_assoc > s.cap_h_align / 2) { ctx->last_error = "alignments publication failed"; return SHK_ERR_HIP; }
-  ctx->last_align_valid = s.align != 0;
-  ctx->last_align = s.host_batch ? s.h_align : s.d_align;
-  ctx->last_align_n = n_assoc;
-  if (s.pairs && s.host_batch && n_assoc > s.cap_h_pairs) { ctx->last_error = "pairs publication failed"; return SHK_ERR_HIP; }
-  ctx->last_pairs_valid = s.pairs != 0;
-  ctx->last_pairs = s.host_batch ? s.h_pairs : s.d_pairs;
-  ctx->last_pairs_n = n_assoc;
-  if (s.rescue && s.host_batch && n_assoc > s.cap_h_rescue) { ctx->last_error = "rescue publication failed"; return SHK_ERR_HIP; }
-  ctx->last_rescue_valid = s.rescue != 0;
-  ctx->last_rescue = s.host_batch ? s.h_rescue : s.d_rescue;
-  ctx->last_rescue_n = n_assoc;
+  return hand_out_records(ctx, s, s.host_batch, false, n_assoc);
+}
+
+static bool tickets_outstanding(const shk_ctx *ctx)
+{
+  for (int i = 0; i < PIPE_DEPTH; ++i)
+    if (ctx->slots[i].ticket != 0 && !ctx->slots[i].waited) return true;
+  return false;
+}
+
+// what a mode that reads the placement table asks of the index, in this order: finalized, built with shk_ref_keep_positions, at most
+// 65 536 records (NEED_GENE_START: and the genes' starts, which such an index carries) and, NEED_BASES, built with shk_ref_keep_bases
+enum { NEED_GENE_START = 1, NEED_BASES = 2 };
+static int check_mode_index(shk_ctx *ctx, const char *who, unsigned need)
+{
+  const std::string w(who);
+  if (ctx->mode != 2) { ctx->last_error = w + ": the index is not finalized"; return SHK_ERR_STATE; }
+  if (!ctx->idx.ptab_lg) { ctx->last_error = w + ": the index was finalized without shk_ref_keep_positions"; return SHK_ERR_STATE; }
+  if (ctx->n_records > 65536 || ctx->idx.wrap || ((need & NEED_GENE_START) && !ctx->idx.gene_start)) {
+    ctx->last_error = w + ": more than 65 536 records (gene ids wrap)";
+    return SHK_ERR_STATE;
+  }
+  if ((need & NEED_BASES) && !ctx->idx.recbase) { ctx->last_error = w + ": the index was finalized without shk_ref_keep_bases"; return SHK_ERR_STATE; }
   return SHK_OK;
 }
 
 int shk_evidence_enable(shk_ctx *ctx, int enable)
 {
   if (!ctx) return SHK_ERR_ARG;
-  for (int i = 0; i < PIPE_DEPTH; ++i)
-    if (ctx->slots[i].ticket != 0 && !ctx->slots[i].waited) {
-      ctx->last_error = "shk_evidence_enable: tickets are outstanding (wait for them first)";
-      return SHK_ERR_STATE;
-    }
+  if (tickets_outstanding(ctx)) { ctx->last_error = "shk_evidence_enable: tickets are outstanding (wait for them first)"; return SHK_ERR_STATE; }
   ctx->evidence = enable != 0;
   return SHK_OK;
 }
@@ -1301,9 +1260,9 @@ int shk_evidence_enable(shk_ctx *ctx, int enable)
 int shk_evidence_last(const shk_ctx *ctx, shk_evidence *out)
 {
   if (!ctx || !out) return SHK_ERR_ARG;
-  if (!ctx->last_evid_valid) return SHK_ERR_STATE;
-  out->n = ctx->last_evid_n;
-  out->reads = ctx->last_evid;
+  if (!ctx->last_rec.evid_valid) return SHK_ERR_STATE;
+  out->n = ctx->last_rec.n;
+  out->reads = ctx->last_rec.evid;
   return SHK_OK;
 }
 
@@ -1311,11 +1270,7 @@ int shk_candidates_enable(shk_ctx *ctx, uint32_t m)
 {
   if (!ctx) return SHK_ERR_ARG;
   if (m > SHK_MAX_CANDIDATES) { ctx->last_error = "shk_candidates_enable: m must be at most SHK_MAX_CANDIDATES"; return SHK_ERR_ARG; }
-  for (int i = 0; i < PIPE_DEPTH; ++i)
-    if (ctx->slots[i].ticket != 0 && !ctx->slots[i].waited) {
-      ctx->last_error = "shk_candidates_enable: tickets are outstanding (wait for them first)";
-      return SHK_ERR_STATE;
-    }
+  if (tickets_outstanding(ctx)) { ctx->last_error = "shk_candidates_enable: tickets are outstanding (wait for them first)"; return SHK_ERR_STATE; }
   ctx->cand_m = m;
   return SHK_OK;
 }
@@ -1323,11 +1278,11 @@ int shk_candidates_enable(shk_ctx *ctx, uint32_t m)
 int shk_candidates_last(const shk_ctx *ctx, shk_candidates *out)
 {
   if (!ctx || !out) return SHK_ERR_ARG;
-  if (!ctx->last_cand_valid) return SHK_ERR_STATE;
-  out->n = ctx->last_evid_n;   // (the batch whose result was handed out last: one n for both kinds of record)
-  out->m = ctx->last_cand_m;
-  out->reads = ctx->last_cand_reads;
-  out->entries = ctx->last_cand_entries;
+  if (!ctx->last_rec.cand_valid) return SHK_ERR_STATE;
+  out->n = ctx->last_rec.n;   // (the batch whose result was handed out last: one n for both kinds of record)
+  out->m = ctx->last_rec.cand_m;
+  out->reads = ctx->last_rec.cand_reads;
+  out->entries = ctx->last_rec.cand_entries;
   return SHK_OK;
 }
 
@@ -1359,15 +1314,9 @@ int shk_ref_keep_bases(shk_ctx *ctx)
 int shk_placement_enable(shk_ctx *ctx, int enable)
 {
   if (!ctx) return SHK_ERR_ARG;
-  for (int i = 0; i < PIPE_DEPTH; ++i)
-    if (ctx->slots[i].ticket != 0 && !ctx->slots[i].waited) {
-      ctx->last_error = "shk_placement_enable: tickets are outstanding (wait for them first)";
-      return SHK_ERR_STATE;
-    }
+  if (tickets_outstanding(ctx)) { ctx->last_error = "shk_placement_enable: tickets are outstanding (wait for them first)"; return SHK_ERR_STATE; }
   if (enable) {
-    if (ctx->mode != 2) { ctx->last_error = "shk_placement_enable: the index is not finalized"; return SHK_ERR_STATE; }
-    if (!ctx->idx.ptab_lg) { ctx->last_error = "shk_placement_enable: the index was finalized without shk_ref_keep_positions"; return SHK_ERR_STATE; }
-    if (ctx->n_records > 65536 || ctx->idx.wrap) { ctx->last_error = "shk_placement_enable: more than 65 536 records (gene ids wrap)"; return SHK_ERR_STATE; }
+    if (const int rc = check_mode_index(ctx, "shk_placement_enable", 0)) return rc;
   }
   ctx->placement = enable != 0;
   return SHK_OK;
@@ -1376,9 +1325,9 @@ int shk_placement_enable(shk_ctx *ctx, int enable)
 int shk_placement_last(const shk_ctx *ctx, shk_placements *out)
 {
   if (!ctx || !out) return SHK_ERR_ARG;
-  if (!ctx->last_place_valid) return SHK_ERR_STATE;
-  out->n_assoc = ctx->last_place_n;
-  out->entries = ctx->last_place;
+  if (!ctx->last_rec.place_valid) return SHK_ERR_STATE;
+  out->n_assoc = ctx->last_rec.n_assoc;
+  out->entries = ctx->last_rec.place;
   return SHK_OK;
 }
 
@@ -1386,15 +1335,9 @@ int shk_segments_enable(shk_ctx *ctx, uint32_t m)
 {
   if (!ctx) return SHK_ERR_ARG;
   if (m > SHK_MAX_SEGMENTS) { ctx->last_error = "shk_segments_enable: m must be at most SHK_MAX_SEGMENTS"; return SHK_ERR_ARG; }
-  for (int i = 0; i < PIPE_DEPTH; ++i)
-    if (ctx->slots[i].ticket != 0 && !ctx->slots[i].waited) {
-      ctx->last_error = "shk_segments_enable: tickets are outstanding (wait for them first)";
-      return SHK_ERR_STATE;
-    }
+  if (tickets_outstanding(ctx)) { ctx->last_error = "shk_segments_enable: tickets are outstanding (wait for them first)"; return SHK_ERR_STATE; }
   if (m) {
-    if (ctx->mode != 2) { ctx->last_error = "shk_segments_enable: the index is not finalized"; return SHK_ERR_STATE; }
-    if (!ctx->idx.ptab_lg) { ctx->last_error = "shk_segments_enable: the index was finalized without shk_ref_keep_positions"; return SHK_ERR_STATE; }
-    if (ctx->n_records > 65536 || ctx->idx.wrap) { ctx->last_error = "shk_segments_enable: more than 65 536 records (gene ids wrap)"; return SHK_ERR_STATE; }
+    if (const int rc = check_mode_index(ctx, "shk_segments_enable", 0)) return rc;
   }
   ctx->seg_m = m;
   return SHK_OK;
@@ -1403,31 +1346,22 @@ int shk_segments_enable(shk_ctx *ctx, uint32_t m)
 int shk_segments_last(const shk_ctx *ctx, shk_segments *out)
 {
   if (!ctx || !out) return SHK_ERR_ARG;
-  if (!ctx->last_seg_valid) return SHK_ERR_STATE;
-  out->n_assoc = ctx->last_seg_n;
-  out->m = ctx->last_seg_m;
-  out->n_keys = ctx->last_seg_keys;
-  out->entries = ctx->last_seg_entries;
+  if (!ctx->last_rec.seg_valid) return SHK_ERR_STATE;
+  out->n_assoc = ctx->last_rec.n_assoc;
+  out->m = ctx->last_rec.seg_m;
+  out->n_keys = ctx->last_rec.seg_keys;
+  out->entries = ctx->last_rec.seg_entries;
   return SHK_OK;
 }
 
 // ---- depth mode (depth.hip): the state lives in the context, the batches' tails add to it ----
-static bool tickets_outstanding(const shk_ctx *ctx)
-{
-  for (int i = 0; i < PIPE_DEPTH; ++i)
-    if (ctx->slots[i].ticket != 0 && !ctx->slots[i].waited) return true;
-  return false;
-}
-
 // both kinds of depth (plain intervals, unions of kept spans) over the one state
 static int depth_enable_kind(shk_ctx *ctx, uint32_t min_support, bool spliced, const char *who)
 {
   if (!ctx) return SHK_ERR_ARG;
   if (tickets_outstanding(ctx)) { ctx->last_error = std::string(who) + ": tickets are outstanding (wait for them first)"; return SHK_ERR_STATE; }
   if (min_support) {
-    if (ctx->mode != 2) { ctx->last_error = std::string(who) + ": the index is not finalized"; return SHK_ERR_STATE; }
-    if (!ctx->idx.ptab_lg) { ctx->last_error = std::string(who) + ": the index was finalized without shk_ref_keep_positions"; return SHK_ERR_STATE; }
-    if (ctx->n_records > 65536 || ctx->idx.wrap || !ctx->idx.gene_start) { ctx->last_error = std::string(who) + ": more than 65 536 records (gene ids wrap)"; return SHK_ERR_STATE; }
+    if (const int rc = check_mode_index(ctx, who, NEED_GENE_START)) return rc;
     if (ctx->d_depth_diff && ctx->depth_dirty && spliced != ctx->depth_spliced) {
       ctx->last_error = std::string(who) + ": the state holds depth of the other kind (plain / spliced): shk_depth_reset first";
       return SHK_ERR_STATE;
@@ -1545,9 +1479,7 @@ int shk_junctions_enable(shk_ctx *ctx, uint32_t min_support, uint64_t capacity)
   if (!ctx) return SHK_ERR_ARG;
   if (tickets_outstanding(ctx)) { ctx->last_error = "shk_junctions_enable: tickets are outstanding (wait for them first)"; return SHK_ERR_STATE; }
   if (min_support) {
-    if (ctx->mode != 2) { ctx->last_error = "shk_junctions_enable: the index is not finalized"; return SHK_ERR_STATE; }
-    if (!ctx->idx.ptab_lg) { ctx->last_error = "shk_junctions_enable: the index was finalized without shk_ref_keep_positions"; return SHK_ERR_STATE; }
-    if (ctx->n_records > 65536 || ctx->idx.wrap || !ctx->idx.gene_start) { ctx->last_error = "shk_junctions_enable: more than 65 536 records (gene ids wrap)"; return SHK_ERR_STATE; }
+    if (const int rc = check_mode_index(ctx, "shk_junctions_enable", NEED_GENE_START)) return rc;
     if (capacity > (1ull << 40)) { ctx->last_error = "shk_junctions_enable: capacity beyond 2^40 entries"; return SHK_ERR_ARG; }
     uint64_t cap = 64;
     while (cap < capacity) cap <<= 1;
@@ -1630,10 +1562,7 @@ static int pileup_enable_kind(shk_ctx *ctx, uint32_t min_support, bool aligned, 
   if (!ctx) return SHK_ERR_ARG;
   if (tickets_outstanding(ctx)) { ctx->last_error = std::string(who) + ": tickets are outstanding (wait for them first)"; return SHK_ERR_STATE; }
   if (min_support) {
-    if (ctx->mode != 2) { ctx->last_error = std::string(who) + ": the index is not finalized"; return SHK_ERR_STATE; }
-    if (!ctx->idx.ptab_lg) { ctx->last_error = std::string(who) + ": the index was finalized without shk_ref_keep_positions"; return SHK_ERR_STATE; }
-    if (ctx->n_records > 65536 || ctx->idx.wrap || !ctx->idx.gene_start) { ctx->last_error = std::string(who) + ": more than 65 536 records (gene ids wrap)"; return SHK_ERR_STATE; }
-    if (aligned && !ctx->idx.recbase) { ctx->last_error = std::string(who) + ": the index was finalized without shk_ref_keep_bases"; return SHK_ERR_STATE; }
+    if (const int rc = check_mode_index(ctx, who, NEED_GENE_START | (aligned ? NEED_BASES : 0u))) return rc;
     if (ctx->d_pileup_mates && ctx->pileup_dirty && aligned != ctx->pileup_aligned) {
       ctx->last_error = std::string(who) + ": the state holds pileup of the other kind (owned / aligned): shk_pileup_reset first";
       return SHK_ERR_STATE;
@@ -1777,10 +1706,7 @@ int shk_alignments_enable(shk_ctx *ctx, uint32_t min_support)
   if (!ctx) return SHK_ERR_ARG;
   if (tickets_outstanding(ctx)) { ctx->last_error = "shk_alignments_enable: tickets are outstanding (wait for them first)"; return SHK_ERR_STATE; }
   if (min_support) {
-    if (ctx->mode != 2) { ctx->last_error = "shk_alignments_enable: the index is not finalized"; return SHK_ERR_STATE; }
-    if (!ctx->idx.ptab_lg) { ctx->last_error = "shk_alignments_enable: the index was finalized without shk_ref_keep_positions"; return SHK_ERR_STATE; }
-    if (ctx->n_records > 65536 || ctx->idx.wrap || !ctx->idx.gene_start) { ctx->last_error = "shk_alignments_enable: more than 65 536 records (gene ids wrap)"; return SHK_ERR_STATE; }
-    if (!ctx->idx.recbase) { ctx->last_error = "shk_alignments_enable: the index was finalized without shk_ref_keep_bases"; return SHK_ERR_STATE; }
+    if (const int rc = check_mode_index(ctx, "shk_alignments_enable", NEED_GENE_START | NEED_BASES)) return rc;
   }
   ctx->align = min_support;
   return SHK_OK;
@@ -1799,9 +1725,9 @@ int shk_alignments_extend(shk_ctx *ctx, uint32_t mismatch_penalty, uint32_t end_
 int shk_alignments_last(const shk_ctx *ctx, shk_alignments *out)
 {
   if (!ctx || !out) return SHK_ERR_ARG;
-  if (!ctx->last_align_valid) return SHK_ERR_STATE;
-  out->n_assoc = ctx->last_align_n;
-  out->entries = ctx->last_align;
+  if (!ctx->last_rec.align_valid) return SHK_ERR_STATE;
+  out->n_assoc = ctx->last_rec.n_assoc;
+  out->entries = ctx->last_rec.align;
   return SHK_OK;
 }
 
@@ -1812,10 +1738,7 @@ int shk_pairs_enable(shk_ctx *ctx, uint32_t min_intron, uint32_t max_frag, uint3
   if (tickets_outstanding(ctx)) { ctx->last_error = "shk_pairs_enable: tickets are outstanding (wait for them first)"; return SHK_ERR_STATE; }
   if (n_bins) {
     if (n_bins < 2 || n_bins > 4096 || min_intron < 1) { ctx->last_error = "shk_pairs_enable: n_bins is 0 or 2 .. 4096 and min_intron at least 1"; return SHK_ERR_ARG; }
-    if (ctx->mode != 2) { ctx->last_error = "shk_pairs_enable: the index is not finalized"; return SHK_ERR_STATE; }
-    if (!ctx->idx.ptab_lg) { ctx->last_error = "shk_pairs_enable: the index was finalized without shk_ref_keep_positions"; return SHK_ERR_STATE; }
-    if (ctx->n_records > 65536 || ctx->idx.wrap || !ctx->idx.gene_start) { ctx->last_error = "shk_pairs_enable: more than 65 536 records (gene ids wrap)"; return SHK_ERR_STATE; }
-    if (!ctx->idx.recbase) { ctx->last_error = "shk_pairs_enable: the index was finalized without shk_ref_keep_bases"; return SHK_ERR_STATE; }
+    if (const int rc = check_mode_index(ctx, "shk_pairs_enable", NEED_GENE_START | NEED_BASES)) return rc;
     if (!ctx->align) { ctx->last_error = "shk_pairs_enable: alignments mode is off (shk_alignments_enable first)"; return SHK_ERR_STATE; }
     if (ctx->d_frag && n_bins != ctx->frag_bins) {
       if (ctx->frag_dirty) { ctx->last_error = "shk_pairs_enable: another n_bins than the state's (shk_fragments_reset first)"; return SHK_ERR_ARG; }
@@ -1843,9 +1766,9 @@ int shk_pairs_enable(shk_ctx *ctx, uint32_t min_intron, uint32_t max_frag, uint3
 int shk_pairs_last(const shk_ctx *ctx, shk_pairs *out)
 {
   if (!ctx || !out) return SHK_ERR_ARG;
-  if (!ctx->last_pairs_valid) return SHK_ERR_STATE;
-  out->n_assoc = ctx->last_pairs_n;
-  out->entries = ctx->last_pairs;
+  if (!ctx->last_rec.pairs_valid) return SHK_ERR_STATE;
+  out->n_assoc = ctx->last_rec.n_assoc;
+  out->entries = ctx->last_rec.pairs;
   return SHK_OK;
 }
 
@@ -1859,10 +1782,7 @@ int shk_rescue_enable(shk_ctx *ctx, uint32_t min_intron, uint32_t max_frag, uint
       ctx->last_error = "shk_rescue_enable: max_frag is 0 or 1 .. 4096, min_intron at least 1, max_cost and min_gap at most 255";
       return SHK_ERR_ARG;
     }
-    if (ctx->mode != 2) { ctx->last_error = "shk_rescue_enable: the index is not finalized"; return SHK_ERR_STATE; }
-    if (!ctx->idx.ptab_lg) { ctx->last_error = "shk_rescue_enable: the index was finalized without shk_ref_keep_positions"; return SHK_ERR_STATE; }
-    if (ctx->n_records > 65536 || ctx->idx.wrap || !ctx->idx.gene_start) { ctx->last_error = "shk_rescue_enable: more than 65 536 records (gene ids wrap)"; return SHK_ERR_STATE; }
-    if (!ctx->idx.recbase) { ctx->last_error = "shk_rescue_enable: the index was finalized without shk_ref_keep_bases"; return SHK_ERR_STATE; }
+    if (const int rc = check_mode_index(ctx, "shk_rescue_enable", NEED_GENE_START | NEED_BASES)) return rc;
     if (!ctx->align) { ctx->last_error = "shk_rescue_enable: alignments mode is off (shk_alignments_enable first)"; return SHK_ERR_STATE; }
     ctx->rescue_min_intron = min_intron;
     ctx->rescue_max_cost = max_cost;
@@ -1875,9 +1795,9 @@ int shk_rescue_enable(shk_ctx *ctx, uint32_t min_intron, uint32_t max_frag, uint
 int shk_rescue_last(const shk_ctx *ctx, shk_rescues *out)
 {
   if (!ctx || !out) return SHK_ERR_ARG;
-  if (!ctx->last_rescue_valid) return SHK_ERR_STATE;
-  out->n_assoc = ctx->last_rescue_n;
-  out->entries = ctx->last_rescue;
+  if (!ctx->last_rec.rescue_valid) return SHK_ERR_STATE;
+  out->n_assoc = ctx->last_rec.n_assoc;
+  out->entries = ctx->last_rec.rescue;
   return SHK_OK;
 }
 

@@ -322,39 +322,113 @@ constexpr uint32_t CLS_MIN_FILL = 16;     // by classes only if a non-empty clas
 // ---- one batch in flight ---------------------------------------------------------------------
 constexpr int PIPE_DEPTH = 3;      // batches shk_classify_submit keeps in flight per context
 
+struct Ctx;
+int set_hip_error(Ctx *ctx, hipError_t e, const char *what);
+
+// a buffer that only grows, for callers that keep pointer and capacity themselves (Ctx::d_scratch, the variants' records); Array's rule
+template <typename T>
+int ensure_capacity(Ctx *ctx, T **ptr, size_t *cap, size_t need)
+{
+  if (need <= *cap && *ptr) return SHK_OK;
+  if (*ptr) {
+    hipError_t e = hipFree(*ptr);
+    *ptr = nullptr;
+    *cap = 0;
+    if (e != hipSuccess) return set_hip_error(ctx, e, "hipFree");
+  }
+  size_t want = need + need / 4 + 64;
+  hipError_t e = hipMalloc((void **)ptr, want * sizeof(T));
+  if (e != hipSuccess) return set_hip_error(ctx, e, "hipMalloc");
+  *cap = want;
+  return SHK_OK;
+}
+
+// ---- a growable buffer that owns its memory: device (hipMalloc) or pinned host (hipHostMalloc); cap counts entries.  Movable, not
+// copyable, freed by its destructor: a Slot frees what it owns, `s = Slot{}` included ----
+template <typename T, bool PINNED>
+struct Array {
+  T *p = nullptr;
+  size_t cap = 0;
+  Array() = default;
+  Array(const Array &) = delete;
+  Array &operator=(const Array &) = delete;
+  Array(Array &&o) noexcept : p(o.p), cap(o.cap) { o.p = nullptr; o.cap = 0; }
+  Array &operator=(Array &&o) noexcept
+  {
+    if (this != &o) { release(); p = o.p; cap = o.cap; o.p = nullptr; o.cap = 0; }
+    return *this;
+  }
+  ~Array() { release(); }
+  void release()
+  {
+    if (p) (void)(PINNED ? hipHostFree(p) : hipFree(p));
+    p = nullptr;
+    cap = 0;
+  }
+  // at least `need` entries (a quarter more and 64 where it has to grow; what it held is gone then)
+  int reserve(Ctx *ctx, size_t need)
+  {
+    if constexpr (!PINNED) {
+      return ensure_capacity(ctx, &p, &cap, need);
+    } else {
+      if (need <= cap && p) return SHK_OK;
+      release();
+      const size_t want = need + need / 4 + 64;
+      hipError_t e = hipHostMalloc((void **)&p, want * sizeof(T), hipHostMallocDefault);
+      if (e != hipSuccess) return set_hip_error(ctx, e, "hipHostMalloc");
+      cap = want;
+      return SHK_OK;
+    }
+  }
+};
+template <typename T> using DevArray = Array<T, false>;
+template <typename T> using PinArray = Array<T, true>;
+
+// one kind of per-batch record: the device array the kernels write and the pinned mirror a host batch's records are published into
+// (launch_publish_records); a batch hands out the one its caller can read
+template <typename T>
+struct Mirrored {
+  DevArray<T> d;
+  PinArray<T> h;
+  const T *handed(bool host_batch) const { return host_batch ? h.p : d.p; }
+};
+
+// associations that segment arrays (two headers and 2 x m entries each) hold at m entries per mate
+template <bool PINNED>
+uint64_t segments_cap(const Array<uint32_t, PINNED> &keys, const Array<shk_segment, PINNED> &entries, uint32_t m)
+{
+  if (!m) return 0;
+  const uint64_t by_keys = keys.cap / 2, by_entries = entries.cap / (2ull * m);
+  return by_keys < by_entries ? by_keys : by_entries;
+}
+
 struct Slot {
   // device copies of a host batch (host-buffer entry points only)
-  uint8_t *d_seq1 = nullptr, *d_seq2 = nullptr, *d_qual1 = nullptr, *d_qual2 = nullptr;
-  uint64_t *d_off1 = nullptr, *d_off2 = nullptr;
-  size_t cap_seq1 = 0, cap_seq2 = 0, cap_qual1 = 0, cap_qual2 = 0, cap_off1 = 0, cap_off2 = 0;
+  DevArray<uint8_t> d_seq1, d_seq2, d_qual1, d_qual2;
+  DevArray<uint64_t> d_off1, d_off2;
   // device results
-  uint32_t *d_count = nullptr;    size_t cap_count = 0;
-  uint16_t *d_inl = nullptr;      size_t cap_inl = 0;
-  uint32_t *d_gene_off = nullptr; size_t cap_gene_off = 0;
-  uint16_t *d_gene_ids = nullptr; size_t cap_gene_ids = 0;
-  shk_read_evidence *d_evid = nullptr; size_t cap_evid = 0;   // evidence mode: one record per read (allocated with the first such batch)
-  shk_read_candidates *d_cand_reads = nullptr; size_t cap_cand_reads = 0;   // candidates mode: one header per read and cand_m entries
-  shk_candidate *d_cand_entries = nullptr; size_t cap_cand_entries = 0;     //  (allocated with the first such batch)
-  uint32_t *d_long_queue = nullptr; size_t cap_long_queue = 0;
-  uint32_t *d_tie_queue = nullptr;  size_t cap_tie_queue = 0;
+  DevArray<uint32_t> d_count;
+  DevArray<uint16_t> d_inl;
+  DevArray<uint32_t> d_gene_off;
+  DevArray<uint16_t> d_gene_ids;
+  Mirrored<shk_read_evidence> rec_evid;                // evidence mode: one record per read (allocated with the first such batch)
+  Mirrored<shk_read_candidates> rec_cand_reads;        // candidates mode: one header per read and cand_m entries
+  Mirrored<shk_candidate> rec_cand_entries;            //  (allocated with the first such batch)
+  DevArray<uint32_t> d_long_queue, d_tie_queue;
   uint32_t *d_counters = nullptr;
   uint32_t *d_uni_flag = nullptr;  // UNI_FLAG_WORDS words: verdict of uniform_check_kernel / class_plan_kernel (0 ragged, 1 uniform, 2 by classes), lengths, scratch
-  uint4 *d_plan = nullptr; size_t cap_plan = 0;   // read plans of a ragged batch (ClassifyParams::plan_tab)
+  DevArray<uint4> d_plan;          // read plans of a ragged batch (ClassifyParams::plan_tab)
   // a batch taken class by class (ClassifyParams::cls_*)
-  uint4 *d_cls_entries = nullptr; size_t cap_cls_entries = 0;
-  uint4 *d_cls_list = nullptr;    size_t cap_cls_list = 0;
+  DevArray<uint4> d_cls_entries, d_cls_list;
   uint32_t *d_cls_share = nullptr;
-  uint32_t *d_cls_hist = nullptr; size_t cap_cls_hist = 0;
-  uint64_t *d_scan_temp = nullptr; size_t cap_scan_temp = 0;
+  DevArray<uint32_t> d_cls_hist;
+  DevArray<uint64_t> d_scan_temp;
   ClassifyOut *d_out = nullptr;
   ClassifyOut out_shadow{};        // what *d_out holds (rewritten only when a buffer moved)
   // pinned host: counters, result offsets and ids
   uint32_t *h_counters = nullptr;  // CTR_WORDS
-  uint32_t *h_gene_off = nullptr;  size_t cap_h_gene_off = 0;
-  uint16_t *h_gene_ids = nullptr;  size_t cap_h_gene_ids = 0;
-  shk_read_evidence *h_evid = nullptr; size_t cap_h_evid = 0;   // (host batches in evidence mode; filled by publish_evidence_kernel)
-  shk_read_candidates *h_cand_reads = nullptr; size_t cap_h_cand_reads = 0;   // (host batches in candidates mode; filled by publish_evidence_kernel)
-  shk_candidate *h_cand_entries = nullptr; size_t cap_h_cand_entries = 0;
+  PinArray<uint32_t> h_gene_off;
+  PinArray<uint16_t> h_gene_ids;
   hipEvent_t ev_h2d = nullptr, ev_done = nullptr, ev_d2h = nullptr;
   // the batch
   uint64_t ticket = 0;             // 0 = free
@@ -363,58 +437,51 @@ struct Slot {
   ClassifyParams p{};              // launch parameters (kept for the slow paths)
   uint32_t fast_cap = 0, gen_slots = 0;
   bool host_batch = false;
-  bool evidence = false;           // submitted in evidence mode: the evidence instantiations ran and d_evid (h_evid) hold its records
+  bool evidence = false;           // submitted in evidence mode: the evidence instantiations ran and rec_evid holds its records
   uint32_t cand_m = 0;             // submitted in candidates mode with this many entries per read (0: not): the candidates instantiations ran
   bool long_speculative = false;   // (device-resident submit) the caller's length bound was taken on trust: checked in wait
   // placement mode: one record per association, as many as d_gene_ids holds (allocated with the first such batch)
-  bool placement = false;          // submitted in placement mode: placement_kernel ran behind the assembly and d_place (h_place) hold its records
-  shk_placement *d_place = nullptr; size_t cap_place = 0;
-  shk_placement *h_place = nullptr; size_t cap_h_place = 0;   // (host batches; filled by publish_placements_kernel)
-  // depth mode: submitted with this min_support (0: not): placement_kernel ran (d_place holds its records) and depth_accumulate_kernel behind it
+  bool placement = false;          // submitted in placement mode: placement_kernel ran behind the assembly and rec_place holds its records
+  Mirrored<shk_placement> rec_place;
+  // depth mode: submitted with this min_support (0: not): placement_kernel ran (rec_place.d holds its records) and depth_accumulate_kernel behind it
   uint32_t depth = 0;
   // segments mode: submitted with this many entries per mate (0: not): segments_kernel ran behind the assembly; per association two headers
-  // (d_seg_keys) and 2 x seg_m entries (d_seg_entries), allocated with the first such batch for as many associations as d_gene_ids holds
+  // (rec_seg_keys) and 2 x seg_m entries (rec_seg_entries), allocated with the first such batch for as many associations as d_gene_ids holds
   uint32_t seg_m = 0;
-  uint32_t *d_seg_keys = nullptr; size_t cap_seg_keys = 0;
-  shk_segment *d_seg_entries = nullptr; size_t cap_seg_entries = 0;
-  uint32_t *h_seg_keys = nullptr; size_t cap_h_seg_keys = 0;        // (host batches; filled by publish_segments_kernel)
-  shk_segment *h_seg_entries = nullptr; size_t cap_h_seg_entries = 0;
+  Mirrored<uint32_t> rec_seg_keys;
+  Mirrored<shk_segment> rec_seg_entries;
   // spliced depth and the junction table (spliced.hip): submitted with these floors (0: not).  They read segments_kernel's records at
   // m = SHK_MAX_SEGMENTS: segments mode's own when it runs at that m, else arrays of their own (allocated with the first such batch,
   // never handed out) that a second launch of segments_kernel fills
   uint32_t sp_depth = 0, sp_junc = 0;
-  uint32_t *d_sp_keys = nullptr; size_t cap_sp_keys = 0;
-  shk_segment *d_sp_entries = nullptr; size_t cap_sp_entries = 0;
+  DevArray<uint32_t> d_sp_keys;
+  DevArray<shk_segment> d_sp_entries;
   // pileup mode (pileup.hip): submitted with this floor (0: not).  The third reader of those records at m = SHK_MAX_SEGMENTS, from the same
   // arrays: segments mode's own at that m, else d_sp_*, which are filled when ANY of spliced depth, the junction table and pileup is on
   uint32_t pileup = 0;
   // alignments mode (align.hip): submitted with this floor (0: not).  The fourth reader of those records, and the one whose result is per
-  // association: two 64-byte records each (d_align, allocated with the first such batch for as many associations as d_gene_ids holds;
-  // cap_align, cap_h_align count mates' records)
+  // association: two 64-byte records each (rec_align, allocated with the first such batch for as many associations as d_gene_ids holds;
+  // its capacities count mates' records)
   uint32_t align = 0;
-  shk_mate_alignment *d_align = nullptr; size_t cap_align = 0;
-  shk_mate_alignment *h_align = nullptr; size_t cap_h_align = 0;   // (host batches; filled by publish_alignments_kernel)
+  Mirrored<shk_mate_alignment> rec_align;
   // end extension (shk_alignments_extend) as submitted: mismatch penalty (0: off) and end bonus; aligned pileup (shk_pileup_enable_aligned):
   // submitted with this floor (0: not) -- align_kernel's accumulating instantiation adds the batch to Ctx::d_pileup, pileup_kernel does not run
   uint32_t ext_p = 0, ext_b = 0;
   uint32_t pileup_al = 0;
   // pairs mode (pairs.hip): submitted with this n_bins (0: not; only with `align`): pair_kernel ran behind the storing align_kernel, one
-  // 32-byte record per association (d_pairs, allocated with the first such batch for as many associations as d_gene_ids holds);
+  // 32-byte record per association (rec_pairs, allocated with the first such batch for as many associations as d_gene_ids holds);
   // pairs_count: the batch is added to Ctx::d_frag (not a shk_count_work batch)
   uint32_t pairs = 0, pairs_min_intron = 0, pairs_max_frag = 0;
   bool pairs_count = false;
-  shk_pair *d_pairs = nullptr; size_t cap_pairs = 0;
-  shk_pair *h_pairs = nullptr; size_t cap_h_pairs = 0;   // (host batches; filled by publish_pairs_kernel)
+  Mirrored<shk_pair> rec_pairs;
   // rescue mode (rescue.hip): submitted with this max_frag (0: not; only with `align`): rescue_scan_kernel and rescue_kernel ran behind the
-  // storing align_kernel and in front of pair_kernel, one 16-byte record per association (d_rescue) and a queue of the attempted
+  // storing align_kernel and in front of pair_kernel, one 16-byte record per association (rec_rescue) and a queue of the attempted
   // associations (d_rescue_queue: 16 bytes that hold the count, then (read, association) pairs), both allocated with the first such batch
   uint32_t rescue = 0, rescue_min_intron = 0, rescue_max_cost = 0, rescue_min_gap = 0;
-  shk_rescue *d_rescue = nullptr; size_t cap_rescue = 0;
-  uint2 *d_rescue_queue = nullptr; size_t cap_rescue_queue = 0;
-  shk_rescue *h_rescue = nullptr; size_t cap_h_rescue = 0;   // (host batches; filled by publish_rescue_kernel)
+  Mirrored<shk_rescue> rec_rescue;
+  DevArray<uint2> d_rescue_queue;
 };
 
-struct Ctx;
 
 // one entry of the junction table (spliced.hip): key = (gene_start[g] + donor) << 32 | (gene_start[g] + acceptor)
 struct JunctionEntry {
@@ -433,14 +500,11 @@ int build_placement_table(Ctx *ctx, const uint8_t *d_bytes, uint64_t total, cons
                           uint64_t *keys_a, uint64_t *keys_b);
 // placement.hip: per association of the batch in `s` the best diagonal per mate, behind the kernels that wrote gene_off / gene_ids
 int launch_placement(Ctx *ctx, const Slot &s, hipStream_t stream);
-int launch_publish_placements(const uint32_t *counters, const shk_placement *src, shk_placement *h_dst, uint64_t h_cap, hipStream_t stream);
 // segments.hip: per association of the batch in `s` and per mate its best s.seg_m diagonals with their first and last voting slot
 int launch_segments(Ctx *ctx, const Slot &s, hipStream_t stream);
 // the same kernel at m entries per mate into other arrays (cap_assoc: associations they hold): what spliced.hip reads when segments mode is off or narrower
 int launch_segments_into(Ctx *ctx, const Slot &s, uint32_t m, uint32_t *d_keys, shk_segment *d_entries, uint64_t cap_assoc, hipStream_t stream);
-uint64_t segments_cap(const Slot &s);   // associations d_seg_keys / d_seg_entries hold at s.seg_m
-int launch_publish_segments(const Slot &s, uint64_t h_cap, hipStream_t stream);   // h_cap: associations the pinned arrays (and the device's) hold
-// depth.hip: the batch in `s` (its placements in s.d_place) into the context's difference array, behind launch_placement; skip_if_long: as launch_gene_hist
+// depth.hip: the batch in `s` (its placements in s.rec_place.d) into the context's difference array, behind launch_placement; skip_if_long: as launch_gene_hist
 int launch_depth_accumulate(Ctx *ctx, const Slot &s, bool skip_if_long, hipStream_t stream);
 // spliced.hip: the batch in `s` from its segments at m = SHK_MAX_SEGMENTS (`entries`, cap_assoc associations) into the depth state (s.sp_depth)
 // and / or the junction table (s.sp_junc), behind segments_kernel; skip_if_long: as launch_gene_hist
@@ -448,19 +512,16 @@ int launch_spliced_accumulate(Ctx *ctx, const Slot &s, const shk_segment *entrie
 // pileup.hip: the batch in `s` from the same records into Ctx::d_pileup at floor s.pileup, behind segments_kernel; skip_if_long: as launch_gene_hist
 int launch_pileup(Ctx *ctx, const Slot &s, const shk_segment *entries, uint64_t cap_assoc, bool skip_if_long, hipStream_t stream);
 // align.hip: per association of the batch in `s` and per mate its blocks on the gene's record with their match and mismatch counts, from the
-// same records and DeviceIndex::recbase into s.d_align at floor s.align, behind segments_kernel; skip_if_long: as launch_gene_hist
-// store: the records go to s.d_align at floor s.align; accumulate: the final blocks' bases go to Ctx::d_pileup at floor s.pileup_al (one launch
+// same records and DeviceIndex::recbase into s.rec_align.d at floor s.align, behind segments_kernel; skip_if_long: as launch_gene_hist
+// store: the records go to s.rec_align.d at floor s.align; accumulate: the final blocks' bases go to Ctx::d_pileup at floor s.pileup_al (one launch
 // does both where the floors are equal).  With s.ext_p == 0 and no accumulation the kernel launched is the one this mode always launched
 int launch_alignments(Ctx *ctx, const Slot &s, const shk_segment *entries, uint64_t cap_assoc, bool skip_if_long, bool store, bool accumulate, hipStream_t stream);
-int launch_publish_alignments(const Slot &s, uint64_t h_cap, hipStream_t stream);   // h_cap: associations the pinned array (and the device's) holds
-// pairs.hip: per association of the batch in `s` its pair record from the two mates' records in s.d_align (cap_assoc: launch_alignments') into
-// s.d_pairs and, where s.pairs_count, the batch into Ctx::d_frag; directly behind the storing launch_alignments; skip_if_long: as launch_gene_hist
+// pairs.hip: per association of the batch in `s` its pair record from the two mates' records in s.rec_align.d (cap_assoc: launch_alignments') into
+// s.rec_pairs.d and, where s.pairs_count, the batch into Ctx::d_frag; directly behind the storing launch_alignments; skip_if_long: as launch_gene_hist
 int launch_pairs(Ctx *ctx, const Slot &s, uint64_t cap_assoc, bool skip_if_long, hipStream_t stream);
-int launch_publish_pairs(const Slot &s, uint64_t h_cap, hipStream_t stream);   // h_cap: associations the pinned array (and the device's) holds
-// rescue.hip: per association of the batch in `s` its rescue record into s.d_rescue and, where a mate is rescued, that mate's record in
-// s.d_align; directly behind the storing launch_alignments and in front of launch_pairs (cap_assoc, skip_if_long: launch_pairs')
+// rescue.hip: per association of the batch in `s` its rescue record into s.rec_rescue.d and, where a mate is rescued, that mate's record in
+// s.rec_align.d; directly behind the storing launch_alignments and in front of launch_pairs (cap_assoc, skip_if_long: launch_pairs')
 int launch_rescue(Ctx *ctx, const Slot &s, uint64_t cap_assoc, bool skip_if_long, hipStream_t stream);
-int launch_publish_rescue(const Slot &s, uint64_t h_cap, hipStream_t stream);   // h_cap: associations the pinned array (and the device's) holds
 // variants.hip: d_pileup[i] += d_add[i] over n_entries counters (d_add 16-byte aligned: SHK_ERR_ARG otherwise), *d_pileup_mates += mates, on ctx->stream
 int launch_pileup_add(Ctx *ctx, const uint32_t *d_add, uint64_t n_entries, uint64_t mates);
 // variants.hip: the sites of the pileup state against DeviceIndex::recbase: their number into *n_sites (host; the stream is drained) and, with
@@ -487,8 +548,9 @@ int launch_fill_offsets(uint64_t *off, uint64_t n_plus_1, uint64_t stride, hipSt
 int launch_vouch_check(const ClassifyParams &p, uint32_t L1, uint32_t L2, uint32_t *counters, hipStream_t stream);
 int launch_publish_results(const uint32_t *counters, uint32_t *h_counters, const uint32_t *gene_off, uint32_t *h_gene_off, uint64_t n_off,
                            const uint16_t *gene_ids, uint16_t *h_gene_ids, uint64_t h_ids_cap, const uint32_t *uni_flag, hipStream_t stream);
-int launch_publish_evidence(const shk_read_evidence *evid, shk_read_evidence *h_evid, uint64_t n, hipStream_t stream);
-int launch_publish_words(const uint32_t *src, uint32_t *h_dst, uint64_t n_words, hipStream_t stream);   // the same kernel over any 16-byte aligned words (candidates)
+// a host batch's records of one kind -> pinned host memory: `units` records of words_per_unit 32-bit words each from src (16-byte aligned, as
+// h_dst).  With `counters`: units = min(the batch's associations, limit), none for a batch that overflowed; nullptr: units = limit
+int launch_publish_records(const uint32_t *counters, const void *src, void *h_dst, uint64_t limit, uint32_t words_per_unit, hipStream_t stream);
 int launch_classify_uni(Ctx *ctx, const ClassifyParams &p, uint32_t max_slots, int rmode, hipStream_t stream);   // 0 ragged, 1 uniform, 2 by classes (CLS)
 int launch_class_prepass(const ClassifyParams &p, uint32_t slot_cap, uint32_t *flag, hipStream_t stream);   // behind launch_uniform_check: histogram, plan, scatter
 bool class_kernel_available(const Ctx *ctx, uint32_t max_slots);
@@ -502,6 +564,30 @@ int launch_anchor_verdict(const ClassifyParams &p, bool pow2, bool ragged, hipSt
 uint32_t fast_kernel_max_slots();
 uint32_t fast_kernel_unroll(uint32_t max_slots);  // U of the specialisation chosen for max_slots (0 = unknown)
 uint32_t uni_kernel_max_groups(uint32_t max_slots);   // staging groups per pair classify_uni_kernel can take at that specialisation
+
+// the records of the batch whose result was handed out last, per kind (shk_*_last).  valid = false: that batch had none of the kind, or it
+// was refused, or it was a measurement (shk_count_work).  Pointers into the batch's Slot: pinned host memory for a host batch, else device
+struct LastRecords {
+  uint64_t n = 0, n_assoc = 0;      // the batch's reads (evidence, candidates) and associations (every other kind)
+  bool evid_valid = false;
+  const shk_read_evidence *evid = nullptr;
+  bool cand_valid = false;
+  uint32_t cand_m = 0;
+  const shk_read_candidates *cand_reads = nullptr;
+  const shk_candidate *cand_entries = nullptr;
+  bool place_valid = false;
+  const shk_placement *place = nullptr;
+  bool seg_valid = false;
+  uint32_t seg_m = 0;
+  const uint32_t *seg_keys = nullptr;
+  const shk_segment *seg_entries = nullptr;
+  bool align_valid = false;
+  const shk_mate_alignment *align = nullptr;
+  bool pairs_valid = false;
+  const shk_pair *pairs = nullptr;
+  bool rescue_valid = false;
+  const shk_rescue *rescue = nullptr;
+};
 
 struct Ctx {
   shk_params prm{};
@@ -549,32 +635,16 @@ struct Ctx {
   uint32_t env_cls_min_fill = CLS_MIN_FILL;   // SHK_CLS_MIN_FILL: pairs per non-empty class a batch needs to go class by class (0: never; tests: 1)
   // which classify kernel the last batch's main launch was (shk_last_kernel): the choice can depend on the batch before it
   char last_kernel[160] = "";
-  // evidence mode (shk_evidence_enable): batches submitted while it is on run the evidence instantiations.  last_evid: the
-  // records of the batch whose result was handed out last (last_evid_valid = false: that batch had none, or it was refused)
-  bool evidence = false;
-  bool last_evid_valid = false;
-  const shk_read_evidence *last_evid = nullptr;
-  uint64_t last_evid_n = 0;
-  // candidates mode (shk_candidates_enable), the same way: cand_m entries per read for the batches submitted from now on (0: off)
-  uint32_t cand_m = 0;
-  bool last_cand_valid = false;
-  uint32_t last_cand_m = 0;
-  const shk_read_candidates *last_cand_reads = nullptr;
-  const shk_candidate *last_cand_entries = nullptr;
-  // placement mode (shk_ref_keep_positions, shk_placement_enable), the same way
-  bool keep_positions = false;      // finalize builds DeviceIndex::ptab
-  bool kmer_table = true;           // finalize builds DeviceIndex::kxtab where it applies (shk_ref_kmer_table; SHK_NO_KMER_TABLE=1: never)
-  bool placement = false;
-  bool last_place_valid = false;
-  const shk_placement *last_place = nullptr;
-  uint64_t last_place_n = 0;
-  // segments mode (shk_segments_enable; segments.hip), the same way: seg_m entries per mate for the batches submitted from now on (0: off)
-  uint32_t seg_m = 0;
-  bool last_seg_valid = false;
-  uint32_t last_seg_m = 0;
-  const uint32_t *last_seg_keys = nullptr;
-  const shk_segment *last_seg_entries = nullptr;
-  uint64_t last_seg_n = 0;
+  // what finalize builds beside the filter
+  bool keep_positions = false;      // DeviceIndex::ptab (shk_ref_keep_positions)
+  bool kmer_table = true;           // DeviceIndex::kxtab where it applies (shk_ref_kmer_table; SHK_NO_KMER_TABLE=1: never)
+  // the per-batch record modes: what the batches submitted from now on run with (0 / false: off).  Their records are handed out with the
+  // batch's result: last_rec
+  bool evidence = false;            // shk_evidence_enable: the evidence instantiations
+  uint32_t cand_m = 0;              // shk_candidates_enable: entries per read
+  bool placement = false;           // shk_placement_enable (an index built with shk_ref_keep_positions)
+  uint32_t seg_m = 0;               // shk_segments_enable (segments.hip): entries per mate
+  LastRecords last_rec;
   // depth mode (shk_depth_enable; depth.hip): the state outlives the mode's being switched off
   std::vector<uint64_t> gene_start;            // host copy of DeviceIndex::gene_start (empty: the index carries none)
   uint32_t depth = 0;                          // min_support for the batches submitted from now on (0: off)
@@ -608,9 +678,6 @@ struct Ctx {
   // alignments mode (shk_alignments_enable; align.hip), as segments mode: the floor for the batches submitted from now on (0: off)
   uint32_t align = 0;
   uint32_t ext_p = 0, ext_b = 0;               // shk_alignments_extend: mismatch penalty (0: off) and end bonus for the batches submitted from now on
-  bool last_align_valid = false;
-  const shk_mate_alignment *last_align = nullptr;
-  uint64_t last_align_n = 0;
   // pairs mode (shk_pairs_enable; pairs.hip): per-batch records as alignments mode's, and the fragments state, which like the depth state
   // outlives the mode's being switched off
   uint32_t pairs_bins = 0;                     // n_bins for the batches submitted from now on (0: off)
@@ -619,15 +686,9 @@ struct Ctx {
   unsigned long long *d_frag = nullptr;        // hist[frag_bins], classes[6] (allocated by the first enable)
   bool frag_dirty = false;                     // a pairs batch was submitted since the first enable / the last reset
   bool env_pairs_global = false;               // SHK_PAIRS_GLOBAL_ATOMICS=1: the histogram by one global atomic per pair (A/B timing only)
-  bool last_pairs_valid = false;
-  const shk_pair *last_pairs = nullptr;
-  uint64_t last_pairs_n = 0;
   // rescue mode (shk_rescue_enable; rescue.hip): per-batch records as pairs mode's; no state of its own
   uint32_t rescue_max_frag = 0;                // for the batches submitted from now on (0: off)
   uint32_t rescue_min_intron = 0, rescue_max_cost = 0, rescue_min_gap = 0;
-  bool last_rescue_valid = false;
-  const shk_rescue *last_rescue = nullptr;
-  uint64_t last_rescue_n = 0;
 
   // timing
   bool timing = false;
@@ -636,30 +697,12 @@ struct Ctx {
   shk_timing last{};
 };
 
-// error helpers
-int set_hip_error(Ctx *ctx, hipError_t e, const char *what);
+// error helper
 #define SHK_HIP(ctx, call)                                            \
   do {                                                                \
     hipError_t e__ = (call);                                          \
     if (e__ != hipSuccess) return shk::set_hip_error(ctx, e__, #call); \
   } while (0)
-
-template <typename T>
-int ensure_capacity(Ctx *ctx, T **ptr, size_t *cap, size_t need)
-{
-  if (need <= *cap && *ptr) return SHK_OK;
-  if (*ptr) {
-    hipError_t e = hipFree(*ptr);
-    *ptr = nullptr;
-    *cap = 0;
-    if (e != hipSuccess) return set_hip_error(ctx, e, "hipFree");
-  }
-  size_t want = need + need / 4 + 64;
-  hipError_t e = hipMalloc((void **)ptr, want * sizeof(T));
-  if (e != hipSuccess) return set_hip_error(ctx, e, "hipMalloc");
-  *cap = want;
-  return SHK_OK;
-}
 
 }  // namespace shk
 

@@ -169,11 +169,11 @@ int launch_spliced_accumulate(Ctx *ctx, const Slot &s, const shk_segment *entrie
   }
   if (s.n == 0 || (!depth && !junc)) return SHK_OK;
   SplicedParams P{};
-  P.gene_off = s.d_gene_off;
-  P.gene_ids = s.d_gene_ids;
+  P.gene_off = s.d_gene_off.p;
+  P.gene_ids = s.d_gene_ids.p;
   P.counters = s.d_counters;
   P.n = s.n;
-  P.cap = std::min<uint64_t>(std::min<uint64_t>(s.cap_gene_ids, cap_assoc), 0xFFFFFFFFull);   // (launch_segments')
+  P.cap = std::min<uint64_t>(std::min<uint64_t>(s.d_gene_ids.cap, cap_assoc), 0xFFFFFFFFull);   // (launch_segments')
   P.off[0] = s.p.seq1 ? s.p.off1 : nullptr;
   P.off[1] = s.p.seq2 ? s.p.off2 : nullptr;
   P.entries = entries;
