@@ -681,6 +681,43 @@ int shk_variants_summary(shk_ctx *ctx, const shk_variant_params *p, shk_gene_var
  *        base is 0.25 - 0.75 P < 0, and no bonus waits at the record's end;
  *      - trailing bases that are neither are not taken (ties go to the smallest e) unless the bonus carries the extension to the end;
  *      - with P = 0 the step is off and the records are bit-identical to those without it.
+ * 3b. SPLICED ENDS (shk_splice_sites_set, shk_alignments_splice; off by default), after gap closure and BEFORE step 3a, on a mate with
+ *    n_blocks >= 1, with the context's list of SITES and min_overhang (1 .. SHK_SPLICE_MAX_OVERHANG), max_cost and min_gap (0 .. 64).
+ *    A site (d, a) of gene g says: record bases [d, a) of g are an intron.  A side of a junction becomes a kept span only where it
+ *    holds s_min unique k-mers, at least k + s_min - 1 read bases; a shorter overhang past a junction is silent and stays outside
+ *    every block.  This step tries such an end across every listed intron it could have crossed and keeps the placement where it is
+ *    good and clearly the best.  "Not a match" is step 4's kind, as in a split's cost: a read byte that is no base or is masked, and
+ *    a record code 4, are not a match.
+ *      RIGHT END.  The last block is A = {x, q, len}; (xe, qe) = (x + len, q + len), h = L - qe.  The end is ATTEMPTED iff
+ *      min_overhang <= h <= SHK_SPLICE_MAX_OVERHANG and the mate has at most 3 blocks at that moment.  B = min(SHK_SPLICE_BACK,
+ *      len - 1).  The EVALUATED read bases are p = qe - B .. L - 1 (B + h <= 64 of them); on A's diagonal base p lies on record base
+ *      xA(p) = xe + (p - qe).  A site (d, a) of the gene is a CANDIDATE iff
+ *          xe - B <= d <= xe + h - 1      (A keeps at least one base and at least one base crosses),
+ *          a + (xe + h - d) <= len_g      (the far side lies inside the record),
+ *      and d < a, which every listed site satisfies.  Under the candidate base p lies on xA(p) if xA(p) < d, else on xA(p) + (a - d);
+ *      cost(d, a) = the number of evaluated bases that are not a match there.  The NULL candidate leaves every evaluated base on
+ *      xA(p) (a coordinate at or beyond len_g is not a match); its shift is 0, a site's SHIFT is a - d >= 1.
+ *        best   the candidate of smallest cost, ties to the LARGEST d, then the largest a (the left block keeps the shared bases,
+ *               as trimming and closure rule);
+ *        cost2  the smallest cost over the null candidate and all candidates whose shift differs from best's.  (Two sites of one
+ *               shift describe the same placement up to where the bases between their donors lie -- the junction table produces
+ *               such pairs from mates with an error next to a junction --, and they must not make each other ambiguous.)
+ *      The end is PLACED iff a candidate exists, cost(best) <= max_cost and cost2 - cost(best) >= min_gap (as signed numbers).
+ *      Placing:  len_A += d - xe (which may be negative), and the block {a, qe + (d - xe), h - (d - xe)} is added behind A: it ends
+ *      at the mate's last base.
+ *      LEFT END.  The mirror image on block 0 = {x0, q0, len}: h = q0 under the same bounds, B = min(SHK_SPLICE_BACK, len - 1), the
+ *      evaluated bases are p = 0 .. q0 + B - 1 with xB(p) = x0 + (p - q0).  A site is a candidate iff
+ *          x0 - h + 1 <= a <= x0 + B,     d - (q0 - x0 + a) >= 0      (the new block starts inside the record).
+ *      Base p lies on xB(p) if xB(p) >= a, else on xB(p) - (a - d).  Null candidate, tie rule (largest d, then largest a), cost2 and
+ *      the three conditions are the right end's.  Placing adds the block {d - n, 0, n} with n = q0 - x0 + a in front of block 0, and
+ *      block 0 becomes {a, n, len - (a - x0)}.
+ *    The left end is done first, then the right; the right end's B and its count of blocks are those after the left.  A mate ends
+ *    with at most SHK_MAX_SEGMENTS blocks.  Step 3a runs afterwards: it finds H = 0 at a placed end and treats an unplaced end as
+ *    before; step 4 counts over the final blocks.  Example (k = 17, exons [0, 80) and [140, 220), site (80, 140)): the mate
+ *    s[20:80] + s[140:150] has the block {20, 0, 60} and h = 10; with the site it becomes {20, 0, 60}, {140, 60, 10}: 60M60N10M.
+ *    What the step does NOT do: an overhang that itself holds a second junction; an overhang longer than SHK_SPLICE_MAX_OVERHANG
+ *    bases; a mate with no block; sites learned within the run.  Depth, spliced depth and the junction table accumulate from the
+ *    spans in front of align_kernel and do not see a placed overhang.
  * 4. COUNTING, over the final blocks.  For the read byte's c = to_int[byte behind the -q mask] and the record's code r at a block base:
  *    c == 0 or r == 4: neither a match nor a mismatch; otherwise b = c - 1 on strand 0 and 3 - (c - 1) on strand 1, and b == r is a
  *    match, anything else a mismatch.  (For a split's cost a base that is neither counts as not a match.)
@@ -693,8 +730,8 @@ int shk_variants_summary(shk_ctx *ctx, const shk_variant_params *p, shk_gene_var
  *
  * What the mode does NOT do:
  *   - by default the mate's ends outside its outermost blocks are not extended: they become soft clips (step 3a extends them base
- *     by base where shk_alignments_extend asks for it; an overhang past a junction still stays a clip: the mode does not look for
- *     the other side of the intron);
+ *     by base where shk_alignments_extend asks for it; an overhang past a junction stays a clip unless step 3b places it across a
+ *     LISTED junction: the mode does not discover the other side of an intron by itself);
  *   - the records themselves make no pair-level claim and carry no mapping quality: orientation, template length, the proper-pair
  *     flag and MAPQ are pairs mode's (the next section), which reads these records and changes none of them.
  *
@@ -722,6 +759,23 @@ int shk_alignments_enable(shk_ctx *ctx, uint32_t min_support);
  * The command's --extend-ends is P = 4, B = 5: the familiar match 1 / mismatch 4 / clip 5.  With P = 0 the kernel launched is the
  * one that ran before this call existed.  New: no counterpart. */
 int shk_alignments_extend(shk_ctx *ctx, uint32_t mismatch_penalty, uint32_t end_bonus);
+/* Step 3b's site list: copies sites[0 .. n) to the device (the caller's array is free afterwards) and replaces an earlier list; n == 0
+ * drops the list and switches the step off.  The intron of a site is record bases [donor, acceptor) of gene.  SHK_ERR_STATE before
+ * shk_ref_finalize, without shk_ref_keep_positions, on an index of more than 65 536 records, and while tickets are outstanding;
+ * SHK_ERR_ARG unless n < 2^31 and the list is strictly ascending in (gene, donor, acceptor) with gene < n_records and
+ * 1 <= donor < acceptor <= len_g - 1.  On the device: one offset per gene, the sites in (donor, acceptor) order (the right end searches
+ * by donor) and the same sites in (acceptor, donor) order (the left end searches by acceptor), both built on the host: 16 bytes per
+ * site and 4 per gene.  The host's own copy is freed with the context.  New: no counterpart. */
+#define SHK_SPLICE_MAX_OVERHANG 48
+#define SHK_SPLICE_BACK         16
+typedef struct shk_splice_site { uint32_t gene, donor, acceptor; } shk_splice_site;
+int shk_splice_sites_set(shk_ctx *ctx, const shk_splice_site *sites, uint64_t n);
+/* Step 3b's parameters for the batches submitted AFTERWARDS: min_overhang = 0 switches the step off (the default),
+ * 1 .. SHK_SPLICE_MAX_OVERHANG on; max_cost and min_gap 0 .. 64; anything else is SHK_ERR_ARG.  SHK_ERR_STATE while tickets are
+ * outstanding, and when switching on without a site list.  It takes effect only where alignments mode or aligned pileup runs
+ * (shk_alignments_extend's rule).  The command's defaults are 3, 2, 2.  With the step off the kernel launched and every record are
+ * those from before this call existed.  New: no counterpart. */
+int shk_alignments_splice(shk_ctx *ctx, uint32_t min_overhang, uint32_t max_cost, uint32_t min_gap);
 /* The alignments of the batch whose result was handed out LAST, with shk_segments_last's rules: that result's lifetime and memory
  * space (pinned host memory for host batches, DEVICE memory for resident ones).  SHK_ERR_STATE if that batch was submitted with
  * the mode off, if its wait returned an error, behind shk_count_work, or if no batch has been waited for yet.  New: no counterpart. */

@@ -137,12 +137,16 @@ EXPORTS = [
     "shk_alignments_enable", "shk_alignments_last", "shk_alignment_cigar", "shk_alignments_extend", "shk_pileup_enable_aligned",
     "shk_pairs_enable", "shk_pairs_last", "shk_fragments_get", "shk_fragments_reset",
     "shk_rescue_enable", "shk_rescue_last",
+    "shk_splice_sites_set", "shk_alignments_splice",
     "shk_debug_assemble_one",
 ]
 SHK_PIPE_DEPTH = 3
 SHK_DIST_ID_BYTES = 128
 SHK_MAX_CANDIDATES = 8
 SHK_MAX_SEGMENTS = 4
+SHK_SPLICE_MAX_OVERHANG = 48
+SHK_SPLICE_BACK = 16
+SPLICE_SITE_DTYPE = np.dtype([("gene", "<u4"), ("donor", "<u4"), ("acceptor", "<u4")])   # shk_splice_site, 12 bytes
 
 _lib = None
 
@@ -240,6 +244,8 @@ def load():
         "shk_fragments_reset": (C.c_int, [p]),
         "shk_rescue_enable": (C.c_int, [p, C.c_uint32, C.c_uint32, C.c_uint32, C.c_uint32]),
         "shk_rescue_last": (C.c_int, [p, C.POINTER(ShkRescues)]),
+        "shk_splice_sites_set": (C.c_int, [p, p, C.c_uint64]),
+        "shk_alignments_splice": (C.c_int, [p, C.c_uint32, C.c_uint32, C.c_uint32]),
         "shk_debug_assemble_one": (C.c_int, [p, p, C.c_uint64, C.c_uint32, C.c_uint32, C.c_uint64, C.c_uint32, C.c_int, C.c_int, p, p, p,
                                              C.POINTER(C.c_uint64), p]),
     }
@@ -735,6 +741,27 @@ class SharkHip:
         """end extension for the batches submitted from now on: a mate's outermost blocks grow over the clipped ends base by base, match
         +1, mismatch -penalty, +bonus for reaching the mate's end; penalty 0 switches it off (the default), 1 .. 15 on; bonus 0 .. 15"""
         self._check(self.L.shk_alignments_extend(self.h, int(penalty), int(bonus)), "shk_alignments_extend")
+
+    def splice_sites_set(self, sites):
+        """the site list of spliced ends (step 3b): an array of SPLICE_SITE_DTYPE records, or anything np.asarray turns into an (n, 3)
+        array of (gene, donor, acceptor) -- the intron is record bases [donor, acceptor) of gene --, strictly ascending; replaces an
+        earlier list; an empty one drops the list and switches the step off; refused while tickets are outstanding"""
+        a = np.asarray(sites)
+        if a.dtype != SPLICE_SITE_DTYPE:
+            a = np.ascontiguousarray(np.asarray(a, dtype=np.int64).reshape(-1, 3))
+            if a.size and (a.min() < 0 or a.max() > 0xFFFFFFFF):
+                raise SharkHipError("shk_splice_sites_set: a site's fields are 32-bit unsigned numbers")
+            a = a.astype("<u4")
+        a = np.ascontiguousarray(a)
+        n = a.shape[0]
+        self._check(self.L.shk_splice_sites_set(self.h, _ptr(a) if n else None, n), "shk_splice_sites_set")
+
+    def alignments_splice(self, min_overhang=3, max_cost=2, min_gap=2):
+        """spliced ends for the batches submitted from now on: a clipped end of min_overhang .. 48 bases is tried across every listed
+        junction it could have crossed and placed where the best costs at most max_cost not-a-matches and every other placement
+        (staying on the block's diagonal included) at least min_gap more; min_overhang 0 switches the step off (the default); needs
+        a site list"""
+        self._check(self.L.shk_alignments_splice(self.h, int(min_overhang), int(max_cost), int(min_gap)), "shk_alignments_splice")
 
     def alignments_last(self):
         """alignments of the batch whose result was handed out last: an (n_assoc, 2) array of ALIGNMENT_DTYPE records, parallel to

@@ -19,6 +19,11 @@
 // two overhangs against the record 64 bases per pass -- two ballots, two popcounts per lane, one wave maximum -- when the first block
 // becomes the open block and before the last one is counted; accumulation (aligned pileup) adds every base of a final block to the
 // pileup state with one atomic where the counting loop has it loaded.  With both off the kernel is the code it always was.
+//
+// A third switch: spliced ends (the header's step 3b) try a mate's clipped end of a few bases across the listed junctions
+// it could have crossed -- one lane per evaluated read base, one record byte, one ballot and one popcount per candidate site, the sites of
+// the range found by a binary search -- behind gap closure and in front of end extension: where block 0 is about to be finished, and in the last pass.
+// A placement adds a block through the walk itself: the one place that finishes a block stays the only one.
 #include <hip/hip_runtime.h>
 
 #include <algorithm>
@@ -64,6 +69,24 @@ struct AlignParamsX : AlignParams {
   uint32_t *counts;                // aligned pileup: [(gene_start[g] + x) * 4 + b]; `out` may then be nullptr and n_store 0: no records are stored
   unsigned long long *mates;
 };
+
+// what the splicing instantiations take on top of those (step 3b; shk_splice_sites_set's three arrays and shk_alignments_splice's values)
+// One pointer and one word: where the compiler keeps a kernel argument in registers across the loops, these cost three, not ten.
+struct AlignParamsS : AlignParamsX {
+  const uint32_t *spl;             // Ctx::d_splice: the offsets, the sites by donor, the sites by acceptor (splice_layout)
+  uint32_t spl_prm;                // min_overhang 1 .. SHK_SPLICE_MAX_OVERHANG | max_cost << 8 | min_gap << 16
+};
+
+// The gene's sites in Ctx::d_splice's layout: [g], [g + 1] of the n_genes + 1 offsets, behind them (at an even word) n = off[n_genes] pairs
+// {donor, acceptor} ascending per gene in (donor, acceptor) -- the right end's -- and n pairs {acceptor, donor} ascending per gene in
+// (acceptor, donor) -- the left end's.
+__device__ __forceinline__ const uint2 *splice_sites(const uint32_t *__restrict__ spl, uint32_t n_genes, uint32_t g, bool by_acceptor, uint32_t &n_sites)
+{
+  const uint32_t s0 = spl[g], s1 = spl[g + 1u];
+  n_sites = s1 - s0;
+  const uint2 *const sites = reinterpret_cast<const uint2 *>(spl + splice_sites_word(n_genes));
+  return sites + s0 + (by_acceptor ? spl[n_genes] : 0u);
+}
 
 // one mate's bytes behind the -q mask, read in the record's orientation
 struct Mate {
@@ -169,12 +192,70 @@ __device__ __forceinline__ uint32_t extend_end(const Mate &M, const uint8_t *__r
   return best_e;
 }
 
+// Spliced ends (the header's step 3b) of one end.  Lane t < n_eval holds evaluated read base t as b (4 in every other lane: the caller's
+// load), which lies on record base x0 + t on the block's own diagonal.  `sites` are the gene's {key, other} pairs ascending in (key, other): {donor, acceptor} for the right end,
+// {acceptor, donor} for the left (LEFT); the candidates are those with key in [key_lo, key_hi] whose far block stays inside the record
+// (right: acceptor + far <= len_g with far = xe + h - donor = end - donor; left: donor - (acceptor - end) >= 0 with end = x0 - q0 of the
+// block, the record coordinate of read base 0 on its diagonal).  A lane's record base under a candidate: right, x < donor ? x : x + shift;
+// left, x >= acceptor ? x : x - shift.  One ballot and one popcount price a candidate; the lower bound of key_lo is one binary search, the
+// range ends at the first key beyond key_hi.  best's cost and index and the smallest cost of another shift (the null candidate's included)
+// are scalars.  Returns whether the end is placed, and then the site in (donor, acceptor).
+template <bool LEFT>
+__device__ __forceinline__ bool splice_end(const uint32_t b, const uint8_t *__restrict__ rec, int32_t len_g, const uint2 *__restrict__ sites, uint32_t n_sites,
+                                           int32_t key_lo, int32_t key_hi, int32_t end, int32_t x0, uint32_t n_eval, uint32_t max_cost, uint32_t min_gap,
+                                           uint32_t lane, int32_t &donor, int32_t &acceptor)
+{
+  uint32_t lo = 0, hi = n_sites;   // the first site with key >= key_lo
+  while (lo < hi) {
+    const uint32_t mid = lo + ((hi - lo) >> 1);
+    if ((int32_t)__builtin_amdgcn_readfirstlane(sites[mid].x) < key_lo) lo = mid + 1u;
+    else hi = mid;
+  }
+  // a lane outside the evaluated bases holds no base: it is "not a match" under every candidate, 64 - n_eval of them, taken off each cost
+  const int32_t x = x0 + (int32_t)lane;
+  const uint32_t idle = 64u - n_eval;
+  // best's cost and its index (c1 == NONE: no candidate yet); c2: the smallest cost over the null candidate and the sites of another shift
+  // than best's.  best's (donor, acceptor) are read again where they are compared: two scalar registers fewer across the loop
+  constexpr uint32_t NONE = 0xFFFFFFFFu;
+  uint32_t c1 = NONE, i1 = 0;
+  uint32_t c2 = (uint32_t)__popcll(__ballot(!(b < 4u && b == record_base(rec, len_g, x)))) - idle;
+  for (uint32_t i = lo; i < n_sites; ++i) {
+    const int32_t key = (int32_t)__builtin_amdgcn_readfirstlane(sites[i].x), other = (int32_t)__builtin_amdgcn_readfirstlane(sites[i].y);
+    if (key > key_hi) break;
+    const int32_t d = LEFT ? other : key, a = LEFT ? key : other, shift = a - d;
+    if (LEFT ? d - (a - end) < 0 : a + (end - d) > len_g) continue;
+    const int32_t xc = LEFT ? (x >= a ? x : x - shift) : (x < d ? x : x + shift);
+    const uint32_t c = (uint32_t)__popcll(__ballot(!(b < 4u && b == record_base(rec, len_g, xc)))) - idle;
+    const int32_t key1 = (int32_t)__builtin_amdgcn_readfirstlane(sites[i1].x), other1 = (int32_t)__builtin_amdgcn_readfirstlane(sites[i1].y);
+    const int32_t d1 = LEFT ? other1 : key1, a1 = LEFT ? key1 : other1;
+    // ties: the largest donor, then the largest acceptor
+    const bool wins = c < c1 || (c == c1 && (d > d1 || (d == d1 && a > a1)));
+    if (c1 != NONE && shift == a1 - d1) {
+      // the same placement up to where the bases between the two donors lie: the two do not compete
+      if (wins) { c1 = c; i1 = i; }
+    } else if (wins) {
+      c2 = c1 < c2 ? c1 : c2;   // (everything seen so far but the null candidate costs at least what the best did)
+      c1 = c; i1 = i;
+    } else {
+      c2 = c < c2 ? c : c2;
+    }
+  }
+  if (c1 == NONE || c1 > max_cost || (int32_t)c2 - (int32_t)c1 < (int32_t)min_gap) return false;
+  const int32_t key1 = (int32_t)__builtin_amdgcn_readfirstlane(sites[i1].x), other1 = (int32_t)__builtin_amdgcn_readfirstlane(sites[i1].y);
+  donor = LEFT ? other1 : key1;
+  acceptor = LEFT ? key1 : other1;
+  return true;
+}
+
 // The kernel.  EXT: the ends are extended (step 3a; P.ext_p >= 1, P.ext_b).  ACC: every base of a final block is added to the pileup state
 // where it is counted (P.counts, P.mates), and records are stored only where P.n_store says so.  The kernel takes its arguments by value
 // as a template parameter: behind a function that takes them by reference the same statements cost one scalar register more.
-// align_kernel<false, false, AlignParams> is the code and the arguments alignments mode always had; the other three take AlignParamsX,
-// whose fields a discarded branch never names.
-template <bool EXT, bool ACC, class Params>
+// align_kernel<false, false, false, AlignParams> is the code and the arguments alignments mode always had; the other three take AlignParamsX,
+// whose fields a discarded branch never names.  SPL: the ends are tried across the listed junctions (step 3b; AlignParamsS) -- a left
+// placement, tried where block 0 is about to be finished (behind its gap's closure), makes the new block the open block and the shortened
+// block 0 the pass's, whose own block goes back to the walk as a span; a right placement gives the last pass a block and runs that pass
+// again.  So a block is still finished in exactly one place and the loops carry no new value.
+template <bool EXT, bool ACC, bool SPL, class Params>
 __global__ __launch_bounds__(PL_THREADS) void align_kernel(const Params P)
 {
   // the batch will be assembled again and comes through here again; or it will be refused in wait (pileup_kernel's rule)
@@ -251,6 +332,87 @@ __global__ __launch_bounds__(PL_THREADS) void align_kernel(const Params P)
               if (!bl) continue;
             }
             if (al) {
+              if constexpr (SPL) {
+                // Step 3b stands behind step 3: the gap behind the open block is closed first (below it then finds R == 0).
+                if (bl) {
+                  const int32_t R = bq - (aq + al), G = bx - (ax + al);
+                  if (R >= 1 && R <= (int32_t)AL_MAX_CLOSE && G >= R) {
+                    const int32_t s = (int32_t)close_gap(M, rec, len_g, aq + al, ax + al, bx, (uint32_t)R, lane);
+                    al += s;
+                    bx -= R - s; bq -= R - s; bl += R - s;
+                  }
+                }
+                // Block 0 is about to be finished: its left end across a junction, where the mate has at most 3 blocks -- block 0, this
+                // pass's, and those the spans still ahead yield, which trimming alone decides: the walk is done ahead over them.  A placement
+                // makes the NEW block the open block and the shortened block 0 this pass's; the block this pass had goes back to the walk as
+                // span 0 (or, in the last pass, the pass comes again), so the new block is finished here, in the one place that finishes blocks
+                if (!n_blocks && aq >= (int32_t)(P.spl_prm & 255u) && aq <= (int32_t)SHK_SPLICE_MAX_OVERHANG) {
+                  uint32_t more = bl ? 1u : 0u;
+                  int32_t reach_w = reach, cursor_w = cursor;
+#pragma unroll
+                  for (uint32_t t = 0; t + 2u < SHK_MAX_SEGMENTS; ++t) {
+                    if (r + 1u + t < S.n) {
+                      const int32_t lo = S.lo[t] > reach_w ? S.lo[t] : reach_w;
+                      const int32_t hi = S.hi[t] < len_g ? S.hi[t] : len_g;
+                      reach_w = S.hi[t] > reach_w ? S.hi[t] : reach_w;
+                      const int32_t over = cursor_w - (lo - S.pos[t]);
+                      if (hi > lo && lo + (over > 0 ? over : 0) < hi) {
+                        cursor_w = hi - S.pos[t];
+                        ++more;
+                      }
+                    }
+                  }
+                  if (more <= 2u) {
+                    uint32_t n_sites;
+                    const uint2 *const sites = splice_sites(P.spl, P.n_genes, P.gene_ids[j], true, n_sites);
+                    const int32_t B = al - 1 < (int32_t)SHK_SPLICE_BACK ? al - 1 : (int32_t)SHK_SPLICE_BACK;
+                    int32_t d, a;
+                    const uint32_t b = (int32_t)lane < aq + B ? read_base(M, (int32_t)lane) : 4u;
+                    if (splice_end<true>(b, rec, len_g, sites, n_sites, ax - aq + 1, ax + B, ax - aq, ax - aq, (uint32_t)(aq + B), (P.spl_prm >> 8) & 255u,
+                                         P.spl_prm >> 16, lane, d, a)) {
+                      if (bl) {
+                        S.lo[3] = S.lo[2]; S.lo[2] = S.lo[1]; S.lo[1] = S.lo[0]; S.lo[0] = bx;
+                        S.hi[3] = S.hi[2]; S.hi[2] = S.hi[1]; S.hi[1] = S.hi[0]; S.hi[0] = bx + bl;
+                        S.pos[3] = S.pos[2]; S.pos[2] = S.pos[1]; S.pos[1] = S.pos[0]; S.pos[0] = bx - bq;
+                        reach = 0;       // (the span sets it again: it reached furthest, or it had yielded no block)
+                        cursor = bq;
+                      }
+                      const int32_t n = aq - ax + a;
+                      bx = a; bq = n; bl = al - (a - ax);
+                      ax = d - n; aq = 0; al = n;
+                      --r;
+                    }
+                  }
+                }
+                // the last pass: the right end across a junction, where the mate has at most 3 blocks with the open one (the pass comes
+                // again for the new block, whose h is 0)
+                if (!bl && n_blocks <= 2u) {
+                  const int32_t xe = ax + al, qe = aq + al, h = L - qe;
+                  if (h >= (int32_t)(P.spl_prm & 255u) && h <= (int32_t)SHK_SPLICE_MAX_OVERHANG) {
+                    uint32_t n_sites;
+                    const uint2 *const sites = splice_sites(P.spl, P.n_genes, P.gene_ids[j], false, n_sites);
+                    const int32_t B = al - 1 < (int32_t)SHK_SPLICE_BACK ? al - 1 : (int32_t)SHK_SPLICE_BACK;
+                    int32_t d, a;
+                    const uint32_t b = (int32_t)lane < B + h ? read_base(M, qe - B + (int32_t)lane) : 4u;
+                    if (splice_end<false>(b, rec, len_g, sites, n_sites, xe - B, xe + h - 1, xe + h, xe - B, (uint32_t)(B + h), (P.spl_prm >> 8) & 255u,
+                                          P.spl_prm >> 16, lane, d, a)) {
+                      al += d - xe;
+                      bx = a; bq = qe + (d - xe); bl = h - (d - xe);
+                      --r;
+                    }
+                  }
+                }
+                if constexpr (EXT) {
+                  // step 3a's left end, behind step 3b: block 0 as it is finished (a placed end has no clip left: H == 0)
+                  if (!n_blocks) {
+                    const int32_t H = aq < ax ? aq : ax;
+                    if (H > 0) {
+                      const int32_t e = (int32_t)extend_end(M, rec, len_g, aq - 1, ax - 1, -1, H, aq <= ax, P.ext_p, P.ext_b, lane);
+                      ax -= e; aq -= e; al += e;
+                    }
+                  }
+                }
+              }
               if constexpr (EXT) {
                 // the last pass: the open block is the last one, its right end is extended before it is counted
                 if (!bl) {
@@ -258,7 +420,7 @@ __global__ __launch_bounds__(PL_THREADS) void align_kernel(const Params P)
                   if (H > 0) al += (int32_t)extend_end(M, rec, len_g, aq + al, ax + al, 1, H, hq <= hx, P.ext_p, P.ext_b, lane);
                 }
               }
-              if (bl) {
+              if (!SPL && bl) {
                 const int32_t R = bq - (aq + al), G = bx - (ax + al);
                 if (R >= 1 && R <= (int32_t)AL_MAX_CLOSE && G >= R) {
                   const int32_t s = (int32_t)close_gap(M, rec, len_g, aq + al, ax + al, bx, (uint32_t)R, lane);
@@ -294,7 +456,7 @@ __global__ __launch_bounds__(PL_THREADS) void align_kernel(const Params P)
               word = w == 0u ? (uint32_t)ax : (w == 1u ? (uint32_t)aq : (w == 2u ? (uint32_t)al : word));
               ++n_blocks;
             }
-            if constexpr (EXT) {
+            if constexpr (EXT && !SPL) {
               // the first block becomes the open block: its left end is extended (closure moves only A's right and B's left)
               if (!n_blocks && bl) {
                 const int32_t H = bq < bx ? bq : bx;
@@ -335,7 +497,7 @@ int launch_alignments(Ctx *ctx, const Slot &s, const shk_segment *entries, uint6
     return SHK_ERR_STATE;
   }
   if (s.n == 0) return SHK_OK;
-  AlignParamsX P{};
+  AlignParamsS P{};
   P.gene_off = s.d_gene_off.p;
   P.gene_ids = s.d_gene_ids.p;
   P.counters = s.d_counters;
@@ -362,11 +524,25 @@ int launch_alignments(Ctx *ctx, const Slot &s, const shk_segment *entries, uint6
   const unsigned blocks = (unsigned)std::min<uint64_t>((s.n + PL_WAVES - 1) / PL_WAVES, 2048);
   P.n_waves = blocks * PL_WAVES;
   const bool ext = s.ext_p != 0;
+  // step 3b as submitted; the list is the context's (it changes only while no ticket is outstanding)
+  const bool spl = s.spl_h != 0;
+  if (spl && !ctx->d_splice) {
+    ctx->last_error = "spliced ends without a site list";
+    return SHK_ERR_STATE;
+  }
+  P.spl = ctx->d_splice;
+  P.spl_prm = s.spl_h | s.spl_cost << 8 | s.spl_gap << 16;   // (at most 48, 64, 64)
+  const AlignParamsX &PX = P;
   // (everything new off: the kernel and the arguments this mode always had)
-  if (!ext && !accumulate) hipLaunchKernelGGL((align_kernel<false, false, AlignParams>), dim3(blocks), dim3(PL_THREADS), 0, stream, static_cast<const AlignParams &>(P));
-  else if (ext && !accumulate) hipLaunchKernelGGL((align_kernel<true, false, AlignParamsX>), dim3(blocks), dim3(PL_THREADS), 0, stream, P);
-  else if (!ext) hipLaunchKernelGGL((align_kernel<false, true, AlignParamsX>), dim3(blocks), dim3(PL_THREADS), 0, stream, P);
-  else hipLaunchKernelGGL((align_kernel<true, true, AlignParamsX>), dim3(blocks), dim3(PL_THREADS), 0, stream, P);
+  if (spl) {
+    if (!ext && !accumulate) hipLaunchKernelGGL((align_kernel<false, false, true, AlignParamsS>), dim3(blocks), dim3(PL_THREADS), 0, stream, P);
+    else if (ext && !accumulate) hipLaunchKernelGGL((align_kernel<true, false, true, AlignParamsS>), dim3(blocks), dim3(PL_THREADS), 0, stream, P);
+    else if (!ext) hipLaunchKernelGGL((align_kernel<false, true, true, AlignParamsS>), dim3(blocks), dim3(PL_THREADS), 0, stream, P);
+    else hipLaunchKernelGGL((align_kernel<true, true, true, AlignParamsS>), dim3(blocks), dim3(PL_THREADS), 0, stream, P);
+  } else if (!ext && !accumulate) hipLaunchKernelGGL((align_kernel<false, false, false, AlignParams>), dim3(blocks), dim3(PL_THREADS), 0, stream, static_cast<const AlignParams &>(P));
+  else if (ext && !accumulate) hipLaunchKernelGGL((align_kernel<true, false, false, AlignParamsX>), dim3(blocks), dim3(PL_THREADS), 0, stream, PX);
+  else if (!ext) hipLaunchKernelGGL((align_kernel<false, true, false, AlignParamsX>), dim3(blocks), dim3(PL_THREADS), 0, stream, PX);
+  else hipLaunchKernelGGL((align_kernel<true, true, false, AlignParamsX>), dim3(blocks), dim3(PL_THREADS), 0, stream, PX);
   const hipError_t e = hipGetLastError();
   return e == hipSuccess ? SHK_OK : set_hip_error(ctx, e, "align_kernel");
 }

@@ -32,6 +32,7 @@
 #include <string>
 #include <thread>
 #include <tuple>
+#include <unordered_map>
 #include <utility>
 #include <vector>
 
@@ -147,6 +148,13 @@ const char *USAGE_MESSAGE =
     "          --extend-bonus N              its bonus for reaching the mate's end (0 .. 15, default:5)\n"
     "          --pileup-aligned              --pileup / --variants count the bases of the alignment --sam shows (trimmed, gaps closed,\n"
     "                                        ends extended under --extend-ends) instead of the bases under the voting windows\n"
+    "          --splice-junctions FILE       --sam and --pileup-aligned: try a mate's clipped end of a few bases across the introns FILE lists\n"
+    "                                        (what --junctions writes: <gene> <donor> <acceptor> <intron> [<mates>]; the intron is record\n"
+    "                                        bases [donor, donor + intron)) and place it where that is good and clearly the best\n"
+    "          --splice-min-mates N          FILE's lines with fewer mates are left out (default:1)\n"
+    "          --splice-min-overhang N       the shortest clipped end that is tried (1 .. 48, default:3)\n"
+    "          --splice-max-cost N           read bases of the evaluated end that may disagree with the record (0 .. 64, default:2)\n"
+    "          --splice-min-gap N            by how many such bases every other placement must be worse (0 .. 64, default:2)\n"
     "          --kmer-table                  one gene, k <= 17: also build the exact table keyed by the k-mer itself (no XXH64 per probe; the\n"
     "                                        same output).  Costs tens of milliseconds when the index is built and pays on the GPU\n"
     "                                        alone, so it is off here, where the host and the link bound a run\n"
@@ -203,6 +211,9 @@ struct Options {
   bool sam_rescue = false;                // (--sam-rescue; --rescue-max-cost, --rescue-min-gap)
   unsigned rescue_max_cost = 8, rescue_min_gap = 4;
   bool rescue_sub_flag_given = false;
+  std::string splice_path;                // (--splice-junctions; --splice-min-mates, --splice-min-overhang, --splice-max-cost, --splice-min-gap)
+  unsigned splice_min_mates = 1, splice_min_overhang = 3, splice_max_cost = 2, splice_min_gap = 2;
+  bool splice_sub_flag_given = false;
   std::string fragments_path;
   FILE *fragments_file = nullptr;  // (--fragments, likewise; written once, after the last batch)
   unsigned fragments_max = 1000, fragments_bins = 1024, fragments_min_intron = 0;   // (0: --sam-min-intron's value)
@@ -424,6 +435,30 @@ const OptionRow OPTION_TABLE[] = {
        o.rescue_sub_flag_given = true;
        if (o.rescue_min_gap > 255) reject(USAGE_MESSAGE, "shark: --rescue-min-gap must be 0 to 255.");
      }},
+    {1039, "splice-junctions", true, [](Options &o, const char *v) { o.splice_path = value_of<std::string>(v); }},
+    {1040, "splice-min-mates", true,
+     [](Options &o, const char *v) {
+       o.splice_min_mates = value_of<unsigned>(v);
+       o.splice_sub_flag_given = true;
+     }},
+    {1041, "splice-min-overhang", true,
+     [](Options &o, const char *v) {
+       o.splice_min_overhang = value_of<unsigned>(v);
+       o.splice_sub_flag_given = true;
+       if (o.splice_min_overhang < 1 || o.splice_min_overhang > SHK_SPLICE_MAX_OVERHANG) reject(USAGE_MESSAGE, "shark: --splice-min-overhang must be 1 to 48.");
+     }},
+    {1042, "splice-max-cost", true,
+     [](Options &o, const char *v) {
+       o.splice_max_cost = value_of<unsigned>(v);
+       o.splice_sub_flag_given = true;
+       if (o.splice_max_cost > 64) reject(USAGE_MESSAGE, "shark: --splice-max-cost must be 0 to 64.");
+     }},
+    {1043, "splice-min-gap", true,
+     [](Options &o, const char *v) {
+       o.splice_min_gap = value_of<unsigned>(v);
+       o.splice_sub_flag_given = true;
+       if (o.splice_min_gap > 64) reject(USAGE_MESSAGE, "shark: --splice-min-gap must be 0 to 64.");
+     }},
 };
 
 // Reads per device batch when --batch does not say.  A batch costs the device path 0.5-2 ms of launches, copies and bookkeeping
@@ -506,6 +541,9 @@ Options parse_arguments(int argc, char **argv)
   if (opt.sam_rescue && opt.fragments_min_intron < 1)
     reject(USAGE_MESSAGE, "shark: --sam-rescue needs an intron length of at least 1 (--sam-min-intron, --fragments-min-intron).");
   if (opt.pileup_aligned && opt.pileup_path.empty() && opt.variants_path.empty()) reject(USAGE_MESSAGE, "shark: --pileup-aligned needs --pileup FILE or --variants FILE.");
+  if (opt.splice_sub_flag_given && opt.splice_path.empty())
+    reject(USAGE_MESSAGE, "shark: --splice-min-mates, --splice-min-overhang, --splice-max-cost and --splice-min-gap need --splice-junctions FILE.");
+  if (!opt.splice_path.empty() && opt.sam_path.empty() && !opt.pileup_aligned) reject(USAGE_MESSAGE, "shark: --splice-junctions needs --sam FILE or --pileup-aligned.");
   if (opt.extend_sub_flag_given && !opt.extend_ends) reject(USAGE_MESSAGE, "shark: --extend-penalty and --extend-bonus need --extend-ends.");
   if (opt.extend_ends && opt.sam_path.empty() && !opt.pileup_aligned) reject(USAGE_MESSAGE, "shark: --extend-ends needs --sam FILE or --pileup-aligned.");
   if (opt.out1_path.empty()) opt.out1_path = "sharked_sample.1";
@@ -2178,6 +2216,44 @@ class ParallelFeed {
   std::thread gz_joiner_;
 };
 
+// ---- --splice-junctions: the file's lines as the sorted, merged site list of shk_splice_sites_set.  A line `<gene> <donor> <acceptor> <intron>
+// [<mates>]` becomes (gene, donor, donor + intron): the intron interval of the alignment blocks (the left block keeps the microhomology), not
+// the file's acceptor column, which is the right span's lo and includes the overlap.  Returns the message of the line that is malformed, names
+// an unknown gene or lies outside its record (empty: none). ----
+std::string read_splice_sites(const Options &opt, const std::vector<std::string> &legend_ID, const std::vector<uint64_t> &gene_start,
+                              std::vector<shk_splice_site> &sites)
+{
+  std::ifstream in(opt.splice_path);
+  if (!in) return "shark: cannot open the --splice-junctions file " + opt.splice_path;
+  std::unordered_map<std::string, uint32_t> index;
+  for (size_t g = legend_ID.size(); g-- > 0;) index[legend_ID[g]] = (uint32_t)g;   // (a name given twice: the first record, as --depth's readers take it)
+  std::string line;
+  for (uint64_t n = 1; std::getline(in, line); ++n) {
+    const std::string where = "shark: --splice-junctions " + opt.splice_path + " line " + std::to_string(n) + ": ";
+    std::istringstream fields(line);
+    std::vector<std::string> f;
+    for (std::string w; fields >> w;) f.push_back(w);
+    if (f.empty()) continue;
+    uint64_t v[4] = {0, 0, 0, 1};
+    bool ok = f.size() == 4 || f.size() == 5;
+    for (size_t i = 1; ok && i < f.size(); ++i) {
+      ok = !f[i].empty() && f[i].size() <= 10 && f[i].find_first_not_of("0123456789") == std::string::npos;
+      if (ok) v[i - 1] = std::stoull(f[i]);
+    }
+    if (!ok) return where + "malformed (<gene> <donor> <acceptor> <intron> [<mates>])";
+    const auto it = index.find(f[0]);
+    if (it == index.end()) return where + "unknown gene " + f[0];
+    const uint32_t g = it->second;
+    const uint64_t len_g = (size_t)g + 1 < gene_start.size() ? gene_start[g + 1] - gene_start[g] : 0;
+    if (!(v[0] >= 1 && v[2] >= 1 && v[0] + v[2] + 1 <= len_g)) return where + "the site lies outside its record";
+    if (v[3] >= opt.splice_min_mates) sites.push_back({g, (uint32_t)v[0], (uint32_t)(v[0] + v[2])});
+  }
+  const auto key = [](const shk_splice_site &t) { return std::make_tuple(t.gene, t.donor, t.acceptor); };
+  std::sort(sites.begin(), sites.end(), [&](const shk_splice_site &a, const shk_splice_site &b) { return key(a) < key(b); });
+  sites.erase(std::unique(sites.begin(), sites.end(), [&](const shk_splice_site &a, const shk_splice_site &b) { return key(a) == key(b); }), sites.end());
+  return std::string();
+}
+
 // ---- 1+2. reference: legend in file order (FastaSplitter.hpp:48) + index -- while the readers already parse the sample.
 // Returns the message of the failure that ended it (empty: none). ----
 std::string build_index(const Options &opt, GpuStart &gpu, std::vector<std::string> &legend_ID)
@@ -2414,6 +2490,30 @@ int run_sample(const Options &opt, GpuStart &gpu, BatchPool &pool, std::vector<s
         std::cerr << "shark: end extension could not be switched on: " << shk_strerror(rc) << " " << shk_last_error(ctx) << std::endl;
         return EXIT_FAILURE;
       }
+  // (--splice-junctions: every worker gets the same list and the same parameters, for --sam and for --pileup-aligned; an empty list leaves the step off)
+  if (!opt.splice_path.empty()) {
+    std::vector<uint64_t> gene_start(legend_ID.size() + 1, 0);
+    std::vector<shk_splice_site> sites;
+    std::string error;
+    if (const int rc = gpu.ctxs.empty() ? SHK_ERR_STATE : shk_depth_layout(gpu.ctxs[0], gene_start.data(), (uint32_t)legend_ID.size()))
+      error = std::string("shark: --splice-junctions is not available for this reference: ") + shk_strerror(rc);
+    else error = read_splice_sites(opt, legend_ID, gene_start, sites);
+    if (!error.empty()) {
+      feed.stop();
+      std::cerr << error << std::endl;
+      return EXIT_FAILURE;
+    }
+    if (!sites.empty())
+      for (shk_ctx *ctx : gpu.ctxs) {
+        int rc = shk_splice_sites_set(ctx, sites.data(), sites.size());
+        if (!rc) rc = shk_alignments_splice(ctx, opt.splice_min_overhang, opt.splice_max_cost, opt.splice_min_gap);
+        if (rc) {
+          feed.stop();
+          std::cerr << "shark: spliced ends could not be switched on: " << shk_strerror(rc) << " " << shk_last_error(ctx) << std::endl;
+          return EXIT_FAILURE;
+        }
+      }
+  }
   // (--sam: every worker's batches carry their mates' alignments; --fragments: the same records are what pairs mode reads)
   if (opt.sam_file || opt.fragments_file)
     for (shk_ctx *ctx : gpu.ctxs)

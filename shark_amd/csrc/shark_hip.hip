@@ -13,6 +13,7 @@
 #include <unistd.h>
 #include <cstring>
 #include <new>
+#include <tuple>
 
 #include "device_scan.hpp"
 #include "shark_internal.hpp"
@@ -392,6 +393,9 @@ static int enqueue_classify(Ctx *ctx, Slot &s, const shk_batch *b, uint32_t max_
   s.align = ctx->align;
   s.ext_p = ctx->ext_p;
   s.ext_b = ctx->ext_b;
+  s.spl_h = ctx->spl_h;
+  s.spl_cost = ctx->spl_cost;
+  s.spl_gap = ctx->spl_gap;
   s.pairs = s.align ? ctx->pairs_bins : 0u;      // (pair records only behind alignment records)
   s.pairs_min_intron = ctx->pairs_min_intron;
   s.pairs_max_frag = ctx->pairs_max_frag;
@@ -859,6 +863,7 @@ void shk_destroy(shk_ctx *ctx)
   hipFree(ctx->d_junc_tab); hipFree(ctx->d_junc_dropped);
   hipFree(ctx->d_pileup); hipFree(ctx->d_pileup_mates);
   hipFree(ctx->d_frag);
+  hipFree(ctx->d_splice);
   hipFree(ctx->d_var_waves); hipFree(ctx->d_var_temp); hipFree(ctx->d_var_out); hipFree(ctx->d_var_summary);
   dist_release(ctx);
   for (auto e : ctx->ev_start) (void)hipEventDestroy(e);
@@ -1719,6 +1724,92 @@ int shk_alignments_extend(shk_ctx *ctx, uint32_t mismatch_penalty, uint32_t end_
   if (tickets_outstanding(ctx)) { ctx->last_error = "shk_alignments_extend: tickets are outstanding (wait for them first)"; return SHK_ERR_STATE; }
   ctx->ext_p = mismatch_penalty;
   ctx->ext_b = end_bonus;
+  return SHK_OK;
+}
+
+// ---- spliced ends (align.hip's step 3b): the context's site list and the step's parameters ----
+static void splice_sites_drop(shk_ctx *ctx)
+{
+  (void)hipFree(ctx->d_splice);
+  ctx->d_splice = nullptr;
+  ctx->splice_sites.clear();
+  ctx->splice_sites.shrink_to_fit();
+}
+
+int shk_splice_sites_set(shk_ctx *ctx, const shk_splice_site *sites, uint64_t n)
+{
+  if (!ctx || (!sites && n)) return SHK_ERR_ARG;
+  if (const int rc = check_mode_index(ctx, "shk_splice_sites_set", NEED_GENE_START)) return rc;
+  if (tickets_outstanding(ctx)) { ctx->last_error = "shk_splice_sites_set: tickets are outstanding (wait for them first)"; return SHK_ERR_STATE; }
+  if (n >= (1ull << 31)) { ctx->last_error = "shk_splice_sites_set: fewer than 2^31 sites"; return SHK_ERR_ARG; }
+  const uint64_t n_genes = ctx->gene_start.size() - 1;
+  for (uint64_t i = 0; i < n; ++i) {
+    const shk_splice_site &t = sites[i];
+    const uint64_t len_g = t.gene < n_genes ? ctx->gene_start[t.gene + 1] - ctx->gene_start[t.gene] : 0;
+    const bool inside = t.gene < n_genes && t.donor >= 1 && t.donor < t.acceptor && (uint64_t)t.acceptor + 1 <= len_g;
+    const bool ascends = i == 0 || std::make_tuple(sites[i - 1].gene, sites[i - 1].donor, sites[i - 1].acceptor) < std::make_tuple(t.gene, t.donor, t.acceptor);
+    if (!inside || !ascends) {
+      ctx->last_error = "shk_splice_sites_set: site " + std::to_string(i) + (inside ? " does not ascend in (gene, donor, acceptor)" : " lies outside its record (gene < n_records, 1 <= donor < acceptor <= len - 1)");
+      return SHK_ERR_ARG;
+    }
+  }
+  SHK_HIP(ctx, hipSetDevice(ctx->prm.device));
+  SHK_HIP(ctx, hipStreamSynchronize(ctx->stream));   // (the list a batch read may go)
+  if (n == 0) {
+    splice_sites_drop(ctx);
+    ctx->spl_h = 0;
+    return SHK_OK;
+  }
+  std::vector<uint32_t> off;
+  std::vector<uint2> by_donor, by_acceptor;
+  std::vector<shk_splice_site> own;
+  try {
+    off.assign(n_genes + 1, 0);
+    by_donor.resize(n);
+    by_acceptor.resize(n);
+    own.assign(sites, sites + n);
+    for (uint64_t i = 0; i < n; ++i) {
+      ++off[own[i].gene + 1];
+      by_donor[i] = by_acceptor[i] = make_uint2(own[i].donor, own[i].acceptor);
+    }
+    for (uint64_t g = 0; g < n_genes; ++g) off[g + 1] += off[g];
+    for (uint64_t g = 0; g < n_genes; ++g) {
+      std::sort(by_acceptor.begin() + off[g], by_acceptor.begin() + off[g + 1], [](const uint2 &a, const uint2 &b) { return a.y != b.y ? a.y < b.y : a.x < b.x; });
+    }
+    for (uint2 &t : by_acceptor) std::swap(t.x, t.y);   // {acceptor, donor}
+  } catch (...) {
+    return SHK_ERR_NOMEM;
+  }
+  // the new list is whole on the device before the earlier one goes: a call that fails leaves the context as it was
+  const size_t word = shk::splice_sites_word((uint32_t)n_genes);
+  uint32_t *d_new = nullptr;
+  SHK_HIP(ctx, hipMalloc((void **)&d_new, (word + 4 * n) * sizeof(uint32_t)));
+  hipError_t e = hipMemcpyAsync(d_new, off.data(), off.size() * sizeof(uint32_t), hipMemcpyHostToDevice, ctx->stream);
+  if (e == hipSuccess) e = hipMemcpyAsync(d_new + word, by_donor.data(), n * sizeof(uint2), hipMemcpyHostToDevice, ctx->stream);
+  if (e == hipSuccess) e = hipMemcpyAsync(d_new + word + 2 * n, by_acceptor.data(), n * sizeof(uint2), hipMemcpyHostToDevice, ctx->stream);
+  if (e == hipSuccess) e = hipStreamSynchronize(ctx->stream);   // (the vectors go with this call)
+  if (e != hipSuccess) {
+    (void)hipFree(d_new);
+    return shk::set_hip_error(ctx, e, "shk_splice_sites_set: copying the list");
+  }
+  splice_sites_drop(ctx);
+  ctx->splice_sites.swap(own);
+  ctx->d_splice = d_new;
+  return SHK_OK;
+}
+
+int shk_alignments_splice(shk_ctx *ctx, uint32_t min_overhang, uint32_t max_cost, uint32_t min_gap)
+{
+  if (!ctx) return SHK_ERR_ARG;
+  if (min_overhang > SHK_SPLICE_MAX_OVERHANG || max_cost > 64 || min_gap > 64) {
+    ctx->last_error = "shk_alignments_splice: min_overhang is at most SHK_SPLICE_MAX_OVERHANG, max_cost and min_gap at most 64";
+    return SHK_ERR_ARG;
+  }
+  if (tickets_outstanding(ctx)) { ctx->last_error = "shk_alignments_splice: tickets are outstanding (wait for them first)"; return SHK_ERR_STATE; }
+  if (min_overhang && !ctx->d_splice) { ctx->last_error = "shk_alignments_splice: no site list (shk_splice_sites_set first)"; return SHK_ERR_STATE; }
+  ctx->spl_h = min_overhang;
+  ctx->spl_cost = max_cost;
+  ctx->spl_gap = min_gap;
   return SHK_OK;
 }
 

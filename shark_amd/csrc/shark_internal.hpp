@@ -468,6 +468,8 @@ struct Slot {
   // submitted with this floor (0: not) -- align_kernel's accumulating instantiation adds the batch to Ctx::d_pileup, pileup_kernel does not run
   uint32_t ext_p = 0, ext_b = 0;
   uint32_t pileup_al = 0;
+  // spliced ends (shk_alignments_splice) as submitted: min_overhang (0: off), max_cost, min_gap; the site list is the context's
+  uint32_t spl_h = 0, spl_cost = 0, spl_gap = 0;
   // pairs mode (pairs.hip): submitted with this n_bins (0: not; only with `align`): pair_kernel ran behind the storing align_kernel, one
   // 32-byte record per association (rec_pairs, allocated with the first such batch for as many associations as d_gene_ids holds);
   // pairs_count: the batch is added to Ctx::d_frag (not a shk_count_work batch)
@@ -482,6 +484,9 @@ struct Slot {
   DevArray<uint2> d_rescue_queue;
 };
 
+
+// Ctx::d_splice: the word at which the site arrays start behind the n_genes + 1 offsets (even: the pairs are 8-byte aligned)
+__host__ __device__ inline uint32_t splice_sites_word(uint32_t n_genes) { return (n_genes + 2u) & ~1u; }
 
 // one entry of the junction table (spliced.hip): key = (gene_start[g] + donor) << 32 | (gene_start[g] + acceptor)
 struct JunctionEntry {
@@ -678,6 +683,11 @@ struct Ctx {
   // alignments mode (shk_alignments_enable; align.hip), as segments mode: the floor for the batches submitted from now on (0: off)
   uint32_t align = 0;
   uint32_t ext_p = 0, ext_b = 0;               // shk_alignments_extend: mismatch penalty (0: off) and end bonus for the batches submitted from now on
+  // spliced ends (shk_splice_sites_set, shk_alignments_splice): the list as it was given (sorted by (gene, donor, acceptor)), on the device a
+  // per-gene offset array and the sites as {donor, acceptor} in that order and as {acceptor, donor} in (acceptor, donor) order per gene
+  std::vector<shk_splice_site> splice_sites;
+  uint32_t *d_splice = nullptr;                // one allocation: n_genes + 1 offsets, then from word splice_sites_word(n_genes) on the two site arrays
+  uint32_t spl_h = 0, spl_cost = 0, spl_gap = 0;   // shk_alignments_splice: min_overhang (0: off), max_cost, min_gap for the batches submitted from now on
   // pairs mode (shk_pairs_enable; pairs.hip): per-batch records as alignments mode's, and the fragments state, which like the depth state
   // outlives the mode's being switched off
   uint32_t pairs_bins = 0;                     // n_bins for the batches submitted from now on (0: off)
