@@ -50,11 +50,11 @@ def _kind(b, r):
     return "=" if b == r else "X"
 
 
-def mate_alignment(mate, rows, k, s_min, record, stats=None):
+def mate_alignment(mate, rows, k, s_min, record, stats=None, gaps=None):
     """(n_blocks, strand, matches, mismatches, [(x, q, len)]) of one masked mate (bytes) with its segment rows (strand, pos, support,
     first, last; rank order) against its gene's record (bytes).  stats: a dict whose 'trimmed', 'closed', 'open_insertion',
     'open_wide' and 'dropped' are counted up (blocks that lost bases to trimming, gaps closed, gaps left open with G < R, with
-    R > 64, pieces that yielded no block)"""
+    R > 64, pieces that yielded no block); gaps: a list that receives (R, G, closed) of every gap with R >= 1"""
     L, len_g = len(mate), len(record)
     spans = capi.kept_spans(rows, L, k, s_min)
     if not spans:
@@ -95,6 +95,8 @@ def mate_alignment(mate, rows, k, s_min, record, stats=None):
         assert R >= 0 and G >= 0
         if R == 0:
             continue
+        if gaps is not None:
+            gaps.append((R, G, not (R > MAX_CLOSE or G < R)))
         if R > MAX_CLOSE or G < R:
             if stats is not None:
                 key = "open_wide" if R > MAX_CLOSE else "open_insertion"

@@ -22,7 +22,7 @@ import numpy as np
 
 from shark_amd import capi
 from tests.align_model import _kind, mate_alignment, oriented_codes, record_codes, to_record
-from tests.extend_model import check_params, extend_alignment
+from tests.extend_model import best_extension, check_params, extend_alignment
 from tests.placement_model import masked_mates
 
 MAX_OVERHANG = 48
@@ -177,19 +177,21 @@ def splice_alignment(al, mate, record, sites, params, stats=None, candidates=ran
     return (len(blocks), strand, matches, mismatches, blocks)
 
 
-def mate_alignment_spliced(mate, rows, k, s_min, record, sites, params, P, B, stats=None, ext_stats=None, candidates=ranged_candidates):
-    """steps 1 .. 3, 3b, 3a, 4 of one mate; params = (min_overhang, max_cost, min_gap), min_overhang == 0: step 3b is off"""
+def mate_alignment_spliced(mate, rows, k, s_min, record, sites, params, P, B, stats=None, ext_stats=None, candidates=ranged_candidates,
+                           scorer=best_extension, align_stats=None, gaps=None):
+    """steps 1 .. 3, 3b, 3a, 4 of one mate; params = (min_overhang, max_cost, min_gap), min_overhang == 0: step 3b is off.  stats are
+    step 3b's counters, ext_stats step 3a's, align_stats and gaps align_model.mate_alignment's"""
     check_params(P, B)
     check_splice(*params)
-    al = mate_alignment(mate, rows, k, s_min, record)
+    al = mate_alignment(mate, rows, k, s_min, record, align_stats, gaps)
     al = splice_alignment(al, mate, record, sites, params, stats, candidates)
-    return al if P == 0 else extend_alignment(al, mate, record, P, B, ext_stats)
+    return al if P == 0 else extend_alignment(al, mate, record, P, B, ext_stats, scorer)
 
 
 def expected_alignments_spliced(model, batch, gene_off, gene_ids, rows, s_min, sites, params, P=0, B=0, min_quality=0, stats=None,
-                                candidates=ranged_candidates):
+                                candidates=ranged_candidates, scorer=best_extension, ext_stats=None, align_stats=None, gaps=None):
     """extend_model.expected_alignments_extended with step 3b in front of 3a: (n_assoc, 2) records of capi.ALIGNMENT_DTYPE.
-    sites: a checked list of (gene, donor, acceptor)"""
+    sites: a checked list of (gene, donor, acceptor); ext_stats, align_stats, gaps: mate_alignment_spliced's"""
     if s_min < 1:
         raise ValueError("min_support must be at least 1")
     per_gene = sites_by_gene(sites)
@@ -202,7 +204,7 @@ def expected_alignments_spliced(model, batch, gene_off, gene_ids, rows, s_min, s
             for t, mate in enumerate(pair):
                 if mate is not None:
                     out[j, t] = to_record(mate_alignment_spliced(mate, rows[j, t], model.k, s_min, record, per_gene.get(g, []), params, P, B,
-                                                                 stats, None, candidates))
+                                                                 stats, ext_stats, candidates, scorer, align_stats, gaps))
     return out
 
 
