@@ -73,11 +73,11 @@ struct AlignParamsX : AlignParams {
 // what the splicing instantiations take on top of those (step 3b; shk_splice_sites_set's three arrays and shk_alignments_splice's values)
 // One pointer and one word: where the compiler keeps a kernel argument in registers across the loops, these cost three, not ten.
 struct AlignParamsS : AlignParamsX {
-  const uint32_t *spl;             // Ctx::d_splice: the offsets, the sites by donor, the sites by acceptor (splice_layout)
+  const uint32_t *spl;             // SpliceSites::d: the offsets, the sites by donor, the sites by acceptor (splice_layout)
   uint32_t spl_prm;                // min_overhang 1 .. SHK_SPLICE_MAX_OVERHANG | max_cost << 8 | min_gap << 16
 };
 
-// The gene's sites in Ctx::d_splice's layout: [g], [g + 1] of the n_genes + 1 offsets, behind them (at an even word) n = off[n_genes] pairs
+// The gene's sites in SpliceSites::d's layout: [g], [g + 1] of the n_genes + 1 offsets, behind them (at an even word) n = off[n_genes] pairs
 // {donor, acceptor} ascending per gene in (donor, acceptor) -- the right end's -- and n pairs {acceptor, donor} ascending per gene in
 // (acceptor, donor) -- the left end's.
 __device__ __forceinline__ const uint2 *splice_sites(const uint32_t *__restrict__ spl, uint32_t n_genes, uint32_t g, bool by_acceptor, uint32_t &n_sites)
@@ -492,7 +492,7 @@ int launch_alignments(Ctx *ctx, const Slot &s, const shk_segment *entries, uint6
     ctx->last_error = "alignments mode without its state";
     return SHK_ERR_STATE;
   }
-  if (accumulate && (!s.pileup_al || !ctx->d_pileup || !ctx->d_pileup_mates || (store && s.align != s.pileup_al))) {
+  if (accumulate && (!s.pileup_al || !ctx->pileup.counts.p || !ctx->pileup.mates.p || (store && s.align != s.pileup_al))) {
     ctx->last_error = "aligned pileup without its state";
     return SHK_ERR_STATE;
   }
@@ -518,19 +518,19 @@ int launch_alignments(Ctx *ctx, const Slot &s, const shk_segment *entries, uint6
   P.n_store[1] = !store ? 0u : AL_WORDS;
   P.ext_p = s.ext_p;
   P.ext_b = s.ext_b;
-  P.counts = accumulate ? ctx->d_pileup : nullptr;
-  P.mates = accumulate ? ctx->d_pileup_mates : nullptr;
+  P.counts = accumulate ? ctx->pileup.counts.p : nullptr;
+  P.mates = accumulate ? ctx->pileup.mates.p : nullptr;
   // one wave per read up to 2 048 workgroups, persistent beyond (launch_segments' bound)
   const unsigned blocks = (unsigned)std::min<uint64_t>((s.n + PL_WAVES - 1) / PL_WAVES, 2048);
   P.n_waves = blocks * PL_WAVES;
   const bool ext = s.ext_p != 0;
   // step 3b as submitted; the list is the context's (it changes only while no ticket is outstanding)
   const bool spl = s.spl_h != 0;
-  if (spl && !ctx->d_splice) {
+  if (spl && !ctx->splice.d.p) {
     ctx->last_error = "spliced ends without a site list";
     return SHK_ERR_STATE;
   }
-  P.spl = ctx->d_splice;
+  P.spl = ctx->splice.d.p;
   P.spl_prm = s.spl_h | s.spl_cost << 8 | s.spl_gap << 16;   // (at most 48, 64, 64)
   const AlignParamsX &PX = P;
   // (everything new off: the kernel and the arguments this mode always had)

@@ -136,7 +136,7 @@ __global__ __launch_bounds__(DP_THREADS) void depth_summary_kernel(const uint32_
 int launch_depth_accumulate(Ctx *ctx, const Slot &s, bool skip_if_long, hipStream_t stream)
 {
   const DeviceIndex &ix = ctx->idx;
-  if (!ix.gene_start || !ctx->d_depth_diff || !ctx->d_depth_mates || !s.rec_place.d.p) { ctx->last_error = "depth mode without its state"; return SHK_ERR_STATE; }
+  if (!ix.gene_start || !ctx->depth.counts.p || !ctx->depth.mates.p || !s.rec_place.d.p) { ctx->last_error = "depth mode without its state"; return SHK_ERR_STATE; }
   if (s.n == 0) return SHK_OK;
   DepthParams P{};
   P.gene_off = s.d_gene_off.p;
@@ -151,11 +151,11 @@ int launch_depth_accumulate(Ctx *ctx, const Slot &s, bool skip_if_long, hipStrea
   P.n_genes = (uint32_t)(ctx->gene_start.size() - 1);
   P.min_support = s.depth;
   P.skip_if_long = skip_if_long ? 1u : 0u;
-  P.diff = ctx->d_depth_diff;
-  P.mates = ctx->d_depth_mates;
+  P.diff = ctx->depth.counts.p;
+  P.mates = ctx->depth.mates.p;
   // one thread per read up to 2 048 workgroups (launch_placement's bound), persistent beyond
   const uint64_t want = (s.n + DP_THREADS - 1) / DP_THREADS;
-  ctx->depth_scan_current = false;
+  ctx->depth.scan_current = false;
   hipLaunchKernelGGL(depth_accumulate_kernel, dim3((unsigned)std::min<uint64_t>(want, 2048)), dim3(DP_THREADS), 0, stream, P);
   const hipError_t e = hipGetLastError();
   return e == hipSuccess ? SHK_OK : set_hip_error(ctx, e, "depth_accumulate_kernel");
@@ -165,12 +165,14 @@ int depth_scan(Ctx *ctx)
 {
   const uint64_t entries = ctx->gene_start.back() + 1;
   // (no batch has added to the state since the last scan: a caller that reads gene after gene pays for one scan)
-  if (ctx->depth_scan_current) return SHK_OK;
-  if (!ctx->d_depth_scan) SHK_HIP(ctx, hipMalloc((void **)&ctx->d_depth_scan, entries * sizeof(uint32_t)));
-  if (!ctx->d_depth_scan_temp) SHK_HIP(ctx, hipMalloc((void **)&ctx->d_depth_scan_temp, scan_temp_words(entries) * sizeof(uint64_t)));
-  (void)exclusive_scan_u32(ctx->d_depth_diff, ctx->d_depth_scan, entries, ctx->d_depth_scan_temp, ctx->stream);
+  DepthState &D = ctx->depth;
+  if (D.scan_current) return SHK_OK;
+  int rc;
+  if (!D.scan.p && (rc = D.scan.alloc_exact(ctx, entries))) return rc;
+  if (!D.scan_temp.p && (rc = D.scan_temp.alloc_exact(ctx, scan_temp_words(entries)))) return rc;
+  (void)exclusive_scan_u32(D.counts.p, D.scan.p, entries, D.scan_temp.p, ctx->stream);
   SHK_HIP(ctx, hipGetLastError());
-  ctx->depth_scan_current = true;
+  D.scan_current = true;
   return SHK_OK;
 }
 
@@ -178,9 +180,11 @@ int launch_depth_summary(Ctx *ctx)
 {
   const uint32_t n_genes = (uint32_t)(ctx->gene_start.size() - 1);
   if (n_genes == 0) return SHK_OK;
-  if (!ctx->d_depth_summary) SHK_HIP(ctx, hipMalloc((void **)&ctx->d_depth_summary, (size_t)n_genes * sizeof(shk_gene_depth)));
-  hipLaunchKernelGGL(depth_summary_kernel, dim3(std::min<uint32_t>(n_genes, 2048u)), dim3(DP_THREADS), 0, ctx->stream, (const uint32_t *)(ctx->d_depth_scan + 1),
-                     (const uint64_t *)ctx->idx.gene_start, n_genes, ctx->d_depth_summary);
+  DepthState &D = ctx->depth;
+  if (!D.summary.p)
+    if (const int rc = D.summary.alloc_exact(ctx, n_genes)) return rc;
+  hipLaunchKernelGGL(depth_summary_kernel, dim3(std::min<uint32_t>(n_genes, 2048u)), dim3(DP_THREADS), 0, ctx->stream, (const uint32_t *)(D.scan.p + 1),
+                     (const uint64_t *)ctx->idx.gene_start, n_genes, D.summary.p);
   SHK_HIP(ctx, hipGetLastError());
   return SHK_OK;
 }

@@ -183,7 +183,7 @@ __global__ __launch_bounds__(PR_THREADS) void pair_kernel(const PairParams P)
 
 int launch_pairs(Ctx *ctx, const Slot &s, uint64_t cap_assoc, bool skip_if_long, hipStream_t stream)
 {
-  if (!s.pairs || !s.align || !s.rec_align.d.p || !s.rec_pairs.d.p || s.pairs > PR_MAX_BINS || (s.pairs_count && (!ctx->d_frag || ctx->frag_bins != s.pairs))) {
+  if (!s.pairs || !s.align || !s.rec_align.d.p || !s.rec_pairs.d.p || s.pairs > PR_MAX_BINS || (s.pairs_count && ctx->frag.bins() != s.pairs)) {
     ctx->last_error = "pairs mode without its state";
     return SHK_ERR_STATE;
   }
@@ -196,7 +196,7 @@ int launch_pairs(Ctx *ctx, const Slot &s, uint64_t cap_assoc, bool skip_if_long,
   P.off[1] = s.p.seq2 ? s.p.off2 : nullptr;
   P.align = reinterpret_cast<const uint4 *>(s.rec_align.d.p);
   P.out = reinterpret_cast<uint4 *>(s.rec_pairs.d.p);
-  P.state = s.pairs_count ? ctx->d_frag : nullptr;
+  P.state = s.pairs_count ? ctx->frag.hist.p : nullptr;
   // (launch_alignments' bound on the associations its records hold, and this mode's own array)
   P.cap = (uint32_t)std::min<uint64_t>(std::min<uint64_t>(std::min<uint64_t>(s.d_gene_ids.cap, cap_assoc), std::min<uint64_t>(s.rec_align.d.cap / 2, s.rec_pairs.d.cap)), 0xFFFFFFFFull);
   P.skip_if_long = skip_if_long ? 1u : 0u;

@@ -102,7 +102,7 @@ __global__ __launch_bounds__(PL_THREADS) void pileup_kernel(const PileupParams P
 int launch_pileup(Ctx *ctx, const Slot &s, const shk_segment *entries, uint64_t cap_assoc, bool skip_if_long, hipStream_t stream)
 {
   const DeviceIndex &ix = ctx->idx;
-  if (!ix.gene_start || !entries || !s.pileup || !ctx->d_pileup || !ctx->d_pileup_mates) {
+  if (!ix.gene_start || !entries || !s.pileup || !ctx->pileup.counts.p || !ctx->pileup.mates.p) {
     ctx->last_error = "pileup mode without its state";
     return SHK_ERR_STATE;
   }
@@ -122,8 +122,8 @@ int launch_pileup(Ctx *ctx, const Slot &s, const shk_segment *entries, uint64_t 
   P.n_genes = (uint32_t)(ctx->gene_start.size() - 1);
   P.skip_if_long = skip_if_long ? 1u : 0u;
   P.s_min = s.pileup;
-  P.counts = ctx->d_pileup;
-  P.mates = ctx->d_pileup_mates;
+  P.counts = ctx->pileup.counts.p;
+  P.mates = ctx->pileup.mates.p;
   // one wave per read up to 2 048 workgroups, persistent beyond (launch_segments' bound)
   const uint64_t want = (s.n + PL_WAVES - 1) / PL_WAVES;
   hipLaunchKernelGGL(pileup_kernel, dim3((unsigned)std::min<uint64_t>(want, 2048)), dim3(PL_THREADS), 0, stream, P);

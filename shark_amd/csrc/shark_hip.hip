@@ -188,9 +188,9 @@ static int size_scratch(Ctx *ctx, ClassifyParams &p, uint32_t slots, uint64_t n_
   const uint64_t budget_words = (1ull << 31) / 8;  // at most 2 GiB of scratch
   if (waves * stride > budget_words) waves = std::max<uint64_t>(1, budget_words / stride);
   waves = ((waves + 3) / 4) * 4;
-  int r = ensure_capacity(ctx, &ctx->d_scratch, &ctx->cap_scratch, waves * stride);
+  int r = ctx->scratch.reserve(ctx, waves * stride);
   if (r) return r;
-  p.scratch = ctx->d_scratch;
+  p.scratch = ctx->scratch.p;
   p.scratch_stride_words = stride;
   p.scratch_slots = S;
   *n_waves = (unsigned)waves;
@@ -385,29 +385,29 @@ static int enqueue_classify(Ctx *ctx, Slot &s, const shk_batch *b, uint32_t max_
   s.cand_m = ctx->cand_m;
   s.placement = ctx->placement;
   s.seg_m = ctx->seg_m;
-  s.depth = count_genes && !ctx->depth_spliced ? ctx->depth : 0u;   // (shk_count_work is a measurement: its batch is not counted)
-  s.sp_depth = count_genes && ctx->depth_spliced ? ctx->depth : 0u;
-  s.sp_junc = count_genes ? ctx->junc : 0u;
-  s.pileup = count_genes && !ctx->pileup_aligned ? ctx->pileup : 0u;
-  s.pileup_al = count_genes && ctx->pileup_aligned ? ctx->pileup : 0u;
+  s.depth = count_genes && !ctx->depth.kind ? ctx->depth.floor : 0u;   // (shk_count_work is a measurement: its batch is not counted)
+  s.sp_depth = count_genes && ctx->depth.kind ? ctx->depth.floor : 0u;
+  s.sp_junc = count_genes ? ctx->junc.floor : 0u;
+  s.pileup = count_genes && !ctx->pileup.kind ? ctx->pileup.floor : 0u;
+  s.pileup_al = count_genes && ctx->pileup.kind ? ctx->pileup.floor : 0u;
   s.align = ctx->align;
   s.ext_p = ctx->ext_p;
   s.ext_b = ctx->ext_b;
-  s.spl_h = ctx->spl_h;
-  s.spl_cost = ctx->spl_cost;
-  s.spl_gap = ctx->spl_gap;
-  s.pairs = s.align ? ctx->pairs_bins : 0u;      // (pair records only behind alignment records)
-  s.pairs_min_intron = ctx->pairs_min_intron;
-  s.pairs_max_frag = ctx->pairs_max_frag;
+  s.spl_h = ctx->splice.h;
+  s.spl_cost = ctx->splice.cost;
+  s.spl_gap = ctx->splice.gap;
+  s.pairs = s.align ? ctx->frag.n_bins : 0u;      // (pair records only behind alignment records)
+  s.pairs_min_intron = ctx->frag.min_intron;
+  s.pairs_max_frag = ctx->frag.max_frag;
   s.pairs_count = s.pairs && count_genes;
   s.rescue = s.align ? ctx->rescue_max_frag : 0u;   // (rescue only behind alignment records)
   s.rescue_min_intron = ctx->rescue_min_intron;
   s.rescue_max_cost = ctx->rescue_max_cost;
   s.rescue_min_gap = ctx->rescue_min_gap;
-  if (s.pairs_count) ctx->frag_dirty = true;
-  if (s.pileup || s.pileup_al) ctx->pileup_dirty = true;
-  if (s.depth || s.sp_depth) ctx->depth_dirty = true;
-  if (s.sp_junc) ctx->junc_dirty = true;
+  if (s.pairs_count) ctx->frag.dirty = true;
+  if (s.pileup || s.pileup_al) ctx->pileup.dirty = true;
+  if (s.depth || s.sp_depth) ctx->depth.dirty = true;
+  if (s.sp_junc) ctx->junc.dirty = true;
   if ((rc = slot_reserve(ctx, s, n))) return rc;
   s.n = n;
   fill_params(ctx, s, b);
@@ -747,6 +747,24 @@ static void dist_release(Ctx *ctx)
 
 using namespace shk;
 
+// a state whose shape its caller chooses (the junction table's capacity, the fragments state's n_bins), asked for at `entries` entries.  Missing:
+// allocated and cleared.  Of another shape: refused while dirty, otherwise released behind the drained stream, then allocated and cleared
+template <typename T, typename Clear>
+static int state_shape(shk_ctx *ctx, DevArray<T> &arr, size_t entries, bool &dirty, const char *refusal, Clear clear)
+{
+  if (arr.p && arr.cap != entries) {
+    if (dirty) { ctx->last_error = refusal; return SHK_ERR_ARG; }
+    SHK_HIP(ctx, hipSetDevice(ctx->prm.device));
+    SHK_HIP(ctx, hipStreamSynchronize(ctx->stream));
+    (void)arr.release();
+  }
+  if (arr.p) return SHK_OK;
+  SHK_HIP(ctx, hipSetDevice(ctx->prm.device));
+  if (const int rc = arr.alloc_exact(ctx, entries)) return rc;
+  dirty = false;
+  return clear();
+}
+
 extern "C" {
 
 const char *shk_version(void) { return "sharkhip 0.1 (gfx950)"; }
@@ -858,13 +876,7 @@ void shk_destroy(shk_ctx *ctx)
   if (ctx->stream) (void)hipStreamSynchronize(ctx->stream);
   free_index(ctx->idx);
   for (Slot &sl : ctx->slots) slot_free(sl);
-  hipFree(ctx->d_scratch); hipFree(ctx->d_gene_counts); hipFree(ctx->d_gene_totals); hipFree(ctx->d_work_counters);
-  hipFree(ctx->d_depth_diff); hipFree(ctx->d_depth_mates); hipFree(ctx->d_depth_scan); hipFree(ctx->d_depth_scan_temp); hipFree(ctx->d_depth_summary);
-  hipFree(ctx->d_junc_tab); hipFree(ctx->d_junc_dropped);
-  hipFree(ctx->d_pileup); hipFree(ctx->d_pileup_mates);
-  hipFree(ctx->d_frag);
-  hipFree(ctx->d_splice);
-  hipFree(ctx->d_var_waves); hipFree(ctx->d_var_temp); hipFree(ctx->d_var_out); hipFree(ctx->d_var_summary);
+  hipFree(ctx->d_gene_counts); hipFree(ctx->d_gene_totals); hipFree(ctx->d_work_counters);
   dist_release(ctx);
   for (auto e : ctx->ev_start) (void)hipEventDestroy(e);
   for (auto e : ctx->ev_stop) (void)hipEventDestroy(e);
@@ -872,7 +884,7 @@ void shk_destroy(shk_ctx *ctx)
   if (ctx->h2d_stream) (void)hipStreamDestroy(ctx->h2d_stream);
   if (ctx->d2h_stream) (void)hipStreamDestroy(ctx->d2h_stream);
   if (ctx->stream) (void)hipStreamDestroy(ctx->stream);
-  delete ctx;
+  delete ctx;   // (the general kernel's scratch and the accumulated states free themselves here: the device is current, the streams were drained)
 }
 
 int shk_ref_add(shk_ctx *ctx, const char *seq, uint64_t len)
@@ -1231,11 +1243,15 @@ int shk_classify_wait(shk_ctx *ctx, uint64_t ticket, shk_result *result)
   return hand_out_records(ctx, s, s.host_batch, false, n_assoc);
 }
 
-static bool tickets_outstanding(const shk_ctx *ctx)
+// what every enable, read-out and reset of a mode or state refuses: a change while a submitted batch was not waited for
+static int refuse_tickets(shk_ctx *ctx, const char *who)
 {
   for (int i = 0; i < PIPE_DEPTH; ++i)
-    if (ctx->slots[i].ticket != 0 && !ctx->slots[i].waited) return true;
-  return false;
+    if (ctx->slots[i].ticket != 0 && !ctx->slots[i].waited) {
+      ctx->last_error = std::string(who) + ": tickets are outstanding (wait for them first)";
+      return SHK_ERR_STATE;
+    }
+  return SHK_OK;
 }
 
 // what a mode that reads the placement table asks of the index, in this order: finalized, built with shk_ref_keep_positions, at most
@@ -1257,7 +1273,7 @@ static int check_mode_index(shk_ctx *ctx, const char *who, unsigned need)
 int shk_evidence_enable(shk_ctx *ctx, int enable)
 {
   if (!ctx) return SHK_ERR_ARG;
-  if (tickets_outstanding(ctx)) { ctx->last_error = "shk_evidence_enable: tickets are outstanding (wait for them first)"; return SHK_ERR_STATE; }
+  if (const int rc = refuse_tickets(ctx, "shk_evidence_enable")) return rc;
   ctx->evidence = enable != 0;
   return SHK_OK;
 }
@@ -1275,7 +1291,7 @@ int shk_candidates_enable(shk_ctx *ctx, uint32_t m)
 {
   if (!ctx) return SHK_ERR_ARG;
   if (m > SHK_MAX_CANDIDATES) { ctx->last_error = "shk_candidates_enable: m must be at most SHK_MAX_CANDIDATES"; return SHK_ERR_ARG; }
-  if (tickets_outstanding(ctx)) { ctx->last_error = "shk_candidates_enable: tickets are outstanding (wait for them first)"; return SHK_ERR_STATE; }
+  if (const int rc = refuse_tickets(ctx, "shk_candidates_enable")) return rc;
   ctx->cand_m = m;
   return SHK_OK;
 }
@@ -1319,7 +1335,7 @@ int shk_ref_keep_bases(shk_ctx *ctx)
 int shk_placement_enable(shk_ctx *ctx, int enable)
 {
   if (!ctx) return SHK_ERR_ARG;
-  if (tickets_outstanding(ctx)) { ctx->last_error = "shk_placement_enable: tickets are outstanding (wait for them first)"; return SHK_ERR_STATE; }
+  if (const int rc = refuse_tickets(ctx, "shk_placement_enable")) return rc;
   if (enable) {
     if (const int rc = check_mode_index(ctx, "shk_placement_enable", 0)) return rc;
   }
@@ -1340,7 +1356,7 @@ int shk_segments_enable(shk_ctx *ctx, uint32_t m)
 {
   if (!ctx) return SHK_ERR_ARG;
   if (m > SHK_MAX_SEGMENTS) { ctx->last_error = "shk_segments_enable: m must be at most SHK_MAX_SEGMENTS"; return SHK_ERR_ARG; }
-  if (tickets_outstanding(ctx)) { ctx->last_error = "shk_segments_enable: tickets are outstanding (wait for them first)"; return SHK_ERR_STATE; }
+  if (const int rc = refuse_tickets(ctx, "shk_segments_enable")) return rc;
   if (m) {
     if (const int rc = check_mode_index(ctx, "shk_segments_enable", 0)) return rc;
   }
@@ -1359,38 +1375,113 @@ int shk_segments_last(const shk_ctx *ctx, shk_segments *out)
   return SHK_OK;
 }
 
-// ---- depth mode (depth.hip): the state lives in the context, the batches' tails add to it ----
-// both kinds of depth (plain intervals, unions of kept spans) over the one state
-static int depth_enable_kind(shk_ctx *ctx, uint32_t min_support, bool spliced, const char *who)
+// ---- the accumulated states (shark_internal.hpp): they live in the context, the batches' tails add to them ----
+// what every read-out and reset of a state starts with, in this order: the state was enabled once (`what`: how the refusal names it), no
+// ticket is outstanding, the context's device is current
+static int state_ready(shk_ctx *ctx, const char *who, bool enabled, const char *what)
 {
-  if (!ctx) return SHK_ERR_ARG;
-  if (tickets_outstanding(ctx)) { ctx->last_error = std::string(who) + ": tickets are outstanding (wait for them first)"; return SHK_ERR_STATE; }
-  if (min_support) {
-    if (const int rc = check_mode_index(ctx, who, NEED_GENE_START)) return rc;
-    if (ctx->d_depth_diff && ctx->depth_dirty && spliced != ctx->depth_spliced) {
-      ctx->last_error = std::string(who) + ": the state holds depth of the other kind (plain / spliced): shk_depth_reset first";
-      return SHK_ERR_STATE;
-    }
-    if (!ctx->d_depth_diff) {
-      SHK_HIP(ctx, hipSetDevice(ctx->prm.device));
-      const size_t bytes = (size_t)(ctx->gene_start.back() + 1) * sizeof(uint32_t);
-      uint32_t *diff = nullptr;
-      unsigned long long *mates = nullptr;
-      SHK_HIP(ctx, hipMalloc((void **)&diff, bytes));
-      if (hipError_t e = hipMalloc((void **)&mates, sizeof(unsigned long long))) { (void)hipFree(diff); return set_hip_error(ctx, e, "hipMalloc"); }
-      ctx->d_depth_diff = diff;
-      ctx->d_depth_mates = mates;
-      SHK_HIP(ctx, hipMemsetAsync(diff, 0, bytes, ctx->stream));
-      SHK_HIP(ctx, hipMemsetAsync(mates, 0, sizeof(unsigned long long), ctx->stream));
-    }
-    ctx->depth_spliced = spliced;
-  }
-  ctx->depth = min_support;
+  if (!enabled) { ctx->last_error = std::string(who) + ": " + what + " was never enabled on this context"; return SHK_ERR_STATE; }
+  if (const int rc = refuse_tickets(ctx, who)) return rc;
+  SHK_HIP(ctx, hipSetDevice(ctx->prm.device));
   return SHK_OK;
 }
 
-int shk_depth_enable(shk_ctx *ctx, uint32_t min_support) { return depth_enable_kind(ctx, min_support, false, "shk_depth_enable"); }
-int shk_depth_enable_spliced(shk_ctx *ctx, uint32_t min_support) { return depth_enable_kind(ctx, min_support, true, "shk_depth_enable_spliced"); }
+// ---- depth mode (depth.hip) and pileup mode (pileup.hip, align.hip): two states of one type (CounterState), each of two kinds -- depth: plain
+// intervals / the unions of kept spans, pileup: owned pieces / the alignment's final blocks.  What tells the two states apart: ----
+struct CounterRules {
+  CounterState &(*state)(shk_ctx *);
+  const char *what;                    // state_ready's
+  size_t (*entries)(uint64_t bases);   // counters over a reference of that many bases
+  uint32_t per_base;                   // counters per base that a read-out hands back
+  bool scanned;                        // a read-out hands back the scan of the counters (depth_scan), not the counters themselves
+  const char *other_kind;              // the refusal of the other kind on a dirty state
+  uint64_t max_mates;                  // what the 32-bit counters hold, and the read-outs' refusal beyond
+  const char *too_many;
+};
+static const CounterRules DEPTH_RULES = {
+  [](shk_ctx *c) -> CounterState & { return c->depth; }, "depth mode", [](uint64_t bases) { return (size_t)bases + 1; }, 1, true,
+  ": the state holds depth of the other kind (plain / spliced): shk_depth_reset first",
+  0x7FFFFFFFull, ": more than 2^31-1 mates counted since the last reset (32-bit depth counters)"};
+// (four counters per record base, and at least one allocation's worth for an index without a base)
+static const CounterRules PILEUP_RULES = {
+  [](shk_ctx *c) -> CounterState & { return c->pileup; }, "pileup mode", [](uint64_t bases) { return std::max<size_t>((size_t)bases * 4, 4); }, 4, false,
+  ": the state holds pileup of the other kind (owned / aligned): shk_pileup_reset first",
+  0xFFFFFFFFull, ": more than 2^32-1 pileup mates since the last reset (32-bit counters)"};
+
+static int counters_enable(shk_ctx *ctx, const CounterRules &R, uint32_t min_support, bool kind, unsigned need, const char *who)
+{
+  if (!ctx) return SHK_ERR_ARG;
+  if (const int rc = refuse_tickets(ctx, who)) return rc;
+  CounterState &S = R.state(ctx);
+  if (min_support) {
+    if (const int rc = check_mode_index(ctx, who, need)) return rc;
+    if (S.mates.p && S.dirty && kind != S.kind) { ctx->last_error = std::string(who) + R.other_kind; return SHK_ERR_STATE; }
+    if (!S.mates.p) {
+      SHK_HIP(ctx, hipSetDevice(ctx->prm.device));
+      // (out of memory: SHK_ERR_NOMEM, the mode stays off and the state never enabled -- both arrays or none)
+      const size_t n = R.entries(ctx->gene_start.back());
+      DevArray<uint32_t> counts;
+      DevArray<unsigned long long> mates;
+      int rc;
+      if ((rc = counts.alloc_exact(ctx, n)) || (rc = mates.alloc_exact(ctx, 1))) return rc;
+      S.counts = std::move(counts);
+      S.mates = std::move(mates);
+      SHK_HIP(ctx, hipMemsetAsync(S.counts.p, 0, n * sizeof(uint32_t), ctx->stream));
+      SHK_HIP(ctx, hipMemsetAsync(S.mates.p, 0, sizeof(unsigned long long), ctx->stream));
+    }
+    S.kind = kind;
+  }
+  S.floor = min_support;
+  return SHK_OK;
+}
+
+// what every read-out starts with: the state rules, the stream drained behind everything enqueued so far, the mate counter and its guard
+static int counters_read_mates(shk_ctx *ctx, const CounterRules &R, const char *who, uint64_t *n_mates)
+{
+  CounterState &S = R.state(ctx);
+  if (const int rc = state_ready(ctx, who, S.mates.p != nullptr, R.what)) return rc;
+  unsigned long long m = 0;
+  SHK_HIP(ctx, hipMemcpyAsync(&m, S.mates.p, sizeof(m), hipMemcpyDeviceToHost, ctx->stream));
+  SHK_HIP(ctx, hipStreamSynchronize(ctx->stream));
+  if (n_mates) *n_mates = m;
+  if (m > R.max_mates) { ctx->last_error = std::string(who) + R.too_many; return SHK_ERR_INDEX_TOO_LARGE; }
+  return SHK_OK;
+}
+
+// the counters of one gene, or with gene < 0 of all of them (only then may dst be device memory), as the state stands
+static int counters_get(shk_ctx *ctx, const CounterRules &R, const char *who, int64_t gene, uint32_t *dst, uint64_t cap, int device)
+{
+  if (!ctx) return SHK_ERR_ARG;
+  int rc = counters_read_mates(ctx, R, who, nullptr);
+  if (rc) return rc;
+  const std::vector<uint64_t> &gs = ctx->gene_start;
+  if (gene >= 0 && (uint64_t)gene + 1 >= gs.size()) return SHK_ERR_ARG;
+  const uint64_t a = gene < 0 ? 0 : R.per_base * gs[gene], len = R.per_base * (gene < 0 ? gs.back() : gs[gene + 1]) - a;
+  if (cap < len || (!dst && len)) return SHK_ERR_ARG;
+  if (len == 0) return SHK_OK;
+  // (pileup: the counters are the answer: no scan, one copy)
+  if (R.scanned && (rc = depth_scan(ctx))) return rc;
+  const uint32_t *src = R.scanned ? ctx->depth.scan.p + 1 : R.state(ctx).counts.p;
+  SHK_HIP(ctx, hipMemcpyAsync(dst, src + a, len * sizeof(uint32_t), device ? hipMemcpyDeviceToDevice : hipMemcpyDeviceToHost, ctx->stream));
+  SHK_HIP(ctx, hipStreamSynchronize(ctx->stream));
+  return SHK_OK;
+}
+
+static int counters_reset(shk_ctx *ctx, const CounterRules &R, const char *who)
+{
+  if (!ctx) return SHK_ERR_ARG;
+  CounterState &S = R.state(ctx);
+  if (const int rc = state_ready(ctx, who, S.mates.p != nullptr, R.what)) return rc;
+  SHK_HIP(ctx, hipMemsetAsync(S.counts.p, 0, S.counts.cap * sizeof(uint32_t), ctx->stream));
+  SHK_HIP(ctx, hipMemsetAsync(S.mates.p, 0, sizeof(unsigned long long), ctx->stream));
+  if (R.scanned) ctx->depth.scan_current = false;
+  S.dirty = false;
+  SHK_HIP(ctx, hipStreamSynchronize(ctx->stream));
+  return SHK_OK;
+}
+
+int shk_depth_enable(shk_ctx *ctx, uint32_t min_support) { return counters_enable(ctx, DEPTH_RULES, min_support, false, NEED_GENE_START, "shk_depth_enable"); }
+int shk_depth_enable_spliced(shk_ctx *ctx, uint32_t min_support) { return counters_enable(ctx, DEPTH_RULES, min_support, true, NEED_GENE_START, "shk_depth_enable_spliced"); }
 
 int shk_depth_layout(const shk_ctx *ctx, uint64_t *gene_start, uint32_t n_genes)
 {
@@ -1401,126 +1492,79 @@ int shk_depth_layout(const shk_ctx *ctx, uint64_t *gene_start, uint32_t n_genes)
   return SHK_OK;
 }
 
-// what every read-out starts with: the state rules, the stream drained behind everything enqueued so far, the mate counter and its guard
-static int depth_read_mates(shk_ctx *ctx, const char *who, uint64_t *n_mates)
-{
-  if (!ctx->d_depth_diff) { ctx->last_error = std::string(who) + ": depth mode was never enabled on this context"; return SHK_ERR_STATE; }
-  if (tickets_outstanding(ctx)) { ctx->last_error = std::string(who) + ": tickets are outstanding (wait for them first)"; return SHK_ERR_STATE; }
-  SHK_HIP(ctx, hipSetDevice(ctx->prm.device));
-  unsigned long long m = 0;
-  SHK_HIP(ctx, hipMemcpyAsync(&m, ctx->d_depth_mates, sizeof(m), hipMemcpyDeviceToHost, ctx->stream));
-  SHK_HIP(ctx, hipStreamSynchronize(ctx->stream));
-  if (n_mates) *n_mates = m;
-  if (m > 0x7FFFFFFFull) { ctx->last_error = std::string(who) + ": more than 2^31-1 mates counted since the last reset (32-bit depth counters)"; return SHK_ERR_INDEX_TOO_LARGE; }
-  return SHK_OK;
-}
-
 int shk_depth_mates(const shk_ctx *cctx, uint64_t *n_mates)
 {
   if (!cctx || !n_mates) return SHK_ERR_ARG;
-  return depth_read_mates(const_cast<shk_ctx *>(cctx), "shk_depth_mates", n_mates);
+  return counters_read_mates(const_cast<shk_ctx *>(cctx), DEPTH_RULES, "shk_depth_mates", n_mates);
 }
 
-int shk_depth_get_all(shk_ctx *ctx, uint32_t *depth, uint64_t cap, int device)
-{
-  if (!ctx) return SHK_ERR_ARG;
-  int rc = depth_read_mates(ctx, "shk_depth_get_all", nullptr);
-  if (rc) return rc;
-  const uint64_t total = ctx->gene_start.back();
-  if (cap < total || (!depth && total)) return SHK_ERR_ARG;
-  if (total == 0) return SHK_OK;
-  if ((rc = depth_scan(ctx))) return rc;
-  SHK_HIP(ctx, hipMemcpyAsync(depth, ctx->d_depth_scan + 1, total * sizeof(uint32_t), device ? hipMemcpyDeviceToDevice : hipMemcpyDeviceToHost, ctx->stream));
-  SHK_HIP(ctx, hipStreamSynchronize(ctx->stream));
-  return SHK_OK;
-}
-
-int shk_depth_get(shk_ctx *ctx, uint32_t gene, uint32_t *depth, uint64_t cap)
-{
-  if (!ctx) return SHK_ERR_ARG;
-  int rc = depth_read_mates(ctx, "shk_depth_get", nullptr);
-  if (rc) return rc;
-  if ((uint64_t)gene + 1 >= ctx->gene_start.size()) return SHK_ERR_ARG;
-  const uint64_t a = ctx->gene_start[gene], len = ctx->gene_start[gene + 1] - a;
-  if (cap < len || (!depth && len)) return SHK_ERR_ARG;
-  if (len == 0) return SHK_OK;
-  if ((rc = depth_scan(ctx))) return rc;
-  SHK_HIP(ctx, hipMemcpyAsync(depth, ctx->d_depth_scan + 1 + a, len * sizeof(uint32_t), hipMemcpyDeviceToHost, ctx->stream));
-  SHK_HIP(ctx, hipStreamSynchronize(ctx->stream));
-  return SHK_OK;
-}
+int shk_depth_get_all(shk_ctx *ctx, uint32_t *depth, uint64_t cap, int device) { return counters_get(ctx, DEPTH_RULES, "shk_depth_get_all", -1, depth, cap, device); }
+int shk_depth_get(shk_ctx *ctx, uint32_t gene, uint32_t *depth, uint64_t cap) { return counters_get(ctx, DEPTH_RULES, "shk_depth_get", gene, depth, cap, 0); }
 
 int shk_depth_summary(shk_ctx *ctx, shk_gene_depth *out, uint32_t n_genes)
 {
   if (!ctx || (!out && n_genes)) return SHK_ERR_ARG;
-  int rc = depth_read_mates(ctx, "shk_depth_summary", nullptr);
+  int rc = counters_read_mates(ctx, DEPTH_RULES, "shk_depth_summary", nullptr);
   if (rc) return rc;
   if ((uint64_t)n_genes + 1 > ctx->gene_start.size()) return SHK_ERR_ARG;
   if (n_genes == 0) return SHK_OK;
   if ((rc = depth_scan(ctx))) return rc;
   if ((rc = launch_depth_summary(ctx))) return rc;
-  SHK_HIP(ctx, hipMemcpyAsync(out, ctx->d_depth_summary, (size_t)n_genes * sizeof(shk_gene_depth), hipMemcpyDeviceToHost, ctx->stream));
+  SHK_HIP(ctx, hipMemcpyAsync(out, ctx->depth.summary.p, (size_t)n_genes * sizeof(shk_gene_depth), hipMemcpyDeviceToHost, ctx->stream));
   SHK_HIP(ctx, hipStreamSynchronize(ctx->stream));
   return SHK_OK;
 }
 
-int shk_depth_reset(shk_ctx *ctx)
+int shk_depth_reset(shk_ctx *ctx) { return counters_reset(ctx, DEPTH_RULES, "shk_depth_reset"); }
+
+int shk_pileup_enable(shk_ctx *ctx, uint32_t min_support) { return counters_enable(ctx, PILEUP_RULES, min_support, false, NEED_GENE_START, "shk_pileup_enable"); }
+int shk_pileup_enable_aligned(shk_ctx *ctx, uint32_t min_support) { return counters_enable(ctx, PILEUP_RULES, min_support, true, NEED_GENE_START | NEED_BASES, "shk_pileup_enable_aligned"); }
+
+int shk_pileup_mates(const shk_ctx *cctx, uint64_t *n)
 {
-  if (!ctx) return SHK_ERR_ARG;
-  if (!ctx->d_depth_diff) { ctx->last_error = "shk_depth_reset: depth mode was never enabled on this context"; return SHK_ERR_STATE; }
-  if (tickets_outstanding(ctx)) { ctx->last_error = "shk_depth_reset: tickets are outstanding (wait for them first)"; return SHK_ERR_STATE; }
-  SHK_HIP(ctx, hipSetDevice(ctx->prm.device));
-  SHK_HIP(ctx, hipMemsetAsync(ctx->d_depth_diff, 0, (size_t)(ctx->gene_start.back() + 1) * sizeof(uint32_t), ctx->stream));
-  SHK_HIP(ctx, hipMemsetAsync(ctx->d_depth_mates, 0, sizeof(unsigned long long), ctx->stream));
-  ctx->depth_scan_current = false;
-  ctx->depth_dirty = false;
-  SHK_HIP(ctx, hipStreamSynchronize(ctx->stream));
-  return SHK_OK;
+  if (!cctx || !n) return SHK_ERR_ARG;
+  return counters_read_mates(const_cast<shk_ctx *>(cctx), PILEUP_RULES, "shk_pileup_mates", n);
 }
 
-// ---- the junction table (spliced.hip): the state lives in the context, the batches' tails add to it ----
+int shk_pileup_get_all(shk_ctx *ctx, uint32_t *counts, uint64_t cap, int device) { return counters_get(ctx, PILEUP_RULES, "shk_pileup_get_all", -1, counts, cap, device); }
+int shk_pileup_get(shk_ctx *ctx, uint32_t gene, uint32_t *counts, uint64_t cap) { return counters_get(ctx, PILEUP_RULES, "shk_pileup_get", gene, counts, cap, 0); }
+int shk_pileup_reset(shk_ctx *ctx) { return counters_reset(ctx, PILEUP_RULES, "shk_pileup_reset"); }
+
+// ---- the junction table (spliced.hip) ----
 int shk_junctions_enable(shk_ctx *ctx, uint32_t min_support, uint64_t capacity)
 {
   if (!ctx) return SHK_ERR_ARG;
-  if (tickets_outstanding(ctx)) { ctx->last_error = "shk_junctions_enable: tickets are outstanding (wait for them first)"; return SHK_ERR_STATE; }
+  if (const int rc = refuse_tickets(ctx, "shk_junctions_enable")) return rc;
+  JunctionState &J = ctx->junc;
   if (min_support) {
-    if (const int rc = check_mode_index(ctx, "shk_junctions_enable", NEED_GENE_START)) return rc;
+    int rc;
+    if ((rc = check_mode_index(ctx, "shk_junctions_enable", NEED_GENE_START))) return rc;
     if (capacity > (1ull << 40)) { ctx->last_error = "shk_junctions_enable: capacity beyond 2^40 entries"; return SHK_ERR_ARG; }
     uint64_t cap = 64;
     while (cap < capacity) cap <<= 1;
-    if (ctx->d_junc_tab && cap != ctx->junc_cap) {
-      if (ctx->junc_dirty) { ctx->last_error = "shk_junctions_enable: another capacity than the table's (shk_junctions_reset first)"; return SHK_ERR_ARG; }
+    if (!J.dropped.p) {
       SHK_HIP(ctx, hipSetDevice(ctx->prm.device));
-      SHK_HIP(ctx, hipStreamSynchronize(ctx->stream));
-      (void)hipFree(ctx->d_junc_tab);
-      ctx->d_junc_tab = nullptr;
-      ctx->junc_cap = 0;
+      if ((rc = J.dropped.alloc_exact(ctx, 1))) return rc;
     }
-    if (!ctx->d_junc_tab) {
-      SHK_HIP(ctx, hipSetDevice(ctx->prm.device));
-      if (!ctx->d_junc_dropped) SHK_HIP(ctx, hipMalloc((void **)&ctx->d_junc_dropped, sizeof(unsigned long long)));
-      SHK_HIP(ctx, hipMalloc((void **)&ctx->d_junc_tab, (size_t)cap * sizeof(JunctionEntry)));
-      ctx->junc_cap = cap;
-      ctx->junc_dirty = false;
-      if (const int rc = launch_junction_clear(ctx)) return rc;
-    }
+    if ((rc = state_shape(ctx, J.tab, (size_t)cap, J.dirty, "shk_junctions_enable: another capacity than the table's (shk_junctions_reset first)",
+                          [&] { return launch_junction_clear(ctx); })))
+      return rc;
   }
-  ctx->junc = min_support;
+  J.floor = min_support;
   return SHK_OK;
 }
 
 int shk_junctions_get(shk_ctx *ctx, shk_junction *out, uint64_t cap, uint64_t *n)
 {
   if (!ctx || !n) return SHK_ERR_ARG;
-  if (!ctx->d_junc_tab) { ctx->last_error = "shk_junctions_get: the junction table was never enabled on this context"; return SHK_ERR_STATE; }
-  if (tickets_outstanding(ctx)) { ctx->last_error = "shk_junctions_get: tickets are outstanding (wait for them first)"; return SHK_ERR_STATE; }
-  SHK_HIP(ctx, hipSetDevice(ctx->prm.device));
+  const JunctionState &J = ctx->junc;
+  if (const int rc = state_ready(ctx, "shk_junctions_get", J.tab.p != nullptr, "the junction table")) return rc;
   // once per sample: the whole table to the host, the occupied entries ordered there.  Key order IS (gene, donor, acceptor) order: the
   // genes' bases are numbered gene after gene and a donor is at least k, so within the reference donors ascend with (gene, donor)
-  std::vector<JunctionEntry> tab((size_t)ctx->junc_cap);
+  std::vector<JunctionEntry> tab(J.tab.cap);
   unsigned long long dropped = 0;
-  SHK_HIP(ctx, hipMemcpyAsync(&dropped, ctx->d_junc_dropped, sizeof(dropped), hipMemcpyDeviceToHost, ctx->stream));
-  SHK_HIP(ctx, hipMemcpyAsync(tab.data(), ctx->d_junc_tab, tab.size() * sizeof(JunctionEntry), hipMemcpyDeviceToHost, ctx->stream));
+  SHK_HIP(ctx, hipMemcpyAsync(&dropped, J.dropped.p, sizeof(dropped), hipMemcpyDeviceToHost, ctx->stream));
+  SHK_HIP(ctx, hipMemcpyAsync(tab.data(), J.tab.p, tab.size() * sizeof(JunctionEntry), hipMemcpyDeviceToHost, ctx->stream));
   SHK_HIP(ctx, hipStreamSynchronize(ctx->stream));
   if (dropped) {
     ctx->last_error = "shk_junctions_get: the table was full for " + std::to_string(dropped) + " observations (shk_junctions_reset, then a larger capacity)";
@@ -1548,119 +1592,19 @@ int shk_junctions_get(shk_ctx *ctx, shk_junction *out, uint64_t cap, uint64_t *n
 int shk_junctions_reset(shk_ctx *ctx)
 {
   if (!ctx) return SHK_ERR_ARG;
-  if (!ctx->d_junc_tab) { ctx->last_error = "shk_junctions_reset: the junction table was never enabled on this context"; return SHK_ERR_STATE; }
-  if (tickets_outstanding(ctx)) { ctx->last_error = "shk_junctions_reset: tickets are outstanding (wait for them first)"; return SHK_ERR_STATE; }
-  SHK_HIP(ctx, hipSetDevice(ctx->prm.device));
+  if (const int rc = state_ready(ctx, "shk_junctions_reset", ctx->junc.tab.p != nullptr, "the junction table")) return rc;
   if (const int rc = launch_junction_clear(ctx)) return rc;
-  ctx->junc_dirty = false;
+  ctx->junc.dirty = false;
   SHK_HIP(ctx, hipStreamSynchronize(ctx->stream));
   return SHK_OK;
 }
 
-// ---- pileup mode (pileup.hip): the state lives in the context, the batches' tails add to it ----
-// the counters: four per record base, and at least one allocation's worth for an index without a base
-static size_t pileup_bytes(const shk_ctx *ctx) { return std::max<size_t>((size_t)ctx->gene_start.back() * 4 * sizeof(uint32_t), 16); }
-
-// both kinds of pileup (owned pieces, the alignment's final blocks) over the one state
-static int pileup_enable_kind(shk_ctx *ctx, uint32_t min_support, bool aligned, const char *who)
-{
-  if (!ctx) return SHK_ERR_ARG;
-  if (tickets_outstanding(ctx)) { ctx->last_error = std::string(who) + ": tickets are outstanding (wait for them first)"; return SHK_ERR_STATE; }
-  if (min_support) {
-    if (const int rc = check_mode_index(ctx, who, NEED_GENE_START | (aligned ? NEED_BASES : 0u))) return rc;
-    if (ctx->d_pileup_mates && ctx->pileup_dirty && aligned != ctx->pileup_aligned) {
-      ctx->last_error = std::string(who) + ": the state holds pileup of the other kind (owned / aligned): shk_pileup_reset first";
-      return SHK_ERR_STATE;
-    }
-    if (!ctx->d_pileup_mates) {
-      SHK_HIP(ctx, hipSetDevice(ctx->prm.device));
-      const size_t bytes = pileup_bytes(ctx);
-      uint32_t *counts = nullptr;
-      unsigned long long *mates = nullptr;
-      SHK_HIP(ctx, hipMalloc((void **)&counts, bytes));          // (out of memory: SHK_ERR_NOMEM, the mode stays off)
-      if (hipError_t e = hipMalloc((void **)&mates, sizeof(unsigned long long))) { (void)hipFree(counts); return set_hip_error(ctx, e, "hipMalloc"); }
-      ctx->d_pileup = counts;
-      ctx->d_pileup_mates = mates;
-      SHK_HIP(ctx, hipMemsetAsync(counts, 0, bytes, ctx->stream));
-      SHK_HIP(ctx, hipMemsetAsync(mates, 0, sizeof(unsigned long long), ctx->stream));
-    }
-    ctx->pileup_aligned = aligned;
-  }
-  ctx->pileup = min_support;
-  return SHK_OK;
-}
-
-int shk_pileup_enable(shk_ctx *ctx, uint32_t min_support) { return pileup_enable_kind(ctx, min_support, false, "shk_pileup_enable"); }
-int shk_pileup_enable_aligned(shk_ctx *ctx, uint32_t min_support) { return pileup_enable_kind(ctx, min_support, true, "shk_pileup_enable_aligned"); }
-
-// what every read-out starts with: the state rules, the stream drained behind everything enqueued so far, the mate counter and its guard
-static int pileup_read_mates(shk_ctx *ctx, const char *who, uint64_t *n_mates)
-{
-  if (!ctx->d_pileup_mates) { ctx->last_error = std::string(who) + ": pileup mode was never enabled on this context"; return SHK_ERR_STATE; }
-  if (tickets_outstanding(ctx)) { ctx->last_error = std::string(who) + ": tickets are outstanding (wait for them first)"; return SHK_ERR_STATE; }
-  SHK_HIP(ctx, hipSetDevice(ctx->prm.device));
-  unsigned long long m = 0;
-  SHK_HIP(ctx, hipMemcpyAsync(&m, ctx->d_pileup_mates, sizeof(m), hipMemcpyDeviceToHost, ctx->stream));
-  SHK_HIP(ctx, hipStreamSynchronize(ctx->stream));
-  if (n_mates) *n_mates = m;
-  if (m > 0xFFFFFFFFull) { ctx->last_error = std::string(who) + ": more than 2^32-1 pileup mates since the last reset (32-bit counters)"; return SHK_ERR_INDEX_TOO_LARGE; }
-  return SHK_OK;
-}
-
-int shk_pileup_mates(const shk_ctx *cctx, uint64_t *n)
-{
-  if (!cctx || !n) return SHK_ERR_ARG;
-  return pileup_read_mates(const_cast<shk_ctx *>(cctx), "shk_pileup_mates", n);
-}
-
-int shk_pileup_get_all(shk_ctx *ctx, uint32_t *counts, uint64_t cap, int device)
-{
-  if (!ctx) return SHK_ERR_ARG;
-  const int rc = pileup_read_mates(ctx, "shk_pileup_get_all", nullptr);
-  if (rc) return rc;
-  const uint64_t total = 4 * ctx->gene_start.back();
-  if (cap < total || (!counts && total)) return SHK_ERR_ARG;
-  if (total == 0) return SHK_OK;
-  // (the counters are the answer: no scan, one copy)
-  SHK_HIP(ctx, hipMemcpyAsync(counts, ctx->d_pileup, total * sizeof(uint32_t), device ? hipMemcpyDeviceToDevice : hipMemcpyDeviceToHost, ctx->stream));
-  SHK_HIP(ctx, hipStreamSynchronize(ctx->stream));
-  return SHK_OK;
-}
-
-int shk_pileup_get(shk_ctx *ctx, uint32_t gene, uint32_t *counts, uint64_t cap)
-{
-  if (!ctx) return SHK_ERR_ARG;
-  const int rc = pileup_read_mates(ctx, "shk_pileup_get", nullptr);
-  if (rc) return rc;
-  if ((uint64_t)gene + 1 >= ctx->gene_start.size()) return SHK_ERR_ARG;
-  const uint64_t a = 4 * ctx->gene_start[gene], len = 4 * ctx->gene_start[gene + 1] - a;
-  if (cap < len || (!counts && len)) return SHK_ERR_ARG;
-  if (len == 0) return SHK_OK;
-  SHK_HIP(ctx, hipMemcpyAsync(counts, ctx->d_pileup + a, len * sizeof(uint32_t), hipMemcpyDeviceToHost, ctx->stream));
-  SHK_HIP(ctx, hipStreamSynchronize(ctx->stream));
-  return SHK_OK;
-}
-
-int shk_pileup_reset(shk_ctx *ctx)
-{
-  if (!ctx) return SHK_ERR_ARG;
-  if (!ctx->d_pileup_mates) { ctx->last_error = "shk_pileup_reset: pileup mode was never enabled on this context"; return SHK_ERR_STATE; }
-  if (tickets_outstanding(ctx)) { ctx->last_error = "shk_pileup_reset: tickets are outstanding (wait for them first)"; return SHK_ERR_STATE; }
-  SHK_HIP(ctx, hipSetDevice(ctx->prm.device));
-  SHK_HIP(ctx, hipMemsetAsync(ctx->d_pileup, 0, pileup_bytes(ctx), ctx->stream));
-  SHK_HIP(ctx, hipMemsetAsync(ctx->d_pileup_mates, 0, sizeof(unsigned long long), ctx->stream));
-  ctx->pileup_dirty = false;
-  SHK_HIP(ctx, hipStreamSynchronize(ctx->stream));
-  return SHK_OK;
-}
-
+// a caller's counters (another worker's or rank's state) added to the pileup state
 int shk_pileup_add(shk_ctx *ctx, const uint32_t *counts, uint64_t n_entries, uint64_t mates, int device)
 {
   if (!ctx) return SHK_ERR_ARG;
-  if (!ctx->d_pileup_mates) { ctx->last_error = "shk_pileup_add: pileup mode was never enabled on this context"; return SHK_ERR_STATE; }
-  if (tickets_outstanding(ctx)) { ctx->last_error = "shk_pileup_add: tickets are outstanding (wait for them first)"; return SHK_ERR_STATE; }
+  if (const int rc = state_ready(ctx, "shk_pileup_add", ctx->pileup.mates.p != nullptr, "pileup mode")) return rc;
   if (n_entries != 4 * ctx->gene_start.back() || (!counts && n_entries)) { ctx->last_error = "shk_pileup_add: n_entries is not 4 * gene_start[nidx]"; return SHK_ERR_ARG; }
-  SHK_HIP(ctx, hipSetDevice(ctx->prm.device));
   uint32_t *staged = nullptr;
   if (!device && n_entries) {
     // (once per worker or rank and sample: a buffer for the length of the call)
@@ -1681,9 +1625,9 @@ static int variants_check(shk_ctx *ctx, const char *who, const shk_variant_param
     ctx->last_error = std::string(who) + ": parameters outside min_depth >= 1, min_alt >= 1, 1 <= frac_den <= 65535, frac_num <= frac_den";
     return SHK_ERR_ARG;
   }
-  if (!ctx->d_pileup_mates) { ctx->last_error = std::string(who) + ": pileup mode was never enabled on this context"; return SHK_ERR_STATE; }
+  if (!ctx->pileup.mates.p) { ctx->last_error = std::string(who) + ": pileup mode was never enabled on this context"; return SHK_ERR_STATE; }
   if (!ctx->idx.recbase) { ctx->last_error = std::string(who) + ": the index was finalized without shk_ref_keep_bases"; return SHK_ERR_STATE; }
-  return pileup_read_mates(ctx, who, nullptr);   // (tickets, the stream drained, the mate guard)
+  return counters_read_mates(ctx, PILEUP_RULES, who, nullptr);   // (tickets, the stream drained, the mate guard)
 }
 
 int shk_variants_get(shk_ctx *ctx, const shk_variant_params *p, shk_variant *out, uint64_t cap, uint64_t *n)
@@ -1700,7 +1644,7 @@ int shk_variants_summary(shk_ctx *ctx, const shk_variant_params *p, shk_gene_var
   if ((uint64_t)n_genes + 1 > ctx->gene_start.size() || (!out && n_genes)) return SHK_ERR_ARG;
   if (n_genes == 0) return SHK_OK;
   if (const int rc = launch_variants_summary(ctx, *p)) return rc;
-  SHK_HIP(ctx, hipMemcpyAsync(out, ctx->d_var_summary, (size_t)n_genes * sizeof(shk_gene_variants), hipMemcpyDeviceToHost, ctx->stream));
+  SHK_HIP(ctx, hipMemcpyAsync(out, ctx->var.summary.p, (size_t)n_genes * sizeof(shk_gene_variants), hipMemcpyDeviceToHost, ctx->stream));
   SHK_HIP(ctx, hipStreamSynchronize(ctx->stream));
   return SHK_OK;
 }
@@ -1709,7 +1653,7 @@ int shk_variants_summary(shk_ctx *ctx, const shk_variant_params *p, shk_gene_var
 int shk_alignments_enable(shk_ctx *ctx, uint32_t min_support)
 {
   if (!ctx) return SHK_ERR_ARG;
-  if (tickets_outstanding(ctx)) { ctx->last_error = "shk_alignments_enable: tickets are outstanding (wait for them first)"; return SHK_ERR_STATE; }
+  if (const int rc = refuse_tickets(ctx, "shk_alignments_enable")) return rc;
   if (min_support) {
     if (const int rc = check_mode_index(ctx, "shk_alignments_enable", NEED_GENE_START | NEED_BASES)) return rc;
   }
@@ -1721,26 +1665,18 @@ int shk_alignments_extend(shk_ctx *ctx, uint32_t mismatch_penalty, uint32_t end_
 {
   if (!ctx) return SHK_ERR_ARG;
   if (mismatch_penalty > 15 || end_bonus > 15) { ctx->last_error = "shk_alignments_extend: mismatch_penalty and end_bonus are at most 15"; return SHK_ERR_ARG; }
-  if (tickets_outstanding(ctx)) { ctx->last_error = "shk_alignments_extend: tickets are outstanding (wait for them first)"; return SHK_ERR_STATE; }
+  if (const int rc = refuse_tickets(ctx, "shk_alignments_extend")) return rc;
   ctx->ext_p = mismatch_penalty;
   ctx->ext_b = end_bonus;
   return SHK_OK;
 }
 
 // ---- spliced ends (align.hip's step 3b): the context's site list and the step's parameters ----
-static void splice_sites_drop(shk_ctx *ctx)
-{
-  (void)hipFree(ctx->d_splice);
-  ctx->d_splice = nullptr;
-  ctx->splice_sites.clear();
-  ctx->splice_sites.shrink_to_fit();
-}
-
 int shk_splice_sites_set(shk_ctx *ctx, const shk_splice_site *sites, uint64_t n)
 {
   if (!ctx || (!sites && n)) return SHK_ERR_ARG;
   if (const int rc = check_mode_index(ctx, "shk_splice_sites_set", NEED_GENE_START)) return rc;
-  if (tickets_outstanding(ctx)) { ctx->last_error = "shk_splice_sites_set: tickets are outstanding (wait for them first)"; return SHK_ERR_STATE; }
+  if (const int rc = refuse_tickets(ctx, "shk_splice_sites_set")) return rc;
   if (n >= (1ull << 31)) { ctx->last_error = "shk_splice_sites_set: fewer than 2^31 sites"; return SHK_ERR_ARG; }
   const uint64_t n_genes = ctx->gene_start.size() - 1;
   for (uint64_t i = 0; i < n; ++i) {
@@ -1756,8 +1692,9 @@ int shk_splice_sites_set(shk_ctx *ctx, const shk_splice_site *sites, uint64_t n)
   SHK_HIP(ctx, hipSetDevice(ctx->prm.device));
   SHK_HIP(ctx, hipStreamSynchronize(ctx->stream));   // (the list a batch read may go)
   if (n == 0) {
-    splice_sites_drop(ctx);
-    ctx->spl_h = 0;
+    (void)ctx->splice.d.release();
+    std::vector<shk_splice_site>().swap(ctx->splice.sites);
+    ctx->splice.h = 0;
     return SHK_OK;
   }
   std::vector<uint32_t> off;
@@ -1782,19 +1719,16 @@ int shk_splice_sites_set(shk_ctx *ctx, const shk_splice_site *sites, uint64_t n)
   }
   // the new list is whole on the device before the earlier one goes: a call that fails leaves the context as it was
   const size_t word = shk::splice_sites_word((uint32_t)n_genes);
-  uint32_t *d_new = nullptr;
-  SHK_HIP(ctx, hipMalloc((void **)&d_new, (word + 4 * n) * sizeof(uint32_t)));
+  DevArray<uint32_t> fresh;
+  if (const int rc = fresh.alloc_exact(ctx, word + 4 * n)) return rc;
+  uint32_t *const d_new = fresh.p;
   hipError_t e = hipMemcpyAsync(d_new, off.data(), off.size() * sizeof(uint32_t), hipMemcpyHostToDevice, ctx->stream);
   if (e == hipSuccess) e = hipMemcpyAsync(d_new + word, by_donor.data(), n * sizeof(uint2), hipMemcpyHostToDevice, ctx->stream);
   if (e == hipSuccess) e = hipMemcpyAsync(d_new + word + 2 * n, by_acceptor.data(), n * sizeof(uint2), hipMemcpyHostToDevice, ctx->stream);
   if (e == hipSuccess) e = hipStreamSynchronize(ctx->stream);   // (the vectors go with this call)
-  if (e != hipSuccess) {
-    (void)hipFree(d_new);
-    return shk::set_hip_error(ctx, e, "shk_splice_sites_set: copying the list");
-  }
-  splice_sites_drop(ctx);
-  ctx->splice_sites.swap(own);
-  ctx->d_splice = d_new;
+  if (e != hipSuccess) return shk::set_hip_error(ctx, e, "shk_splice_sites_set: copying the list");
+  ctx->splice.d = std::move(fresh);
+  ctx->splice.sites.swap(own);
   return SHK_OK;
 }
 
@@ -1805,11 +1739,11 @@ int shk_alignments_splice(shk_ctx *ctx, uint32_t min_overhang, uint32_t max_cost
     ctx->last_error = "shk_alignments_splice: min_overhang is at most SHK_SPLICE_MAX_OVERHANG, max_cost and min_gap at most 64";
     return SHK_ERR_ARG;
   }
-  if (tickets_outstanding(ctx)) { ctx->last_error = "shk_alignments_splice: tickets are outstanding (wait for them first)"; return SHK_ERR_STATE; }
-  if (min_overhang && !ctx->d_splice) { ctx->last_error = "shk_alignments_splice: no site list (shk_splice_sites_set first)"; return SHK_ERR_STATE; }
-  ctx->spl_h = min_overhang;
-  ctx->spl_cost = max_cost;
-  ctx->spl_gap = min_gap;
+  if (const int rc = refuse_tickets(ctx, "shk_alignments_splice")) return rc;
+  if (min_overhang && !ctx->splice.d.p) { ctx->last_error = "shk_alignments_splice: no site list (shk_splice_sites_set first)"; return SHK_ERR_STATE; }
+  ctx->splice.h = min_overhang;
+  ctx->splice.cost = max_cost;
+  ctx->splice.gap = min_gap;
   return SHK_OK;
 }
 
@@ -1826,31 +1760,22 @@ int shk_alignments_last(const shk_ctx *ctx, shk_alignments *out)
 int shk_pairs_enable(shk_ctx *ctx, uint32_t min_intron, uint32_t max_frag, uint32_t n_bins)
 {
   if (!ctx) return SHK_ERR_ARG;
-  if (tickets_outstanding(ctx)) { ctx->last_error = "shk_pairs_enable: tickets are outstanding (wait for them first)"; return SHK_ERR_STATE; }
+  if (const int rc = refuse_tickets(ctx, "shk_pairs_enable")) return rc;
   if (n_bins) {
     if (n_bins < 2 || n_bins > 4096 || min_intron < 1) { ctx->last_error = "shk_pairs_enable: n_bins is 0 or 2 .. 4096 and min_intron at least 1"; return SHK_ERR_ARG; }
     if (const int rc = check_mode_index(ctx, "shk_pairs_enable", NEED_GENE_START | NEED_BASES)) return rc;
     if (!ctx->align) { ctx->last_error = "shk_pairs_enable: alignments mode is off (shk_alignments_enable first)"; return SHK_ERR_STATE; }
-    if (ctx->d_frag && n_bins != ctx->frag_bins) {
-      if (ctx->frag_dirty) { ctx->last_error = "shk_pairs_enable: another n_bins than the state's (shk_fragments_reset first)"; return SHK_ERR_ARG; }
-      SHK_HIP(ctx, hipSetDevice(ctx->prm.device));
-      SHK_HIP(ctx, hipStreamSynchronize(ctx->stream));
-      (void)hipFree(ctx->d_frag);
-      ctx->d_frag = nullptr;
-      ctx->frag_bins = 0;
-    }
-    if (!ctx->d_frag) {
-      SHK_HIP(ctx, hipSetDevice(ctx->prm.device));
-      const size_t bytes = ((size_t)n_bins + 6) * sizeof(unsigned long long);
-      SHK_HIP(ctx, hipMalloc((void **)&ctx->d_frag, bytes));
-      ctx->frag_bins = n_bins;
-      ctx->frag_dirty = false;
-      SHK_HIP(ctx, hipMemsetAsync(ctx->d_frag, 0, bytes, ctx->stream));
-    }
-    ctx->pairs_min_intron = min_intron;
-    ctx->pairs_max_frag = max_frag;
+    FragmentState &F = ctx->frag;
+    const size_t entries = (size_t)n_bins + 6;
+    if (const int rc = state_shape(ctx, F.hist, entries, F.dirty, "shk_pairs_enable: another n_bins than the state's (shk_fragments_reset first)", [&]() -> int {
+          SHK_HIP(ctx, hipMemsetAsync(F.hist.p, 0, entries * sizeof(unsigned long long), ctx->stream));
+          return SHK_OK;
+        }))
+      return rc;
+    F.min_intron = min_intron;
+    F.max_frag = max_frag;
   }
-  ctx->pairs_bins = n_bins;
+  ctx->frag.n_bins = n_bins;
   return SHK_OK;
 }
 
@@ -1867,7 +1792,7 @@ int shk_pairs_last(const shk_ctx *ctx, shk_pairs *out)
 int shk_rescue_enable(shk_ctx *ctx, uint32_t min_intron, uint32_t max_frag, uint32_t max_cost, uint32_t min_gap)
 {
   if (!ctx) return SHK_ERR_ARG;
-  if (tickets_outstanding(ctx)) { ctx->last_error = "shk_rescue_enable: tickets are outstanding (wait for them first)"; return SHK_ERR_STATE; }
+  if (const int rc = refuse_tickets(ctx, "shk_rescue_enable")) return rc;
   if (max_frag) {
     if (max_frag > 4096 || min_intron < 1 || max_cost > 255 || min_gap > 255) {
       ctx->last_error = "shk_rescue_enable: max_frag is 0 or 1 .. 4096, min_intron at least 1, max_cost and min_gap at most 255";
@@ -1895,12 +1820,10 @@ int shk_rescue_last(const shk_ctx *ctx, shk_rescues *out)
 int shk_fragments_get(shk_ctx *ctx, uint64_t *hist, uint32_t n_bins, uint64_t classes[6])
 {
   if (!ctx || !hist || !classes) return SHK_ERR_ARG;
-  if (!ctx->d_frag) { ctx->last_error = "shk_fragments_get: pairs mode was never enabled on this context"; return SHK_ERR_STATE; }
-  if (tickets_outstanding(ctx)) { ctx->last_error = "shk_fragments_get: tickets are outstanding (wait for them first)"; return SHK_ERR_STATE; }
-  if (n_bins != ctx->frag_bins) { ctx->last_error = "shk_fragments_get: n_bins is not the state's"; return SHK_ERR_ARG; }
-  SHK_HIP(ctx, hipSetDevice(ctx->prm.device));
+  if (const int rc = state_ready(ctx, "shk_fragments_get", ctx->frag.hist.p != nullptr, "pairs mode")) return rc;
+  if (n_bins != ctx->frag.bins()) { ctx->last_error = "shk_fragments_get: n_bins is not the state's"; return SHK_ERR_ARG; }
   std::vector<unsigned long long> h((size_t)n_bins + 6);
-  SHK_HIP(ctx, hipMemcpyAsync(h.data(), ctx->d_frag, h.size() * sizeof(unsigned long long), hipMemcpyDeviceToHost, ctx->stream));
+  SHK_HIP(ctx, hipMemcpyAsync(h.data(), ctx->frag.hist.p, h.size() * sizeof(unsigned long long), hipMemcpyDeviceToHost, ctx->stream));
   SHK_HIP(ctx, hipStreamSynchronize(ctx->stream));
   for (uint32_t b = 0; b < n_bins; ++b) hist[b] = h[b];
   for (uint32_t c = 0; c < 6; ++c) classes[c] = h[(size_t)n_bins + c];
@@ -1910,11 +1833,10 @@ int shk_fragments_get(shk_ctx *ctx, uint64_t *hist, uint32_t n_bins, uint64_t cl
 int shk_fragments_reset(shk_ctx *ctx)
 {
   if (!ctx) return SHK_ERR_ARG;
-  if (!ctx->d_frag) { ctx->last_error = "shk_fragments_reset: pairs mode was never enabled on this context"; return SHK_ERR_STATE; }
-  if (tickets_outstanding(ctx)) { ctx->last_error = "shk_fragments_reset: tickets are outstanding (wait for them first)"; return SHK_ERR_STATE; }
-  SHK_HIP(ctx, hipSetDevice(ctx->prm.device));
-  SHK_HIP(ctx, hipMemsetAsync(ctx->d_frag, 0, ((size_t)ctx->frag_bins + 6) * sizeof(unsigned long long), ctx->stream));
-  ctx->frag_dirty = false;
+  FragmentState &F = ctx->frag;
+  if (const int rc = state_ready(ctx, "shk_fragments_reset", F.hist.p != nullptr, "pairs mode")) return rc;
+  SHK_HIP(ctx, hipMemsetAsync(F.hist.p, 0, F.hist.cap * sizeof(unsigned long long), ctx->stream));
+  F.dirty = false;
   SHK_HIP(ctx, hipStreamSynchronize(ctx->stream));
   return SHK_OK;
 }

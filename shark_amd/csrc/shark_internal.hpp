@@ -325,26 +325,8 @@ constexpr int PIPE_DEPTH = 3;      // batches shk_classify_submit keeps in fligh
 struct Ctx;
 int set_hip_error(Ctx *ctx, hipError_t e, const char *what);
 
-// a buffer that only grows, for callers that keep pointer and capacity themselves (Ctx::d_scratch, the variants' records); Array's rule
-template <typename T>
-int ensure_capacity(Ctx *ctx, T **ptr, size_t *cap, size_t need)
-{
-  if (need <= *cap && *ptr) return SHK_OK;
-  if (*ptr) {
-    hipError_t e = hipFree(*ptr);
-    *ptr = nullptr;
-    *cap = 0;
-    if (e != hipSuccess) return set_hip_error(ctx, e, "hipFree");
-  }
-  size_t want = need + need / 4 + 64;
-  hipError_t e = hipMalloc((void **)ptr, want * sizeof(T));
-  if (e != hipSuccess) return set_hip_error(ctx, e, "hipMalloc");
-  *cap = want;
-  return SHK_OK;
-}
-
-// ---- a growable buffer that owns its memory: device (hipMalloc) or pinned host (hipHostMalloc); cap counts entries.  Movable, not
-// copyable, freed by its destructor: a Slot frees what it owns, `s = Slot{}` included ----
+// ---- a buffer that owns its memory: device (hipMalloc) or pinned host (hipHostMalloc); cap counts entries.  Movable, not
+// copyable, freed by its destructor: a Slot frees what it owns, `s = Slot{}` included, and so does a Ctx (delete ctx) ----
 template <typename T, bool PINNED>
 struct Array {
   T *p = nullptr;
@@ -359,26 +341,28 @@ struct Array {
     return *this;
   }
   ~Array() { release(); }
-  void release()
+  hipError_t release()
   {
-    if (p) (void)(PINNED ? hipHostFree(p) : hipFree(p));
+    const hipError_t e = !p ? hipSuccess : PINNED ? hipHostFree(p) : hipFree(p);
     p = nullptr;
     cap = 0;
+    return e;
   }
-  // at least `need` entries (a quarter more and 64 where it has to grow; what it held is gone then)
+  // exactly n entries, newly allocated (what it held is gone): the context's states, which are sized by the index or by their caller
+  int alloc_exact(Ctx *ctx, size_t n)
+  {
+    hipError_t e = release();
+    if (e != hipSuccess && !PINNED) return set_hip_error(ctx, e, "hipFree");
+    e = PINNED ? hipHostMalloc((void **)&p, n * sizeof(T), hipHostMallocDefault) : hipMalloc((void **)&p, n * sizeof(T));
+    if (e != hipSuccess) return set_hip_error(ctx, e, PINNED ? "hipHostMalloc" : "hipMalloc");
+    cap = n;
+    return SHK_OK;
+  }
+  // at least `need` entries (a quarter more and 64 where it has to grow; what it held is gone then): the buffers that follow the batches
   int reserve(Ctx *ctx, size_t need)
   {
-    if constexpr (!PINNED) {
-      return ensure_capacity(ctx, &p, &cap, need);
-    } else {
-      if (need <= cap && p) return SHK_OK;
-      release();
-      const size_t want = need + need / 4 + 64;
-      hipError_t e = hipHostMalloc((void **)&p, want * sizeof(T), hipHostMallocDefault);
-      if (e != hipSuccess) return set_hip_error(ctx, e, "hipHostMalloc");
-      cap = want;
-      return SHK_OK;
-    }
+    if (need <= cap && p) return SHK_OK;
+    return alloc_exact(ctx, need + need / 4 + 64);
   }
 };
 template <typename T> using DevArray = Array<T, false>;
@@ -465,14 +449,14 @@ struct Slot {
   uint32_t align = 0;
   Mirrored<shk_mate_alignment> rec_align;
   // end extension (shk_alignments_extend) as submitted: mismatch penalty (0: off) and end bonus; aligned pileup (shk_pileup_enable_aligned):
-  // submitted with this floor (0: not) -- align_kernel's accumulating instantiation adds the batch to Ctx::d_pileup, pileup_kernel does not run
+  // submitted with this floor (0: not) -- align_kernel's accumulating instantiation adds the batch to Ctx::pileup, pileup_kernel does not run
   uint32_t ext_p = 0, ext_b = 0;
   uint32_t pileup_al = 0;
   // spliced ends (shk_alignments_splice) as submitted: min_overhang (0: off), max_cost, min_gap; the site list is the context's
   uint32_t spl_h = 0, spl_cost = 0, spl_gap = 0;
   // pairs mode (pairs.hip): submitted with this n_bins (0: not; only with `align`): pair_kernel ran behind the storing align_kernel, one
   // 32-byte record per association (rec_pairs, allocated with the first such batch for as many associations as d_gene_ids holds);
-  // pairs_count: the batch is added to Ctx::d_frag (not a shk_count_work batch)
+  // pairs_count: the batch is added to Ctx::frag (not a shk_count_work batch)
   uint32_t pairs = 0, pairs_min_intron = 0, pairs_max_frag = 0;
   bool pairs_count = false;
   Mirrored<shk_pair> rec_pairs;
@@ -485,7 +469,7 @@ struct Slot {
 };
 
 
-// Ctx::d_splice: the word at which the site arrays start behind the n_genes + 1 offsets (even: the pairs are 8-byte aligned)
+// SpliceSites::d: the word at which the site arrays start behind the n_genes + 1 offsets (even: the pairs are 8-byte aligned)
 __host__ __device__ inline uint32_t splice_sites_word(uint32_t n_genes) { return (n_genes + 2u) & ~1u; }
 
 // one entry of the junction table (spliced.hip): key = (gene_start[g] + donor) << 32 | (gene_start[g] + acceptor)
@@ -496,6 +480,57 @@ struct JunctionEntry {
 };
 static_assert(sizeof(JunctionEntry) == 16, "16-byte entries");
 constexpr unsigned long long JUNCTION_EMPTY = ~0ull;   // (no key: its acceptor half would be base 2^32 - 1 of a reference of fewer than 2^32 bases)
+
+// ---- the context's accumulated states: what the batches' tails add to and the read-outs read.  Each owns its device memory, sized exactly
+// (Array::alloc_exact) by the enable that finds it missing, and outlives its mode's being switched off; all of one state's arrays are
+// allocated or none is ----
+// uint32 counters along the reference with the mates counted into them: the depth state and the pileup state
+struct CounterState {
+  uint32_t floor = 0;                          // min_support for the batches submitted from now on (0: off)
+  bool kind = false;                           // the kind `floor` stands for, one per state: depth plain intervals (false) or the unions of kept spans (true, shk_depth_enable_spliced);
+                                               //  pileup owned pieces (false, pileup.hip) or the alignment's final blocks (true, align.hip)
+  bool dirty = false;                          // a batch of either kind was submitted since the first enable / the last reset
+  // depth: gene_start[nidx] + 1 entries: +1 at a counted mate's first base, -1 behind its last
+  // pileup: gene_start[nidx] x 4 counters, [x * 4 + b]: the observations of base b at x
+  DevArray<uint32_t> counts;
+  DevArray<unsigned long long> mates;          // counted mates since the last reset (not null: the mode was enabled once)
+};
+// depth mode (shk_depth_enable; depth.hip): its counters are a difference array, so its read-outs go through a scan
+struct DepthState : CounterState {
+  DevArray<uint32_t> scan;                     // read-out: exclusive scan of `counts` over all its entries; depth of base x at [1 + x] (allocated by the first read-out)
+  DevArray<uint64_t> scan_temp;
+  bool scan_current = false;                   // `scan` holds the scan of the state as it stands (cleared by every launch that adds to it and by reset)
+  DevArray<shk_gene_depth> summary;            // nidx records (allocated by the first shk_depth_summary)
+};
+// junction table (shk_junctions_enable; spliced.hip)
+struct JunctionState {
+  uint32_t floor = 0;                          // min_support for the batches submitted from now on (0: off)
+  bool dirty = false;                          // a junction batch was submitted since the first enable / the last reset
+  DevArray<JunctionEntry> tab;                 // tab.cap entries, a power of two >= 64 (null: never enabled)
+  DevArray<unsigned long long> dropped;        // observations that found the table full since the last reset (allocated in front of the first table, kept across a new capacity)
+};
+// pairs mode's parameters and the fragments state (shk_pairs_enable; pairs.hip)
+struct FragmentState {
+  uint32_t n_bins = 0;                         // n_bins for the batches submitted from now on (0: off)
+  uint32_t min_intron = 0, max_frag = 0;
+  bool dirty = false;                          // a pairs batch was submitted since the first enable / the last reset
+  DevArray<unsigned long long> hist;           // hist[bins()], classes[6] (null: never enabled)
+  uint32_t bins() const { return hist.p ? (uint32_t)(hist.cap - 6) : 0u; }   // the state's n_bins
+};
+// variants mode's scratch (shk_variants_get / _summary; variants.hip): read-outs of the pileup state; it only grows
+struct VariantScratch {
+  DevArray<uint32_t> waves;                    // sites per wavefront of 256 positions, then their exclusive scan
+  DevArray<uint64_t> temp;                     // exclusive_scan_u32's temp over `waves` (allocated with it)
+  DevArray<shk_variant> out;                   // records
+  DevArray<shk_gene_variants> summary;         // nidx records
+};
+// spliced ends (shk_splice_sites_set, shk_alignments_splice): the list as it was given (sorted by (gene, donor, acceptor)), on the device a
+// per-gene offset array and the sites as {donor, acceptor} in that order and as {acceptor, donor} in (acceptor, donor) order per gene
+struct SpliceSites {
+  std::vector<shk_splice_site> sites;
+  DevArray<uint32_t> d;                        // one allocation: n_genes + 1 offsets, then from word splice_sites_word(n_genes) on the two site arrays
+  uint32_t h = 0, cost = 0, gap = 0;           // shk_alignments_splice: min_overhang (0: off), max_cost, min_gap for the batches submitted from now on
+};
 
 // index_build.hip
 int build_index(Ctx *ctx);
@@ -514,30 +549,30 @@ int launch_depth_accumulate(Ctx *ctx, const Slot &s, bool skip_if_long, hipStrea
 // spliced.hip: the batch in `s` from its segments at m = SHK_MAX_SEGMENTS (`entries`, cap_assoc associations) into the depth state (s.sp_depth)
 // and / or the junction table (s.sp_junc), behind segments_kernel; skip_if_long: as launch_gene_hist
 int launch_spliced_accumulate(Ctx *ctx, const Slot &s, const shk_segment *entries, uint64_t cap_assoc, bool skip_if_long, hipStream_t stream);
-// pileup.hip: the batch in `s` from the same records into Ctx::d_pileup at floor s.pileup, behind segments_kernel; skip_if_long: as launch_gene_hist
+// pileup.hip: the batch in `s` from the same records into Ctx::pileup at floor s.pileup, behind segments_kernel; skip_if_long: as launch_gene_hist
 int launch_pileup(Ctx *ctx, const Slot &s, const shk_segment *entries, uint64_t cap_assoc, bool skip_if_long, hipStream_t stream);
 // align.hip: per association of the batch in `s` and per mate its blocks on the gene's record with their match and mismatch counts, from the
 // same records and DeviceIndex::recbase into s.rec_align.d at floor s.align, behind segments_kernel; skip_if_long: as launch_gene_hist
-// store: the records go to s.rec_align.d at floor s.align; accumulate: the final blocks' bases go to Ctx::d_pileup at floor s.pileup_al (one launch
+// store: the records go to s.rec_align.d at floor s.align; accumulate: the final blocks' bases go to Ctx::pileup at floor s.pileup_al (one launch
 // does both where the floors are equal).  With s.ext_p == 0 and no accumulation the kernel launched is the one this mode always launched
 int launch_alignments(Ctx *ctx, const Slot &s, const shk_segment *entries, uint64_t cap_assoc, bool skip_if_long, bool store, bool accumulate, hipStream_t stream);
 // pairs.hip: per association of the batch in `s` its pair record from the two mates' records in s.rec_align.d (cap_assoc: launch_alignments') into
-// s.rec_pairs.d and, where s.pairs_count, the batch into Ctx::d_frag; directly behind the storing launch_alignments; skip_if_long: as launch_gene_hist
+// s.rec_pairs.d and, where s.pairs_count, the batch into Ctx::frag; directly behind the storing launch_alignments; skip_if_long: as launch_gene_hist
 int launch_pairs(Ctx *ctx, const Slot &s, uint64_t cap_assoc, bool skip_if_long, hipStream_t stream);
 // rescue.hip: per association of the batch in `s` its rescue record into s.rec_rescue.d and, where a mate is rescued, that mate's record in
 // s.rec_align.d; directly behind the storing launch_alignments and in front of launch_pairs (cap_assoc, skip_if_long: launch_pairs')
 int launch_rescue(Ctx *ctx, const Slot &s, uint64_t cap_assoc, bool skip_if_long, hipStream_t stream);
-// variants.hip: d_pileup[i] += d_add[i] over n_entries counters (d_add 16-byte aligned: SHK_ERR_ARG otherwise), *d_pileup_mates += mates, on ctx->stream
+// variants.hip: pileup.counts[i] += d_add[i] over n_entries counters (d_add 16-byte aligned: SHK_ERR_ARG otherwise), *pileup.mates += mates, on ctx->stream
 int launch_pileup_add(Ctx *ctx, const uint32_t *d_add, uint64_t n_entries, uint64_t mates);
 // variants.hip: the sites of the pileup state against DeviceIndex::recbase: their number into *n_sites (host; the stream is drained) and, with
 // out != nullptr, the records in (gene, x) order into out[0 .. *n_sites) (host; SHK_ERR_ARG if cap is smaller, *n_sites set all the same)
 int variants_call(Ctx *ctx, const shk_variant_params &prm, shk_variant *out, uint64_t cap, uint64_t *n_sites);
-// variants.hip: per gene {observed, mismatches, covered, sites} into Ctx::d_var_summary (nidx records), on ctx->stream
+// variants.hip: per gene {observed, mismatches, covered, sites} into Ctx::var.summary (nidx records), on ctx->stream
 int launch_variants_summary(Ctx *ctx, const shk_variant_params &prm);
-int launch_junction_clear(Ctx *ctx);   // every entry of Ctx::d_junc_tab empty, Ctx::d_junc_dropped 0, on ctx->stream
-// the read-out: Ctx::d_depth_scan[1 + x] = depth of base x of the full array (inclusive prefix sum of the difference array), on ctx->stream
+int launch_junction_clear(Ctx *ctx);   // every entry of Ctx::junc.tab empty, its `dropped` 0, on ctx->stream
+// the read-out: Ctx::depth.scan[1 + x] = depth of base x of the full array (inclusive prefix sum of the difference array), on ctx->stream
 int depth_scan(Ctx *ctx);
-// per gene {len, covered, max, sum} of the scanned array into Ctx::d_depth_summary (nidx records), on ctx->stream behind depth_scan
+// per gene {len, covered, max, sum} of the scanned array into Ctx::depth.summary (nidx records), on ctx->stream behind depth_scan
 int launch_depth_summary(Ctx *ctx);
 
 // classify.hip
@@ -612,7 +647,7 @@ struct Ctx {
   Slot slots[PIPE_DEPTH + 1];
   uint64_t next_ticket = 1;
   hipStream_t h2d_stream = nullptr, d2h_stream = nullptr;
-  uint64_t *d_scratch = nullptr;   size_t cap_scratch = 0;
+  DevArray<uint64_t> scratch;
   unsigned long long *d_gene_counts = nullptr;
   unsigned long long *d_gene_totals = nullptr;   // result of the all-reduce (the per-GPU counters stay local)
   unsigned long long *d_work_counters = nullptr;
@@ -650,51 +685,18 @@ struct Ctx {
   bool placement = false;           // shk_placement_enable (an index built with shk_ref_keep_positions)
   uint32_t seg_m = 0;               // shk_segments_enable (segments.hip): entries per mate
   LastRecords last_rec;
-  // depth mode (shk_depth_enable; depth.hip): the state outlives the mode's being switched off
+  // the accumulated states (above), which outlive their modes' being switched off, and the list of splice sites
   std::vector<uint64_t> gene_start;            // host copy of DeviceIndex::gene_start (empty: the index carries none)
-  uint32_t depth = 0;                          // min_support for the batches submitted from now on (0: off)
-  uint32_t *d_depth_diff = nullptr;            // gene_start[nidx] + 1 entries: +1 at a counted mate's first base, -1 behind its last (allocated by the first enable)
-  unsigned long long *d_depth_mates = nullptr; // counted mates since the last reset
-  uint32_t *d_depth_scan = nullptr;            // read-out: exclusive scan of d_depth_diff over all its entries; depth of base x at [1 + x] (allocated by the first read-out)
-  uint64_t *d_depth_scan_temp = nullptr;
-  bool depth_scan_current = false;             // d_depth_scan holds the scan of the state as it stands (cleared by every launch that adds to it and by reset)
-  shk_gene_depth *d_depth_summary = nullptr;   // nidx records (allocated by the first shk_depth_summary)
-  // (shk_depth_enable_spliced) one state holds one kind: plain intervals or the unions of kept spans
-  bool depth_spliced = false;                  // the kind `depth` stands for
-  bool depth_dirty = false;                    // a depth batch of either kind was submitted since the first enable / the last reset
-  // junction table (shk_junctions_enable; spliced.hip): like the depth state it outlives the mode's being switched off
-  uint32_t junc = 0;                           // min_support for the batches submitted from now on (0: off)
-  uint64_t junc_cap = 0;                       // entries, a power of two >= 64 (0: never enabled)
-  JunctionEntry *d_junc_tab = nullptr;
-  unsigned long long *d_junc_dropped = nullptr;   // observations that found the table full since the last reset
-  bool junc_dirty = false;                     // a junction batch was submitted since the first enable / the last reset
-  // pileup mode (shk_pileup_enable; pileup.hip): like the depth state it outlives the mode's being switched off
-  uint32_t pileup = 0;                         // min_support for the batches submitted from now on (0: off)
-  uint32_t *d_pileup = nullptr;                // gene_start[nidx] x 4 counters, [x * 4 + b]: the observations of base b at x (allocated by the first enable)
-  unsigned long long *d_pileup_mates = nullptr;   // pileup mates since the last reset (not null: the mode was enabled once)
-  bool pileup_aligned = false;                 // the kind `pileup` stands for: owned pieces (pileup.hip) or the alignment's final blocks (align.hip)
-  bool pileup_dirty = false;                   // a pileup batch of either kind was submitted since the first enable / the last reset
-  // variants mode (shk_ref_keep_bases, shk_variants_get / _summary; variants.hip): read-outs of the pileup state; scratch only grows
-  bool keep_bases = false;                     // finalize builds DeviceIndex::recbase
-  uint32_t *d_var_waves = nullptr;             // sites per wavefront of 256 positions, then their exclusive scan
-  uint64_t *d_var_temp = nullptr;              // exclusive_scan_u32's temp over d_var_waves (allocated with it)
-  shk_variant *d_var_out = nullptr;   size_t cap_var_out = 0;   // records
-  shk_gene_variants *d_var_summary = nullptr;  // nidx records
+  DepthState depth;
+  JunctionState junc;
+  CounterState pileup;
+  FragmentState frag;
+  bool keep_bases = false;                     // finalize builds DeviceIndex::recbase (shk_ref_keep_bases)
+  VariantScratch var;
+  SpliceSites splice;
   // alignments mode (shk_alignments_enable; align.hip), as segments mode: the floor for the batches submitted from now on (0: off)
   uint32_t align = 0;
   uint32_t ext_p = 0, ext_b = 0;               // shk_alignments_extend: mismatch penalty (0: off) and end bonus for the batches submitted from now on
-  // spliced ends (shk_splice_sites_set, shk_alignments_splice): the list as it was given (sorted by (gene, donor, acceptor)), on the device a
-  // per-gene offset array and the sites as {donor, acceptor} in that order and as {acceptor, donor} in (acceptor, donor) order per gene
-  std::vector<shk_splice_site> splice_sites;
-  uint32_t *d_splice = nullptr;                // one allocation: n_genes + 1 offsets, then from word splice_sites_word(n_genes) on the two site arrays
-  uint32_t spl_h = 0, spl_cost = 0, spl_gap = 0;   // shk_alignments_splice: min_overhang (0: off), max_cost, min_gap for the batches submitted from now on
-  // pairs mode (shk_pairs_enable; pairs.hip): per-batch records as alignments mode's, and the fragments state, which like the depth state
-  // outlives the mode's being switched off
-  uint32_t pairs_bins = 0;                     // n_bins for the batches submitted from now on (0: off)
-  uint32_t pairs_min_intron = 0, pairs_max_frag = 0;
-  uint32_t frag_bins = 0;                      // the state's n_bins (0: never enabled)
-  unsigned long long *d_frag = nullptr;        // hist[frag_bins], classes[6] (allocated by the first enable)
-  bool frag_dirty = false;                     // a pairs batch was submitted since the first enable / the last reset
   bool env_pairs_global = false;               // SHK_PAIRS_GLOBAL_ATOMICS=1: the histogram by one global atomic per pair (A/B timing only)
   // rescue mode (shk_rescue_enable; rescue.hip): per-batch records as pairs mode's; no state of its own
   uint32_t rescue_max_frag = 0;                // for the batches submitted from now on (0: off)

@@ -163,7 +163,7 @@ int launch_spliced_accumulate(Ctx *ctx, const Slot &s, const shk_segment *entrie
 {
   const DeviceIndex &ix = ctx->idx;
   const bool depth = s.sp_depth != 0, junc = s.sp_junc != 0;
-  if (!ix.gene_start || !entries || (depth && (!ctx->d_depth_diff || !ctx->d_depth_mates)) || (junc && (!ctx->d_junc_tab || !ctx->d_junc_dropped || !ctx->junc_cap))) {
+  if (!ix.gene_start || !entries || (depth && (!ctx->depth.counts.p || !ctx->depth.mates.p)) || (junc && (!ctx->junc.tab.p || !ctx->junc.dropped.p))) {
     ctx->last_error = "spliced depth / junction table without its state";
     return SHK_ERR_STATE;
   }
@@ -183,15 +183,15 @@ int launch_spliced_accumulate(Ctx *ctx, const Slot &s, const shk_segment *entrie
   P.skip_if_long = skip_if_long ? 1u : 0u;
   if (depth) {
     P.depth_min = s.sp_depth;
-    P.diff = ctx->d_depth_diff;
-    P.mates = ctx->d_depth_mates;
-    ctx->depth_scan_current = false;
+    P.diff = ctx->depth.counts.p;
+    P.mates = ctx->depth.mates.p;
+    ctx->depth.scan_current = false;
   }
   if (junc) {
     P.junc_min = s.sp_junc;
-    P.tab = ctx->d_junc_tab;
-    P.tab_mask = ctx->junc_cap - 1;
-    P.dropped = ctx->d_junc_dropped;
+    P.tab = ctx->junc.tab.p;
+    P.tab_mask = ctx->junc.tab.cap - 1;
+    P.dropped = ctx->junc.dropped.p;
   }
   // one thread per read up to 2 048 workgroups, persistent beyond (launch_depth_accumulate's bound)
   const uint64_t want = (s.n + SP_THREADS - 1) / SP_THREADS;
@@ -202,8 +202,8 @@ int launch_spliced_accumulate(Ctx *ctx, const Slot &s, const shk_segment *entrie
 
 int launch_junction_clear(Ctx *ctx)
 {
-  const uint64_t want = (ctx->junc_cap + 255) / 256;
-  hipLaunchKernelGGL(junction_clear_kernel, dim3((unsigned)std::min<uint64_t>(want, 2048)), dim3(256), 0, ctx->stream, ctx->d_junc_tab, ctx->junc_cap, ctx->d_junc_dropped);
+  const uint64_t cap = ctx->junc.tab.cap, want = (cap + 255) / 256;
+  hipLaunchKernelGGL(junction_clear_kernel, dim3((unsigned)std::min<uint64_t>(want, 2048)), dim3(256), 0, ctx->stream, ctx->junc.tab.p, cap, ctx->junc.dropped.p);
   const hipError_t e = hipGetLastError();
   return e == hipSuccess ? SHK_OK : set_hip_error(ctx, e, "junction_clear_kernel");
 }

@@ -207,7 +207,7 @@ __global__ __launch_bounds__(VR_THREADS) void pileup_add_kernel(uint4 *__restric
 VarParams var_params(const Ctx *ctx, const shk_variant_params &prm)
 {
   VarParams P{};
-  P.counts = ctx->d_pileup;
+  P.counts = ctx->pileup.counts.p;
   P.recbase = ctx->idx.recbase;
   P.total = ctx->gene_start.back();
   P.min_depth = prm.min_depth; P.min_alt = prm.min_alt; P.frac_num = prm.frac_num; P.frac_den = prm.frac_den;
@@ -218,32 +218,34 @@ VarParams var_params(const Ctx *ctx, const shk_variant_params &prm)
 
 int launch_pileup_add(Ctx *ctx, const uint32_t *d_add, uint64_t n_entries, uint64_t mates)
 {
-  if (!ctx->d_pileup || !ctx->d_pileup_mates) { ctx->last_error = "pileup mode without its state"; return SHK_ERR_STATE; }
+  if (!ctx->pileup.counts.p || !ctx->pileup.mates.p) { ctx->last_error = "pileup mode without its state"; return SHK_ERR_STATE; }
   if (n_entries == 0 && mates == 0) return SHK_OK;
   // (the state comes from hipMalloc; a caller's device pointer has to be as aligned as a base's four counters are)
   if (reinterpret_cast<uintptr_t>(d_add) & 15u) { ctx->last_error = "shk_pileup_add: the device pointer is not 16-byte aligned"; return SHK_ERR_ARG; }
   const uint64_t n_bases = n_entries / 4;
   const unsigned grid = (unsigned)std::max<uint64_t>(1, std::min<uint64_t>((n_bases + VR_THREADS - 1) / VR_THREADS, 8192));
-  hipLaunchKernelGGL(pileup_add_kernel, dim3(grid), dim3(VR_THREADS), 0, ctx->stream, reinterpret_cast<uint4 *>(ctx->d_pileup), reinterpret_cast<const uint4 *>(d_add), n_bases,
-                     ctx->d_pileup_mates, (unsigned long long)mates);
+  hipLaunchKernelGGL(pileup_add_kernel, dim3(grid), dim3(VR_THREADS), 0, ctx->stream, reinterpret_cast<uint4 *>(ctx->pileup.counts.p), reinterpret_cast<const uint4 *>(d_add), n_bases,
+                     ctx->pileup.mates.p, (unsigned long long)mates);
   const hipError_t e = hipGetLastError();
   return e == hipSuccess ? SHK_OK : set_hip_error(ctx, e, "pileup_add_kernel");
 }
 
 int variants_call(Ctx *ctx, const shk_variant_params &prm, shk_variant *out, uint64_t cap, uint64_t *n_sites)
 {
-  if (!ctx->d_pileup || !ctx->idx.recbase || !ctx->idx.gene_start) { ctx->last_error = "variants mode without its state"; return SHK_ERR_STATE; }
+  if (!ctx->pileup.counts.p || !ctx->idx.recbase || !ctx->idx.gene_start) { ctx->last_error = "variants mode without its state"; return SHK_ERR_STATE; }
   const VarParams P = var_params(ctx, prm);
   *n_sites = 0;
   if (P.total == 0) return SHK_OK;
   const uint64_t n_waves = (P.total + VR_WAVE_POS - 1) / VR_WAVE_POS;
   const unsigned grid = (unsigned)((P.total + VR_BLOCK_POS - 1) / VR_BLOCK_POS);   // (total < 2^32: at most 2^22 workgroups)
   // (a property of the index: allocated once)
-  if (!ctx->d_var_waves) SHK_HIP(ctx, hipMalloc((void **)&ctx->d_var_waves, n_waves * sizeof(uint32_t)));
-  if (!ctx->d_var_temp) SHK_HIP(ctx, hipMalloc((void **)&ctx->d_var_temp, scan_temp_words(n_waves) * sizeof(uint64_t)));
-  hipLaunchKernelGGL(variants_count_kernel, dim3(grid), dim3(VR_THREADS), 0, ctx->stream, P, ctx->d_var_waves);
+  VariantScratch &V = ctx->var;
+  int rc;
+  if (!V.waves.p && (rc = V.waves.alloc_exact(ctx, n_waves))) return rc;
+  if (!V.temp.p && (rc = V.temp.alloc_exact(ctx, scan_temp_words(n_waves)))) return rc;
+  hipLaunchKernelGGL(variants_count_kernel, dim3(grid), dim3(VR_THREADS), 0, ctx->stream, P, V.waves.p);
   SHK_HIP(ctx, hipGetLastError());
-  const uint64_t *d_total = exclusive_scan_u32(ctx->d_var_waves, ctx->d_var_waves, n_waves, ctx->d_var_temp, ctx->stream);
+  const uint64_t *d_total = exclusive_scan_u32(V.waves.p, V.waves.p, n_waves, V.temp.p, ctx->stream);
   SHK_HIP(ctx, hipGetLastError());
   uint64_t n = 0;
   SHK_HIP(ctx, hipMemcpyAsync(&n, d_total, sizeof(n), hipMemcpyDeviceToHost, ctx->stream));
@@ -251,30 +253,28 @@ int variants_call(Ctx *ctx, const shk_variant_params &prm, shk_variant *out, uin
   *n_sites = n;
   if (!out || n == 0) return SHK_OK;
   if (cap < n) return SHK_ERR_ARG;
-  if (ctx->cap_var_out < n) {
-    if (ctx->d_var_out) { (void)hipFree(ctx->d_var_out); ctx->d_var_out = nullptr; ctx->cap_var_out = 0; }
-    SHK_HIP(ctx, hipMalloc((void **)&ctx->d_var_out, (size_t)n * sizeof(shk_variant)));
-    ctx->cap_var_out = (size_t)n;
-  }
-  hipLaunchKernelGGL(variants_write_kernel, dim3(grid), dim3(VR_THREADS), 0, ctx->stream, P, (const uint32_t *)ctx->d_var_waves,
-                     (const uint64_t *)ctx->idx.gene_start, (uint32_t)(ctx->gene_start.size() - 1), ctx->d_var_out, n);
+  if (V.out.cap < n && (rc = V.out.alloc_exact(ctx, (size_t)n))) return rc;
+  hipLaunchKernelGGL(variants_write_kernel, dim3(grid), dim3(VR_THREADS), 0, ctx->stream, P, (const uint32_t *)V.waves.p,
+                     (const uint64_t *)ctx->idx.gene_start, (uint32_t)(ctx->gene_start.size() - 1), V.out.p, n);
   SHK_HIP(ctx, hipGetLastError());
-  SHK_HIP(ctx, hipMemcpyAsync(out, ctx->d_var_out, (size_t)n * sizeof(shk_variant), hipMemcpyDeviceToHost, ctx->stream));
+  SHK_HIP(ctx, hipMemcpyAsync(out, V.out.p, (size_t)n * sizeof(shk_variant), hipMemcpyDeviceToHost, ctx->stream));
   SHK_HIP(ctx, hipStreamSynchronize(ctx->stream));
   return SHK_OK;
 }
 
 int launch_variants_summary(Ctx *ctx, const shk_variant_params &prm)
 {
-  if (!ctx->d_pileup || !ctx->idx.recbase || !ctx->idx.gene_start) { ctx->last_error = "variants mode without its state"; return SHK_ERR_STATE; }
+  if (!ctx->pileup.counts.p || !ctx->idx.recbase || !ctx->idx.gene_start) { ctx->last_error = "variants mode without its state"; return SHK_ERR_STATE; }
   const uint32_t n_genes = (uint32_t)(ctx->gene_start.size() - 1);
   if (n_genes == 0) return SHK_OK;
-  if (!ctx->d_var_summary) SHK_HIP(ctx, hipMalloc((void **)&ctx->d_var_summary, (size_t)n_genes * sizeof(shk_gene_variants)));
-  SHK_HIP(ctx, hipMemsetAsync(ctx->d_var_summary, 0, (size_t)n_genes * sizeof(shk_gene_variants), ctx->stream));
+  DevArray<shk_gene_variants> &summary = ctx->var.summary;
+  if (!summary.p)
+    if (const int rc = summary.alloc_exact(ctx, n_genes)) return rc;
+  SHK_HIP(ctx, hipMemsetAsync(summary.p, 0, (size_t)n_genes * sizeof(shk_gene_variants), ctx->stream));
   const VarParams P = var_params(ctx, prm);
   if (P.total == 0) return SHK_OK;
   const unsigned grid = (unsigned)((P.total + VR_BLOCK_POS - 1) / VR_BLOCK_POS);
-  hipLaunchKernelGGL(variants_summary_kernel, dim3(grid), dim3(VR_THREADS), 0, ctx->stream, P, (const uint64_t *)ctx->idx.gene_start, n_genes, ctx->d_var_summary);
+  hipLaunchKernelGGL(variants_summary_kernel, dim3(grid), dim3(VR_THREADS), 0, ctx->stream, P, (const uint64_t *)ctx->idx.gene_start, n_genes, summary.p);
   SHK_HIP(ctx, hipGetLastError());
   return SHK_OK;
 }
