@@ -790,6 +790,78 @@ int shk_alignments_last(const shk_ctx *ctx, shk_alignments *out);
  * behind L.  New: no counterpart. */
 int shk_alignment_cigar(const shk_mate_alignment *a, uint32_t L, uint32_t min_intron, char *buf, size_t cap, uint32_t *nm);
 
+/* ---- indels: the insertions and deletions the mates' alignments show, tabled on the device over all batches ---- */
+/* Variants mode reports where the sample differs from the record by one base; the CIGAR of a mate's alignment spells an inserted or
+ * deleted stretch as I or D, one text line per mate.  Indels mode aggregates those gaps: one table entry per distinct event, with the
+ * number of mates that show it on either strand.  It rests on the alignments section's definitions, unchanged: FINAL BLOCKS (those
+ * after trimming, closure and, at the context's current parameters, steps 3b and 3a), read coordinate q, the read base on the record's
+ * strand (0 .. 3; 4 for a byte that is no base or is masked by -q) and the record's code r (0 .. 3, else 4).
+ *
+ * GAP.  For each association, each mate of it with n_blocks >= 2 and each consecutive pair of its blocks (A, B):
+ *   xa = x_A + len_A,  qa = q_A + len_A,  R = q_B - qa,  G = x_B - xa.
+ *     R == 0 and 1 <= G < min_intron    DELETION of record bases [xa, xa + G)                               counted as `deletions`
+ *     G == 0 and R >= 1                 INSERTION of the R read bases s[t] = read base qa + t, t < R,
+ *                                       in front of record base xa                                         counted as `insertions`
+ *     R >= 1 and G >= 1                 COMPLEX (closure left it open: G < R or R > 64), not tabled        counted as `complex_gaps`
+ *     R == 0 and (G == 0 or G >= min_intron)   nothing (blocks that touch; an intron)
+ *   min_intron is 1 .. 65535, so a tabled deletion's length fits 16 bits.
+ * TABLED.  A deletion always is.  An insertion is iff R <= SHK_INDEL_MAX_INS and every s[t] < 4; otherwise it counts, in place of
+ *   `insertions`, under `long_insertions` (R > SHK_INDEL_MAX_INS) or `nonbase_insertions` (R <= SHK_INDEL_MAX_INS and some s[t] == 4: an
+ *   N, another byte, a base masked by -q).  So deletions + insertions = the tabled events, `dropped` ones included.
+ * LEFT-NORMALISATION of a tabled event, over g's record [0, len_g):
+ *   deletion   d = the largest number such that for every i in [xa - d, xa): r[i] < 4 and r[i] == r[i + G].  The event is the deletion of
+ *              [xa - d, xa - d + G): x = xa - d, len = G.
+ *   insertion  T[j] = r[j] for j < xa and T[xa + t] = s[t] for t < R.  d = the largest number such that for every i in [xa - d, xa):
+ *              r[i] < 4 and T[i] == T[i + R].  The event is at x = xa - d with the bases s'[t] = T[xa - d + t], t < R: len = R.
+ *   d is bounded only by x = 0 and by a record code of 4.  Alignments mode gives bases that two blocks could both hold to the LEFT block, so a
+ *   raw event sits at the right end of its repeat; the same haplotype gets the same key whichever equivalent placement a mate's blocks took.
+ * KEY.  (gene, x, kind, len, seq): kind 0 = deletion (seq = 0), kind 1 = insertion (seq = sum of s'[t] << 2 t).  Per key the table holds
+ *   fwd and rev: the observations from mates whose record has strand 0 and 1, since the last reset, over the counted batches -- depth's
+ *   rules word for word: mates are counted, not fragments; a read tied over several genes counts in each; integers only; a batch is counted
+ *   exactly once (a batch with more associations than the result buffer holds or with reads beyond a length bound taken on trust is counted
+ *   when its tail runs again; a batch vouched for wrongly and a shk_count_work batch are not counted).
+ * STATS.  Seven 64-bit counters since the last reset: mates (records with n_blocks >= 1 that were examined), deletions, insertions,
+ *   complex_gaps, long_insertions, nonbase_insertions, and dropped (a tabled event that found no entry: the table was full).
+ * Example (k = 17): one A more in the record's run A x 8 at [200, 208) comes out of align_kernel as blocks that end and start at 208 with
+ *   R = 1; d = 8, the key is (g, 200, 1, 1, A).  One CAG less in CAG x 4 at [400, 412): xa = 409 .. 412 by the mate's errors, G = 3, the key
+ *   (g, 400, 0, 3, 0).
+ *
+ * What the mode does NOT do: allele fractions (shk_depth_get and shk_pileup_get give the denominators); insertions above
+ * SHK_INDEL_MAX_INS bases; complex gaps; realigning mates around a called event.  Closure, trimming and the junction table are unchanged.
+ *
+ * Independent of every other mode: gene_off, gene_ids, n_assoc, shk_last_kernel, shk_gene_counts and every other mode's records and state
+ * are the same with the mode on and off.  indel_kernel reads align_kernel's 64-byte records directly behind that kernel (in front of
+ * rescue mode: a rescued mate's one block is no gap): with alignments mode on at the same floor one align_kernel launch serves both;
+ * otherwise its storing instantiation runs once more, at this mode's floor, into an array of the context's own, allocated with the first
+ * such batch and never handed out.  With the mode off no launch and no allocation is added.  New: the reference has no counterpart. */
+#define SHK_INDEL_MAX_INS 12
+typedef struct shk_indel { uint32_t gene, x, kind, len, seq, fwd, rev, reserved; } shk_indel;   /* 32 bytes */
+typedef struct shk_indel_stats { uint64_t mates, deletions, insertions, complex_gaps, long_insertions, nonbase_insertions, dropped; } shk_indel_stats;
+/* Switches the mode on with s_min = min_support (>= 1) or off (0; the other arguments are ignored, the table is kept) for the batches
+ * submitted AFTERWARDS, through any of the four families.  min_intron 1 .. 65535, else SHK_ERR_ARG.  State rules are
+ * shk_alignments_enable's: switching on returns SHK_ERR_STATE before shk_ref_finalize, without shk_ref_keep_positions, on an index of more
+ * than 65 536 records, without shk_ref_keep_bases; either way while tickets are outstanding.  Capacity rules are shk_junctions_enable's:
+ * table entries, rounded up to a power of two of at least 64, 16 bytes each {key, fwd, rev}; the first enable allocates and clears the
+ * table; a later enable with another capacity or another min_intron returns SHK_ERR_ARG unless the table is clean (no batch submitted
+ * with the mode on and nothing added since the first enable or the last shk_indels_reset). */
+int shk_indels_enable(shk_ctx *ctx, uint32_t min_support, uint32_t min_intron, uint64_t capacity);
+/* The read-outs, with shk_junctions_get's rules: SHK_ERR_STATE if the mode was never enabled on this context or while tickets are
+ * outstanding; stream-ordered behind everything enqueued so far; the table is left untouched.  While `dropped` is not 0 shk_indels_get
+ * returns SHK_ERR_INDEX_TOO_LARGE until shk_indels_reset (nothing partial is handed out).
+ *   shk_indels_get     *n = the number of keys with fwd + rev >= min_mates; out != NULL: those keys sorted by (gene, x, kind, len, seq)
+ *                      into out[0 .. *n) (host memory; SHK_ERR_ARG if cap < *n, *n is set all the same).  out == NULL: only *n
+ *   shk_indels_stats   the seven counters
+ *   shk_indels_add     adds in[0 .. n) (host memory) to the table -- fwd to fwd, rev to rev, a new key where the table has none -- and,
+ *                      with stats != NULL, its counters to the table's: how N workers' tables become one.  SHK_ERR_ARG unless every entry
+ *                      has gene < n_records, kind 0 with 1 <= len <= 65535 and seq == 0 or kind 1 with 1 <= len <= SHK_INDEL_MAX_INS and
+ *                      no bit of seq at or above 2 len, x + (kind 0 ? len : 0) <= len_g, x < len_g, and reserved == 0 (nothing is added
+ *                      then).  Stream-ordered; returns when done
+ *   shk_indels_reset   empties the table and zeroes the counters (the mode, the capacity and min_intron stay as they are) */
+int shk_indels_get(shk_ctx *ctx, uint32_t min_mates, shk_indel *out, uint64_t cap, uint64_t *n);
+int shk_indels_stats(shk_ctx *ctx, shk_indel_stats *out);
+int shk_indels_add(shk_ctx *ctx, const shk_indel *in, uint64_t n, const shk_indel_stats *stats /* may be NULL */);
+int shk_indels_reset(shk_ctx *ctx);
+
 /* ---- pairs: what the two mates of an association say together -- orientation, template, proper pair, MAPQ, fragment sizes ---- */
 /* Alignments mode stops at the mate.  Pairs mode reads the two 64-byte records of an association side by side, the mates' lengths and
  * the read's number of associations, and hands out one 32-byte record per ASSOCIATION plus one aggregate over the sample: the

@@ -75,6 +75,20 @@ assert ALIGNMENT_DTYPE.itemsize == 64
 SAM_DEFAULT_MIN_INTRON = 20
 
 
+# shk_indel as a numpy record (32 bytes) and shk_indel_stats' counters in their order
+INDEL_DTYPE = np.dtype([("gene", np.uint32), ("x", np.uint32), ("kind", np.uint32), ("len", np.uint32), ("seq", np.uint32),
+                        ("fwd", np.uint32), ("rev", np.uint32), ("reserved", np.uint32)])
+assert INDEL_DTYPE.itemsize == 32
+INDEL_STAT_NAMES = ("mates", "deletions", "insertions", "complex_gaps", "long_insertions", "nonbase_insertions", "dropped")
+SHK_INDEL_MAX_INS = 12
+INDELS_DEFAULT_CAPACITY = 1 << 20
+INDELS_DEFAULT_MIN_MATES = 2
+
+
+class ShkIndelStats(C.Structure):
+    _fields_ = [(name, C.c_uint64) for name in INDEL_STAT_NAMES]
+
+
 class ShkPairs(C.Structure):
     _fields_ = [("n_assoc", C.c_uint64), ("entries", C.c_void_p)]
 
@@ -138,6 +152,7 @@ EXPORTS = [
     "shk_pairs_enable", "shk_pairs_last", "shk_fragments_get", "shk_fragments_reset",
     "shk_rescue_enable", "shk_rescue_last",
     "shk_splice_sites_set", "shk_alignments_splice",
+    "shk_indels_enable", "shk_indels_get", "shk_indels_stats", "shk_indels_add", "shk_indels_reset",
     "shk_debug_assemble_one",
 ]
 SHK_PIPE_DEPTH = 3
@@ -246,6 +261,11 @@ def load():
         "shk_rescue_last": (C.c_int, [p, C.POINTER(ShkRescues)]),
         "shk_splice_sites_set": (C.c_int, [p, p, C.c_uint64]),
         "shk_alignments_splice": (C.c_int, [p, C.c_uint32, C.c_uint32, C.c_uint32]),
+        "shk_indels_enable": (C.c_int, [p, C.c_uint32, C.c_uint32, C.c_uint64]),
+        "shk_indels_get": (C.c_int, [p, C.c_uint32, p, C.c_uint64, C.POINTER(C.c_uint64)]),
+        "shk_indels_stats": (C.c_int, [p, C.POINTER(ShkIndelStats)]),
+        "shk_indels_add": (C.c_int, [p, p, C.c_uint64, C.POINTER(ShkIndelStats)]),
+        "shk_indels_reset": (C.c_int, [p]),
         "shk_debug_assemble_one": (C.c_int, [p, p, C.c_uint64, C.c_uint32, C.c_uint32, C.c_uint64, C.c_uint32, C.c_int, C.c_int, p, p, p,
                                              C.POINTER(C.c_uint64), p]),
     }
@@ -777,6 +797,41 @@ class SharkHip:
             return np.zeros((0, 2), dtype=ALIGNMENT_DTYPE)
         raw = np.ctypeslib.as_array(C.cast(al.entries, C.POINTER(C.c_uint32)), shape=(n, 2, 16)).copy()
         return alignments_from_raw(raw)
+
+    # ---- indels: the insertions and deletions the mates' alignments show, tabled on the device over all batches --------
+    def indels_enable(self, min_support=8, min_intron=SAM_DEFAULT_MIN_INTRON, capacity=INDELS_DEFAULT_CAPACITY):
+        """batches submitted from now on add the gaps between their mates' final blocks (alignments mode's walk at s_min = min_support
+        with the context's extension and splice parameters) to a table on the device of `capacity` entries (rounded up to a power of
+        two >= 64): deletions shorter than min_intron and insertions of at most SHK_INDEL_MAX_INS bases, left-normalised; 0 switches
+        the mode off and keeps the table; needs an index built with keep_bases"""
+        self._check(self.L.shk_indels_enable(self.h, int(min_support), int(min_intron), int(capacity)), "shk_indels_enable")
+
+    def indels_get(self, min_mates=0):
+        """the table's keys with fwd + rev >= min_mates: a structured array (INDEL_DTYPE) sorted by (gene, x, kind, len, seq)"""
+        n = C.c_uint64()
+        self._check(self.L.shk_indels_get(self.h, int(min_mates), None, 0, C.byref(n)), "shk_indels_get")
+        out = np.zeros(int(n.value), dtype=INDEL_DTYPE)
+        if len(out):
+            self._check(self.L.shk_indels_get(self.h, int(min_mates), _ptr(out), len(out), C.byref(n)), "shk_indels_get")
+        return out[:int(n.value)]
+
+    def indels_stats(self):
+        """the seven counters since the last reset, as a dict keyed by INDEL_STAT_NAMES"""
+        st = ShkIndelStats()
+        self._check(self.L.shk_indels_stats(self.h, C.byref(st)), "shk_indels_stats")
+        return {name: int(getattr(st, name)) for name in INDEL_STAT_NAMES}
+
+    def indels_add(self, entries, stats=None):
+        """adds another context's table (INDEL_DTYPE records, as indels_get hands them out) and, with `stats` (indels_stats' dict), its
+        counters to this context's: how several workers' tables become one"""
+        a = np.ascontiguousarray(entries, dtype=INDEL_DTYPE)
+        st = None
+        if stats is not None:
+            st = ShkIndelStats(*[int(stats[name]) for name in INDEL_STAT_NAMES])
+        self._check(self.L.shk_indels_add(self.h, _ptr(a) if len(a) else None, len(a), C.byref(st) if st is not None else None), "shk_indels_add")
+
+    def indels_reset(self):
+        self._check(self.L.shk_indels_reset(self.h), "shk_indels_reset")
 
     # ---- pairs: per association what its two mates' alignments say together, and the sample's fragment-size histogram --------
     def pairs_enable(self, min_intron=SAM_DEFAULT_MIN_INTRON, max_frag=FRAGMENTS_DEFAULT_MAX, n_bins=FRAGMENTS_DEFAULT_BINS):

@@ -485,24 +485,17 @@ __global__ __launch_bounds__(PL_THREADS) void align_kernel(const Params P)
 
 }  // namespace
 
-int launch_alignments(Ctx *ctx, const Slot &s, const shk_segment *entries, uint64_t cap_assoc, bool skip_if_long, bool store, bool accumulate, hipStream_t stream)
+// the launch: records (store) at floor s_min into out[0 .. out_cap) and / or the final blocks' bases (accumulate) into Ctx::pileup
+static int launch_align_kernel(Ctx *ctx, const Slot &s, const shk_segment *entries, uint64_t cap_assoc, bool skip_if_long, bool store, bool accumulate, uint32_t s_min,
+                               shk_mate_alignment *out, uint64_t out_cap, hipStream_t stream)
 {
   const DeviceIndex &ix = ctx->idx;
-  if (!ix.gene_start || !ix.recbase || !entries || (!store && !accumulate) || (store && (!s.align || !s.rec_align.d.p))) {
-    ctx->last_error = "alignments mode without its state";
-    return SHK_ERR_STATE;
-  }
-  if (accumulate && (!s.pileup_al || !ctx->pileup.counts.p || !ctx->pileup.mates.p || (store && s.align != s.pileup_al))) {
-    ctx->last_error = "aligned pileup without its state";
-    return SHK_ERR_STATE;
-  }
-  if (s.n == 0) return SHK_OK;
   AlignParamsS P{};
   P.gene_off = s.d_gene_off.p;
   P.gene_ids = s.d_gene_ids.p;
   P.counters = s.d_counters;
   P.n = s.n;
-  P.cap = (uint32_t)std::min<uint64_t>(std::min<uint64_t>(std::min<uint64_t>(s.d_gene_ids.cap, cap_assoc), store ? s.rec_align.d.cap / 2 : ~0ull), 0xFFFFFFFFull);   // (launch_segments')
+  P.cap = (uint32_t)std::min<uint64_t>(std::min<uint64_t>(std::min<uint64_t>(s.d_gene_ids.cap, cap_assoc), store ? out_cap / 2 : ~0ull), 0xFFFFFFFFull);   // (launch_segments')
   P.seq[0] = s.p.seq1; P.off[0] = s.p.off1; P.qual[0] = s.p.hasq ? s.p.qual1 : nullptr;
   P.seq[1] = s.p.seq2; P.off[1] = s.p.off2; P.qual[1] = s.p.hasq ? s.p.qual2 : nullptr;
   P.mq = s.p.mq;
@@ -512,8 +505,8 @@ int launch_alignments(Ctx *ctx, const Slot &s, const shk_segment *entries, uint6
   P.recbase = ix.recbase;
   P.n_genes = (uint32_t)(ctx->gene_start.size() - 1);
   P.skip_if_long = skip_if_long ? 1u : 0u;
-  P.s_min = store ? s.align : s.pileup_al;
-  P.out = store ? reinterpret_cast<uint32_t *>(s.rec_align.d.p) : nullptr;
+  P.s_min = s_min;
+  P.out = store ? reinterpret_cast<uint32_t *>(out) : nullptr;
   P.n_store[0] = !store ? 0u : (P.seq[1] ? AL_WORDS : 2u * AL_WORDS);
   P.n_store[1] = !store ? 0u : AL_WORDS;
   P.ext_p = s.ext_p;
@@ -545,6 +538,33 @@ int launch_alignments(Ctx *ctx, const Slot &s, const shk_segment *entries, uint6
   else hipLaunchKernelGGL((align_kernel<true, true, false, AlignParamsX>), dim3(blocks), dim3(PL_THREADS), 0, stream, PX);
   const hipError_t e = hipGetLastError();
   return e == hipSuccess ? SHK_OK : set_hip_error(ctx, e, "align_kernel");
+}
+
+int launch_alignments(Ctx *ctx, const Slot &s, const shk_segment *entries, uint64_t cap_assoc, bool skip_if_long, bool store, bool accumulate, hipStream_t stream)
+{
+  const DeviceIndex &ix = ctx->idx;
+  if (!ix.gene_start || !ix.recbase || !entries || (!store && !accumulate) || (store && (!s.align || !s.rec_align.d.p))) {
+    ctx->last_error = "alignments mode without its state";
+    return SHK_ERR_STATE;
+  }
+  if (accumulate && (!s.pileup_al || !ctx->pileup.counts.p || !ctx->pileup.mates.p || (store && s.align != s.pileup_al))) {
+    ctx->last_error = "aligned pileup without its state";
+    return SHK_ERR_STATE;
+  }
+  if (s.n == 0) return SHK_OK;
+  return launch_align_kernel(ctx, s, entries, cap_assoc, skip_if_long, store, accumulate, store ? s.align : s.pileup_al, s.rec_align.d.p, s.rec_align.d.cap, stream);
+}
+
+int launch_alignments_into(Ctx *ctx, const Slot &s, const shk_segment *entries, uint64_t cap_assoc, bool skip_if_long, uint32_t s_min, shk_mate_alignment *out,
+                           uint64_t out_cap, hipStream_t stream)
+{
+  const DeviceIndex &ix = ctx->idx;
+  if (!ix.gene_start || !ix.recbase || !entries || !s_min || !out) {
+    ctx->last_error = "alignment records of the context's own without their state";
+    return SHK_ERR_STATE;
+  }
+  if (s.n == 0) return SHK_OK;
+  return launch_align_kernel(ctx, s, entries, cap_assoc, skip_if_long, true, false, s_min, out, out_cap, stream);
 }
 
 }  // namespace shk

@@ -42,6 +42,7 @@
 #include "fastq_partition.hpp"
 #include "fastx_reader.hpp"
 #include "gzip_parallel.hpp"
+#include "indel_host.hpp"
 
 namespace {
 
@@ -118,6 +119,16 @@ const char *USAGE_MESSAGE =
     "          --variants-min-depth N        mates that must show a base at a site (default:8)\n"
     "          --variants-min-alt N          mates that must show the alternative base (default:3)\n"
     "          --variants-min-frac P/Q       the alternative base's share of those mates, at least P/Q (default:1/5; P <= Q <= 65535)\n"
+    "          --indels FILE                 write <gene> <x> <I|D> <len> <seq> <fwd> <rev> per insertion or deletion the sample's alignments\n"
+    "                                        show (the gaps between the blocks --sam shows, moved as far left as the record allows and\n"
+    "                                        tabled on the GPUs): x 0-based, seq the inserted bases on the record's strand or *, fwd and rev\n"
+    "                                        the mates on either strand; sorted by gene, x, kind, len, seq (honours --extend-ends and\n"
+    "                                        --splice-junctions; the same refusals as --sam)\n"
+    "          --indels-min-support N        unique k-mers a diagonal of a mate needs to become a block (default:8)\n"
+    "          --indels-min-intron N         record bases from which on a gap is an intron, not a deletion (1 .. 65535, default:20)\n"
+    "          --indels-min-mates N          mates an event needs to be written (default:2)\n"
+    "          --indels-capacity N           entries of the table per worker, rounded up to a power of two (default:1048576, 16 bytes each;\n"
+    "                                        it must hold every distinct event: a full table is an error, not a shorter file)\n"
     "          --sam FILE                    write the gapped alignment of every placed mate to its gene's record as SAM: one line per\n"
     "                                        association and mate with at least one block, in input order (header: @HD, one @SQ per gene;\n"
     "                                        MAPQ 255, TLEN 0, NM:i: from the record's bases; the mate's ends outside its blocks are soft\n"
@@ -141,14 +152,14 @@ const char *USAGE_MESSAGE =
     "          --fragments-max N             the longest fragment of a proper pair (default:1000)\n"
     "          --fragments-bins N            bins of the histogram, the last one open-ended (2 .. 4096, default:1024)\n"
     "          --fragments-min-intron N      record bases a gap needs to count as an intron of the pair (default: --sam-min-intron's)\n"
-    "          --extend-ends                 --sam and --pileup-aligned: grow a mate's outermost blocks over its clipped ends base by base\n"
+    "          --extend-ends                 --sam, --pileup-aligned and --indels: grow a mate's outermost blocks over its clipped ends base by base\n"
     "                                        (match 1, mismatch 4, 5 for reaching the mate's end), so that a substitution within k of\n"
     "                                        an end is shown instead of clipped\n"
     "          --extend-penalty N            the mismatch penalty of --extend-ends (1 .. 15, default:4)\n"
     "          --extend-bonus N              its bonus for reaching the mate's end (0 .. 15, default:5)\n"
     "          --pileup-aligned              --pileup / --variants count the bases of the alignment --sam shows (trimmed, gaps closed,\n"
     "                                        ends extended under --extend-ends) instead of the bases under the voting windows\n"
-    "          --splice-junctions FILE       --sam and --pileup-aligned: try a mate's clipped end of a few bases across the introns FILE lists\n"
+    "          --splice-junctions FILE       --sam, --pileup-aligned and --indels: try a mate's clipped end of a few bases across the introns FILE lists\n"
     "                                        (what --junctions writes: <gene> <donor> <acceptor> <intron> [<mates>]; the intron is record\n"
     "                                        bases [donor, donor + intron)) and place it where that is good and clearly the best\n"
     "          --splice-min-mates N          FILE's lines with fewer mates are left out (default:1)\n"
@@ -203,6 +214,11 @@ struct Options {
   std::string variants_path;
   FILE *variants_file = nullptr;   // (--variants, likewise; written once, after the last batch and after --pileup's file)
   unsigned variants_min_support = 8;
+  std::string indels_path;
+  FILE *indels_file = nullptr;     // (--indels, likewise; written once, after the last batch)
+  unsigned indels_min_support = 8, indels_min_intron = 20, indels_min_mates = 2;
+  uint64_t indels_capacity = 1u << 20;    // (--indels-capacity; entries per worker: 16 MiB)
+  bool indels_sub_flag_given = false;
   std::string sam_path;
   FILE *sam_file = nullptr;        // (--sam, likewise; the header is written once the reference is read, the lines per batch)
   unsigned sam_min_support = 8, sam_min_intron = 20;
@@ -459,6 +475,30 @@ const OptionRow OPTION_TABLE[] = {
        o.splice_sub_flag_given = true;
        if (o.splice_min_gap > 64) reject(USAGE_MESSAGE, "shark: --splice-min-gap must be 0 to 64.");
      }},
+    {1044, "indels", true, [](Options &o, const char *v) { o.indels_path = value_of<std::string>(v); }},
+    {1045, "indels-min-support", true,
+     [](Options &o, const char *v) {
+       o.indels_min_support = value_of<unsigned>(v);
+       o.indels_sub_flag_given = true;
+       if (o.indels_min_support < 1) reject(USAGE_MESSAGE, "shark: --indels-min-support must be at least 1.");
+     }},
+    {1046, "indels-min-intron", true,
+     [](Options &o, const char *v) {
+       o.indels_min_intron = value_of<unsigned>(v);
+       o.indels_sub_flag_given = true;
+       if (o.indels_min_intron < 1 || o.indels_min_intron > 65535) reject(USAGE_MESSAGE, "shark: --indels-min-intron must be 1 to 65535.");
+     }},
+    {1047, "indels-min-mates", true,
+     [](Options &o, const char *v) {
+       o.indels_min_mates = value_of<unsigned>(v);
+       o.indels_sub_flag_given = true;
+     }},
+    {1048, "indels-capacity", true,
+     [](Options &o, const char *v) {
+       o.indels_capacity = value_of<uint64_t>(v);
+       o.indels_sub_flag_given = true;
+       if (o.indels_capacity < 1 || o.indels_capacity > (1ull << 32)) reject(USAGE_MESSAGE, "shark: --indels-capacity must be in the range [1, 4294967296].");
+     }},
 };
 
 // Reads per device batch when --batch does not say.  A batch costs the device path 0.5-2 ms of launches, copies and bookkeeping
@@ -528,6 +568,8 @@ Options parse_arguments(int argc, char **argv)
   if (opt.variants_sub_flag_given && opt.variants_path.empty()) reject(USAGE_MESSAGE, "shark: --variants-min-support, --variants-min-depth, --variants-min-alt and --variants-min-frac need --variants FILE.");
   if (!opt.variants_path.empty() && !opt.pileup_path.empty() && opt.variants_min_support != opt.pileup_min_support)
     reject(USAGE_MESSAGE, "shark: --variants-min-support and --pileup-min-support must be equal (there is one pileup).");
+  if (opt.indels_sub_flag_given && opt.indels_path.empty())
+    reject(USAGE_MESSAGE, "shark: --indels-min-support, --indels-min-intron, --indels-min-mates and --indels-capacity need --indels FILE.");
   if (opt.sam_sub_flag_given && opt.sam_path.empty()) reject(USAGE_MESSAGE, "shark: --sam-min-support and --sam-min-intron need --sam FILE.");
   if (opt.sam_pairs && opt.sam_path.empty()) reject(USAGE_MESSAGE, "shark: --sam-pairs needs --sam FILE.");
   if (opt.sam_rescue && opt.sam_path.empty()) reject(USAGE_MESSAGE, "shark: --sam-rescue needs --sam FILE.");
@@ -543,9 +585,9 @@ Options parse_arguments(int argc, char **argv)
   if (opt.pileup_aligned && opt.pileup_path.empty() && opt.variants_path.empty()) reject(USAGE_MESSAGE, "shark: --pileup-aligned needs --pileup FILE or --variants FILE.");
   if (opt.splice_sub_flag_given && opt.splice_path.empty())
     reject(USAGE_MESSAGE, "shark: --splice-min-mates, --splice-min-overhang, --splice-max-cost and --splice-min-gap need --splice-junctions FILE.");
-  if (!opt.splice_path.empty() && opt.sam_path.empty() && !opt.pileup_aligned) reject(USAGE_MESSAGE, "shark: --splice-junctions needs --sam FILE or --pileup-aligned.");
+  if (!opt.splice_path.empty() && opt.sam_path.empty() && !opt.pileup_aligned && opt.indels_path.empty()) reject(USAGE_MESSAGE, "shark: --splice-junctions needs --sam FILE or --pileup-aligned (or --indels FILE).");
   if (opt.extend_sub_flag_given && !opt.extend_ends) reject(USAGE_MESSAGE, "shark: --extend-penalty and --extend-bonus need --extend-ends.");
-  if (opt.extend_ends && opt.sam_path.empty() && !opt.pileup_aligned) reject(USAGE_MESSAGE, "shark: --extend-ends needs --sam FILE or --pileup-aligned.");
+  if (opt.extend_ends && opt.sam_path.empty() && !opt.pileup_aligned && opt.indels_path.empty()) reject(USAGE_MESSAGE, "shark: --extend-ends needs --sam FILE or --pileup-aligned (or --indels FILE).");
   if (opt.out1_path.empty()) opt.out1_path = "sharked_sample.1";
   if (opt.out2_path.empty() && !opt.sample2_path.empty()) opt.out2_path = "sharked_sample.2";
   // --devices alone says how many workers there are; with --gpus N it has to name N devices
@@ -2275,6 +2317,7 @@ std::string build_index(const Options &opt, GpuStart &gpu, std::vector<std::stri
       if (opt.pileup_file && legend_ID.size() > 65536) return "shark: --pileup is not available for a reference of more than 65536 records (gene ids wrap there).";
       if (opt.variants_file && legend_ID.size() > 65536) return "shark: --variants is not available for a reference of more than 65536 records (gene ids wrap there).";
       if (opt.sam_file && legend_ID.size() > 65536) return "shark: --sam is not available for a reference of more than 65536 records (gene ids wrap there).";
+      if (opt.indels_file && legend_ID.size() > 65536) return "shark: --indels is not available for a reference of more than 65536 records (gene ids wrap there).";
       if (opt.fragments_file && legend_ID.size() > 65536) return "shark: --fragments is not available for a reference of more than 65536 records (gene ids wrap there).";
       const size_t len = strnlen(rec.seq.data(), rec.seq.size());  // C-string semantics (main.cpp:164)
       if (opt.sam_file) sam_header += "@SQ\tSN:" + legend_ID.back() + "\tLN:" + std::to_string(len) + "\n";
@@ -2288,7 +2331,7 @@ std::string build_index(const Options &opt, GpuStart &gpu, std::vector<std::stri
   pelapsed("Transcript file processed");
   timeline("reference read");
   if (opt.placements_file || opt.depth_file || opt.segments_file || opt.junctions_file || opt.pileup_file || opt.variants_file || opt.sam_file ||
-      opt.fragments_file)
+      opt.fragments_file || opt.indels_file)
     for (auto *ctx : gpu.ctxs)
       if (const int rc = shk_ref_keep_positions(ctx)) return std::string("shark: ") + shk_strerror(rc);
   // (the k-mer keyed table repays its enumeration behind several hundred million pairs classified at the GPU's speed: not in a run of this command)
@@ -2298,7 +2341,8 @@ std::string build_index(const Options &opt, GpuStart &gpu, std::vector<std::stri
   // (--sam: every worker's alignments kernel reads them)
   // (--pileup-aligned: the accumulating alignments kernel reads them as well)
   // (--fragments: alignments mode runs for it as it does for --sam)
-  if (opt.variants_file || opt.sam_file || opt.pileup_aligned || opt.fragments_file)
+  // (--indels: the alignments kernel runs for it, and its own kernel reads them when it moves an event)
+  if (opt.variants_file || opt.sam_file || opt.pileup_aligned || opt.fragments_file || opt.indels_file)
     for (auto *ctx : gpu.ctxs)
       if (const int rc = shk_ref_keep_bases(ctx)) return std::string("shark: ") + shk_strerror(rc);
   {
@@ -2520,6 +2564,14 @@ int run_sample(const Options &opt, GpuStart &gpu, BatchPool &pool, std::vector<s
       if (const int rc = shk_alignments_enable(ctx, opt.sam_min_support)) {
         feed.stop();
         std::cerr << "shark: alignments mode could not be switched on: " << shk_strerror(rc) << " " << shk_last_error(ctx) << std::endl;
+        return EXIT_FAILURE;
+      }
+  // (--indels: every worker adds its batches' events to its own table; write_indels sums the tables in worker 0's at the end)
+  if (opt.indels_file)
+    for (shk_ctx *ctx : gpu.ctxs)
+      if (const int rc = shk_indels_enable(ctx, opt.indels_min_support, opt.indels_min_intron, opt.indels_capacity)) {
+        feed.stop();
+        std::cerr << "shark: indels mode could not be switched on: " << shk_strerror(rc) << " " << shk_last_error(ctx) << std::endl;
         return EXIT_FAILURE;
       }
   // (--sam-pairs, --fragments: every worker's batches carry their pair records and add to that worker's fragments state;
@@ -2874,6 +2926,54 @@ bool write_fragments(const Options &opt, std::vector<shk_ctx *> &ctxs)
   return ok;
 }
 
+// --indels: the workers' tables (one per context, each over the batches that worker classified) and their counters added into worker 0's
+// on its device (shk_indels_get, shk_indels_stats, shk_indels_add), then worker 0 is asked once for the events with --indels-min-mates
+// mates: one line each (indel_host.hpp) in the library's order.  The counters go to the log.  A table that was full -- a worker's or the
+// sum -- is an error and leaves an empty file, never a shorter table
+bool write_indels(const Options &opt, std::vector<shk_ctx *> &ctxs, const std::vector<std::string> &legend_ID)
+{
+  int rc = SHK_OK;
+  size_t at = 0;
+  std::vector<shk_indel> rows;
+  uint64_t n = 0;
+  for (size_t g = 1; g < ctxs.size() && rc == SHK_OK; ++g) {
+    at = g;
+    shk_indel_stats st{};
+    rc = shk_indels_get(ctxs[g], 0, nullptr, 0, &n);
+    rows.resize((size_t)n);
+    if (rc == SHK_OK && n) rc = shk_indels_get(ctxs[g], 0, rows.data(), n, &n);
+    if (rc == SHK_OK) rc = shk_indels_stats(ctxs[g], &st);
+    if (rc == SHK_OK) {
+      at = 0;
+      rc = shk_indels_add(ctxs[0], rows.data(), n, &st);
+    }
+  }
+  shk_indel_stats st{};
+  if (rc == SHK_OK) {
+    at = 0;
+    rc = shk_indels_get(ctxs[0], opt.indels_min_mates, nullptr, 0, &n);
+    rows.resize((size_t)n);
+    if (rc == SHK_OK && n) rc = shk_indels_get(ctxs[0], opt.indels_min_mates, rows.data(), n, &n);
+    if (rc == SHK_OK) rc = shk_indels_stats(ctxs[0], &st);
+  }
+  if (rc != SHK_OK) {
+    std::cerr << "shark: the indel table of worker " << at << " could not be read: " << shk_strerror(rc) << " " << shk_last_error(ctxs[at])
+              << (rc == SHK_ERR_INDEX_TOO_LARGE ? " (run again with a larger --indels-capacity)" : "") << std::endl;
+    fclose(opt.indels_file);
+    return false;
+  }
+  pelapsed("Indels: " + std::to_string(st.mates) + " aligned mates, " + std::to_string(st.deletions) + " deletions, " + std::to_string(st.insertions) +
+           " insertions, " + std::to_string(st.complex_gaps) + " complex gaps, " + std::to_string(st.long_insertions) + " long and " +
+           std::to_string(st.nonbase_insertions) + " non-base insertions; " + std::to_string(n) + " events written");
+  std::string text;
+  static const std::string no_name;
+  for (const shk_indel &e : rows) shk::indel_line(e, e.gene < legend_ID.size() ? legend_ID[e.gene] : no_name, text);
+  bool ok = fwrite(text.data(), 1, text.size(), opt.indels_file) == text.size();
+  ok = (fclose(opt.indels_file) == 0) && ok;
+  if (!ok) std::cerr << "shark: cannot write the indels file " << opt.indels_path << std::endl;
+  return ok;
+}
+
 // --variants: a variant call is not linear in the counters, so the workers' states are summed first -- every other worker's array and
 // mate counter added into worker 0's on its device (shk_pileup_get_all, shk_pileup_add) -- and worker 0 is asked once.  One line per
 // site: <gene> <x> <ref> <alt> <A> <C> <G> <T>, genes in id order, x ascending (the order the library hands them out in).  Runs behind
@@ -2939,6 +3039,7 @@ int main(int argc, char *argv[])
   if (opt_parsed.variants_path != "" && samples_can_be_opened(opt_parsed, false)) opt_parsed.variants_file = fopen(opt_parsed.variants_path.c_str(), "w");   // (--variants: likewise)
   if (opt_parsed.sam_path != "" && samples_can_be_opened(opt_parsed, false)) opt_parsed.sam_file = fopen(opt_parsed.sam_path.c_str(), "w");   // (--sam: likewise)
   if (opt_parsed.fragments_path != "" && samples_can_be_opened(opt_parsed, false)) opt_parsed.fragments_file = fopen(opt_parsed.fragments_path.c_str(), "w");   // (--fragments: likewise)
+  if (opt_parsed.indels_path != "" && samples_can_be_opened(opt_parsed, false)) opt_parsed.indels_file = fopen(opt_parsed.indels_path.c_str(), "w");   // (--indels: likewise)
   const Options opt = opt_parsed;
   if (opt.verbose) timeline.on();
   timeline("arguments parsed");
@@ -2993,6 +3094,10 @@ int main(int argc, char *argv[])
     std::cerr << "shark: cannot open the fragments file " << opt.fragments_path << std::endl;
     return EXIT_FAILURE;
   }
+  if (opt.indels_path != "" && !opt.indels_file) {
+    std::cerr << "shark: cannot open the indels file " << opt.indels_path << std::endl;
+    return EXIT_FAILURE;
+  }
 
   BatchPool &pool = *new BatchPool;     // (never destroyed: the process leaves through _exit)
   GpuStart gpu(opt, pool);              // the contexts come up on a thread of their own from here on
@@ -3005,6 +3110,7 @@ int main(int argc, char *argv[])
   if (opt.pileup_file && !write_pileup(opt, gpu.ctxs, legend_ID)) return EXIT_FAILURE;
   if (opt.variants_file && !write_variants(opt, gpu.ctxs, legend_ID)) return EXIT_FAILURE;
   if (opt.fragments_file && !write_fragments(opt, gpu.ctxs)) return EXIT_FAILURE;
+  if (opt.indels_file && !write_indels(opt, gpu.ctxs, legend_ID)) return EXIT_FAILURE;
 
   if ((opt.gene_counts_path != "" || (opt.verbose && opt.gpus > 1)) && !gene_counts(opt, gpu.ctxs, legend_ID)) return EXIT_FAILURE;
   if (opt.verbose) {

@@ -269,7 +269,7 @@ static int enqueue_record_modes(Ctx *ctx, Slot &s, bool skip_if_long)
   // kernel into arrays nobody else sees --: spliced depth and the junction table; pileup; aligned pileup (align_kernel's accumulating
   // instantiation in pileup_kernel's stead: the same launch as alignments mode's where the two floors are equal, else one of its own);
   // alignments mode, the one with records of its own per association
-  if (!(s.sp_depth || s.sp_junc || s.pileup || s.align || s.pileup_al)) return SHK_OK;
+  if (!(s.sp_depth || s.sp_junc || s.pileup || s.align || s.pileup_al || s.indels)) return SHK_OK;
   const shk_segment *entries = s.rec_seg_entries.d.p;
   uint64_t cap_assoc = segments_cap(s.rec_seg_keys.d, s.rec_seg_entries.d, s.seg_m);
   if (s.seg_m != SHK_MAX_SEGMENTS) {
@@ -283,9 +283,18 @@ static int enqueue_record_modes(Ctx *ctx, Slot &s, bool skip_if_long)
   if (s.pileup && (rc = launch_pileup(ctx, s, entries, cap_assoc, skip_if_long, st))) return rc;
   const bool acc_with_records = s.pileup_al && s.pileup_al == s.align;
   if (s.pileup_al && !acc_with_records && (rc = launch_alignments(ctx, s, entries, cap_assoc, skip_if_long, false, true, st))) return rc;
+  // (indels mode reads align_kernel's records at its own floor: alignments mode's where the floors are equal, else those of one more storing
+  //  launch into an array nobody else sees; indel_kernel directly behind the launch that stored them)
+  const bool indels_with_records = s.indels && s.indels == s.align;
+  if (s.indels && !indels_with_records) {
+    if ((rc = s.d_indel_align.reserve(ctx, 2 * ids))) return rc;
+    if ((rc = launch_alignments_into(ctx, s, entries, cap_assoc, skip_if_long, s.indels, s.d_indel_align.p, s.d_indel_align.cap, st))) return rc;
+    if ((rc = launch_indels(ctx, s, s.d_indel_align.p, std::min<uint64_t>(cap_assoc, s.d_indel_align.cap / 2), skip_if_long, st))) return rc;
+  }
   if (!s.align) return SHK_OK;
   if ((rc = s.rec_align.d.reserve(ctx, 2 * ids))) return rc;
   if ((rc = launch_alignments(ctx, s, entries, cap_assoc, skip_if_long, true, acc_with_records, st))) return rc;
+  if (indels_with_records && (rc = launch_indels(ctx, s, s.rec_align.d.p, std::min<uint64_t>(cap_assoc, s.rec_align.d.cap / 2), skip_if_long, st))) return rc;
   // (rescue mode: a mate without a block placed beside its partner, in front of everything that reads the alignment records)
   if (s.rescue) {
     if ((rc = s.rec_rescue.d.reserve(ctx, ids))) return rc;
@@ -408,6 +417,9 @@ static int enqueue_classify(Ctx *ctx, Slot &s, const shk_batch *b, uint32_t max_
   if (s.pileup || s.pileup_al) ctx->pileup.dirty = true;
   if (s.depth || s.sp_depth) ctx->depth.dirty = true;
   if (s.sp_junc) ctx->junc.dirty = true;
+  s.indels = count_genes ? ctx->indel.floor : 0u;
+  s.indels_min_intron = ctx->indel.min_intron;
+  if (s.indels) ctx->indel.dirty = true;
   if ((rc = slot_reserve(ctx, s, n))) return rc;
   s.n = n;
   fill_params(ctx, s, b);
@@ -1595,6 +1607,137 @@ int shk_junctions_reset(shk_ctx *ctx)
   if (const int rc = state_ready(ctx, "shk_junctions_reset", ctx->junc.tab.p != nullptr, "the junction table")) return rc;
   if (const int rc = launch_junction_clear(ctx)) return rc;
   ctx->junc.dirty = false;
+  SHK_HIP(ctx, hipStreamSynchronize(ctx->stream));
+  return SHK_OK;
+}
+
+// ---- indels mode (indels.hip): the table and its counters live in the context, the batches' tails add to them ----
+int shk_indels_enable(shk_ctx *ctx, uint32_t min_support, uint32_t min_intron, uint64_t capacity)
+{
+  if (!ctx) return SHK_ERR_ARG;
+  if (const int rc = refuse_tickets(ctx, "shk_indels_enable")) return rc;
+  IndelState &I = ctx->indel;
+  if (min_support) {
+    int rc;
+    if (min_intron < 1 || min_intron > 65535) { ctx->last_error = "shk_indels_enable: min_intron is 1 .. 65535"; return SHK_ERR_ARG; }
+    if ((rc = check_mode_index(ctx, "shk_indels_enable", NEED_GENE_START | NEED_BASES))) return rc;
+    if (capacity > (1ull << 40)) { ctx->last_error = "shk_indels_enable: capacity beyond 2^40 entries"; return SHK_ERR_ARG; }
+    if (ctx->gene_start.back() >= 0xFFFFFFFFull) { ctx->last_error = "shk_indels_enable: the records hold 2^32 - 1 bases or more (32-bit positions in the table's keys)"; return SHK_ERR_STATE; }
+    uint64_t cap = 64;
+    while (cap < capacity) cap <<= 1;
+    if (I.tab.p && I.dirty && min_intron != I.min_intron) {
+      ctx->last_error = "shk_indels_enable: another min_intron than the table's (shk_indels_reset first)";
+      return SHK_ERR_ARG;
+    }
+    if (!I.stats.p) {
+      SHK_HIP(ctx, hipSetDevice(ctx->prm.device));
+      if ((rc = I.stats.alloc_exact(ctx, INDEL_STATS))) return rc;
+    }
+    if ((rc = state_shape(ctx, I.tab, (size_t)cap, I.dirty, "shk_indels_enable: another capacity than the table's (shk_indels_reset first)",
+                          [&] { return launch_indel_clear(ctx); })))
+      return rc;
+    I.min_intron = min_intron;
+  }
+  I.floor = min_support;
+  return SHK_OK;
+}
+
+// the table's counters as they stand, behind everything enqueued so far
+static int indel_read_stats(shk_ctx *ctx, unsigned long long st[INDEL_STATS])
+{
+  SHK_HIP(ctx, hipMemcpyAsync(st, ctx->indel.stats.p, INDEL_STATS * sizeof(unsigned long long), hipMemcpyDeviceToHost, ctx->stream));
+  SHK_HIP(ctx, hipStreamSynchronize(ctx->stream));
+  return SHK_OK;
+}
+
+int shk_indels_get(shk_ctx *ctx, uint32_t min_mates, shk_indel *out, uint64_t cap, uint64_t *n)
+{
+  if (!ctx || !n) return SHK_ERR_ARG;
+  const IndelState &I = ctx->indel;
+  if (const int rc = state_ready(ctx, "shk_indels_get", I.tab.p != nullptr, "indels mode")) return rc;
+  // once per sample: the whole table to the host, the occupied entries ordered there.  Key order IS (gene, x, kind, len, seq) order: the
+  // genes' bases are numbered gene after gene, and the event's half of the key is laid out in that order (indel_key)
+  std::vector<IndelEntry> tab(I.tab.cap);
+  unsigned long long st[INDEL_STATS];
+  SHK_HIP(ctx, hipMemcpyAsync(tab.data(), I.tab.p, tab.size() * sizeof(IndelEntry), hipMemcpyDeviceToHost, ctx->stream));
+  if (const int rc = indel_read_stats(ctx, st)) return rc;
+  if (st[INDEL_STATS - 1]) {
+    ctx->last_error = "shk_indels_get: the table was full for " + std::to_string(st[INDEL_STATS - 1]) + " observations (shk_indels_reset, then a larger capacity)";
+    return SHK_ERR_INDEX_TOO_LARGE;
+  }
+  tab.erase(std::remove_if(tab.begin(), tab.end(), [&](const IndelEntry &e) { return e.key == INDEL_EMPTY || (uint64_t)e.fwd + e.rev < min_mates; }), tab.end());
+  *n = tab.size();
+  if (!out) return SHK_OK;
+  if (cap < tab.size()) return SHK_ERR_ARG;
+  std::sort(tab.begin(), tab.end(), [](const IndelEntry &a, const IndelEntry &b) { return a.key < b.key; });
+  const std::vector<uint64_t> &gs = ctx->gene_start;
+  for (size_t i = 0; i < tab.size(); ++i) {
+    const uint64_t gx = tab[i].key >> 32;
+    // x < len_g strictly: the last gene that starts at or in front of it (genes without a record have no bases)
+    const size_t g = (size_t)(std::upper_bound(gs.begin(), gs.end(), gx) - gs.begin()) - 1;
+    out[i].gene = (uint32_t)g;
+    out[i].x = (uint32_t)(gx - gs[g]);
+    indel_key_event((uint32_t)tab[i].key, out[i]);
+    out[i].fwd = tab[i].fwd;
+    out[i].rev = tab[i].rev;
+    out[i].reserved = 0;
+  }
+  return SHK_OK;
+}
+
+int shk_indels_stats(shk_ctx *ctx, shk_indel_stats *out)
+{
+  if (!ctx || !out) return SHK_ERR_ARG;
+  if (const int rc = state_ready(ctx, "shk_indels_stats", ctx->indel.tab.p != nullptr, "indels mode")) return rc;
+  unsigned long long st[INDEL_STATS];
+  if (const int rc = indel_read_stats(ctx, st)) return rc;
+  *out = shk_indel_stats{st[0], st[1], st[2], st[3], st[4], st[5], st[6]};
+  return SHK_OK;
+}
+
+int shk_indels_add(shk_ctx *ctx, const shk_indel *in, uint64_t n, const shk_indel_stats *stats)
+{
+  if (!ctx || (!in && n)) return SHK_ERR_ARG;
+  if (const int rc = state_ready(ctx, "shk_indels_add", ctx->indel.tab.p != nullptr, "indels mode")) return rc;
+  std::vector<IndelEntry> keyed;
+  try {
+    keyed.resize(n);
+  } catch (...) {
+    return SHK_ERR_NOMEM;
+  }
+  for (uint64_t i = 0; i < n; ++i) {
+    unsigned long long key = 0;
+    if (const int bad = indel_entry_key(in[i], ctx->gene_start.data(), ctx->gene_start.size() - 1, &key)) {
+      ctx->last_error = "shk_indels_add: entry " + std::to_string(i) + " " + INDEL_ENTRY_RULES[bad];   // (the validation: indel_host.hpp)
+      return SHK_ERR_ARG;
+    }
+    keyed[i] = IndelEntry{key, in[i].fwd, in[i].rev};
+  }
+  if (n == 0 && !stats) return SHK_OK;
+  // (once per worker and sample: a buffer for the length of the call; the entries, then the counters)
+  DevArray<IndelEntry> staged;
+  if (const int rc = staged.alloc_exact(ctx, n + 4)) return rc;
+  unsigned long long st[INDEL_STATS] = {0, 0, 0, 0, 0, 0, 0};
+  if (stats) {
+    const uint64_t v[INDEL_STATS] = {stats->mates, stats->deletions, stats->insertions, stats->complex_gaps, stats->long_insertions, stats->nonbase_insertions, stats->dropped};
+    for (uint32_t c = 0; c < INDEL_STATS; ++c) st[c] = v[c];
+  }
+  unsigned long long *const d_stats = reinterpret_cast<unsigned long long *>(staged.p + n);   // (4 entries = 8 words >= INDEL_STATS)
+  if (n) SHK_HIP(ctx, hipMemcpyAsync(staged.p, keyed.data(), n * sizeof(IndelEntry), hipMemcpyHostToDevice, ctx->stream));
+  SHK_HIP(ctx, hipMemcpyAsync(d_stats, st, sizeof(st), hipMemcpyHostToDevice, ctx->stream));
+  ctx->indel.dirty = true;
+  int rc = launch_indel_add(ctx, staged.p, n, stats ? d_stats : nullptr);
+  const hipError_t e = hipStreamSynchronize(ctx->stream);
+  if (rc == SHK_OK && e != hipSuccess) rc = set_hip_error(ctx, e, "hipStreamSynchronize");
+  return rc;
+}
+
+int shk_indels_reset(shk_ctx *ctx)
+{
+  if (!ctx) return SHK_ERR_ARG;
+  if (const int rc = state_ready(ctx, "shk_indels_reset", ctx->indel.tab.p != nullptr, "indels mode")) return rc;
+  if (const int rc = launch_indel_clear(ctx)) return rc;
+  ctx->indel.dirty = false;
   SHK_HIP(ctx, hipStreamSynchronize(ctx->stream));
   return SHK_OK;
 }

@@ -10,6 +10,7 @@
 #include "../../include/shark_hip.h"
 #include "lds_table.hpp"   // LTAB_*: the LDS-resident exact table of a tiny index
 #include "kmer_table.hpp"  // KXTAB_*: the same for a one-gene index, keyed by the canonical k-mer itself
+#include "indel_host.hpp"  // indel_key and the host-only parts of indels mode
 
 namespace shk {
 
@@ -466,6 +467,11 @@ struct Slot {
   uint32_t rescue = 0, rescue_min_intron = 0, rescue_max_cost = 0, rescue_min_gap = 0;
   Mirrored<shk_rescue> rec_rescue;
   DevArray<uint2> d_rescue_queue;
+  // indels mode (indels.hip): submitted with this floor (0: not) and min_intron.  It reads align_kernel's records at that floor: alignments
+  // mode's own where it runs at the same floor, else an array of its own (allocated with the first such batch, never handed out) that the
+  // storing align_kernel fills once more
+  uint32_t indels = 0, indels_min_intron = 0;
+  DevArray<shk_mate_alignment> d_indel_align;
 };
 
 
@@ -508,6 +514,22 @@ struct JunctionState {
   bool dirty = false;                          // a junction batch was submitted since the first enable / the last reset
   DevArray<JunctionEntry> tab;                 // tab.cap entries, a power of two >= 64 (null: never enabled)
   DevArray<unsigned long long> dropped;        // observations that found the table full since the last reset (allocated in front of the first table, kept across a new capacity)
+};
+// one entry of the indel table (indels.hip): key = (gene_start[g] + x) << 32 | kind << 31 | the event (indel_key, indel_host.hpp)
+struct IndelEntry {
+  unsigned long long key;   // INDEL_EMPTY: free
+  uint32_t fwd, rev;        // observations since the last reset from mates whose record has strand 0 / 1
+};
+static_assert(sizeof(IndelEntry) == 16, "16-byte entries");
+constexpr unsigned long long INDEL_EMPTY = ~0ull;   // (no key: its position would be base 2^32 - 1 of a reference of fewer than 2^32 - 1 bases)
+constexpr uint32_t INDEL_STATS = 7;                  // shk_indel_stats' counters, in its order
+// indels mode's parameters and the indel table (shk_indels_enable; indels.hip)
+struct IndelState {
+  uint32_t floor = 0;                          // min_support for the batches submitted from now on (0: off)
+  uint32_t min_intron = 0;                     // the table's (set by the enable that found it clean)
+  bool dirty = false;                          // an indels batch was submitted or entries were added since the first enable / the last reset
+  DevArray<IndelEntry> tab;                    // tab.cap entries, a power of two >= 64 (null: never enabled)
+  DevArray<unsigned long long> stats;          // INDEL_STATS counters since the last reset (allocated in front of the first table, kept across a new capacity)
 };
 // pairs mode's parameters and the fragments state (shk_pairs_enable; pairs.hip)
 struct FragmentState {
@@ -569,6 +591,16 @@ int launch_pileup_add(Ctx *ctx, const uint32_t *d_add, uint64_t n_entries, uint6
 int variants_call(Ctx *ctx, const shk_variant_params &prm, shk_variant *out, uint64_t cap, uint64_t *n_sites);
 // variants.hip: per gene {observed, mismatches, covered, sites} into Ctx::var.summary (nidx records), on ctx->stream
 int launch_variants_summary(Ctx *ctx, const shk_variant_params &prm);
+// align.hip: the storing launch at floor s_min into `out` (out_cap mates' records) instead of s.rec_align.d: what indels mode reads when
+// alignments mode is off or at another floor; extension and spliced ends as submitted
+int launch_alignments_into(Ctx *ctx, const Slot &s, const shk_segment *entries, uint64_t cap_assoc, bool skip_if_long, uint32_t s_min, shk_mate_alignment *out,
+                           uint64_t out_cap, hipStream_t stream);
+// indels.hip: the gaps between the blocks of the batch's records in `records` (cap_assoc associations; align_kernel's at floor s.indels) into
+// Ctx::indel, directly behind the align_kernel that stored them; skip_if_long: as launch_gene_hist
+int launch_indels(Ctx *ctx, const Slot &s, const shk_mate_alignment *records, uint64_t cap_assoc, bool skip_if_long, hipStream_t stream);
+int launch_indel_clear(Ctx *ctx);      // every entry of Ctx::indel.tab empty, its counters 0, on ctx->stream
+// indels.hip: n validated entries {key, fwd, rev} (device memory) into the table and, with d_stats, INDEL_STATS counters onto its counters, on ctx->stream
+int launch_indel_add(Ctx *ctx, const IndelEntry *d_in, uint64_t n, const unsigned long long *d_stats);
 int launch_junction_clear(Ctx *ctx);   // every entry of Ctx::junc.tab empty, its `dropped` 0, on ctx->stream
 // the read-out: Ctx::depth.scan[1 + x] = depth of base x of the full array (inclusive prefix sum of the difference array), on ctx->stream
 int depth_scan(Ctx *ctx);
@@ -691,6 +723,7 @@ struct Ctx {
   JunctionState junc;
   CounterState pileup;
   FragmentState frag;
+  IndelState indel;
   bool keep_bases = false;                     // finalize builds DeviceIndex::recbase (shk_ref_keep_bases)
   VariantScratch var;
   SpliceSites splice;
