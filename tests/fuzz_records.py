@@ -2,7 +2,8 @@
 """(test infrastructure)  Randomised differential test of the record modes -- everything behind the classify kernel -- against their
 exact Python models, every mode on at once: evidence, candidates, placement, segments, alignments with gap closure, end extension and
 spliced ends, rescue, pairs and the fragments state, plain or spliced depth, the junction table, owned or aligned pileup and the
-variants read from it.  Three separable parts, so that the CPU can do everything but the comparison:
+variants read from it, and the indel table with its counters (at alignments mode's floor, at another, or without alignments mode; its
+parameters come from a random stream of their own, and it is off in one case of five).  Three separable parts, so that the CPU can do everything but the comparison:
 
   draw(seed, bias)        a case from numpy alone: reference, batch, every mode's parameters, the entry family.  No GPU, no oracle.
   expected(case, oracle)  the CPU oracle's associations and, chained in the order the crafted tests use, every model's records and
@@ -14,7 +15,8 @@ The mates are hostile on purpose: besides tests/spliced_synth.py's classes (tran
 random) there are insertions of 1 to 70 junk bases at a junction, empty mates, mates shorter than k and of exactly k bases, unspliced
 mates of 129 to 700 bases from a long record, N, lower case and other bytes, and SILENCED mates: a copy of record bases beside a
 cleanly placed partner with just enough evenly spread substitutions to leave fewer than s_min clean windows (tests/rescue_cases.py's
-idea), which is what reaches rescue_kernel's placing path.
+idea), which is what reaches rescue_kernel's placing path.  The `indel` bias draws genes whose exons hold a low-complexity stretch and
+mates with one planted event inside an exon (indel_gene, indel_mate): what indel_kernel's left-normalisation works on.
 
 tests/test_fuzz_records_cpu.py runs draw and expected over the committed schedule and asserts what the schedule covers;
 tests/test_gpu_fuzz_records.py runs the schedule in the `-m gpu` suite.  By hand on a GPU box:
@@ -35,10 +37,12 @@ from tests import synth
 from tests.candidates_model import expected_candidates
 from tests.depth_model import expected_depth, model_layout
 from tests.evidence_model import expected_evidence
+from tests.align_model import expected_alignments
 from tests.extend_model import best_extension, expected_aligned_pileup
+from tests.indels_model import expected_indels, new_stats, record_events, table_array
 from tests.pairs_model import Fragments, expected_pairs
 from tests.pileup_model import expected_pileup
-from tests.placement_model import expected_placements
+from tests.placement_model import expected_placements, masked_mates
 from tests.rescue_cases import silencing
 from tests.rescue_model import expected_rescue
 from tests.segments_model import SegmentsModel, expected_segments
@@ -47,10 +51,16 @@ from tests.spliced_model import expected_junction_table, expected_spliced_depth,
 from tests.variants_model import DEFAULTS as VARIANT_DEFAULTS
 from tests.variants_model import expected_summary, expected_variants
 
-BIASES = ("", "splice", "rescue", "tie", "wide")
+BIASES = ("", "splice", "rescue", "tie", "wide", "indel")
+# the random streams' keys, each an explicit number: default_rng([seed, key]) draws a case's reference, batch and every mode but indels,
+# default_rng([seed, key, 1]) indels mode's parameters (a second stream: the first one's consumption is what it was before that mode)
+BIAS_KEY = {"": 0, "splice": 1, "rescue": 2, "tie": 3, "wide": 4, "indel": 6}
+WIDE_B_KEY, WIDE_C_KEY = 5, 7
+assert sorted(BIAS_KEY) == sorted(BIASES) and len(set(BIAS_KEY.values()) | {WIDE_B_KEY, WIDE_C_KEY}) == len(BIASES) + 2
 KS = (5, 11, 16, 17, 21, 31)
+FLOORS = (1, 3, 6, 8, 12)
 FAMILIES = ("classify", "submit", "classify_device", "submit_device")
-CLASSES = ("transcript", "record", "deleted", "repeated", "random", "insertion", "empty", "short", "exact_k", "long", "silenced")
+CLASSES = ("transcript", "record", "deleted", "repeated", "random", "insertion", "empty", "short", "exact_k", "long", "silenced", "indel")
 BF_BITS = 1 << 26
 JUNCTION_CAPACITY = 1 << 16          # (a batch tied over six genes at k = 5 and floor 1 shows more than 4 096 distinct junctions)
 VARIANT_PARAMS = (VARIANT_DEFAULTS, (1, 1, 0, 1))
@@ -60,6 +70,8 @@ DEPTH_LANES = 2048 * 256                     # depth_accumulate_kernel, spliced_
 WIDE_B_BLOCK, WIDE_B_TIMES, WIDE_B_REST = 1021, 513, 836
 WIDE_B_PAIRS = DEPTH_LANES + 321
 assert WIDE_B_BLOCK * WIDE_B_TIMES + WIDE_B_REST == WIDE_B_PAIRS
+WIDE_C_FLOOR, WIDE_C_MIN_INTRON = 8, 20      # wide case (c): indel_kernel, one thread per read as well; (b)'s shape, a batch of its own
+INDEL_COUNTERS = ("deletions", "insertions", "complex_gaps", "long_insertions", "nonbase_insertions")      # the five classifying ones
 LETTERS = np.frombuffer(b"NRYKMSWBDHV", dtype=np.uint8)       # (letters only: under -q the reference is undefined on bytes below '@')
 
 
@@ -105,14 +117,52 @@ def spliced_gene(rng, n_introns, k, hostile=0.0):
         at += len(e)
     rec = np.concatenate(parts)
     if hostile:
-        u = rng.random(len(rec))
-        u[[0, -1]] = 1.0
-        rec[u < hostile] |= 0x20
-        rec[u < hostile / 2] = ord("N")
-        rec[u < hostile / 8] = ord("-")
+        spoil_record(rng, rec, hostile)
     tr = np.concatenate([rec[a:b] for a, b in spans])
     cuts = np.cumsum([b - a for a, b in spans])[:-1].tolist()
     return dict(rec=rec, tr=tr, introns=introns, cuts=cuts)
+
+
+def spoil_record(rng, rec, hostile):
+    """lower case, N and '-' in a record, never at its two ends"""
+    u = rng.random(len(rec))
+    u[[0, -1]] = 1.0
+    rec[u < hostile] |= 0x20
+    rec[u < hostile / 2] = ord("N")
+    rec[u < hostile / 8] = ord("-")
+
+
+def indel_gene(rng, n_introns, margin, hostile=0.0):
+    """the gene of the `indel` bias: spliced_gene's dict and introns, but exons long enough to hold an event with a block of the drawn
+    floor on either side (margin = the clean bases such a block needs), and inside every exon a planted low-complexity STRETCH of 8 to
+    80 bases -- a homopolymer, a di- or a trinucleotide repeat --, where an event shifts left by more than its own length.
+    spans: the exons' record ranges; stretches: per exon (record offset, length, unit length)"""
+    parts, introns, spans, stretches, at = [], [], [], [], 0
+    for i in range(n_introns + 1):
+        left, right = (synth.random_seq(rng, int(rng.integers(margin + 30, margin + 71))) for _ in range(2))
+        u = int(rng.choice([1, 1, 2, 2, 3]))
+        unit = synth.random_seq(rng, u)
+        if u > 1 and len(set(unit.tolist())) == 1:
+            unit[0] = synth.ACGT[(int(np.searchsorted(synth.ACGT, unit[0])) + 1) % 4]
+        n = int(rng.choice([8, 12, 20, 30, 45, 64, 80, int(rng.integers(8, 81))]))
+        e = np.concatenate([left, np.tile(unit, n // u + 1)[:n], right])
+        if i:
+            gap = synth.random_seq(rng, int(rng.integers(30, 91)))
+            same = int(rng.integers(1, 4)) if rng.random() < 0.3 else 0
+            gap[:same] = e[:same]
+            parts.append(gap)
+            introns.append((at, at + len(gap), same))
+            at += len(gap)
+        parts.append(e)
+        spans.append((at, at + len(e)))
+        stretches.append((at + len(left), n, u))
+        at += len(e)
+    rec = np.concatenate(parts)
+    if hostile:
+        spoil_record(rng, rec, hostile)
+    tr = np.concatenate([rec[a:b] for a, b in spans])
+    cuts = np.cumsum([b - a for a, b in spans])[:-1].tolist()
+    return dict(rec=rec, tr=tr, introns=introns, cuts=cuts, spans=spans, stretches=stretches, margin=margin)
 
 
 def long_gene(rng):
@@ -135,10 +185,53 @@ def substituted(m, at):
 # ---------------------------------------------------------------------------
 # the mates
 # ---------------------------------------------------------------------------
+def indel_mate(rng, gene):
+    """a transcript or record mate of an indel_gene with ONE planted event inside an exon, at least the gene's margin of bases away from
+    the mate's ends and, for the events outside the stretch, from the exon's: a deletion of 1 to 30 record bases, an insertion of 1 to 12
+    or of 13 to 40 random bases, a tandem duplication (the inserted bases copy the record bases in front of them), or -- every third mate
+    -- units of the exon's low-complexity stretch lost or gained somewhere inside it (or one random base gained there); the mate then
+    spans the whole stretch.  Which gaps come out of it is the alignment model's business"""
+    m = gene["margin"]
+    e = int(rng.integers(0, len(gene["spans"])))
+    a, b = gene["spans"][e]
+    s0, sn, u = gene["stretches"][e]
+    rec = gene["rec"]
+    if rng.random() < 0.5:
+        src, shift = rec, 0
+    else:
+        src, shift = gene["tr"], sum(y - x for x, y in gene["spans"][:e]) - a
+    what = str(rng.choice(["deletion", "insertion", "long", "duplication", "stretch", "stretch"]))
+    gone, piece = 0, np.zeros(0, np.uint8)
+    if what == "stretch":
+        n = min(u * int(rng.choice([1, 1, 2, 3, 5])), sn)
+        if rng.random() < 0.5:
+            x = s0 + int(rng.integers(0, sn - n + 1))
+            gone = n
+        else:
+            x = s0 + int(rng.integers(0, sn + 1))
+            piece = rec[x - n:x].copy() if x - n >= s0 else rec[x:x + n].copy()
+            if rng.random() < 0.2:
+                piece = synth.random_seq(rng, 1)
+        lo, hi = s0, s0 + sn
+    else:
+        if what == "deletion":
+            gone = int(rng.integers(1, 31))
+        x = int(rng.integers(a + m, b - m - gone + 1))
+        if what != "deletion":
+            n = int(rng.integers(13, 41)) if what == "long" or (what == "duplication" and rng.random() < 0.2) else int(rng.integers(1, 13))
+            piece = rec[x - min(n, x - a):x].copy() if what == "duplication" else synth.random_seq(rng, n)
+        lo, hi = x, x + gone
+    la, lb = x - lo + m + int(rng.integers(0, 21)), hi - (x + gone) + m + int(rng.integers(0, 21))
+    p = x + shift
+    return np.concatenate([src[max(0, p - la):p], piece, src[p + gone:p + gone + lb]])
+
+
 def one_mate(rng, kind, gene, long, k):
     """one mate of class `kind` in the record's orientation"""
     rec, tr = gene["rec"], gene["tr"]
     L = int(rng.integers(60, 121))
+    if kind == "indel":
+        return indel_mate(rng, gene)
     if kind == "empty":
         return np.zeros(0, np.uint8)
     if kind in ("short", "exact_k"):
@@ -298,15 +391,47 @@ def draw_sites(rng, panel_of_record, lengths, crowded):
 # ---------------------------------------------------------------------------
 # draw
 # ---------------------------------------------------------------------------
+def draw_indels(rng, md, panel, forced):
+    """indels mode's (floor, min_intron), or None: off in one case of five.  From a stream of its own, which every case consumes alike.
+    The floor: alignments mode's (one align_kernel launch serves both); aligned pileup's where that is another (the accumulating launch
+    serves nobody else: a second storing one); another one (with aligned pileup at a third floor: three launches in one tail, two of them
+    storing); one of its own without alignments mode (the context's private array is the only record array).  min_intron: 1 (no
+    deletion at all), 2, 3, the CLI's 20, 65 535 (every intron a deletion) and an intron's length of this panel or one more: a gap of
+    exactly min_intron is nothing, one of min_intron - 1 a deletion.  forced (the wide and the overflow case): on, at a floor whose
+    records the models compute anyway"""
+    al_floor = md["al_floor"]
+    pile_floor = md["pileup"][1] if md["pileup"][0] == "aligned" else 0
+    introns = [a - d for g in panel for d, a, _ in g["introns"]]
+    edge = introns[int(rng.integers(0, len(introns)))] + int(rng.integers(0, 2)) if introns else 20
+    min_intron = int(rng.choice([1, 2, 3, 20, 20, 65535, edge, edge]))
+    off, v, own = rng.random() < 0.2, rng.random(), int(rng.choice(FLOORS))
+    others = [f for f in FLOORS if f not in (al_floor, pile_floor)]
+    other = others[int(rng.integers(0, len(others)))]
+    if forced:
+        return (al_floor or pile_floor or own, 20 if min_intron == 1 else min_intron)
+    if off:
+        return None
+    if not al_floor:
+        return (own, min_intron)
+    if v < 0.4:
+        return (al_floor, min_intron)
+    if v < 0.6 and pile_floor and pile_floor != al_floor:
+        return (pile_floor, min_intron)
+    return (other, min_intron)
+
+
 def draw(seed, bias=""):
     """a case: a dict of plain Python numbers, lists and numpy arrays, deterministic in (seed, bias)"""
-    rng = np.random.default_rng([int(seed), BIASES.index(bias)])
+    rng = np.random.default_rng([int(seed), BIAS_KEY[bias]])
     wide = bias == "wide"
     k = int(rng.choice(KS))
     # ---- the reference
     n_genes = 2 if wide else int(rng.integers(1, 5))
     hostile = float(rng.choice([0.0, 0.0, 0.02])) if not wide else 0.0
-    panel = [spliced_gene(rng, int(rng.integers(1 if wide else 0, 5)), k, hostile) for _ in range(n_genes)]
+    if bias == "indel":
+        panel = [indel_gene(rng, int(rng.integers(0, 4)), k + max(FLOORS) + 3, hostile) for _ in range(n_genes)]
+    else:
+        panel = [spliced_gene(rng, int(rng.integers(1 if wide else 0, 5)), k, hostile) for _ in range(n_genes)]
     twins = 0
     if bias == "tie" or (not wide and rng.random() < 0.25):
         twins = 6 if (bias == "tie" and rng.random() < 0.5) else int(rng.integers(2, 7))
@@ -324,7 +449,7 @@ def draw(seed, bias=""):
         genes_of_record.append(None)
     lengths = [len(r) for r in records]
     # ---- the modes
-    al_floor = int(rng.choice([1, 3, 6, 8, 12]))
+    al_floor = int(rng.choice(FLOORS))
     if long is not None and rng.random() < 0.3:
         al_floor = 40
     md = dict(evidence=not wide, cand_m=0 if wide else int(rng.integers(1, SHK_MAX_CANDIDATES + 1)), placement=True,
@@ -361,6 +486,7 @@ def draw(seed, bias=""):
         md["pairs"] = (int(rng.choice([1, 20, 30, 1000])), int(rng.choice([1, 50, 300, 611, 1000, 4096, 100000])), int(rng.choice([2, 64, 1024, 4096])))
         md["rescue"] = (int(rng.choice([1, 20, 30])), int(rng.choice([1, 40, 90, 200] if small else [1, 90, 200, 611, 1000, 4096])),
                         int(rng.choice([0, 1, 2, 4, 8, 8, 16, 255])), int(rng.choice([0, 1, 4, 4, 255])))
+    md["indels"] = draw_indels(np.random.default_rng([int(seed), BIAS_KEY[bias], 1]), md, panel, forced=wide or overflow)
     # ---- the batch
     paired = True if wide else bool(rng.random() < 0.8)
     n = WIDE_A_PAIRS if wide else (1520 if overflow else int(rng.choice([1, 63, 64, 65, 200, 200, 300, 300])))
@@ -371,6 +497,8 @@ def draw(seed, bias=""):
         weights["silenced"] = 0.45 if paired else 0.0
     if bias == "splice":
         weights["transcript"] = 0.6
+    if bias == "indel":
+        weights["indel"] = 0.8
     if wide or overflow:
         weights = dict(transcript=0.85, record=0.05, deleted=0.05, insertion=0.05)
     s_floor = al_floor or md["pileup"][1]
@@ -409,6 +537,7 @@ def draw(seed, bias=""):
     elif family == "submit_device":
         bound = min(int(rng.choice([longest, longest, max(1, longest // 3)])), largest_submit_bound(k, paired))
     return dict(seed=int(seed), bias=bias, k=k, c=0.0, min_quality=q, records=records, lengths=lengths, twins=twins, has_long=long is not None,
+                intron_lengths=[sorted({a - d for d, a, _ in g["introns"]}) if g else [] for g in genes_of_record],
                 modes=md, sites=sites, paired=paired, n=n, batch=batch, classes=sorted(classes), longest=longest, family=family, bound=bound,
                 times=2 if family in ("submit", "submit_device") else 1)
 
@@ -427,12 +556,27 @@ def variant(case, **changes):
     return out
 
 
+def emptied_from(batch, keep):
+    """the batch with every mate of the pairs from `keep` on empty: as many reads, fewer associations"""
+    out = dict(batch)
+    for m in ("1", "2"):
+        if batch["seq" + m] is None:
+            continue
+        off = batch["off" + m].copy()
+        off[keep:] = off[keep]
+        out["off" + m] = off
+        for part in ("seq", "qual"):
+            if batch[part + m] is not None:
+                out[part + m] = batch[part + m][:int(off[keep])].copy()
+    return out
+
+
 def describe(case):
     md = case["modes"]
-    return "seed=%d bias=%s k=%d records=%d twins=%d n=%d%s q=%d %s bound=%d/%d seg=%d cand=%d depth=%s junc=%d pileup=%s al=%d ext=%s splice=%s sites=%d pairs=%s rescue=%s" % (
+    return "seed=%d bias=%s k=%d records=%d twins=%d n=%d%s q=%d %s bound=%d/%d seg=%d cand=%d depth=%s junc=%d pileup=%s al=%d ext=%s splice=%s sites=%d pairs=%s rescue=%s indels=%s" % (
         case["seed"], case["bias"] or "-", case["k"], len(case["records"]), case["twins"], case["n"], "x2" if case["paired"] else "", case["min_quality"],
         case["family"], case["bound"], case["longest"], md["seg_m"], md["cand_m"], md["depth"], md["junc_floor"], md["pileup"], md["al_floor"], md["ext"],
-        md["splice"], len(case["sites"]), md["pairs"], md["rescue"])
+        md["splice"], len(case["sites"]), md["pairs"], md["rescue"], md["indels"])
 
 
 # ---------------------------------------------------------------------------
@@ -441,6 +585,44 @@ def describe(case):
 def _bump(cov, key, by=1):
     if by:
         cov[key] = cov.get(key, 0) + int(by)
+
+
+def indel_coverage(cov, case, records, goff, gids, gene_records, stats):
+    """what indels mode's model met in the case: tests/indels_model.py's record_events once more, record by record, for the facts that
+    its table does not keep (an event's shift, whether its read was tied, what -q did to an insertion)"""
+    q, min_intron = case["min_quality"], case["modes"]["indels"][1]
+    for name in INDEL_COUNTERS:
+        _bump(cov, "indels." + name, stats[name])
+    _bump(cov, "indels.single_end", not case["paired"] and stats["mates"] > 0)
+    largest = 0
+    plain = list(masked_mates(case["batch"], 0)) if q else None
+    for i, pair in enumerate(masked_mates(case["batch"], q)):
+        for j in range(int(goff[i]), int(goff[i + 1])):
+            g = int(gids[j])
+            for t, mate in enumerate(pair):
+                rec = records[j, t]
+                n = int(rec["n_blocks"])
+                if mate is None or n < 2:
+                    continue
+                st, shifts = new_stats(), []
+                events = record_events(rec, mate, gene_records.get(g, b""), min_intron, st, shifts)
+                for (x, kind, length, seq), d in zip(events, shifts):
+                    _bump(cov, "indels.rev" if int(rec["strand"]) & 1 else "indels.fwd")
+                    _bump(cov, "indels.shift_ge_1", d >= 1)
+                    _bump(cov, "indels.shift_over_len", kind == 1 and d > length)
+                    _bump(cov, "indels.tied", int(goff[i + 1]) - int(goff[i]) >= 2)
+                    _bump(cov, "indels.intron_as_deletion", kind == 0 and length >= 30 and length in case["intron_lengths"][g])
+                    largest = max(largest, d)
+                if q and st["nonbase_insertions"]:
+                    clear = new_stats()
+                    record_events(rec, plain[i][t], gene_records.get(g, b""), min_intron, clear)
+                    _bump(cov, "indels.masked", st["nonbase_insertions"] - clear["nonbase_insertions"])
+                b = rec["block"]
+                for r in range(n - 1):
+                    R = int(b[r + 1][1]) - int(b[r][1]) - int(b[r][2])
+                    G = int(b[r + 1][0]) - int(b[r][0]) - int(b[r][2])
+                    _bump(cov, "indels.gap_eq_min_intron", R == 0 and G == min_intron)
+    cov["indels.largest_shift"] = largest
 
 
 def expected(case, oracle, candidates=ranged_candidates, scorer=best_extension, memo=None):
@@ -581,6 +763,43 @@ def expected(case, oracle, candidates=ranged_candidates, scorer=best_extension, 
         out["pileup"] = (counts, mates * times)
         out["variants"] = [(expected_variants(counts, sm.records, gs, prm), expected_summary(counts, sm.records, gs, prm)) for prm in VARIANT_PARAMS]
         _bump(cov, "variant_site", len(out["variants"][0][0]) > 0 or len(out["variants"][1][0]) > 0)
+    # ---- indels: align_kernel's records at the mode's own floor, BEFORE rescue rewrites them
+    if md["indels"]:
+        floor, min_intron = md["indels"]
+        recs_i = before if floor == md["al_floor"] else records_at(floor, False)
+        table, stats = expected_indels(recs_i, batch, goff, gids, sm.records, min_intron, q)
+        arr = table_array(table)
+        arr["fwd"] *= np.uint32(times)
+        arr["rev"] *= np.uint32(times)
+        out["indels"] = (arr, {name: v * times for name, v in stats.items()})
+        if overflow:
+            # The overflow repair: the tail's first pass must count nothing.  Its kernels return early, so the record arrays hold what
+            # was there before -- in a fresh context nothing in particular.  So this case is PRIMED: the same reads go through the
+            # context first with the last ones emptied until the associations fit (the same n: no array is allocated anew), indels
+            # mode and the record modes on, every other accumulator off.  The arrays then hold valid records of this very batch's
+            # first reads when the overflowing batch's first pass comes by -- in EVERY slot: a context hands its SHK_PIPE_DEPTH
+            # slots out in turn, so the primer goes through as often.  A read's associations and records are its own, so the
+            # primer's state is the model's over the same records with the emptied reads' associations gone
+            keep = int(np.searchsorted(goff, slot_reserve(case["n"]) * 3 // 4, side="right")) - 1
+            pgoff = goff.copy()
+            pgoff[keep:] = goff[keep]
+            primer = emptied_from(batch, keep)
+            ptab, pst = expected_indels(recs_i, primer, pgoff, gids, sm.records, min_intron, q)
+            D = capi.SHK_PIPE_DEPTH
+            both = {key: [f * times + D * ptab.get(key, (0, 0))[0], r * times + D * ptab.get(key, (0, 0))[1]] for key, (f, r) in table.items()}
+            assert set(ptab) <= set(table)
+            out["indels"] = (table_array(both), {name: v * times + D * pst[name] for name, v in stats.items()})
+            out["primer"] = dict(batch=primer, goff=pgoff.astype(np.uint32), gids=gids[:int(pgoff[-1])].astype(np.uint16))
+            assert 0 < pst["deletions"] + pst["insertions"] and 0 < int(pgoff[-1]) <= slot_reserve(case["n"])
+        out["indel_records"] = recs_i
+        indel_coverage(cov, case, recs_i, goff, gids, sm.records, stats)
+        _bump(cov, "indels.floor_same" if floor == md["al_floor"] else "indels.without_alignments" if not md["al_floor"] else "indels.floor_other")
+        _bump(cov, "indels.third_launch", kind == "aligned" and len({floor, md["pileup"][1], md["al_floor"]}) == 3 and md["al_floor"] > 0)
+        _bump(cov, "indels.before_rescue", bool(md["rescue"]) and floor == md["al_floor"] and al.tobytes() != before.tobytes())
+        _bump(cov, "indels.with_overflow", overflow)
+        _bump(cov, "indels.with_length_repair", too_long)
+        _bump(cov, "indels.with_length_repair.submit_device", too_long and case["family"] == "submit_device")
+    out["expect_indels"] = bool(md["indels"])
     out["stored"] = bool(md["al_floor"])
     out["model"], out["rows4"], out["before_rescue"] = sm, rows4, (before if md["al_floor"] else None)
     cov["instantiation"] = (ext, int(kind == "aligned"), spl)
@@ -627,6 +846,8 @@ def set_modes(h, case):
         h.pairs_enable(*md["pairs"])
     if md["rescue"]:
         h.rescue_enable(*md["rescue"])
+    if md["indels"]:
+        h.indels_enable(md["indels"][0], md["indels"][1], JUNCTION_CAPACITY)
 
 
 def build_context(case, oracle_nidx):
@@ -734,7 +955,22 @@ def compare_states(h, case, want):
         bad = first_difference("fragment classes", classes, want["fragments"][1]) or first_difference("fragment histogram", hist, want["fragments"][0])
         if bad:
             return bad
+    if md["indels"]:
+        stats = h.indels_stats()
+        bad = compare_indels(None if stats["dropped"] else h.indels_get(0), stats, want["indels"])
+        if bad:
+            return bad
     return first_difference("depth layout", h.depth_layout(), want["gene_start"])
+
+
+def compare_indels(table, stats, want):
+    """None, or the first of the seven counters that differs (dropped is 0 in the model: the table is large enough), or the table's first
+    differing entry.  The counters first: shk_indels_get refuses while anything was dropped (table None)"""
+    for name in capi.INDEL_STAT_NAMES:
+        if stats[name] != want[1][name]:
+            return "indel counter %s: got %d, model %d" % (name, stats[name], want[1][name])
+    assert stats == want[1]
+    return first_difference("indel table", table, want[0])
 
 
 def run(case, oracle, want=None):
@@ -746,6 +982,14 @@ def run(case, oracle, want=None):
     h = build_context(case, want["nidx"])
     replay = "  (replay: python tests/fuzz_records.py 1 %d %s)" % (case["seed"], case["bias"])
     try:
+        if want.get("primer"):
+            quiet = dict(md, evidence=False, cand_m=0, depth=None, junc_floor=0, pileup=None, pairs=None, rescue=None)
+            set_modes(h, dict(case, modes=quiet))
+            for _ in range(capi.SHK_PIPE_DEPTH):
+                goff, gids = h.classify(*_args(want["primer"]["batch"]))
+                bad = first_difference("gene_off", goff, want["primer"]["goff"]) or first_difference("gene_ids", gids, want["primer"]["gids"])
+                if bad:
+                    return bad + " (the primer, against the oracle)", dict(family=case["family"])
         set_modes(h, case)
         family = case["family"]
         hand_outs = []
@@ -796,7 +1040,7 @@ def draw_wide_depth(seed):
     """(records, block, remainder) of wide case (b): the block's 1 021 pairs come from the first two genes, the remainder's 836 from the
     third as well.  513 x 1 021 = 523 773, so the second trip -- the 321 reads from 524 288 on -- lies wholly inside the remainder (whose
     first 515 pairs end the first trip) and covers bases that no pair of the block covers"""
-    rng = np.random.default_rng([int(seed), len(BIASES)])
+    rng = np.random.default_rng([int(seed), WIDE_B_KEY])
     panel = [spliced_gene(rng, 1 + i, 17) for i in range(3)]
     w = dict(transcript=0.8, record=0.1, deleted=0.05, insertion=0.05)
     b1, b2, _ = draw_mates(rng, panel[:2], None, WIDE_B_BLOCK, 17, 8, 1000, w, 0.01)
@@ -874,6 +1118,78 @@ def run_wide_depth(case, oracle, want=None):
 
 
 # ---------------------------------------------------------------------------
+# wide case (c): the second trip of indel_kernel's stride loop
+# ---------------------------------------------------------------------------
+def draw_wide_indels(seed):
+    """(b)'s construction with content of its own: three indel_genes at k = 17; the block's 1 021 pairs come from the first two, the
+    remainder's 836 mostly from the third and mostly of the `indel` class, so that the second trip's 321 pairs show events -- and keys --
+    that nothing in front of them shows"""
+    rng = np.random.default_rng([int(seed), WIDE_C_KEY])
+    panel = [indel_gene(rng, 1 + i, 17 + max(FLOORS) + 3) for i in range(3)]
+    b1, b2, _ = draw_mates(rng, panel[:2], None, WIDE_B_BLOCK, 17, WIDE_C_FLOOR, 1000, dict(transcript=0.6, record=0.1, deleted=0.05, insertion=0.05, indel=0.2), 0.01)
+    r1, r2, _ = draw_mates(rng, panel[2:] * 3 + panel[:2], None, WIDE_B_REST, 17, WIDE_C_FLOOR, 1000, dict(transcript=0.2, record=0.05, deleted=0.05, indel=0.7), 0.01)
+    return dict(seed=int(seed), k=17, records=[g["rec"] for g in panel], block=synth.batch_from_lists(b1, b2), rest=synth.batch_from_lists(r1, r2),
+                longest=max(len(m) for m in b1 + b2 + r1 + r2))
+
+
+def expected_wide_indels(case, oracle):
+    """T x model(block) + model(remainder): the table's counts and the seven counters are sums over mates as well.  Alignments mode is
+    off: the records are those of align_kernel's storing launch at the mode's own floor.  `tail`: the table and counters of the second
+    trip's 321 pairs alone; `tail_only`: its keys that neither the block nor the remainder's pairs in front of them show"""
+    T = WIDE_B_TIMES
+    recs = [bytes(r) for r in case["records"]]
+    o = oracle.Shark(k=17, c=0.0, bf_bits=BF_BITS, min_quality=0)
+    nidx = o.build(recs)
+    sm = SegmentsModel(recs, 17)
+    out = dict(nidx=nidx)
+    first = DEPTH_LANES - T * WIDE_B_BLOCK
+
+    def part(b):
+        goff, gids = o.classify(*_args(b))
+        rows = expected_segments(sm, b, goff, gids, 4)[1]
+        al = expected_alignments(sm, b, goff, gids, rows, WIDE_C_FLOOR)
+        return np.asarray(goff).astype(np.int64), np.asarray(gids), expected_indels(al, b, goff, gids, sm.records, WIDE_C_MIN_INTRON)
+
+    def cut(b, lo, hi):
+        return synth.batch_from_lists(*[[b["seq" + m][int(b["off" + m][i]):int(b["off" + m][i + 1])] for i in range(lo, hi)] for m in ("1", "2")])
+
+    (bo, bi, (btab, bst)), (ro, ri, (rtab, rst)) = part(case["block"]), part(case["rest"])
+    out["goff"] = np.concatenate([[0]] + [bo[1:] + t * bo[-1] for t in range(T)] + [ro[1:] + T * bo[-1]]).astype(np.uint32)
+    out["gids"] = np.concatenate([np.tile(bi, T), ri]).astype(np.uint16)
+    table = {key: [f * T, r * T] for key, (f, r) in btab.items()}
+    for key, (f, r) in rtab.items():
+        e = table.setdefault(key, [0, 0])
+        e[0], e[1] = e[0] + f, e[1] + r
+    out["indels"] = (table_array(table), {name: bst[name] * T + rst[name] for name in bst})
+    head, tail = part(cut(case["rest"], 0, first))[2], part(cut(case["rest"], first, WIDE_B_REST))[2]
+    assert {name: head[1][name] + tail[1][name] for name in rst} == rst                  # (sums over mates: the remainder is its two parts)
+    out["tail"], out["tail_only"] = tail, sorted(set(tail[0]) - set(btab) - set(head[0]))
+    o.close()
+    return out
+
+
+def run_wide_indels(case, oracle, want=None):
+    """None or the mismatch's message: one context, one classify, indels mode alone"""
+    import torch  # noqa: F401
+    from shark_amd import SharkHip
+    want = want or expected_wide_indels(case, oracle)
+    batch = tiled(case["block"], WIDE_B_TIMES, case["rest"])
+    assert len(batch["off1"]) - 1 == WIDE_B_PAIRS > DEPTH_LANES
+    h = SharkHip(k=17, c=0.0, bf_bits=BF_BITS)
+    try:
+        assert h.build([bytes(r) for r in case["records"]], keep_positions=False, keep_bases=True)["nidx"] == want["nidx"]
+        h.indels_enable(WIDE_C_FLOOR, WIDE_C_MIN_INTRON, JUNCTION_CAPACITY)
+        goff, gids = h.classify(*_args(batch))
+        bad = first_difference("gene_off", goff, want["goff"]) or first_difference("gene_ids", gids, want["gids"])
+        if bad:
+            return bad
+        stats = h.indels_stats()
+        return compare_indels(None if stats["dropped"] else h.indels_get(0), stats, want["indels"])
+    finally:
+        h.close()
+
+
+# ---------------------------------------------------------------------------
 # the replay and soak driver
 # ---------------------------------------------------------------------------
 def main():
@@ -890,7 +1206,7 @@ def main():
         want = expected(case, pyoracle)
         bad, facts = run(case, pyoracle, want)
         for key, v in want["coverage"].items():
-            if isinstance(v, int) and key != "widest":
+            if isinstance(v, int) and key not in ("widest", "indels.largest_shift"):
                 total[key] = total.get(key, 0) + v
         print("%4d %s assoc=%d long=%d %s" % (it, describe(case), facts["n_assoc"], facts["last_n_long"], "ok" if not bad else "MISMATCH"), flush=True)
         if bad:
