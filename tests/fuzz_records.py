@@ -625,11 +625,12 @@ def indel_coverage(cov, case, records, goff, gids, gene_records, stats):
     cov["indels.largest_shift"] = largest
 
 
-def expected(case, oracle, candidates=ranged_candidates, scorer=best_extension, memo=None):
+def expected(case, oracle, candidates=ranged_candidates, scorer=best_extension, memo=None, primed=True):
     """every record array and accumulator state of the case, from the oracle's associations and the models; states are those after
     case["times"] counted batches (the ticket families submit the batch twice).  `coverage` counts what the case exercised.  memo: a
     dict shared by variants of ONE case over the SAME batch (variant() with other modes): associations, placements, segments and the
-    alignment records per floor are then computed once"""
+    alignment records per floor are then computed once.  primed=False (tests/fuzz_sessions.py: the batch comes behind others through a
+    live context, whose arrays hold those batches' records) leaves the overflow case's primer out: the states are the batch's own"""
     memo = {} if memo is None else memo
 
     def once(key, fn):
@@ -772,7 +773,7 @@ def expected(case, oracle, candidates=ranged_candidates, scorer=best_extension, 
         arr["fwd"] *= np.uint32(times)
         arr["rev"] *= np.uint32(times)
         out["indels"] = (arr, {name: v * times for name, v in stats.items()})
-        if overflow:
+        if overflow and primed:
             # The overflow repair: the tail's first pass must count nothing.  Its kernels return early, so the record arrays hold what
             # was there before -- in a fresh context nothing in particular.  So this case is PRIMED: the same reads go through the
             # context first with the last ones emptied until the associations fit (the same n: no array is allocated anew), indels
