@@ -1134,6 +1134,16 @@ int shk_debug_assemble_one(shk_ctx *ctx, const uint32_t *count, uint64_t n, uint
                            uint32_t ctr_long, int skip_if_long, int count_genes, uint32_t *gene_off, uint16_t *gene_ids,
                            uint32_t *counters /* [SHK_DEBUG_COUNTER_WORDS] */, uint64_t *gene0_added, uint32_t *guard_changed /* [12] */);
 
+/* Test-only: what became of the speculation on the last batch finished.  Behind a batch that the device judged uniform,
+ * shk_classify_device launches the next batch's uniform kernel for the same lengths at once and has the device look at the offsets
+ * BESIDE that launch (index of one record whose uniform batches take the exact table in LDS, a length bound that fits, no
+ * record mode, no accumulating state; SHK_NO_SPECULATE=1, read by shk_create: never).  0: the batch was not speculated on; 1: it was,
+ * and its lengths were the expected ones; 2: it was, they were not, and the batch was run again the ordinary way.  Results, shk_last_kernel,
+ * shk_gene_counts and the last_n_* figures are the same in all three cases; in shk_timing, prepass_ms of a speculated batch is about 0
+ * (no pass over the offsets stands in front of its classify launch), and for a batch that was run again (2) prepass_ms and total_ms are
+ * those of the first, wasted pass: the second run is not timed. */
+int shk_debug_last_speculation(const shk_ctx *ctx);
+
 /* pinned host memory helpers for callers that stream batches */
 void *shk_alloc_pinned(size_t bytes);
 void  shk_free_pinned(void *p);

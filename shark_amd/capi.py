@@ -154,6 +154,7 @@ EXPORTS = [
     "shk_splice_sites_set", "shk_alignments_splice",
     "shk_indels_enable", "shk_indels_get", "shk_indels_stats", "shk_indels_add", "shk_indels_reset",
     "shk_debug_assemble_one",
+    "shk_debug_last_speculation",
 ]
 SHK_PIPE_DEPTH = 3
 SHK_DIST_ID_BYTES = 128
@@ -268,6 +269,7 @@ def load():
         "shk_indels_reset": (C.c_int, [p]),
         "shk_debug_assemble_one": (C.c_int, [p, p, C.c_uint64, C.c_uint32, C.c_uint32, C.c_uint64, C.c_uint32, C.c_int, C.c_int, p, p, p,
                                              C.POINTER(C.c_uint64), p]),
+        "shk_debug_last_speculation": (C.c_int, [p]),
     }
     variant = bool(os.environ.get("SHK_LIB_PATH"))
     for name, (res, args) in later.items():
@@ -367,6 +369,10 @@ class SharkHip:
     def last_kernel(self):
         """the classify kernel instantiation the last batch ran (rocprofv3's name for it)"""
         return self.L.shk_last_kernel(self.h).decode()
+
+    def debug_last_speculation(self):
+        """test-only: 0 = the last batch was not speculated on, 1 = speculated and held, 2 = speculated and run again (include/shark_hip.h)"""
+        return int(self.L.shk_debug_last_speculation(self.h))
 
     def copy_bf(self):
         nw = (self.bf_bits + 63) // 64

@@ -1172,7 +1172,10 @@ __global__ __launch_bounds__(256) void publish_results_kernel(const uint32_t *__
       for (uint64_t i = m8 * 8 + tid; i < m; i += nth) h_gene_ids[i] = gene_ids[i];
     }
   }
-  if (tid < CTR_WORDS) h_counters[tid] = tid == CTR_VERDICT ? (uni_flag ? 1u + uni_flag[0] : 0u) : counters[tid];
+  // (the device's verdict and, beside it, the lengths it found: the host speculates on them for the next batch -- shark_hip.hip, enqueue_classify)
+  if (tid < CTR_WORDS)
+    h_counters[tid] = tid == CTR_VERDICT ? (uni_flag ? 1u + uni_flag[0] : 0u)
+                    : ((tid == CTR_UNI_L1 || tid == CTR_UNI_L2) ? (uni_flag ? uni_flag[1u + (uint32_t)tid - CTR_UNI_L1] : 0u) : counters[tid]);
 }
 
 // ... and a host batch's records of every other kind (evidence, candidates, placements, segments, alignments, pairs, rescue), the same way: one
@@ -1407,6 +1410,12 @@ int launch_classify_uni(Ctx *ctx, const ClassifyParams &p_in, uint32_t max_slots
   const uint64_t want = (p.n + wpb - 1) / wpb;
   const unsigned grid = (unsigned)(want < cap ? want : cap);
   if ((rmode == 2 || rmode == 3) && !lx) return SHK_OK;      // (no such instantiation on this index: the verdict is never "by classes" / "offsets" there)
+  // a speculated launch (ClassifyParams::spec) is safe through the guard in the kernel's prologue, which only the uniform exact-table
+  // instantiations without CLS and TRO carry (classify_uni.hpp): anything else must not be launched with the mark
+  if (p.spec && !(lx && rmode == 1)) {
+    ctx->last_error = "a speculated launch needs the uniform exact-table kernel";
+    return SHK_ERR_ARG;
+  }
   if (u == 2) launch_uni_u2(p, mode, hasq, big, lx, rmode, grid, stream);
   else if (u == 3) launch_uni_u3(p, mode, hasq, big, lx, rmode, grid, stream);
   else if (u == 4) launch_uni_u4(p, mode, hasq, big, lx, rmode, grid, stream);
@@ -1422,15 +1431,17 @@ int launch_classify_uni(Ctx *ctx, const ClassifyParams &p_in, uint32_t max_slots
                p.tile_first ? " +tiles-first" : "", p.lx_multi ? " +sparse-first-rounds" : (p.lx_gene != 0xFFFFFFFFu ? " +sparse-first-round" : ""));
     return SHK_OK;
   }
-  // (with p.uni_flag both instantiations are launched and one returns at once: the name says UNI = "device")
+  // (with p.uni_flag both instantiations are launched and one returns at once: the name says UNI = "device"; a speculated launch
+  //  stands for exactly those launches and carries their name)
+  const bool by_device = p.uni_flag != nullptr || p.spec != 0u;
   if (uni || !p.uni_flag)
     snprintf(ctx->last_kernel, sizeof(ctx->last_kernel), "classify_uni_kernel<%u, %d, %s, %d, %s>%s%s%s", u, mode, hasq ? "true" : "false",
-             (lx && (u <= 5 || u == 10)) ? 21 : ((big && (u <= 5 || u == 10)) ? 20 : 18), p.uni_flag ? "device" : (uni ? "true" : "false"),
+             (lx && (u <= 5 || u == 10)) ? 21 : ((big && (u <= 5 || u == 10)) ? 20 : 18), by_device ? "device" : (uni ? "true" : "false"),
              (!pm_lds(mode) && p.ref_total) ? " +anchored-extension" : "", pre ? " +pre-verdict" : "",
              (lx && p.lx_gene != 0xFFFFFFFFu) ? " +sparse-first-round" : ((lx && p.lx_multi) ? " +sparse-first-rounds" : ""));
-  if (lx && p.tri && (uni || !p.uni_flag) && (p.uni_flag || tri_applies_host(p.uni_L1, p.uni_L2, p.k, 64u * u))) {
+  if (lx && p.tri && (uni || !p.uni_flag) && (by_device || tri_applies_host(p.uni_L1, p.uni_L2, p.k, 64u * u))) {
     const size_t l = strlen(ctx->last_kernel);
-    snprintf(ctx->last_kernel + l, sizeof(ctx->last_kernel) - l, "%s%s", p.uni_flag ? " +three-pairs-if-they-fit" : " +three-pairs", p.tile_first ? " +tiles-first" : "");
+    snprintf(ctx->last_kernel + l, sizeof(ctx->last_kernel) - l, "%s%s", by_device ? " +three-pairs-if-they-fit" : " +three-pairs", p.tile_first ? " +tiles-first" : "");
   }
   return SHK_OK;
 }
@@ -1467,13 +1478,16 @@ int launch_class_prepass(const ClassifyParams &p, uint32_t slot_cap, uint32_t *f
   return hipGetLastError() == hipSuccess ? SHK_OK : SHK_ERR_HIP;
 }
 
-int launch_uniform_check(const ClassifyParams &p, uint32_t slot_cap, uint32_t *flag, hipStream_t stream)
+int launch_uniform_check(const ClassifyParams &p, uint32_t slot_cap, uint32_t *flag, hipStream_t stream, bool beside)
 {
   // (flag[] is zero: cleared with the batch's counters, shark_hip.hip enqueue_classify)
   // (every workgroup ends with an atomic on the same word -- and three more when the batch is ragged --, 40-50 ns each one after the
   //  other: 1 024 workgroups spent half of the kernel's 0.08 ms there.  So 256 workgroups -- of 1 024 threads for large batches:
   //  160 MB of offsets per 10 M pairs want more loads in flight than 65 536 threads have)
-  const unsigned threads = p.n >= (1ull << 20) ? 1024u : 256u;
+  // (beside: the check of a speculated batch, on a stream of its own while the exact-table kernel holds every CU with one 1 024-thread
+  //  workgroup, 448 of a SIMD's 512 VGPRs and all but 2.5 KB of the LDS: one wave per SIMD of this kernel's 64 VGPRs still fits, so
+  //  256 threads per workgroup, one workgroup per CU at most -- and nobody waits for it until the classify kernel has finished)
+  const unsigned threads = (p.n >= (1ull << 20) && !beside) ? 1024u : 256u;
   const uint64_t want = (p.n + threads - 1) / threads;
   hipLaunchKernelGGL(uniform_check_kernel, dim3((unsigned)(want < 1 ? 1 : (want < 256 ? want : 256))), dim3(threads), 0, stream, p, slot_cap, flag);
   return hipGetLastError() == hipSuccess ? SHK_OK : SHK_ERR_HIP;

@@ -300,6 +300,17 @@ __global__ __launch_bounds__((UniGeom<U, MODE, LSL>::THREADS), (UniGeom<U, MODE,
   uint32_t *const dyn_ctr = reinterpret_cast<uint32_t *>(lds + UG::SUM_WORDS64 + WAVES * WORDS * AREAS);
   const int lane = threadIdx.x & 63;
   const uint32_t wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
+  if (UNI && !CLS && !TRO && LSL == 21 && P.spec) {   // (the instantiations a speculated launch can name: launch_uni_u, rmode 1 with the exact table in LDS)
+    // A speculated launch (shark_internal.hpp, ClassifyParams::spec): the lengths are the batch before's, and nobody has looked at
+    // this batch's offsets yet.  It works only on a batch whose offsets start at 0 and end at n L per mate: it then touches exactly the
+    // bytes a truly uniform batch of the same n and lengths touches -- bases [0, n L) per mate, no offset --, and all of them lie
+    // below what the batch's own offsets claim.  Speculation adds no new address.  (A batch of other lengths that passes, 151 + 149
+    // in place of 150 + 150, is classified with its reads cut at the wrong places: the check beside this launch says so and the
+    // assembly hands the batch back to the host -- device_scan.hip, scan_tile_offsets_one_kernel.)  Four scalar loads, dead before the loop
+    bool fits = P.off1[0] == 0ull && P.off1[P.n] == P.n * (uint64_t)P.uni_L1;
+    if (P.seq2) fits = fits && P.off2[0] == 0ull && P.off2[P.n] == P.n * (uint64_t)P.uni_L2;
+    if (!fits) return;
+  }
   uint32_t L1 = P.uni_L1, L2 = P.uni_L2;
   if (P.uni_flag) {
     // every launch is made when only the device knows what the batch is like -- 0: ragged, 1: uniform, 2: by classes, 3: mixed lengths

@@ -156,7 +156,8 @@ const uint64_t *exclusive_scan_u32(const uint32_t *in, uint32_t *out, uint64_t n
 // the thread that writes the total does finalize_total_kernel's job, and gene_hist_kernel's as well -- every association is gene 0's
 __global__ __launch_bounds__(SCAN_OFFS_THREADS) void scan_tile_offsets_one_kernel(uint64_t *__restrict__ tile_sums, uint64_t ntiles, uint64_t *__restrict__ total_out,
                                                                                   uint32_t *__restrict__ counters, uint64_t gene_ids_cap, uint32_t count_genes,
-                                                                                  uint32_t skip_if_long, unsigned long long *__restrict__ gene_counts)
+                                                                                  uint32_t skip_if_long, unsigned long long *__restrict__ gene_counts,
+                                                                                  const uint32_t *__restrict__ spec_verdict, uint32_t spec_L1, uint32_t spec_L2)
 {
   __shared__ uint64_t lds[SCAN_OFFS_THREADS / 64];
   const uint64_t per = (ntiles + SCAN_OFFS_THREADS - 1) / SCAN_OFFS_THREADS;
@@ -191,8 +192,16 @@ __global__ __launch_bounds__(SCAN_OFFS_THREADS) void scan_tile_offsets_one_kerne
   counters[CTR_ASSOC_LO] = (uint32_t)tot;
   counters[CTR_ASSOC_HI] = (uint32_t)(tot >> 32);
   counters[CTR_OVERFLOW] = overflow ? 1u : 0u;
+  // a speculated batch (OneRecordResult::spec_verdict): uniform_check_kernel's words are final by now.  Not uniform, or of other
+  // lengths than the classify launch assumed: the counts scanned here mean nothing.  The host sees the word, runs the batch again
+  // and this kernel counts it then
+  bool miss = false;
+  if (spec_verdict) {
+    miss = spec_verdict[0] != 1u || spec_verdict[1] != spec_L1 || spec_verdict[2] != spec_L2;
+    if (miss) counters[CTR_SPEC_MISS] = 1u;
+  }
   // (gene_hist_kernel's rule: a batch that the host finishes by its slow path comes through here again and is counted then)
-  if (count_genes && !overflow && !(skip_if_long && counters[CTR_LONG]) && tot) atomicAdd(&gene_counts[0], (unsigned long long)tot);
+  if (count_genes && !overflow && !miss && !(skip_if_long && counters[CTR_LONG]) && tot) atomicAdd(&gene_counts[0], (unsigned long long)tot);
 }
 
 // the tile's associations are all gene 0's, and the workgroup writes them: ids [tile_offs[b], tile_offs[b] + the tile's sum), cut at
@@ -260,7 +269,7 @@ const uint64_t *exclusive_scan_assemble_one(const uint32_t *count, uint32_t *gen
   if (vec) hipLaunchKernelGGL(scan_tile_sums_kernel<true>, dim3((unsigned)ntiles), dim3(SCAN_THREADS), 0, stream, count, n, temp);
   else hipLaunchKernelGGL(scan_tile_sums_kernel<false>, dim3((unsigned)ntiles), dim3(SCAN_THREADS), 0, stream, count, n, temp);
   hipLaunchKernelGGL(scan_tile_offsets_one_kernel, dim3(1), dim3(SCAN_OFFS_THREADS), 0, stream, temp, ntiles, total, r.counters, r.gene_ids_cap,
-                     r.count_genes ? 1u : 0u, r.skip_if_long ? 1u : 0u, r.gene_counts);
+                     r.count_genes ? 1u : 0u, r.skip_if_long ? 1u : 0u, r.gene_counts, r.spec_verdict, r.spec_L1, r.spec_L2);
   if (vec) hipLaunchKernelGGL(scan_apply_fill_kernel<true>, dim3((unsigned)ntiles), dim3(SCAN_THREADS), 0, stream, count, gene_off, n, temp, r.gene_ids,
                               r.gene_ids_cap, r.counters);
   else hipLaunchKernelGGL(scan_apply_fill_kernel<false>, dim3((unsigned)ntiles), dim3(SCAN_THREADS), 0, stream, count, gene_off, n, temp, r.gene_ids,

@@ -37,6 +37,11 @@ struct OneRecordResult {
   uint32_t *counters;                   // the batch's counter block (shark_internal.hpp, CTR_*)
   unsigned long long *gene_counts;      // the context's per-gene counters (only [0] is touched); may be null when !count_genes
   bool count_genes, skip_if_long;
+  // a speculated batch (shark_hip.hip, enqueue_classify): uniform_check_kernel's words {verdict, L1, L2}, final before this scan starts,
+  // and the lengths its classify launch assumed.  Anything but "uniform, of these lengths": the epilogue sets counters[CTR_SPEC_MISS]
+  // and adds nothing to gene_counts.  nullptr: not speculated
+  const uint32_t *spec_verdict = nullptr;
+  uint32_t spec_L1 = 0, spec_L2 = 0;
 };
 const uint64_t *exclusive_scan_assemble_one(const uint32_t *count, uint32_t *gene_off, uint64_t n, uint64_t *temp, const OneRecordResult &r,
                                             hipStream_t stream);

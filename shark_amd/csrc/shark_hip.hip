@@ -325,7 +325,9 @@ static int enqueue_tail(Ctx *ctx, Slot &s, bool skip_hist_if_long, bool count_ge
   // launches (device_scan.hpp, OneRecordResult): no finalize, gather, EMIT or histogram launch.  SHK_PLAIN_TAIL=1: the sequence below
   const bool one_record = ctx->n_records == 1 && !ctx->idx.wrap && !ctx->env_plain_tail;
   if (one_record) {
-    const OneRecordResult r{s.d_gene_ids.p, s.d_gene_ids.cap, s.d_counters, ctx->d_gene_counts, count_genes, skip_hist_if_long};
+    // (a speculated batch: the scan's epilogue compares the check's words with what the classify launch assumed -- enqueue_classify)
+    const OneRecordResult r{s.d_gene_ids.p, s.d_gene_ids.cap, s.d_counters, ctx->d_gene_counts, count_genes, skip_hist_if_long,
+                            s.speculated ? s.d_uni_flag : nullptr, s.p.uni_L1, s.p.uni_L2};
     (void)exclusive_scan_assemble_one(s.d_count.p, s.d_gene_off.p, n + 1, s.d_scan_temp.p, r, st);
     SHK_HIP(ctx, hipGetLastError());
   } else {
@@ -368,6 +370,8 @@ enum LongMode {
 static void note_verdict(Ctx *ctx, uint32_t v)
 {
   ctx->last_verdict = v;
+  ctx->spec_prev.valid = false;   // (classify_resident says so again behind a batch of its own)
+  ctx->last_speculation = 0;
   if (char *e = strstr(ctx->last_kernel, " verdict=")) *e = 0;
   if (v) {
     const size_t l = strlen(ctx->last_kernel);
@@ -385,7 +389,7 @@ enum UniMode {
 
 static int enqueue_classify(Ctx *ctx, Slot &s, const shk_batch *b, uint32_t max_slots, int long_mode, uint32_t n_long_host,
                             uint32_t long_slots_host, bool count_genes, int uni_mode = UNI_ASK_DEVICE, uint32_t uni_L1 = 0, uint32_t uni_L2 = 0,
-                            bool groups_fit = true)
+                            bool groups_fit = true, bool may_speculate = false)
 {
   hipStream_t st = ctx->stream;
   const uint64_t n = b->n;
@@ -458,6 +462,23 @@ static int enqueue_classify(Ctx *ctx, Slot &s, const shk_batch *b, uint32_t max_
   const bool tro_ask = tro_avail && uni_mode == UNI_ASK_DEVICE;
   if (tro_host) by_classes = false;
   const bool with_plans = table_kernel && uni_mode != UNI_YES;
+  // Speculation.  A sequencer's stream has one length per mate, batch after batch: behind a batch that the device judged uniform with
+  // lengths (L1, L2), shk_classify_device launches the uniform kernel for THOSE lengths at once, as if the host knew them, and
+  // uniform_check_kernel looks at this batch's offsets beside it on a stream of its own: nothing the kernel computes depends on the
+  // check when the lengths are what they were.  No offsets form, no ragged form, no plan-table fill.  The launch is marked
+  // (ClassifyParams::spec): the kernel returns at once unless the batch's first and last offsets are those of such a batch, so it reads
+  // nothing that the batch's own offsets do not claim.  The tail waits for the check; the scan's epilogue compares the check's words
+  // with the lengths assumed and, where they differ, counts nothing and raises CTR_SPEC_MISS: classify_resident runs the batch again.
+  // Only where all of this holds: shk_classify_device with a length bound that fits (no host round trip in this function), lengths for
+  // the device to judge, an index of one record without wrap whose uniform batches take the exact table in LDS and whose tail is the
+  // scan's own, no record mode and no accumulating state, a batch before of the same pairedness, presence of qualities and
+  // specialisation.  SHK_NO_SPECULATE=1: never
+  const Ctx::SpecPrev &sp = ctx->spec_prev;
+  const bool modes_on = s.evidence || s.cand_m || s.placement || s.seg_m || s.depth || s.sp_depth || s.sp_junc || s.pileup || s.pileup_al || s.align || s.indels;
+  const bool spec = may_speculate && !ctx->env_no_speculate && stream_is_uniform && sp.valid && long_mode == LONG_NONE_EXPECTED && table_kernel &&
+                    ctx->n_records == 1 && !ctx->idx.wrap && !ctx->env_plain_tail && class_kernel_available(ctx, max_slots) && !modes_on &&
+                    sp.paired == (b->seq2 != nullptr) && sp.quals == (b->qual1 != nullptr) && sp.max_slots == max_slots;
+  s.speculated = spec;
   if (by_classes) {
     // (32 bytes per pair of extra HBM: a device too full for them classifies the batch with the ragged instantiation instead)
     if (s.d_cls_entries.reserve(ctx, (size_t)(2 * n)) != SHK_OK ||
@@ -512,7 +533,14 @@ static int enqueue_classify(Ctx *ctx, Slot &s, const shk_batch *b, uint32_t max_
       uni_mode = UNI_ASK_DEVICE;
       SHK_HIP(ctx, hipMemsetAsync(s.d_cls_hist.p, 0, classes * sizeof(uint32_t), st));
     }
-    if (uni_mode == UNI_ASK_DEVICE) {
+    if (spec) {
+      // (the check itself is launched with the classify kernel, below)
+      s.p.tro = tro_ask ? (ctx->env_force_tro ? 2u : 1u) : 0u;
+      // (the lengths as the host's: uni_flag stays nullptr until the launch is made)
+      s.p.uni_L1 = sp.L1;
+      s.p.uni_L2 = sp.L2;
+      s.p.spec = 1u;
+    } else if (uni_mode == UNI_ASK_DEVICE) {
       s.p.tro = tro_ask ? (ctx->env_force_tro ? 2u : 1u) : 0u;
       if ((rc = launch_uniform_check(s.p, s.fast_cap, s.d_uni_flag, st))) return rc;
       if (by_classes && (rc = launch_class_prepass(s.p, s.fast_cap, s.d_uni_flag, st))) return rc;
@@ -524,7 +552,8 @@ static int enqueue_classify(Ctx *ctx, Slot &s, const shk_batch *b, uint32_t max_
       // (a resident batch whose caller vouched for the lengths: nobody has looked at its offsets)
       if (uni_mode == UNI_YES && !s.host_batch && n != 0 && (rc = launch_vouch_check(s.p, uni_L1, uni_L2, s.d_counters, st))) return rc;
     }
-    if (with_plans) SHK_HIP(ctx, hipMemsetAsync(s.d_plan.p, 0, classes * sizeof(uint4), st));
+    // (a speculated batch launches no reader of the plans; should it come through again, classify_resident clears them)
+    if (with_plans && !spec) SHK_HIP(ctx, hipMemsetAsync(s.d_plan.p, 0, classes * sizeof(uint4), st));
   }
   if (ctx->timing) SHK_HIP(ctx, hipEventRecord(e0, st));
 
@@ -546,6 +575,30 @@ static int enqueue_classify(Ctx *ctx, Slot &s, const shk_batch *b, uint32_t max_
   if (!ctx->idx.wrap) {
     if (!table_kernel) {
       if ((rc = launch_classify_fast(ctx, s.p, max_slots, st, s.evidence, s.cand_m != 0))) return rc;           // bit-vector probe chains; every index in evidence mode
+    } else if (spec) {
+      // the check beside the classify kernel, on the context's second stream: behind the fills of the counter / flag words, and nobody
+      // waits for it before the tail.  Then the uniform launch alone, exactly the form that applies to the speculated lengths; then the
+      // check's words are awaited and the tail reports the device's verdict as ever.  An error on the way: the check may be running
+      // -- it reads the caller's offsets and writes the flag words --, so the second stream is drained before the error is returned
+      // (SHK_SPECULATE_IN_FRONT=1, A/B timing: the check in front of the launch on the one stream, as without speculation; the launches
+      //  that are left out stay out)
+      hipError_t e = hipSuccess;
+      if (ctx->env_spec_in_front) {
+        rc = launch_uniform_check(s.p, s.fast_cap, s.d_uni_flag, st);
+        if (!rc) rc = launch_classify_uni(ctx, s.p, max_slots, 1, st);
+      } else {
+        e = hipEventRecord(ctx->ev_chk_go, st);
+        if (e == hipSuccess) e = hipStreamWaitEvent(ctx->chk_stream, ctx->ev_chk_go, 0);
+        rc = e == hipSuccess ? launch_uniform_check(s.p, s.fast_cap, s.d_uni_flag, ctx->chk_stream, true) : set_hip_error(ctx, e, "the check's start event");
+        if (!rc && (e = hipEventRecord(ctx->ev_chk_done, ctx->chk_stream)) != hipSuccess) rc = set_hip_error(ctx, e, "hipEventRecord(ctx->ev_chk_done, ctx->chk_stream)");
+        if (!rc) rc = launch_classify_uni(ctx, s.p, max_slots, 1, st);
+        if (!rc && (e = hipStreamWaitEvent(st, ctx->ev_chk_done, 0)) != hipSuccess) rc = set_hip_error(ctx, e, "hipStreamWaitEvent(st, ctx->ev_chk_done, 0)");
+      }
+      if (rc) {
+        (void)hipStreamSynchronize(ctx->chk_stream);
+        return rc;
+      }
+      s.p.uni_flag = s.d_uni_flag;
     } else {
       // what the host knows decides the launch; when only the device knows, both are made and one returns at once
       if (uni_mode != UNI_NO && (rc = launch_classify_uni(ctx, s.p, max_slots, 1, st))) return rc;
@@ -633,6 +686,30 @@ static int hand_out_records(Ctx *ctx, const Slot &s, bool host, bool measurement
   return SHK_OK;
 }
 
+// A speculated batch whose offsets were not what its classify launch assumed (CTR_SPEC_MISS; enqueue_classify): the launch returned from
+// its prologue or classified reads cut at the wrong places, and the scan counted nothing.  The batch comes through again: the counters and
+// count[] cleared, the plans cleared, then exactly the launches the path without speculation makes behind the check -- whose verdict is
+// where it was, and which is not repeated --, the tail, a synchronisation.  The result is that of the kernels that path would have run,
+// and the batch is counted here, once; finish_classify's slow paths follow as behind any batch
+static int redo_speculated(Ctx *ctx, Slot &s, uint32_t max_slots, bool count_genes)
+{
+  hipStream_t st = ctx->stream;
+  int rc;
+  s.speculated = false;
+  s.p.spec = 0u;
+  s.p.uni_L1 = s.p.uni_L2 = 0u;
+  s.p.uni_flag = s.d_uni_flag;
+  SHK_HIP(ctx, hipMemsetAsync(s.d_counters, 0, COUNTER_BLOCK_WORDS * sizeof(uint32_t), st));   // (the check's words behind them stay)
+  SHK_HIP(ctx, hipMemsetAsync(s.d_count.p, 0, (s.n + 1) * sizeof(uint32_t), st));
+  if (s.p.plan_tab) SHK_HIP(ctx, hipMemsetAsync(s.p.plan_tab, 0, (size_t)s.p.plan_cap * sizeof(uint4), st));
+  if ((rc = launch_classify_uni(ctx, s.p, max_slots, 1, st))) return rc;
+  if (s.p.tro && (rc = launch_classify_uni(ctx, s.p, max_slots, 3, st))) return rc;
+  if ((rc = launch_classify_uni(ctx, s.p, max_slots, 0, st))) return rc;
+  if ((rc = enqueue_tail(ctx, s, true, count_genes))) return rc;
+  SHK_HIP(ctx, hipStreamSynchronize(st));
+  return SHK_OK;
+}
+
 // a batch resident in HBM, start to finish (shk_classify_device, shk_count_work)
 static int classify_resident(Ctx *ctx, const shk_batch *b, uint32_t max_read_len, shk_result *res, shk_work_counters *wc = nullptr)
 {
@@ -648,10 +725,19 @@ static int classify_resident(Ctx *ctx, const shk_batch *b, uint32_t max_read_len
   const uint64_t hint_groups = (((uint64_t)max_read_len + 7) >> 3) * (paired ? 2 : 1);   // (no bound given: the table kernel queues what it cannot stage)
   // (UNI_ASK_DEVICE: the lengths passed here only size the plan table of a batch that turns out ragged: the caller's bound per mate)
   if ((rc = enqueue_classify(ctx, s, b, max_slots, long_mode, 0, 0, wc == nullptr, UNI_ASK_DEVICE, max_read_len, paired ? max_read_len : 0,
-                             hint_groups <= uni_kernel_max_groups(max_slots))))
+                             hint_groups <= uni_kernel_max_groups(max_slots), wc == nullptr)))
     return rc;
   SHK_HIP(ctx, hipStreamSynchronize(st));
+  int speculation = s.speculated ? 1 : 0;
+  if (s.speculated && s.h_counters[CTR_SPEC_MISS]) {
+    if ((rc = redo_speculated(ctx, s, max_slots, wc == nullptr))) return rc;
+    speculation = 2;
+  }
   bool redone = false;
+  // (behind a batch that was run again too.  Of the two slow paths only the long reads' can follow a missed speculation today: speculation
+  //  needs an index of one record, where a read has at most one association and gene_ids holds 2 n + 4 096 -- CTR_OVERFLOW is never
+  //  raised there, so "missed, then overflow" is a sequence no test can drive; tests/test_gpu_speculative_uniform.py drives "missed,
+  //  then long reads")
   if ((rc = finish_classify(ctx, s, long_mode == LONG_NONE_EXPECTED, wc == nullptr, &redone))) return rc;
   const uint64_t n_assoc = ((uint64_t)s.h_counters[CTR_ASSOC_HI] << 32) | s.h_counters[CTR_ASSOC_LO];
 
@@ -678,6 +764,10 @@ static int classify_resident(Ctx *ctx, const shk_batch *b, uint32_t max_read_len
   ctx->last.last_n_long = s.h_counters[CTR_LONG];
   ctx->last.last_n_tie = s.h_counters[CTR_TIE];
   note_verdict(ctx, s.h_counters[CTR_VERDICT]);
+  // (what the next batch of shk_classify_device may speculate on: the device's own "uniform", with the lengths it found)
+  if (!wc && s.h_counters[CTR_VERDICT] == 2u)
+    ctx->spec_prev = Ctx::SpecPrev{true, paired, b->qual1 != nullptr, max_slots, s.h_counters[CTR_UNI_L1], s.h_counters[CTR_UNI_L2]};
+  ctx->last_speculation = speculation;
 #ifdef SHK_ANCH_STATS   // (experiments: reads the anchored extension settled early / settled after probing its open slots)
   ctx->last.last_n_long = s.h_counters[CTR_UNUSED3];
   ctx->last.last_n_tie = s.h_counters[CTR_UNUSED5];
@@ -831,6 +921,8 @@ int shk_create(const shk_params *prm, shk_ctx **out)
     ctx->env_no_pre_verdict = getenv("SHK_NO_PRE_VERDICT") != nullptr;
     ctx->env_no_tri = getenv("SHK_NO_TRI") != nullptr;
     { const char *pt = getenv("SHK_PLAIN_TAIL"); ctx->env_plain_tail = pt && pt[0] == '1'; }
+    { const char *ns = getenv("SHK_NO_SPECULATE"); ctx->env_no_speculate = ns && ns[0] == '1'; }
+    { const char *sf = getenv("SHK_SPECULATE_IN_FRONT"); ctx->env_spec_in_front = sf && sf[0] == '1'; }
     ctx->env_pairs_global = getenv("SHK_PAIRS_GLOBAL_ATOMICS") != nullptr;
     ctx->env_no_tro = getenv("SHK_NO_TRO") != nullptr;
     ctx->env_force_tro = getenv("SHK_FORCE_TRO") != nullptr;
@@ -852,6 +944,10 @@ int shk_create(const shk_params *prm, shk_ctx **out)
   CR_HIP(hipStreamCreateWithFlags(&ctx->stream, hipStreamNonBlocking));
   CR_HIP(hipStreamCreateWithFlags(&ctx->h2d_stream, hipStreamNonBlocking));
   CR_HIP(hipStreamCreateWithFlags(&ctx->d2h_stream, hipStreamNonBlocking));
+  // (and the one a speculated batch's check runs on, beside the classify kernel: enqueue_classify)
+  CR_HIP(hipStreamCreateWithFlags(&ctx->chk_stream, hipStreamNonBlocking));
+  CR_HIP(hipEventCreateWithFlags(&ctx->ev_chk_go, hipEventDisableTiming));
+  CR_HIP(hipEventCreateWithFlags(&ctx->ev_chk_done, hipEventDisableTiming));
   stamp("three streams");
   DeviceIndex &ix = ctx->idx;
   ix.bf_bits = prm->bf_bits;
@@ -886,6 +982,7 @@ void shk_destroy(shk_ctx *ctx)
   if (ctx->h2d_stream) (void)hipStreamSynchronize(ctx->h2d_stream);
   if (ctx->d2h_stream) (void)hipStreamSynchronize(ctx->d2h_stream);
   if (ctx->stream) (void)hipStreamSynchronize(ctx->stream);
+  if (ctx->chk_stream) (void)hipStreamSynchronize(ctx->chk_stream);
   free_index(ctx->idx);
   for (Slot &sl : ctx->slots) slot_free(sl);
   hipFree(ctx->d_gene_counts); hipFree(ctx->d_gene_totals); hipFree(ctx->d_work_counters);
@@ -896,6 +993,9 @@ void shk_destroy(shk_ctx *ctx)
   if (ctx->h2d_stream) (void)hipStreamDestroy(ctx->h2d_stream);
   if (ctx->d2h_stream) (void)hipStreamDestroy(ctx->d2h_stream);
   if (ctx->stream) (void)hipStreamDestroy(ctx->stream);
+  if (ctx->ev_chk_go) (void)hipEventDestroy(ctx->ev_chk_go);
+  if (ctx->ev_chk_done) (void)hipEventDestroy(ctx->ev_chk_done);
+  if (ctx->chk_stream) (void)hipStreamDestroy(ctx->chk_stream);
   delete ctx;   // (the general kernel's scratch and the accumulated states free themselves here: the device is current, the streams were drained)
 }
 
@@ -946,6 +1046,7 @@ const char *shk_probe_mode(const shk_ctx *ctx)
 }
 
 const char *shk_last_kernel(const shk_ctx *ctx) { return ctx ? ctx->last_kernel : ""; }
+int shk_debug_last_speculation(const shk_ctx *ctx) { return ctx ? ctx->last_speculation : 0; }
 
 int shk_index_copy_bf(const shk_ctx *cctx, uint64_t *words, uint64_t n_words)
 {

@@ -298,6 +298,10 @@ struct ClassifyParams {
   unsigned long long *work_counters;
   // timing-only ablation switches (env SHK_ABLATE; results are wrong when set; never set in tests/bench)
   uint32_t ablate;
+  // 1 = a speculated launch (shark_hip.hip, enqueue_classify): uni_L1 / uni_L2 are the lengths the device found in the batch BEFORE this
+  // one, and uniform_check_kernel looks at this batch's offsets beside the launch, not in front of it.  The uniform instantiations
+  // return from their prologue unless the batch's first and last offsets are those of such a batch (classify_uni.hpp)
+  uint32_t spec;
 };
 
 enum {
@@ -311,7 +315,10 @@ enum {
   CTR_ASSOC_LO = 6,  // number of associations of the batch (the scan's total), 64 bits
   CTR_ASSOC_HI = 7,
   CTR_VERDICT = 8,   // (host copy only) 1 + uni_flag[0] of a batch the device looked at: 1 ragged, 2 uniform, 3 by classes; 0: the host knew
-  CTR_WORDS = 9
+  CTR_UNI_L1 = 9,    // (host copy only) uni_flag[1], uni_flag[2] of such a batch: the one length per mate, or the longest mates; 0: the host knew
+  CTR_UNI_L2 = 10,
+  CTR_SPEC_MISS = 11, // 1 = a speculated batch whose offsets are not what the launch assumed (scan_tile_offsets_one_kernel): nothing was counted, the host runs it again
+  CTR_WORDS = 12
 };
 
 constexpr uint32_t UNI_FLAG_WORDS = 16;
@@ -422,6 +429,7 @@ struct Slot {
   ClassifyParams p{};              // launch parameters (kept for the slow paths)
   uint32_t fast_cap = 0, gen_slots = 0;
   bool host_batch = false;
+  bool speculated = false;         // the uniform launch was made with the lengths of the batch before, the check beside it (enqueue_classify)
   bool evidence = false;           // submitted in evidence mode: the evidence instantiations ran and rec_evid holds its records
   uint32_t cand_m = 0;             // submitted in candidates mode with this many entries per read (0: not): the candidates instantiations ran
   bool long_speculative = false;   // (device-resident submit) the caller's length bound was taken on trust: checked in wait
@@ -628,7 +636,7 @@ int launch_class_prepass(const ClassifyParams &p, uint32_t slot_cap, uint32_t *f
 bool class_kernel_available(const Ctx *ctx, uint32_t max_slots);
 bool offsets_kernel_available(const Ctx *ctx, uint32_t max_slots, bool hasq);
 bool offsets_kernel_fits(const Ctx *ctx, uint32_t max_slots, uint32_t L1, uint32_t L2);
-int launch_uniform_check(const ClassifyParams &p, uint32_t slot_cap, uint32_t *flag, hipStream_t stream);
+int launch_uniform_check(const ClassifyParams &p, uint32_t slot_cap, uint32_t *flag, hipStream_t stream, bool beside = false);   // beside: while a classify kernel holds the CUs
 bool uni_kernel_available(const Ctx *ctx);
 // anchor_verdict.hip
 bool anchor_verdict_applies(const ClassifyParams &p);
@@ -704,6 +712,17 @@ struct Ctx {
   bool env_ktab_nt = false, env_ktab_plain = false;   // SHK_KTAB_NT=1 / 0: the minimiser table probed with / without non-temporal loads whatever its size (A/B timing, tests)
   bool env_force_generic = false, env_big_lds_always = false, env_cls_always = false;   // SHK_CLS_MIN_FILL given: no adapting to the stream
   uint32_t last_verdict = 0;        // CTR_VERDICT of the last batch finished
+  // speculation (shark_hip.hip, enqueue_classify): what shk_classify_device's last batch was like when the device judged it uniform
+  struct SpecPrev {
+    bool valid = false;             // the batch finished last came through shk_classify_device and the device's verdict was "uniform"
+    bool paired = false, quals = false;
+    uint32_t max_slots = 0, L1 = 0, L2 = 0;
+  } spec_prev;
+  bool env_no_speculate = false;    // SHK_NO_SPECULATE=1: the check always in front of the classify launches (A/B timing, tests)
+  bool env_spec_in_front = false;   // SHK_SPECULATE_IN_FRONT=1: a speculated batch's check in front of its classify launch on the one stream (A/B timing)
+  int last_speculation = 0;         // shk_debug_last_speculation: 0 not speculated, 1 speculated and held, 2 speculated and redone
+  hipStream_t chk_stream = nullptr; // a speculated batch's uniform_check_kernel runs here, beside the classify kernel
+  hipEvent_t ev_chk_go = nullptr, ev_chk_done = nullptr;
   uint32_t env_cls_min_fill = CLS_MIN_FILL;   // SHK_CLS_MIN_FILL: pairs per non-empty class a batch needs to go class by class (0: never; tests: 1)
   // which classify kernel the last batch's main launch was (shk_last_kernel): the choice can depend on the batch before it
   char last_kernel[160] = "";
